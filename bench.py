@@ -1,13 +1,15 @@
 """bench.py -- 512x512 tiles/sec of the U-Net hot path on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--size S] [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1]): ``rs predict`` of the ResNet-50 U-Net, batch 16 x 3x512x512 fp32 per GPU, 2
 classes: layout conversion -> 61 convolutions -> fused final 1x1 + softmax, i.e. everything ``rs predict`` runs on the
 device per batch (reference tools/predict.py:83-87).  Inputs are synthetic and already resident in HBM when the timed
 region starts.  Tiles shard across ranks with no data-path collective ("weak" scaling: B tiles per GPU per step).
 
-One JSON line on stdout (rank 0): metric/value/unit... (the predict leg), plus
+One JSON line on stdout (rank 0): metric/value/unit/ms_per_step/step_ms... of the timed leg (the predict leg by default).
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs (--dump-outputs) and the line.  With --full
+the line also carries
   "train"        -- the train leg of the metric (configs[2]: bf16, bs 32 per GPU, fwd + Lovasz + bwd + gradient
                     all-reduce + Adam): value (tiles/s over all ranks), ms_per_step, its own roofline object;
   "legs"         -- the remaining BASELINE configurations, same timing discipline, short loops: configs[4] (4-band RGB+IR,
@@ -17,7 +19,14 @@ One JSON line on stdout (rank 0): metric/value/unit... (the predict leg), plus
   "roofline"     -- dominant kernel, algorithmic FLOPs / HIP-event time over the launches of one pass, vs the fp32
                     MFMA peak of MI355X_MICROARCH.md (157.3 TFLOP/s);
   "cpu_baseline" -- the CPU oracle (oracle/robosat_ref.py, kind "port") timed on this box's host cores on a bounded
-                    sample of the same workload (N=1, rank 0 only).
+                    sample of the same workload (N=1, rank 0 only);
+and the full record (per-kernel tables, every step time) is written next to it (--full-json).
+
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller goes to DIR as float32 .npy
+files (rank 0): `probs.npy`, the softmax probabilities [B, classes, S, S] of a predict step (a fixed, seeded sample of
+them past 60 MB), or `loss.npy` of a train step.  The weights and inputs are seeded, so two builds run with
+the same arguments can be compared output for output.  (A train step's loss also depends on how many untimed settle
+steps ran before it.)
 """
 
 import argparse
@@ -88,10 +97,17 @@ def parse():
     ap.add_argument("--full-json", type=str, default="",
                     help="where the FULL record goes (per-kernel tables, every step time, counter provenance); default "
                          "gpurun_out/bench_full.json.  stdout carries the compact line (<= 4 KB) only")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: roofline passes, parity vs the CPU oracle, the train leg, the "
+                         "other BASELINE legs, mIoU, the CPU baseline and the full record (--layers-json / --full-json imply it)")
     ap.add_argument("--force-reducer", action="store_true",
                     help="train legs at ONE rank: run the data-parallel GradReducer anyway, over a world-size-1 RCCL group (the "
                          "backend == nccl branch, its stream ordering and the in-place AVG on arena views execute for real)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or bool(args.layers_json or args.full_json)
+    return args
 
 
 def build_model(classes, device, train=False, dtype="fp32", channels=3):
@@ -336,10 +352,11 @@ class Leg:
             phase, dtype, batch, size, classes, channels, loss, tag)
 
 
-def run_phase(leg, steps, warmup, device, dist, rank, no_parity=False, grad_dtype="fp32", force_reducer=False):
-    """Builds the model for `leg`, runs `warmup` untimed + `steps` timed steps bracketed by barrier + synchronize, and
-    returns (max-over-ranks seconds, per-step milliseconds of this rank from HIP events between the steps, the EAGER step
-    function, a callable producing rank 0's parity record, whether the timed steps were hipGraph replays)."""
+def run_phase(leg, steps, warmup, device, dist, rank, no_parity=False, grad_dtype="fp32", force_reducer=False, dump=""):
+    """Builds the model for `leg`, runs `warmup` untimed + `steps` timed steps bracketed by barrier + synchronize, writes the
+    last timed step's output to `dump` (rank 0, when given), and returns (max-over-ranks seconds, per-step milliseconds of
+    this rank from HIP events between the steps, the EAGER step function, a callable producing rank 0's parity record,
+    whether the timed steps were hipGraph replays)."""
 
     import torch.distributed as td
 
@@ -465,6 +482,8 @@ def run_phase(leg, steps, warmup, device, dist, rank, no_parity=False, grad_dtyp
         if gc_was_on:
             gc.enable()
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(steps)]
+    if dump and rank == 0:
+        dump_outputs(dump, {"loss" if train else "probs": last})
     if dist:
         t = torch.tensor([el], device=device, dtype=torch.float64)
         td.all_reduce(t, op=td.ReduceOp.MAX)
@@ -480,6 +499,26 @@ def run_phase(leg, steps, warmup, device, dist, rank, no_parity=False, grad_dtyp
 
     run_phase.peak_gb = round(torch.cuda.max_memory_allocated(device) / 2**30, 2)  # (read by the caller right after)
     return el, step_ms, step, parity, bool(train and graphed and stepper.captured)
+
+
+DUMP_LIMIT_BYTES = 60 * 10**6  # (data bytes of all files together; the .npy headers add 128 bytes each)
+
+
+def dump_outputs(out_dir, arrays):
+    """`arrays` (name -> tensor) as float32 `out_dir/<name>.npy`.  Past DUMP_LIMIT_BYTES in all, each array is replaced by
+    the same fixed, seeded sample of its flattened elements (sorted positions), in proportion to its size."""
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    host = {name: t.detach().float().cpu().numpy().reshape(-1 if t.dim() == 0 else t.shape) for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def reducer_record():
@@ -737,11 +776,11 @@ def main():
 
     main_leg = Leg(args.phase, args.dtype, per_rank(args.batch), args.size, args.classes, args.channels, args.loss)
     el, step_ms, step, parity, hipgraph = run_phase(main_leg, args.steps, args.warmup, device, dist, rank, args.no_parity, args.grad_dtype,
-                                                    args.force_reducer)
+                                                    args.force_reducer, dump=args.dump_outputs)
     line = None
     # every rank runs the two untimed roofline passes: a train step contains the gradient all-reduce, so rank 0 alone
     # would wait for its peers forever
-    roof, layers = roofline(step)
+    roof, layers = roofline(step) if args.full else (None, None)
     if rank == 0:
         if args.layers_json:
             with open(args.layers_json, "w") as fp:
@@ -762,8 +801,9 @@ def main():
             "flops_basis": "executed (the DecoderBlock phase form runs 4/9 of the section-8d algorithmic multiply-adds: conv3x3 over a "
                            "nearest-x2 upsample == four 2x2 convolutions on the source grid with pre-summed taps; its fp32 Winograd "
                            "F(2x2,2x2) form 1/4; the fp32 eval stride-1 3x3 layers as Winograd F(2x2,3x3) 4/9)",
-            "roofline": roof, "parity": parity(),
         }
+        if args.full:
+            line.update({"roofline": roof, "parity": parity()})
         if args.phase == "train" and reducer_record() is not None:
             line["reducer"] = reducer_record()
     del step  # (the cached blocks stay with the allocator: the next leg reuses them instead of a new round of hipFree / hipMalloc)
@@ -772,7 +812,7 @@ def main():
 
     # The metric is "train+predict": the headline `value` above is the predict leg (BASELINE configs[1]); the train leg
     # (configs[2]: bf16, bs 32 per GPU, fwd + Lovasz + bwd + RCCL gradient all-reduce + Adam) rides in the same line.
-    if args.phase == "predict" and not args.no_train_leg:
+    if args.full and args.phase == "predict" and not args.no_train_leg:
         tleg = Leg("train", "bf16", per_rank(args.train_batch), args.size, args.classes, args.channels, args.loss)
         ts, tw = max(1, args.train_steps), max(3, min(args.warmup, 5))
         tel, tstep_ms, tstep, tparity, tgraph = run_phase(tleg, ts, tw, device, dist, rank, args.no_parity, args.grad_dtype,
@@ -797,7 +837,7 @@ def main():
     # The other BASELINE configurations, timed the same way (barrier + synchronize, max over ranks) with short loops and no
     # roofline pass: configs[4] (4-band RGB+IR, 4 classes, Lovasz, bf16 bs 32), the reference's own arithmetic for training
     # (fp32, bs 8) and configs[3] (1024^2 tiles, bs 8, fp32 predict).
-    if args.phase == "predict" and not args.no_extra_legs and args.size == 512:
+    if args.full and args.phase == "predict" and not args.no_extra_legs and args.size == 512:
         # predict_fp32_bs32: the north_star words its MFMA target "on 3x3 conv at bs=32 512x512" -- the headline configuration at
         # that batch, with the 3x3 group's fraction of the fp32 MFMA peak (its own roofline pass: `conv3x3`)
         extra = [("predict_fp32_bs32", Leg("predict", "fp32", per_rank(32), 512, 2, 3, "Lovasz"), 10, 3),
@@ -822,7 +862,7 @@ def main():
             if EMPTY_CACHE_BETWEEN_LEGS:
                 torch.cuda.empty_cache()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_miou:
             line["miou"] = miou_vs_cpu_ref(device)
         if world == 1 and not args.no_cpu_baseline:
@@ -837,7 +877,7 @@ def main():
         td.destroy_process_group()
         ctypes.CDLL(None).fflush(None)  # anything RCCL still holds in C stdio goes out BEFORE the JSON line
     if rank == 0:
-        print(json.dumps(compact_line(line, write_full_record(line, args.full_json))), flush=True)
+        print(json.dumps(compact_line(line, write_full_record(line, args.full_json) if args.full else "")), flush=True)
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@
 TAG=$1; shift
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/$TAG; mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou"
 # A box whose GPU faults on the first transfer (seen once in round 4: "Memory access fault by GPU node" in every process,
 # rocprofv3 then sat in each of its 10-minute timeouts: 55 GPU-minutes gone) must cost seconds, not the visit: one tiny
 # device round trip first, and every later command under a timeout sized to its normal duration.
@@ -28,7 +28,7 @@ for STAGE in "$@"; do
   smoke)
     timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2 ;;
   bench)
-    timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --layers-json $OUT/layers_predict.json --full-json $OUT/bench_default_full.json > $OUT/bench_default.log 2>&1; echo "bench exit $?"
+    timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --layers-json $OUT/layers_predict.json --full-json $OUT/bench_default_full.json > $OUT/bench_default.log 2>&1; echo "bench exit $?"
     tail -1 $OUT/bench_default.log > $OUT/bench_default.json; python scripts/bench_brief.py $OUT/bench_default.json
     timeout 240 $B --phase train --dtype bf16 --batch 32 --steps 10 --warmup 3 --layers-json $OUT/layers_train.json --full-json $OUT/bench_train_full.json > $OUT/bench_train.log 2>&1; echo "train bench exit $?"
     tail -1 $OUT/bench_train.log > $OUT/bench_train_bf16_bs32.json; cut -c1-500 $OUT/bench_train_bf16_bs32.json ;;
@@ -36,7 +36,7 @@ for STAGE in "$@"; do
     # does a concurrent SMU poller (what the driver runs beside its bench: one sample every 5 s) move the train leg?  Same
     # command with a much denser poller (every 0.5 s) beside it; compare train.step_ms min / median / max with `bench`.
     ( while true; do rocm-smi --showuse --showmemuse --json > /dev/null 2>&1; sleep 0.5; done ) & SMI=$!
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-extra-legs --no-miou --no-cpu-baseline > $OUT/bench_with_smi.log 2>&1; echo "bench exit $?"
+    timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-extra-legs --no-miou --no-cpu-baseline > $OUT/bench_with_smi.log 2>&1; echo "bench exit $?"
     kill $SMI 2>/dev/null; wait $SMI 2>/dev/null
     tail -1 $OUT/bench_with_smi.log > $OUT/bench_with_smi.json; python scripts/bench_brief.py $OUT/bench_with_smi.json ;;
   trace)
@@ -80,7 +80,7 @@ for STAGE in "$@"; do
     timeout 1500 python -m pytest tests/test_gpu_tiles.py -m gpu -q -rP -k "halo" --timeout 600 > $OUT/pytest_halo.log 2>&1; echo "halo tests exit $?"; tail -15 $OUT/pytest_halo.log | cut -c1-300
     timeout 1200 python -m pytest tests/test_gpu_parallel.py -m gpu -q -rP -k "rccl or miou or weighted" --timeout 900 > $OUT/pytest_dp.log 2>&1; echo "dp tests exit $?"; tail -15 $OUT/pytest_dp.log | cut -c1-400 ;;
   rccl1)
-    # the RCCL branch of the reducer inside the timed train steps, one GPU (bench.py --force-reducer), fp32 and bf16 wire
+    # the RCCL branch of the reducer inside the timed train steps, one GPU (bench.py --full --force-reducer), fp32 and bf16 wire
     for W in fp32 bf16; do
       timeout 200 $B --phase train --dtype bf16 --batch 32 --steps 10 --warmup 3 --force-reducer --grad-dtype $W --no-parity --full-json $OUT/bench_rccl1_$W.json > $OUT/bench_rccl1_$W.log 2>&1; echo "exit $?"
       tail -1 $OUT/bench_rccl1_$W.log | cut -c1-600

@@ -4,7 +4,7 @@
 # process pinned to ONE core that a busy loop shares (the host thread gets ~half a core), each eager and as a hipGraph replay,
 # (c) the graph captured without the weight-gradient side stream.   bash scripts/host_sensitivity.sh OUTDIR
 OUT=$1; mkdir -p $OUT
-B="python bench.py --phase train --dtype bf16 --batch 32 --steps 30 --warmup 5 --no-parity --no-cpu-baseline"
+B="python bench.py --full --phase train --dtype bf16 --batch 32 --steps 30 --warmup 5 --no-parity --no-cpu-baseline"
 brief() { tail -1 $1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(sys.argv[1], d['ms_per_step'], 'ms/step', d['step_ms'], 'hipgraph', d.get('hipgraph'))" "$2"; }
 ROBOSAT_TRAIN_GRAPH=0 timeout 600 $B > $OUT/hs_eager.log 2>&1; brief $OUT/hs_eager.log "eager, free host:        "
 ROBOSAT_TRAIN_GRAPH=1 timeout 600 $B > $OUT/hs_graph.log 2>&1; brief $OUT/hs_graph.log "hipGraph, free host:     "

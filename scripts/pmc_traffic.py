@@ -138,7 +138,7 @@ if __name__ == "__main__":
         "profiled_csrc_digest": kernel_source_digest(),  # (what bench.py compares; written by this script only -- never edited by hand)
         "tag": sys.argv[3] if len(sys.argv) > 3 else None, "date": datetime.datetime.utcnow().strftime("%Y-%m-%dT%H:%MZ"),
         "commit": commit,  # None on the GPU box (the snapshot has no .git): filled in when the file is copied to profiles/
-        "command": "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE> -- python bench.py --no-cpu-baseline --no-parity "
+        "command": "rocprofv3 --kernel-trace --pmc <FETCH_SIZE | WRITE_SIZE> -- python bench.py --full --no-cpu-baseline --no-parity "
                    "--steps 1 --warmup 1 [--no-train-leg | --phase train --dtype bf16 --batch 32] (scripts/gpu_round.sh pmc)",
         "corrections": "KiB units; FETCH_SIZE doubled (gfx950 counts 128-byte requests as 64); WRITE_SIZE as reported"}
     with open(out, "w") as fp:

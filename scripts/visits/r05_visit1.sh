@@ -4,7 +4,7 @@
 # (e) LAST (first run of a kernel written without a GPU: a hang must not cost the rest) conv1x1_ew_bf16 parity + A/B.
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v1; mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou"
 if ! timeout 90 python -c "import torch; x = torch.arange(1 << 20, device='cuda:0', dtype=torch.float32); assert float((x * 2).sum().cpu()) == float((1 << 20) * ((1 << 20) - 1))" > $OUT/sanity.log 2>&1; then
   echo "=== GPU sanity check FAILED"; tail -3 $OUT/sanity.log; exit 3
 fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v20; mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 10 --warmup 3"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 10 --warmup 3"
 timeout 600 python -m pytest tests/test_gpu_bf16.py -m gpu -q --timeout 300 -k "wgrad" > $OUT/pytest.log 2>&1; echo "pytest exit $?"; tail -3 $OUT/pytest.log | cut -c1-300
 run() { env "$1" timeout 200 $B --full-json $OUT/full_$2.json 2>/dev/null | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$*', d['value'], d['ms_per_step'], d['step_ms']['median'], d['step_ms']['min'])"; }

@@ -3,7 +3,7 @@
 # VERDICT r4 asks to bring under 25 ms.
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v23; mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-parity"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-parity"
 if ! timeout 90 python -c "import torch; x = torch.arange(1 << 20, device='cuda:0', dtype=torch.float32); assert float((x * 2).sum().cpu()) == float((1 << 20) * ((1 << 20) - 1))" > $OUT/sanity.log 2>&1; then
   echo "=== GPU sanity check FAILED"; tail -3 $OUT/sanity.log; exit 3
 fi

@@ -7,7 +7,7 @@ if ! timeout 90 python -c "import torch; x = torch.arange(1 << 20, device='cuda:
   echo "=== GPU sanity check FAILED"; tail -3 $OUT/sanity.log; exit 3
 fi
 RS_WGRAD_RING=3 timeout 600 python -m pytest tests/test_gpu_bf16.py tests/test_gpu_train_ops.py -m gpu -q -x --timeout 300 -k "wgrad" > $OUT/pytest_ring3.log 2>&1; echo "pytest exit $?"; tail -3 $OUT/pytest_ring3.log | cut -c1-300
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 20 --warmup 3"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 20 --warmup 3"
 run() { env "$@" timeout 200 $B 2>$OUT/err.log | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$*', d['value'], d['ms_per_step'], d['step_ms']['median'], d['step_ms']['min'])"; }
 {
@@ -18,6 +18,6 @@ run RS_WGRAD_RING=3 RS_WGRAD_BLOCKS=256
 } | tee $OUT/ring_ab.txt
 # per-launch view: the serial roofline pass of one leg each
 for R in 2 3; do
-  RS_WGRAD_RING=$R timeout 200 python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 5 --warmup 2 --full-json $OUT/full_ring$R.json > /dev/null 2>&1
+  RS_WGRAD_RING=$R timeout 200 python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 5 --warmup 2 --full-json $OUT/full_ring$R.json > /dev/null 2>&1
 done
 echo "=== done ($(date +%T))"

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v27; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_bf16.py tests/test_gpu_train_ops.py tests/test_gpu_tiles.py -m gpu -q -x --timeout 600 > $OUT/pytest.log 2>&1; echo "pytest exit $?"; tail -3 $OUT/pytest.log | cut -c1-300
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 20 --warmup 3"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 20 --warmup 3"
 run() { env "$@" timeout 200 $B $EXTRA 2>$OUT/err.log | tail -1 | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$* $EXTRA', d['value'], d['ms_per_step'], d['step_ms']['median'], d['step_ms']['min'])"; }
 {

@@ -1,7 +1,7 @@
 #!/bin/bash
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v3; mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou"
 timeout 300 $B --no-parity --phase train --dtype fp32 --batch 8 --steps 5 --warmup 2 --layers-json $OUT/layers_train_fp32.json --full-json $OUT/train_fp32_full.json > $OUT/train_fp32.log 2>&1; echo "exit $?"; tail -1 $OUT/train_fp32.log | cut -c1-400
 timeout 300 $B --no-parity --phase train --dtype bf16 --batch 32 --steps 10 --warmup 3 --layers-json $OUT/layers_train_bf16.json --full-json $OUT/train_bf16_full.json > $OUT/train_bf16.log 2>&1; echo "exit $?"; tail -1 $OUT/train_bf16.log | cut -c1-400
 for CH in 3 4 3; do

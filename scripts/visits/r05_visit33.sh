@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v33; mkdir -p $OUT
 for i in 1 2; do
-  timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-miou --full-json $OUT/full$i.json > $OUT/bench$i.log 2>&1; echo "exit $?"
+  timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-miou --full-json $OUT/full$i.json > $OUT/bench$i.log 2>&1; echo "exit $?"
   python - $OUT/full$i.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

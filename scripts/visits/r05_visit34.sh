@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/v34; mkdir -p $OUT
 for RA in 0 2 0 2 0 2; do
-  ROBOSAT_BENCH_RUNAHEAD=$RA timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --train-steps 30 --no-cpu-baseline --no-miou --no-extra-legs --no-parity --full-json $OUT/full.json > $OUT/bench.log 2>&1
+  ROBOSAT_BENCH_RUNAHEAD=$RA timeout 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 --train-steps 30 --no-cpu-baseline --no-miou --no-extra-legs --no-parity --full-json $OUT/full.json > $OUT/bench.log 2>&1
   python - $OUT/full.json $RA <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1])); t = d["train"]

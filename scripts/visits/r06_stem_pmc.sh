@@ -2,7 +2,7 @@
 # counters of the fp32 predict pass (one step): MFMA busy / LDS / wait / bank conflicts per kernel -- the stem's row is the question
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/r6stempmc; mkdir -p $OUT
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-train-leg --no-parity --steps 1 --warmup 1"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-train-leg --no-parity --steps 1 --warmup 1"
 C1="SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE"
 cd /tmp
 timeout 200 rocprofv3 --kernel-trace --pmc $C1 --output-format csv -d $OUT/predict -o p -- $B > $OUT/pmc.log 2>&1; echo "exit $?"

@@ -5,7 +5,7 @@ OUT=gpurun_out/r6stem; mkdir -p $OUT
 timeout 600 python -m pytest tests/test_gpu_ops.py -x -q -m gpu -k "stem" > $OUT/tests_stem.log 2>&1; echo "stem tests exit $? $(tail -1 $OUT/tests_stem.log | cut -c1-150)"
 grep -E "Error|error|assert" $OUT/tests_stem.log | head -10
 echo skip-net-tests
-B="python bench.py --no-cpu-baseline --no-extra-legs --no-miou"
+B="python bench.py --full --no-cpu-baseline --no-extra-legs --no-miou"
 for i in 1 2; do
   timeout 300 $B --no-train-leg --steps 30 --warmup 5 --layers-json $OUT/layers_predict_$i.json > $OUT/predict_$i.log 2>&1
   echo "predict run $i: $(tail -1 $OUT/predict_$i.log | python -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"], d.get("step_ms"), d.get("parity"))')"

@@ -6,7 +6,7 @@ REPO=$(pwd); OUT=$REPO/gpurun_out/r6v5; mkdir -p $OUT
 timeout 900 python -m pytest tests/test_gpu_race_screen.py -m gpu -q -rP --timeout 600 > $OUT/race.log 2>&1; echo "race screen exit $? $(tail -1 $OUT/race.log | cut -c1-100)"; grep -E "positive control|INCONCLUSIVE" $OUT/race.log | head -3
 timeout 900 python -m pytest tests/test_gpu_bf16.py tests/test_gpu_train_step.py -m gpu -q --timeout 600 > $OUT/bf16.log 2>&1; echo "bf16 + train step exit $? $(tail -1 $OUT/bf16.log | cut -c1-100)"
 timeout 600 python scripts/flaky_graph_step.py 10 1 > $OUT/flaky_graph.log 2>&1; echo "flaky exit $?"; tail -3 $OUT/flaky_graph.log | cut -c1-300
-B="python $REPO/bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 30 --warmup 3"
+B="python $REPO/bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-parity --phase train --dtype bf16 --batch 32 --steps 30 --warmup 3"
 for i in 1 2 3; do
   for S in "X=default" "RS_WGRAD_RING=2 RS_WGRAD_PHASE4=0 RS_WGRAD_BLOCKS=192"; do
     env $S timeout 200 $B --full-json $OUT/ab.json > $OUT/ab.log 2>&1

@@ -6,7 +6,7 @@
 OUT=gpurun_out/${1:-wpc}; mkdir -p $OUT
 timeout 60 python -c "import torch; x = torch.arange(1 << 20, device='cuda:0', dtype=torch.float32); assert float((x * 2).sum().cpu()) == float((1 << 20) * ((1 << 20) - 1))" || { echo "GPU sanity failed"; exit 3; }
 RS_WINO33_VAR=4 timeout 400 python -m pytest tests/test_gpu_tiles.py -m gpu -q -k "winograd_3x3" --timeout 300 > $OUT/pytest.log 2>&1; echo "pytest (variant on) exit $?"; tail -4 $OUT/pytest.log | cut -c1-300
-B="python bench.py --no-cpu-baseline --no-extra-legs --no-miou --no-train-leg --steps 20 --warmup 5"
+B="python bench.py --full --no-cpu-baseline --no-extra-legs --no-miou --no-train-leg --steps 20 --warmup 5"
 run() {  # tag, env...
   local T=$1; shift
   env "$@" timeout 200 $B $NP --layers-json $OUT/layers_$T.json --full-json $OUT/full_$T.json > $OUT/bench_$T.log 2>&1; echo "bench $T exit $?"

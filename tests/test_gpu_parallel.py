@@ -148,7 +148,7 @@ def test_bench_gpus_flag_starts_that_many_ranks(tmp_path):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1",
-                        "--size", "128", "--train-batch", "2", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True,
+                        "--size", "128", "--train-batch", "2", "--no-cpu-baseline", "--full"], env=env, cwd=ROOT, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -565,7 +565,7 @@ def test_bench_symbols_are_covered(tmp_path):
         env.pop(k, None)
     full = str(tmp_path / "bench_full.json")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--train-steps", "2",
-                        "--no-miou", "--full-json", full],
+                        "--no-miou", "--full", "--full-json", full],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     # stdout: the compact line (what the driver's 8 KB tail must hold whole) -- the train leg's numbers included

@@ -1,6 +1,6 @@
 """Pins the CPU oracle (oracle/robosat_ref.py): (1) against the committed golden vectors, which were produced by
-the UNMODIFIED reference (tests/golden/make_golden.py); (2) against the live reference wherever /root/reference
-exists (dev container).  CPU only."""
+the UNMODIFIED reference (tests/golden/make_golden.py); (2) against the reference's own U-Net and Lovasz loss on the
+seeded weights of the restatement check (tests/golden/make_golden_feeders.py).  CPU only."""
 
 import os
 
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import refshim, robosat_ref as R, seeded
+from oracle import robosat_ref as R, seeded
 
 
 def _oracle_net(num_classes, seed):
@@ -65,22 +65,19 @@ def test_quantize_quirk():
     assert q.tolist() == [1, 128, 255, 0]  # p == 1.0 wraps to bin 0 (reference quirk, predict.py:102-103)
 
 
-@pytest.mark.skipif(not refshim.available(), reason="reference tree only exists in the dev container")
-def test_restatement_equals_live_reference():
-    ref = refshim.load_reference()
-    theirs = ref.unet.UNet(2, pretrained=False)
+def test_restatement_equals_live_reference(golden_dir):
+    """The reference's own U-Net (robosat.unet.UNet, run by tests/golden/make_golden_feeders.py) on seeded weights and
+    input, in eval and train mode, and its LovaszLoss2d on the train-mode output: tests/golden/restatement.npz."""
+    with np.load(os.path.join(golden_dir, "restatement.npz")) as z:
+        ref = {k: z[k] for k in z.files}
     ours = R.UNetRef(2)
-    assert list(theirs.state_dict().keys()) == list(ours.state_dict().keys())
-    sd = seeded.seeded_state_dict(theirs.state_dict(), 7)
-    theirs.load_state_dict(sd)
-    ours.load_state_dict(sd)
+    assert list(ref["keys"]) == list(ours.state_dict().keys())
+    ours.load_state_dict(seeded.seeded_state_dict(ours.state_dict(), 7))
     x = seeded.synthetic_images(1, 3, 64, 64, 7)
     t = seeded.synthetic_targets(1, 2, 64, 64, 7)
     for mode in ("eval", "train"):
-        getattr(theirs, mode)()
         getattr(ours, mode)()
-        a, b = theirs(x), ours(x)
-        assert torch.equal(a, b)
-    la = ref.losses.LovaszLoss2d()(a, t)
+        b = ours(x)
+        assert torch.equal(torch.from_numpy(ref[mode]), b)
     lb = R.lovasz2d(b, t)
-    assert abs(la.item() - lb.item()) <= 1e-6
+    assert abs(float(ref["lovasz"]) - lb.item()) <= 1e-6
