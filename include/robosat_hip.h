@@ -194,6 +194,21 @@ int rs_lovasz_fwd(const float* logits, const long long* targets, float* loss, fl
                   void* workspace, rs_stream_t stream);
 int rs_scale_by_scalar(const float* src, const float* scalar, float* dst, long n, rs_stream_t stream);
 
+/* Lovasz-Softmax (Berman et al. 2018, arXiv 1705.08790), the multi-class loss of the paper.  logits [N,C,H,W] fp32 (C >= 2),
+ * targets [N,H,W] int64 in [0, C).  p = softmax(logits) over C; per segment s -- (image n, class c) when per_image, class c
+ * over the whole batch otherwise -- the errors e_i = |1[y_i = c] - p_{c,i}| (fp32) are sorted descending, EQUAL ERRORS IN
+ * ASCENDING PIXEL INDEX (n, h, w): this tie order makes the gradient a defined function of the input.  With g = sum 1[y = c]
+ * and k_r the labels among the first r + 1: I_r = g - k_r, U_r = g + r + 1 - k_r, delta_0 = 1 / U_0,
+ * delta_r = (I_{r-1} U_r - I_r U_{r-1}) / (U_r U_{r-1}) (integer numerator), L_s = sum_r e_{pi(r)} delta_r (fp64).
+ * loss[0] = mean_n mean_{c in P_n} L_{n,c} (per_image) or mean_{c in P} L_c, P = the classes with g > 0 or, with
+ * all_classes, every class.  grad_unit (optional, NCHW) = d loss / d logits for grad_out = 1 (autograd of this definition
+ * through the softmax; multiply with rs_scale_by_scalar); probs_out (optional, NCHW) receives the fp32 p the keys were made
+ * from.  Deterministic (no float atomics): bit-identical run to run.  RS_EINVAL for C < 2, a non-positive size,
+ * N*C*H*W >= 2^31 or more than 65535 segments. */
+long rs_lovasz_softmax_workspace_bytes(int N, int C, int H, int W, int per_image);
+int rs_lovasz_softmax_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out, int N,
+                          int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream);
+
 /* Metrics.add over a whole batch (metrics.py:27-41): counts[0..3] += (tn, fn, fp, tp) in the reference's naming. */
 int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C, int H,
                         int W, rs_stream_t stream);

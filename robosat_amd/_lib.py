@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROBOSAT_HIP_LIB") or os.path.join(_HERE, "librobosat_hip.so")
 
 RS_EINVAL = -22
-ABI_VERSION = 21
+ABI_VERSION = 22
 RS_F32, RS_BF16 = 0, 1
 
 
@@ -66,6 +66,8 @@ SIGNATURES = {
     "rs_lovasz_workspace_bytes": (c_long, [c_int, c_int, c_int, c_int]),
     "rs_lovasz_fwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
     "rs_scale_by_scalar": (c_int, [P, P, P, c_long, P]),
+    "rs_lovasz_softmax_workspace_bytes": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    "rs_lovasz_softmax_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rs_confusion_counts": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     # bf16 path (activations typed by a dtype code / bf16 entry points)
     "rs_conv2d_fwd_bf16": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),

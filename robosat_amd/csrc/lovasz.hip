@@ -18,6 +18,9 @@
 // stores sprayed over 256 buckets (which cost the first version 0.39 ms per pass against a 0.07 ms traffic bound).
 // The rest is a segmented prefix sum (block sums -> scan -> apply) fused with the Jaccard deltas, the dot product
 // (fp64 partials) and the gradient scatter.  HBM-bound integer/byte work throughout.
+//
+// The same sort and scans also carry the multi-class Lovasz-Softmax loss (rs_lovasz_softmax_fwd, further down): the sort then
+// runs over N*C (or C) segments of one class's errors instead of N segments of C*H*W hinge errors.
 #include "common.h"
 
 namespace {
@@ -151,6 +154,35 @@ __global__ __launch_bounds__(1024) void radix_scan_kernel(uint32_t* __restrict__
   for (int b = b0; b < b1; ++b) {
     const uint32_t t = c[(long)b * 256 + d];
     c[(long)b * 256 + d] = run;
+    run += t;
+  }
+}
+
+// The same scan for FEW long segments (the flattened Lovasz-Softmax: C segments of N*H*W keys, thousands of sort tiles each),
+// where one 1024-thread block per segment walks its tiles' counts in a chain of dependent loads (143 us a pass at 2 x 2048
+// tiles).  In three launches instead: per chunk of kScanTiles tiles, the digit sums (thread d = digit d: coalesced rows);
+// radix_scan_kernel over those chunk sums (= each chunk's first offsets); per chunk, the tiles' offsets from there.
+constexpr int kScanTiles = 64;
+
+__global__ __launch_bounds__(256) void radix_chunk_sum_kernel(const uint32_t* __restrict__ counts, uint32_t* __restrict__ csum,
+                                                              int nblk, int nchunk) {
+  const long n = blockIdx.y;
+  const int b0 = blockIdx.x * kScanTiles, b1 = (b0 + kScanTiles) < nblk ? (b0 + kScanTiles) : nblk;
+  const uint32_t* c = counts + n * nblk * 256 + threadIdx.x;
+  uint32_t s = 0;
+  for (int b = b0; b < b1; ++b) s += c[(long)b * 256];
+  csum[(n * nchunk + blockIdx.x) * 256 + threadIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void radix_chunk_offsets_kernel(uint32_t* __restrict__ counts, const uint32_t* __restrict__ coff,
+                                                                  int nblk, int nchunk) {
+  const long n = blockIdx.y;
+  const int b0 = blockIdx.x * kScanTiles, b1 = (b0 + kScanTiles) < nblk ? (b0 + kScanTiles) : nblk;
+  uint32_t* c = counts + n * nblk * 256 + threadIdx.x;
+  uint32_t run = coff[(n * nchunk + blockIdx.x) * 256 + threadIdx.x];
+  for (int b = b0; b < b1; ++b) {
+    const uint32_t t = c[(long)b * 256];
+    c[(long)b * 256] = run;
     run += t;
   }
 }
@@ -429,28 +461,284 @@ __global__ void scale_by_scalar_kernel(const float* __restrict__ src, const floa
   if (i < n) dst[i] = src[i] * scalar[0];
 }
 
+// ---- Lovasz-Softmax (Berman et al. 2018, arXiv 1705.08790): the multi-class loss of the paper --------------------------
+// p = softmax(x) over the classes.  Segment s = (image n, class c) per image (S = N*C segments of HW keys, position hw) or
+// class c over the batch (S = C segments of N*HW keys, position n*HW + hw).  Keys = desc_key(e), e = |1[y=c] - p_c| in fp32
+// (in [0, 1]), payload = position | m << 31.  The stable sort puts equal errors in ascending position = ascending (n, h, w).
+// Per segment: g = sum m, k_r = labels among ranks 0..r, I_r = g - k_r, U_r = g + r + 1 - k_r,
+//     delta_0 = 1 / U_0 ,  delta_r = (I_{r-1} U_r - I_r U_{r-1}) / (U_r U_{r-1})   (exact int64 numerator, one division)
+//     L_s = sum_r e_{pi(r)} delta_r   (fp64),   loss = sum_s w_s L_s
+// with w_s = [c in P] / (groups * |P|) over the group's classes P (present: g > 0, or all), groups = N per image or 1.
+// dL/dp_{c,i} = w_s (m_i ? -delta : +delta) at rank(i), then dL/dx_c = p_c (G_c - sum_k p_k G_k) per pixel.
+
+template <int VEC>
+__device__ __forceinline__ void lvs_load(const float* xp, float* v) {
+  if constexpr (VEC == 4) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(xp);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = t[e];
+  } else {
+    v[0] = xp[0];
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void lvs_write(float* p, const float* v) {
+  if constexpr (VEC == 4) *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
+  else p[0] = v[0];
+}
+
+// max and 1 / (sum of exp) over the C logits of VEC consecutive pixels (xp: class 0 of the first); the softmax is lvs_prob
+template <int VEC>
+__device__ __forceinline__ void lvs_softmax_stats(const float* xp, long HW, int C, float* mx, float* sum /* -> 1 / sum */) {
+  float v[VEC];
+  lvs_load<VEC>(xp, mx);
+  for (int c = 1; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) mx[e] = fmaxf(mx[e], v[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) sum[e] = 0.f;
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) sum[e] += expf(v[e] - mx[e]);
+  }
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) sum[e] = 1.f / sum[e];  // (one division per pixel, not per class)
+}
+
+// (the keys and the Jacobian kernels both take p from here: the same fp32 value in both)
+__device__ __forceinline__ float lvs_prob(float x, float mx, float inv_sum) { return expf(x - mx) * inv_sum; }
+
+// offset of (class c, pixel q = n*HW + hw) in the segment-major key arrays; the position inside the segment is hw or q
+__device__ __forceinline__ long lvs_seg_off(long q, long n, long hw, int c, int C, long NHW, long HW, int per_image) {
+  return per_image ? ((n * C + c) * HW + hw) : ((long)c * NHW + q);
+}
+
+// one thread per VEC consecutive pixels of one image (VEC = 4 needs HW % 4 == 0): C keys + C payloads each (probs: NCHW p)
+template <int VEC>
+__global__ __launch_bounds__(256) void lovasz_softmax_keys_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                                  float* __restrict__ probs, long NHW, long HW, int C, int per_image) {
+  // the key must be fp32(1 - p) of the very p this kernel writes out: no fusing of 1 - e * inv_sum into one fma
+#pragma clang fp contract(off)
+  const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (q >= NHW) return;
+  const long n = q / HW, hw = q - n * HW;
+  const float* xp = x + n * C * HW + hw;
+  float mx[VEC], sum[VEC], v[VEC], pr[VEC];
+  lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
+  long long t[VEC];
+  if constexpr (VEC == 4) {
+    const lv_i64x2 t0 = *reinterpret_cast<const lv_i64x2*>(tgt + q), t1 = *reinterpret_cast<const lv_i64x2*>(tgt + q + 2);
+    t[0] = t0[0]; t[1] = t0[1]; t[2] = t1[0]; t[3] = t1[1];
+  } else {
+    t[0] = tgt[q];
+  }
+  const uint32_t pos = (uint32_t)(per_image ? hw : q);
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+    uint32_t k[VEC], w[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      pr[e] = lvs_prob(v[e], mx[e], sum[e]);
+      const uint32_t m = (t[e] == c) ? 1u : 0u;
+      k[e] = desc_key(m ? 1.f - pr[e] : pr[e]);
+      w[e] = (pos + (uint32_t)e) | (m << 31);
+    }
+    const long o = lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image);
+    if constexpr (VEC == 4) {
+      *reinterpret_cast<lv_u32x4*>(keys + o) = lv_u32x4{k[0], k[1], k[2], k[3]};
+      *reinterpret_cast<lv_u32x4*>(vals + o) = lv_u32x4{w[0], w[1], w[2], w[3]};
+    } else {
+      keys[o] = k[0];
+      vals[o] = w[0];
+    }
+    if (probs) lvs_write<VEC>(probs + (n * C + c) * HW + hw, pr);
+  }
+}
+
+// lovasz_scan_blocks_kernel that also keeps each segment's total: gts[s] = g (foreground count of the segment)
+__global__ __launch_bounds__(256) void lovasz_softmax_scan_blocks_kernel(uint32_t* __restrict__ bsum, uint32_t* __restrict__ gts,
+                                                                         int nblk) {
+  __shared__ uint32_t sm[4];
+  uint32_t* a = bsum + (long)blockIdx.x * nblk;
+  const int per = (nblk + 255) / 256;
+  const int i0 = threadIdx.x * per;
+  uint32_t s = 0;
+  for (int k = 0; k < per; ++k)
+    if (i0 + k < nblk) s += a[i0 + k];
+  uint32_t total;
+  uint32_t run = block_exclusive_scan_256(s, sm, &total);
+  for (int k = 0; k < per; ++k)
+    if (i0 + k < nblk) {
+      const uint32_t t = a[i0 + k];
+      a[i0 + k] = run;
+      run += t;
+    }
+  if (threadIdx.x == 0) gts[blockIdx.x] = total;
+}
+
+// w[group * C + c] = [c in P] / (groups * |P|): one thread per group (an image, or the whole batch)
+__global__ __launch_bounds__(256) void lovasz_softmax_weights_kernel(const uint32_t* __restrict__ gts, double* __restrict__ w,
+                                                                     int groups, int C, int all_classes) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= groups) return;
+  int cnt = 0;
+  for (int c = 0; c < C; ++c) cnt += (all_classes || gts[(long)n * C + c] > 0) ? 1 : 0;
+  // (cnt >= 1 whenever the group has a pixel: every pixel's class is present)
+  const double inv = cnt > 0 ? 1.0 / ((double)groups * (double)cnt) : 0.0;
+  for (int c = 0; c < C; ++c) w[(long)n * C + c] = (all_classes || gts[(long)n * C + c] > 0) ? inv : 0.0;
+}
+
+// closed-form deltas, weighted fp64 loss partials and the scatter of the weighted dL/dp (segment-major, like the keys)
+__global__ __launch_bounds__(256) void lovasz_softmax_apply_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                                   const uint32_t* __restrict__ boff, const uint32_t* __restrict__ gts,
+                                                                   const double* __restrict__ w, double* __restrict__ partial,
+                                                                   float* __restrict__ gp, long P, int nblk, int xcd_affine) {
+  __shared__ uint32_t sm[4];
+  __shared__ double red[4];
+  long n = blockIdx.y;  // the segment
+  int bx = blockIdx.x;
+  if (xcd_affine) {  // all blocks of a segment on one XCD, as in lovasz_apply_kernel (segment count % 8 == 0)
+    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    const long k = L >> 3;
+    n = (L & 7) + 8 * (k / nblk);
+    bx = (int)(k % nblk);
+  }
+  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
+  uint32_t lab[4], key[4], idx[4];
+  uint32_t s = 0;
+  if ((P & 3) == 0 && r0 + 3 < P) {
+    const lv_u32x4 v = *reinterpret_cast<const lv_u32x4*>(vals + n * P + r0), k = *reinterpret_cast<const lv_u32x4*>(keys + n * P + r0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lab[e] = v[e] >> 31;
+      idx[e] = v[e] & 0x7fffffffu;
+      key[e] = k[e];
+      s += lab[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lab[e] = 0;
+      key[e] = 0;
+      idx[e] = 0;
+      if (r0 + e < P) {
+        const uint32_t v = vals[n * P + r0 + e];
+        lab[e] = v >> 31;
+        idx[e] = v & 0x7fffffffu;
+        key[e] = keys[n * P + r0 + e];
+      }
+      s += lab[e];
+    }
+  }
+  uint32_t total;
+  long long k = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
+  const long long g = gts[n];
+  const double ws = w[n];
+  double acc = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long r = r0 + e;
+    if (r < P) {
+      const long long Ip = g - k, Up = g + r - k;  // I_{r-1}, U_{r-1}
+      k += lab[e];
+      const long long I = g - k, U = g + r + 1 - k;
+      // U_r >= 1 always (U_r - I_r = r + 1); at r = 0, U_{-1} = g may be 0 and delta_0 = J_0 = 1 / U_0
+      const double delta = r == 0 ? 1.0 / (double)U : (double)(Ip * U - I * Up) / (double)(U * Up);
+      acc += (double)key_to_float(key[e]) * delta;
+      if (gp) gp[n * P + idx[e]] = (float)(ws * (lab[e] ? -delta : delta));
+    }
+  }
+  acc = rs_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[n * nblk + bx] = ws * ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// per VEC pixels: grad[n, c] = p_c (G_c - sum_k p_k G_k) with G the weighted dL/dp (segment-major), in fp64
+template <int VEC>
+__global__ __launch_bounds__(256) void lovasz_softmax_jacobian_kernel(const float* __restrict__ x, const float* __restrict__ gp,
+                                                                      float* __restrict__ grad, long NHW, long HW, int C, int per_image) {
+  const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (q >= NHW) return;
+  const long n = q / HW, hw = q - n * HW;
+  const float* xp = x + n * C * HW + hw;
+  float mx[VEC], sum[VEC], v[VEC], gv[VEC], out[VEC];
+  lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
+  double dot[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) dot[e] = 0.0;
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+    lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) dot[e] += (double)lvs_prob(v[e], mx[e], sum[e]) * (double)gv[e];
+  }
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+    lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) out[e] = (float)((double)lvs_prob(v[e], mx[e], sum[e]) * ((double)gv[e] - dot[e]));
+    lvs_write<VEC>(grad + (n * C + c) * HW + hw, out);
+  }
+}
+
 struct Carve {
   long P;
   int nblk_sort, nblk_scan;
   size_t keys0, vals0, keys1, vals1, counts, bsum, partial, total;
 };
 
-Carve carve(int N, int C, int H, int W) {
+// S segments of P keys each, sorted and scanned independently (blockIdx.y = segment in every kernel above)
+Carve carve_segments(long S, long P) {
   Carve c;
-  c.P = (long)C * H * W;
-  c.nblk_sort = rs_cdiv(c.P, sort_chunk((long)N * c.P));
+  c.P = P;
+  c.nblk_sort = rs_cdiv(c.P, sort_chunk(S * c.P));
   c.nblk_scan = rs_cdiv(c.P, kScanChunk);
-  const size_t arr = ((size_t)N * c.P * sizeof(uint32_t) + 255) & ~(size_t)255;
+  const size_t arr = ((size_t)S * c.P * sizeof(uint32_t) + 255) & ~(size_t)255;
   size_t o = 0;
   c.keys0 = o; o += arr;
   c.vals0 = o; o += arr;
   c.keys1 = o; o += arr;
   c.vals1 = o; o += arr;
-  c.counts = o; o += (((size_t)N * c.nblk_sort * 256 * sizeof(uint32_t)) + 255) & ~(size_t)255;
-  c.bsum = o; o += (((size_t)N * c.nblk_scan * sizeof(uint32_t)) + 255) & ~(size_t)255;
-  c.partial = o; o += (((size_t)N * c.nblk_scan * sizeof(double)) + 255) & ~(size_t)255;
+  c.counts = o; o += (((size_t)S * c.nblk_sort * 256 * sizeof(uint32_t)) + 255) & ~(size_t)255;
+  c.bsum = o; o += (((size_t)S * c.nblk_scan * sizeof(uint32_t)) + 255) & ~(size_t)255;
+  c.partial = o; o += (((size_t)S * c.nblk_scan * sizeof(double)) + 255) & ~(size_t)255;
   c.total = o;
   return c;
+}
+
+Carve carve(int N, int C, int H, int W) { return carve_segments(N, (long)C * H * W); }
+
+// Stable LSD radix sort of S segments of cv.P keys each: (k0, v0) -> 4 passes x 8 bits through (k1, v1) -> sorted in (k0, v0).
+// sc_affine: the scatter keeps a segment's tiles on one XCD (needs S % 8 == 0).  csum (nullable): scratch of
+// S * cdiv(nblk_sort, kScanTiles) * 256 words for the chunked digit scan of few long segments; null = one block per segment.
+void radix_sort_segments(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* counts, long S, const Carve& cv,
+                         int sc_affine, hipStream_t s, uint32_t* csum = nullptr) {
+  const int nchunk = rs_cdiv(cv.nblk_sort, kScanTiles);
+  const long P = cv.P;
+  const bool small_chunk = sort_chunk(S * P) == 4096;
+  for (int pass = 0; pass < 4; ++pass) {
+    const uint32_t* ik = (pass & 1) ? k1 : k0;
+    const uint32_t* iv = (pass & 1) ? v1 : v0;
+    uint32_t* ok = (pass & 1) ? k0 : k1;
+    uint32_t* ov = (pass & 1) ? v0 : v1;
+    if (small_chunk) radix_hist_kernel<4096><<<dim3(cv.nblk_sort, S), 256, 0, s>>>(ik, counts, P, cv.nblk_sort, pass * 8);
+    else radix_hist_kernel<8192><<<dim3(cv.nblk_sort, S), 256, 0, s>>>(ik, counts, P, cv.nblk_sort, pass * 8);
+    if (csum) {
+      radix_chunk_sum_kernel<<<dim3(nchunk, S), 256, 0, s>>>(counts, csum, cv.nblk_sort, nchunk);
+      radix_scan_kernel<<<S, 1024, 0, s>>>(csum, nchunk);
+      radix_chunk_offsets_kernel<<<dim3(nchunk, S), 256, 0, s>>>(counts, csum, cv.nblk_sort, nchunk);
+    } else {
+      radix_scan_kernel<<<S, 1024, 0, s>>>(counts, cv.nblk_sort);
+    }
+    if (small_chunk) radix_scatter_kernel<4096><<<dim3(cv.nblk_sort, S), 256, 0, s>>>(ik, iv, ok, ov, counts, P, cv.nblk_sort, pass * 8, sc_affine);
+    else radix_scatter_kernel<8192><<<dim3(cv.nblk_sort, S), 256, 0, s>>>(ik, iv, ok, ov, counts, P, cv.nblk_sort, pass * 8, sc_affine);
+  }
 }
 
 }  // namespace
@@ -475,24 +763,13 @@ extern "C" int rs_lovasz_fwd(const float* logits, const long long* targets, floa
   double* partial = reinterpret_cast<double*>(ws + cv.partial);
   hipStream_t s = (hipStream_t)stream;
   const long P = cv.P, HW = (long)H * W;
-  const bool small_chunk = sort_chunk((long)N * P) == 4096;
   // the sort's scatter passes keep an image's tiles on one XCD too (its digit runs of 64-128 bytes then meet their neighbours'
   // in one L2): -5 % on a bs-32 sort, -3.5 % with four classes, +3 % at 8 images (one image per XCD: no slack) -> from 16 images
   const int sc_affine = (N % 8 == 0 && N >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
 
   if ((HW & 3) == 0) lovasz_keys4_kernel<<<dim3(rs_cdiv(P / 4, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW);
   else lovasz_keys_kernel<<<dim3(rs_cdiv(P, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW);
-  for (int pass = 0; pass < 4; ++pass) {
-    const uint32_t* ik = (pass & 1) ? k1 : k0;
-    const uint32_t* iv = (pass & 1) ? v1 : v0;
-    uint32_t* ok = (pass & 1) ? k0 : k1;
-    uint32_t* ov = (pass & 1) ? v0 : v1;
-    if (small_chunk) radix_hist_kernel<4096><<<dim3(cv.nblk_sort, N), 256, 0, s>>>(ik, counts, P, cv.nblk_sort, pass * 8);
-    else radix_hist_kernel<8192><<<dim3(cv.nblk_sort, N), 256, 0, s>>>(ik, counts, P, cv.nblk_sort, pass * 8);
-    radix_scan_kernel<<<N, 1024, 0, s>>>(counts, cv.nblk_sort);
-    if (small_chunk) radix_scatter_kernel<4096><<<dim3(cv.nblk_sort, N), 256, 0, s>>>(ik, iv, ok, ov, counts, P, cv.nblk_sort, pass * 8, sc_affine);
-    else radix_scatter_kernel<8192><<<dim3(cv.nblk_sort, N), 256, 0, s>>>(ik, iv, ok, ov, counts, P, cv.nblk_sort, pass * 8, sc_affine);
-  }
+  radix_sort_segments(k0, v0, k1, v1, counts, N, cv, sc_affine, s);
   // after 4 passes the sorted data is back in (k0, v0)
   lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(v0, bsum, P, cv.nblk_scan);
   lovasz_scan_blocks_kernel<<<N, 256, 0, s>>>(bsum, cv.nblk_scan);
@@ -506,5 +783,84 @@ extern "C" int rs_lovasz_fwd(const float* logits, const long long* targets, floa
 extern "C" int rs_scale_by_scalar(const float* src, const float* scalar, float* dst, long n, rs_stream_t stream) {
   if (!src || !scalar || !dst || n <= 0) return RS_EINVAL;
   scale_by_scalar_kernel<<<rs_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(src, scalar, dst, n);
+  return RS_LAUNCH_RESULT();
+}
+
+namespace {
+
+// the Lovasz-Softmax workspace: the sort / scan carve of its S segments, then g (uint32) and w (fp64) per segment
+struct SoftmaxCarve {
+  long S;
+  Carve cv;
+  size_t gts, w, csum, total;
+  bool chunked_scan;
+};
+
+bool lovasz_softmax_shape_ok(int N, int C, int H, int W, int per_image) {
+  if (N <= 0 || C < 2 || H <= 0 || W <= 0 || (long)N * C * H * W >= (1L << 31)) return false;
+  return (per_image ? (long)N * C : (long)C) <= 65535;  // (segments = blockIdx.y of the sort kernels)
+}
+
+SoftmaxCarve carve_softmax(int N, int C, int H, int W, int per_image) {
+  SoftmaxCarve c;
+  const long HW = (long)H * W;
+  c.S = per_image ? (long)N * C : (long)C;
+  c.cv = carve_segments(c.S, per_image ? HW : (long)N * HW);
+  size_t o = c.cv.total;
+  c.gts = o; o += ((size_t)c.S * sizeof(uint32_t) + 255) & ~(size_t)255;
+  c.w = o; o += ((size_t)c.S * sizeof(double) + 255) & ~(size_t)255;
+  // more than 256 sort tiles per segment (each of radix_scan_kernel's four thread groups would walk over 64): chunked scan
+  c.chunked_scan = c.cv.nblk_sort > 4 * kScanTiles;
+  c.csum = o;
+  if (c.chunked_scan) o += ((size_t)c.S * rs_cdiv(c.cv.nblk_sort, kScanTiles) * 256 * sizeof(uint32_t) + 255) & ~(size_t)255;
+  c.total = o;
+  return c;
+}
+
+}  // namespace
+
+extern "C" long rs_lovasz_softmax_workspace_bytes(int N, int C, int H, int W, int per_image) {
+  if (!lovasz_softmax_shape_ok(N, C, H, W, per_image)) return RS_EINVAL;
+  return (long)carve_softmax(N, C, H, W, per_image).total;
+}
+
+extern "C" int rs_lovasz_softmax_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out,
+                                     int N, int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream) {
+  if (!logits || !targets || !loss || !workspace || !lovasz_softmax_shape_ok(N, C, H, W, per_image)) return RS_EINVAL;
+  const SoftmaxCarve sc = carve_softmax(N, C, H, W, per_image);
+  const Carve& cv = sc.cv;
+  char* ws = reinterpret_cast<char*>(workspace);
+  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
+  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
+  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
+  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
+  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
+  double* partial = reinterpret_cast<double*>(ws + cv.partial);
+  uint32_t* gts = reinterpret_cast<uint32_t*>(ws + sc.gts);
+  double* w = reinterpret_cast<double*>(ws + sc.w);
+  hipStream_t s = (hipStream_t)stream;
+  const long S = sc.S, HW = (long)H * W, NHW = (long)N * HW;
+  const int pi = per_image ? 1 : 0;
+  const int sc_affine = (S % 8 == 0 && S >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;  // (the rule of rs_lovasz_fwd, per segment)
+
+  if ((HW & 3) == 0)
+    lovasz_softmax_keys_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi);
+  else lovasz_softmax_keys_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi);
+  radix_sort_segments(k0, v0, k1, v1, counts, S, cv, sc_affine, s, sc.chunked_scan ? reinterpret_cast<uint32_t*>(ws + sc.csum) : nullptr);
+  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(v0, bsum, cv.P, cv.nblk_scan);
+  lovasz_softmax_scan_blocks_kernel<<<S, 256, 0, s>>>(bsum, gts, cv.nblk_scan);
+  const int groups = per_image ? N : 1;
+  lovasz_softmax_weights_kernel<<<rs_cdiv(groups, 256), 256, 0, s>>>(gts, w, groups, C, all_classes ? 1 : 0);
+  // the sort is done with (k1, v1): k1 holds the weighted dL/dp, segment-major
+  float* gp = grad_unit ? reinterpret_cast<float*>(k1) : nullptr;
+  const int xcd_affine = (S % 8 == 0 && cv.P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;  // (rs_lovasz_fwd's rule)
+  lovasz_softmax_apply_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(k0, v0, bsum, gts, w, partial, gp, cv.P, cv.nblk_scan, xcd_affine);
+  if (grad_unit) {
+    if ((HW & 3) == 0)
+      lovasz_softmax_jacobian_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, gp, grad_unit, NHW, HW, C, pi);
+    else lovasz_softmax_jacobian_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, gp, grad_unit, NHW, HW, C, pi);
+  }
+  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, S * cv.nblk_scan, 1.f, loss);
   return RS_LAUNCH_RESULT();
 }

@@ -1,6 +1,7 @@
 """Losses of the reference (``robosat/losses.py``) on the MI355X: same class names, constructor arguments and
 ``forward(inputs[N,C,H,W] float32, targets[N,H,W] int64) -> 0-dim tensor`` contract (tools/train.py:97-106,185), with
-the arithmetic in ``librobosat_hip.so`` (``rs_nll_loss_*``, ``rs_lovasz_fwd``).  No CPU path."""
+the arithmetic in ``librobosat_hip.so`` (``rs_nll_loss_*``, ``rs_lovasz_fwd``), and one loss the reference does not have:
+``LovaszSoftmax2d`` (``rs_lovasz_softmax_fwd``).  No CPU path."""
 
 import torch
 import torch.nn as nn
@@ -128,6 +129,19 @@ class _LovaszFn(torch.autograd.Function):
         return ops.scale_by_scalar(grad_unit, grad_out.detach().float().contiguous()), None
 
 
+class _LovaszSoftmaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inputs, targets, per_image, classes):
+        loss, grad_unit, _ = ops.lovasz_softmax_fwd(inputs.detach().float(), targets, per_image, classes, want_grad=True)
+        ctx.save_for_backward(grad_unit)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (grad_unit,) = ctx.saved_tensors
+        return ops.scale_by_scalar(grad_unit, grad_out.detach().float().contiguous()), None, None, None
+
+
 class _WeightedLoss(nn.Module):
     # Set to True on the ranks of a data-parallel job (rs train, bench.py): the batch-level terms of the loss -- the weighted
     # NLL's normaliser, mIoU's branch choice -- are then the GLOBAL batch's, as in the reference's single evaluation over the
@@ -176,3 +190,21 @@ class LovaszLoss2d(nn.Module):
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
         return _LovaszFn.apply(inputs, targets)
+
+
+class LovaszSoftmax2d(nn.Module):
+    """The multi-class Lovasz-Softmax loss of Berman et al. 2018 (arXiv 1705.08790), which the reference's ``LovaszLoss2d``
+    cites but does not implement: softmax over the classes of the LOGITS it is given, then per class the Lovasz extension of
+    the Jaccard loss over the errors ``|1[y = c] - p_c|``, averaged over the classes present (``classes="present"``) or
+    over all of them (``"all"``), per image then over the batch (``per_image=True``) or once over the whole batch."""
+
+    def __init__(self, per_image=True, classes="present"):
+        super().__init__()
+        if classes not in ("present", "all"):
+            raise ValueError("classes must be \"present\" or \"all\" (got {!r})".format(classes))
+        self.per_image = bool(per_image)
+        self.classes = classes
+
+    def forward(self, inputs, targets):
+        inputs, targets = _check(inputs, targets)
+        return _LovaszSoftmaxFn.apply(inputs, targets, self.per_image, self.classes)

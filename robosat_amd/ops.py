@@ -1258,6 +1258,26 @@ def lovasz_fwd(logits, targets, want_grad=True):
     return loss, grad
 
 
+def lovasz_softmax_fwd(logits, targets, per_image=True, classes="present", want_grad=True, want_probs=False):
+    """Lovasz-Softmax (``rs_lovasz_softmax_fwd``): returns (loss, d loss / d logits for grad_out = 1 or None, fp32
+    softmax probabilities NCHW or None)."""
+
+    if classes not in ("present", "all"):
+        raise ValueError("classes must be \"present\" or \"all\" (got {!r})".format(classes))
+    n, c, h, w = logits.shape
+    lib = _lib.lib()
+    pi = 1 if per_image else 0
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    grad = torch.empty_like(logits) if want_grad else None
+    probs = torch.empty_like(logits) if want_probs else None
+    nbytes = lib.rs_lovasz_softmax_workspace_bytes(n, c, h, w, pi)
+    rc = lib.rs_lovasz_softmax_fwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"),
+                                   _dev(grad, "grad"), _dev(probs, "probs"), n, c, h, w, pi, 1 if classes == "all" else 0,
+                                   _workspace(nbytes, logits.device), _stream())
+    check(rc, "rs_lovasz_softmax_fwd")
+    return loss, grad, probs
+
+
 def scale_by_scalar(src, scalar):
     out = torch.empty_like(src)
     check(_lib.lib().rs_scale_by_scalar(_dev(src, "src"), _dev(scalar, "scalar"), _dev(out, "out"), src.numel(), _stream()),

@@ -15,7 +15,10 @@ Differences by design:
     every rank evaluates its shard and the gradients are averaged.  For Lovasz (a mean over images) that is the same number;
     weighted CrossEntropy / Focal exchange their normaliser (the sum of target weights, one scalar all-reduce) so that it is
     the same number there too (robosat_amd/losses.py); mIoULoss2d exchanges its two branch values and takes
-    ``max(miou, nll)`` once over the global batch (three scalars, one all-reduce).
+    ``max(miou, nll)`` once over the global batch (three scalars, one all-reduce).  LovaszSoftmax per image is a mean over
+    images like Lovasz; its flattened form (one sort over the global batch) is refused with more than one rank.
+  * ``[opt] loss = "LovaszSoftmax"``: the multi-class Lovasz-Softmax loss (no ``[weights]`` needed), with the optional keys
+    ``[opt] lovasz_per_image`` (default true) and ``[opt] lovasz_classes`` ("present" | "all", default "present").
   * extension keys, all optional: dataset ``[common] image_dirs / image_modes / mean / std`` (band layout: robosat_amd/bands.py;
     default = the reference's one RGB directory), model ``[model] in_channels``, ``compute_dtype``, ``pretrained``,
     ``device_augment``, ``grad_dtype`` (bf16 gradient exchange), ``graph`` (the step as one hipGraph replay).
@@ -39,7 +42,7 @@ from robosat_amd.bands import bands_from_config, split_per_source
 from robosat_amd.config import check_num_classes, load_config
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
-from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, mIoULoss2d
+from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, mIoULoss2d
 from robosat_amd.metrics import Metrics
 from robosat_amd.transforms import (
     CenterCrop, ConvertImageMode, ImageToTensor, JointCompose, JointRandomHorizontalFlip, JointRandomRotation,
@@ -95,6 +98,25 @@ def argv_from_args(args):
     return argv
 
 
+def lovasz_softmax_options(model, world):
+    """``(per_image, classes)`` of ``[opt] loss = "LovaszSoftmax"`` from the optional ``[opt] lovasz_per_image`` /
+    ``lovasz_classes`` keys; exits with an error on a bad value, and on the flattened form over more than one rank: its mean
+    over the classes of the WHOLE batch needs one sort over the global batch, which no rank holds (a per-shard loss would
+    be a different loss)."""
+
+    opt = model["opt"]
+    per_image = opt.get("lovasz_per_image", True)
+    if not isinstance(per_image, bool):
+        sys.exit("Error: [opt] lovasz_per_image must be true or false")
+    classes = opt.get("lovasz_classes", "present")
+    if classes not in ("present", "all"):
+        sys.exit("Error: [opt] lovasz_classes must be \"present\" or \"all\"")
+    if not per_image and world > 1:
+        sys.exit("Error: [opt] lovasz_per_image = false needs one sort over the global batch and cannot be split over {} "
+                 "data-parallel ranks; train on one GPU (ROBOSAT_GPUS=1) or use lovasz_per_image = true".format(world))
+    return per_image, classes
+
+
 def main(args):
     model = load_config(args.model)
     dataset = load_config(args.dataset)
@@ -113,6 +135,8 @@ def main(args):
         # the reference uses every visible GPU (DataParallel, tools/train.py:69): one process per GPU here
         gpus = int(os.environ.get("ROBOSAT_GPUS", torch.cuda.device_count()))
         nranks = launch.ranks_for_batch(batch_size, gpus)
+        if model["opt"]["loss"] == "LovaszSoftmax":  # (bad keys end here, before any rank starts)
+            lovasz_softmax_options(model, nranks if getattr(args, "spawn", True) else 1)
         # (`spawn=False` on the namespace is the library caller's opt-out: train in THIS process on one GPU)
         if nranks > 1 and getattr(args, "spawn", True):
             status = launch.run_per_gpu(nranks, argv_from_args(args), module="robosat_amd.tools")
@@ -191,6 +215,9 @@ def main(args):
         criterion = FocalLoss2d(weight=weight).to(device)
     elif loss_name == "Lovasz":
         criterion = LovaszLoss2d().to(device)
+    elif loss_name == "LovaszSoftmax":
+        per_image, classes = lovasz_softmax_options(model, world)
+        criterion = LovaszSoftmax2d(per_image=per_image, classes=classes).to(device)
     else:
         sys.exit("Error: Unknown [opt][loss] value !")
     if world > 1 and hasattr(criterion, "global_batch"):
