@@ -264,8 +264,79 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   const int total = nitems * nk;
   const int Ho = 2 * p.Hs, Wo = 2 * p.Ws;
 
+  // ---- the chunk loop, software-pipelined across its one barrier per chunk.  Chunk g runs as
+  //        HEAD  positions 0 .. 8 - TAIL: 4 NM MFMAs each, the filter pieces one position ahead (the TAIL positions' all at once
+  //              at the last one), chunk g + 1's LDS-DMA pieces spread over the first two thirds of the chunk's MFMAs
+  //        -- the wave's LDS reads of stage g & 1 have returned, chunk g + 1 has landed: barrier --
+  //        TAIL  the last TAIL positions' MFMAs, with chunk g + 1's patch reads and B^T d B transform in between them
+  //      so a chunk opens straight into MFMAs: the barrier, the patch reads and the transform no longer stand between two chunks'
+  //      MFMA streams.  Stage g & 1 is free for chunk g + 2 once every wave has passed chunk g's barrier (its last reads of the
+  //      stage are waited for in front of it), and chunk g + 2 is issued in chunk g + 1's head.  Every accumulator receives the
+  //      same MFMAs in the same order from the same transforms as in the unpipelined loop: only issue times moved.
+  constexpr int TAIL = NM >= 4 ? 1 : 2;  // positions behind the barrier: 16 MFMAs to cover every wave's nine patch reads
+  constexpr int NMMA = 36 * NM, NHEAD = (9 - TAIL) * 4 * NM, NT = TAIL * 4 * NM;
+  constexpr int PSTEP = 2 * NMMA / 3 / NI >= 1 ? 2 * NMMA / 3 / NI : 1;
+  static_assert((NI - 1) * PSTEP < NHEAD, "the DMA pieces go out in the chunk's head");
+  f32x4 V[9], Bq[9][NM];  // the chunk's transformed patch and filter pieces; V and Bq[0] are formed in the previous chunk's tail
+  // chunk head: the lane's 3x3 patch from stage L, V' = B^T d B (along x, then along y: [d0 - d1, d1, d2 - d1] each way, on 2-float
+  // halves with v_pk_add_f32: two fp32 subtractions per instruction; as 4-float vector code hipcc emits scalar v_sub_f32: measured
+  // -4 % on the 3x3 form) and the first filter pair B0, between the MFMAs tail(0 .. nt - 1) of the previous chunk: half of them
+  // first (the reads' latency), then one of the transform's six steps per slice of the rest, the filter pair before the last ones
+  auto chunk_head = [&](const unsigned char* L, f32x4(&Vn)[9], f32x4(&B0)[NM], auto tail, auto nt) __attribute__((always_inline)) {
+    constexpr int N = decltype(nt)::value, LEAD = N / 2;
+    f32x4 P[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) P[r][c] = *reinterpret_cast<const f32x4*>(L + addrA[r][c]);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < LEAD; ++i) tail(i);
+    __builtin_amdgcn_sched_barrier(0);
+    f32x2 Tl[3][3], Th[3][3];
+#pragma unroll
+    for (int s = 0; s < 6; ++s) {
+      if (s < 3) {
+        const int r = s;
+        const f32x2 l0 = {P[r][0][0], P[r][0][1]}, h0 = {P[r][0][2], P[r][0][3]};
+        const f32x2 l1 = {P[r][1][0], P[r][1][1]}, h1 = {P[r][1][2], P[r][1][3]};
+        const f32x2 l2 = {P[r][2][0], P[r][2][1]}, h2 = {P[r][2][2], P[r][2][3]};
+        Tl[r][0] = pk_sub(l0, l1);
+        Tl[r][1] = l1;
+        Tl[r][2] = pk_sub(l2, l1);
+        Th[r][0] = pk_sub(h0, h1);
+        Th[r][1] = h1;
+        Th[r][2] = pk_sub(h2, h1);
+      } else {
+        const int c = s - 3;
+        const f32x2 a = pk_sub(Tl[0][c], Tl[1][c]), b = pk_sub(Tl[2][c], Tl[1][c]);
+        const f32x2 d = pk_sub(Th[0][c], Th[1][c]), e = pk_sub(Th[2][c], Th[1][c]);
+        Vn[0 * 3 + c] = f32x4{a[0], a[1], d[0], d[1]};
+        Vn[1 * 3 + c] = f32x4{Tl[1][c][0], Tl[1][c][1], Th[1][c][0], Th[1][c][1]};
+        Vn[2 * 3 + c] = f32x4{b[0], b[1], e[0], e[1]};
+      }
+#pragma unroll
+      for (int i = LEAD + (N - LEAD) * s / 7; i < LEAD + (N - LEAD) * (s + 1) / 7; ++i) tail(i);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int m = 0; m < NM; ++m) B0[m] = *reinterpret_cast<const f32x4*>(L + addrB + (16 * m) * 64);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = LEAD + (N - LEAD) * 6 / 7; i < N; ++i) tail(i);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // MFMA q of the chunk (q = (x * 4 + k) * NM + m: position x, k-step k, cout tile m -- the unpipelined loop's order)
   int g = 0;
   f32x4 acc[9][NM];
+  auto mfma = [&](int q) __attribute__((always_inline)) {
+    const int x = q / (4 * NM), k = (q / NM) % 4, m = q % NM;
+    acc[x][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(Bq[x][m][k], V[x][k], acc[x][m], 0, 0, 0);
+  };
+  rb_dma_wait();
+  __syncthreads();  // chunk 0 is in stage 0
+  chunk_head(smem, V, Bq[0], [](int) {}, std::integral_constant<int, 0>());
+
   for (int seq = 0; seq < nitems; ++seq) {
     if (!DG || (seq & 3) == 0) {  // (DG: the four parity planes of an output item accumulate)
 #pragma unroll
@@ -275,72 +346,43 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
     }
 
     for (int kc = 0; kc < nk; ++kc, ++g) {
-      rb_dma_wait();
-      __syncthreads();  // chunk g is in stage g & 1; stage (g + 1) & 1 is free again
       const unsigned char* L = smem + (g & 1) * STAGE;
-      f32x4 P[3][3];
-#pragma unroll
-      for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) P[r][c] = *reinterpret_cast<const f32x4*>(L + addrA[r][c]);
       const bool more = g + 1 < total;
-      // LDS-DMA pieces of the NEXT chunk, spread evenly over this chunk's MFMAs: the CU's DMA path moves ~23 B/clk and this
-      // kernel needs ~12 B/clk of it (55 KB per 4608 MFMA cycles); issued in a burst the pieces queue up and hold the issuing
-      // waves (front-loading them was measured: no gain)
-      constexpr int NMMA = 36 * NM, PSTEP = NMMA / NI >= 1 ? NMMA / NI : 1;
-      // filter pieces are fetched one transformed position ahead of the MFMAs that use them (the first pair goes out before
-      // the transform's vector ops): in source order hipcc otherwise parks an LDS round trip in front of every group of 8 MFMAs
-      f32x4 Bq[9][NM];
+      // head: filter pieces one position ahead of the MFMAs that use them (sched_barrier keeps hipcc from sinking the reads in
+      // front of every group of 8 MFMAs); chunk g + 1's DMA pieces spread evenly over the first two thirds of the chunk's MFMAs:
+      // the CU's DMA path moves ~23 B/clk and this kernel needs ~12 B/clk of it; issued in a burst the pieces queue up and hold
+      // the issuing waves (measured: -26 %), and the last ones need a third of a chunk to land before the barrier
+      fetch_chunk([&](auto issue) __attribute__((always_inline)) {
 #pragma unroll
-      for (int m = 0; m < NM; ++m) Bq[0][m] = *reinterpret_cast<const f32x4*>(L + addrB + (16 * m) * 64);
-      __builtin_amdgcn_sched_barrier(0);
-      // V = B^T d B: along x, then along y ([d0 - d1, d1, d2 - d1] each way), on 2-float halves with v_pk_add_f32 (two fp32
-      // subtractions per instruction; written as 4-float vector code hipcc emits scalar v_sub_f32: measured -4 % on the 3x3 form)
-      f32x4 V[9];
-      {
-        f32x2 Tl[3][3], Th[3][3];
+        for (int x = 0; x < 9 - TAIL; ++x) {
 #pragma unroll
-        for (int r = 0; r < 3; ++r) {
-          const f32x2 l0 = {P[r][0][0], P[r][0][1]}, h0 = {P[r][0][2], P[r][0][3]};
-          const f32x2 l1 = {P[r][1][0], P[r][1][1]}, h1 = {P[r][1][2], P[r][1][3]};
-          const f32x2 l2 = {P[r][2][0], P[r][2][1]}, h2 = {P[r][2][2], P[r][2][3]};
-          Tl[r][0] = pk_sub(l0, l1);
-          Tl[r][1] = l1;
-          Tl[r][2] = pk_sub(l2, l1);
-          Th[r][0] = pk_sub(h0, h1);
-          Th[r][1] = h1;
-          Th[r][2] = pk_sub(h2, h1);
-        }
+          for (int xr = x + 1; xr < (x + 1 == 9 - TAIL ? 9 : x + 2); ++xr)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const f32x2 a = pk_sub(Tl[0][c], Tl[1][c]), b = pk_sub(Tl[2][c], Tl[1][c]);
-          const f32x2 d = pk_sub(Th[0][c], Th[1][c]), e = pk_sub(Th[2][c], Th[1][c]);
-          V[0 * 3 + c] = f32x4{a[0], a[1], d[0], d[1]};
-          V[1 * 3 + c] = f32x4{Tl[1][c][0], Tl[1][c][1], Th[1][c][0], Th[1][c][1]};
-          V[2 * 3 + c] = f32x4{b[0], b[1], e[0], e[1]};
-        }
-      }
-      auto mfmas = [&](auto issue) __attribute__((always_inline)) {
+            for (int m = 0; m < NM; ++m) Bq[xr][m] = *reinterpret_cast<const f32x4*>(L + addrB + (xr * BN + 16 * m) * 64);
+          __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int x = 0; x < 9; ++x) {
-          if (x + 1 < 9) {
-#pragma unroll
-            for (int m = 0; m < NM; ++m) Bq[x + 1][m] = *reinterpret_cast<const f32x4*>(L + addrB + ((x + 1) * BN + 16 * m) * 64);
-            __builtin_amdgcn_sched_barrier(0);  // (keep these reads in front of the MFMAs below: hipcc sinks them to their first use)
+          for (int i = 0; i < 4 * NM; ++i) {
+            const int q = x * 4 * NM + i;
+            if (q % PSTEP == 0 && q / PSTEP < NI) issue(q / PSTEP);
+            mfma(q);
           }
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int m = 0; m < NM; ++m) {
-              const int q = (x * 4 + k) * NM + m;  // MFMA index within the chunk (compile-time)
-              if (q % PSTEP == 0 && q / PSTEP < NI) issue(q / PSTEP);
-              acc[x][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(Bq[x][m][k], V[x][k], acc[x][m], 0, 0, 0);
-            }
         }
-      };
-      fetch_chunk([&](auto issue) __attribute__((always_inline)) { mfmas(issue); }, !more);
-
-      if (kc == 0 && seq + 1 < nitems) build_table(seq + 1);  // (its buffer held item seq - 1's table: the fetch side left it a whole item ago)
+      }, !more);
+      // the next item's gather table (its buffer held item seq - 1's, whose last reader, the fetch of that item's C2 switch, was
+      // two barriers ago at the latest); published by the barrier below and first read by the fetch of item seq + 1's chunk 0,
+      // in item seq's last chunk -- a later one, since nk >= 2 (wino_plan)
+      if (kc == 0 && seq + 1 < nitems) build_table(seq + 1);
+      rs_lds_writes_done();  // (and every LDS read of stage g & 1 by this wave has returned: other waves refill it behind the barrier)
+      rb_dma_wait();
+      __syncthreads();  // chunk g + 1 is in stage (g + 1) & 1; no wave reads stage g & 1 any more
+      // tail: chunk g's last TAIL positions around chunk g + 1's head (past the block's last chunk: the re-issued pieces, unused)
+      f32x4 Vn[9], B0[NM];
+      chunk_head(smem + ((g + 1) & 1) * STAGE, Vn, B0, [&](int i) __attribute__((always_inline)) { mfma(NHEAD + i); },
+                 std::integral_constant<int, NT>());
+#pragma unroll
+      for (int x = 0; x < 9; ++x) V[x] = Vn[x];
+#pragma unroll
+      for (int m = 0; m < NM; ++m) Bq[0][m] = B0[m];
     }
 
     // ---- Y = A^T M A, ReLU, store: lane = tile l15, couts 32 cg + 16 m + 4 pc + (0..3) -------------------------------------
