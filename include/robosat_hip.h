@@ -511,6 +511,35 @@ int rs_final_conv1x1_quantize_dt(const void* x, int x_dtype, const float* w, con
 int rs_final_conv1x1_argmax_dt(const void* x, int x_dtype, const float* w, const float* bias, uint8_t* out, int N, int H,
                                int W, int Cin, int C, rs_stream_t stream);
 
+/* Dihedral test-time augmentation (csrc/tta.hip; an extension, the reference has none).  A mode is an ordered list of V ops
+ * ops[v] in the encoding of rs_augment_tiles, op = f + 2*k: FLIP_LEFT_RIGHT when f, then k counter-clockwise 90-degree
+ * rotations (np.rot90).  g_v maps tile pixel p to its position in view v; view v of tile n sits at batch index n*V + v.
+ * V is 1, 2, 4 or 8; `ops` is a HOST array of V ints; H, W are multiples of 32; ops with odd k need H == W.
+ *
+ * rs_tta_fan_out: view_v[q] = tile[g_v^-1(q)] -> out [N*V][H][W][4] NHWC4 of `out_dtype` (RS_F32 or RS_BF16, round to nearest
+ * even), channels >= C zero.  x_kind RS_TTA_IN_U8: x = uint8 HWC [N][H][W][C<=4] normalised as rs_u8_to_nhwc4_norm (mean,
+ * std: HOST arrays of C floats); RS_TTA_IN_F32: x = fp32 NCHW [N][C][H][W] taken as it is (rs_nchw_to_nhwc4; mean, std
+ * unused).  Bit-identical to transforming the tile first and then calling those ops.
+ *
+ * rs_tta_merge: probs = the N*V views' fp32 NCHW [N*V][C][H][W] probabilities (16-byte aligned).  For each output pixel p and class c the V
+ * values probs_v[c][g_v(p)] are sorted ascending, added in fp32 one after another from the smallest, and multiplied by 1/V
+ * (exact).  The summands of g(x) at g(p) are the same multiset as those of x at p for every g of a mode that is a group, so
+ * the merge is exactly equivariant: tta(g.x) == g.tta(x) bit for bit, given a batch-independent network.  Then by `mode`:
+ *   RS_TTA_PROBS     out = fp32 [N][C][H][W], uncropped;
+ *   RS_TTA_QUANTIZE  out = uint8 of rs_final_conv1x1_quantize_dt's layout and encoding ([N][H'][W'] for C = 2,
+ *                    [N][H'][W'][C-1] for C > 2, H' = H - 2*overlap; `anchors` = np.linspace(0, 1, 256) in device memory);
+ *   RS_TTA_ARGMAX    out = uint8 [N][H][W], the first maximum over the classes of the merged probabilities.
+ * Neither kernel uses atomics; the results are deterministic. */
+#define RS_TTA_IN_U8 0
+#define RS_TTA_IN_F32 1
+#define RS_TTA_PROBS 0
+#define RS_TTA_QUANTIZE 1
+#define RS_TTA_ARGMAX 2
+int rs_tta_fan_out(const void* x, int x_kind, const float* mean, const float* std, void* out, int out_dtype, const int* ops,
+                   int V, int N, int H, int W, int C, rs_stream_t stream);
+int rs_tta_merge(const float* probs, const int* ops, int V, int mode, const double* anchors, int overlap, void* out, int N,
+                 int C, int H, int W, rs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The callers either side of the network, on the device (csrc/postproc.hip)
  * ---------------------------------------------------------------------------------------------------------- */

@@ -16,8 +16,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROBOSAT_HIP_LIB") or os.path.join(_HERE, "librobosat_hip.so")
 
 RS_EINVAL = -22
-ABI_VERSION = 22
+ABI_VERSION = 23
 RS_F32, RS_BF16 = 0, 1
+RS_TTA_IN_U8, RS_TTA_IN_F32 = 0, 1
+RS_TTA_PROBS, RS_TTA_QUANTIZE, RS_TTA_ARGMAX = 0, 1, 2
 
 
 class ConvDesc(ctypes.Structure):
@@ -141,6 +143,9 @@ SIGNATURES = {
     "rs_u8_to_nhwc4_norm": (c_int, [P, P, POINTER(c_float), POINTER(c_float), c_int, c_int, c_int, c_int, P]),
     "rs_final_conv1x1_quantize_dt": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     "rs_final_conv1x1_argmax_dt": (c_int, [P, c_int, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    # dihedral test-time augmentation (csrc/tta.hip)
+    "rs_tta_fan_out": (c_int, [P, c_int, POINTER(c_float), POINTER(c_float), P, c_int, POINTER(c_int), c_int, c_int, c_int, c_int, c_int, P]),
+    "rs_tta_merge": (c_int, [P, POINTER(c_int), c_int, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P]),
     # callers either side of the network (N2-N4)
     "rs_confusion_matrix": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "rs_label_histogram_u8": (c_int, [P, c_long, P, P]),

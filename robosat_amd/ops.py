@@ -959,6 +959,74 @@ def final_conv1x1_argmax(x, w, bias):
     return out
 
 
+# dihedral test-time augmentation (csrc/tta.hip): ops in the encoding of augment_tiles, op = f + 2*k (FLIP_LEFT_RIGHT when f,
+# then k counter-clockwise rot90s).  Every mode is a group, which makes the sorted merge exactly equivariant.
+TTA_MODES = {"none": (0,), "hflip": (0, 1), "flips": (0, 1, 4, 5), "d4": (0, 1, 2, 3, 4, 5, 6, 7)}
+
+
+def tta_ops(mode, h, w):
+    """The op list of a TTA mode for h x w tiles; ValueError on an unknown mode or on ``d4`` (90-degree turns) off the square."""
+
+    if mode not in TTA_MODES:
+        raise ValueError("unknown TTA mode {!r}: one of {}".format(mode, ", ".join(TTA_MODES)))
+    op_list = list(TTA_MODES[mode])
+    if h != w and any((op >> 1) & 1 for op in op_list):
+        raise ValueError("TTA mode {!r} rotates by 90 degrees and needs square tiles, got {}x{}".format(mode, h, w))
+    return op_list
+
+
+def _tta_fan_out(x, kind, mean, std, op_list, dtype, n, h, w, c):
+    v = len(op_list)
+    out = torch.empty((n * v, h, w, 4), device=x.device, dtype=dtype)
+    fm = fs = None
+    if mean is not None:
+        assert len(mean) == c and len(std) == c
+        fm, fs = (ctypes.c_float * c)(*mean), (ctypes.c_float * c)(*std)
+    rc = _lib.lib().rs_tta_fan_out(_dev(x, "x", x.dtype), kind, fm, fs, _dev(out, "out", dtype), RS_BF16 if dtype == BF16 else RS_F32,
+                                   (ctypes.c_int * v)(*op_list), v, n, h, w, c, _stream())
+    check(rc, "rs_tta_fan_out")
+    return out
+
+
+def tta_fan_out_u8(img, mean, std, op_list, dtype=torch.float32):
+    """uint8 HWC tiles [N,H,W,C] -> the views' normalised NHWC4 [N*V,H,W,4] in ``dtype``: view v of tile n (batch index
+    n*V + v) is ``u8_to_nhwc4_norm`` of the tile transformed by op_list[v], bit for bit."""
+
+    n, h, w, c = img.shape
+    return _tta_fan_out(img, _lib.RS_TTA_IN_U8, mean, std, op_list, dtype, n, h, w, c)
+
+
+def tta_fan_out_f32(x, op_list, dtype=torch.float32):
+    """fp32 NCHW images [N,C,H,W] -> the views' NHWC4 [N*V,H,W,4] in ``dtype`` (``nchw_to_nhwc4`` of each transformed image)."""
+
+    n, c, h, w = x.shape
+    return _tta_fan_out(x, _lib.RS_TTA_IN_F32, None, None, op_list, dtype, n, h, w, c)
+
+
+def tta_merge(probs, op_list, mode="probs", overlap=0):
+    """The views' fp32 probabilities [N*V,C,H,W] -> per pixel and class the sorted fp32 sum of the V view values times 1/V, then
+    by ``mode``: "probs" -> fp32 [N,C,H,W]; "quantize" -> the bytes of ``final_conv1x1_quantize`` (crop of ``overlap``);
+    "argmax" -> uint8 [N,H,W], the first maximum of the merged probabilities."""
+
+    nv, c, h, w = probs.shape
+    v = len(op_list)
+    assert nv % v == 0
+    n = nv // v
+    m = {"probs": _lib.RS_TTA_PROBS, "quantize": _lib.RS_TTA_QUANTIZE, "argmax": _lib.RS_TTA_ARGMAX}[mode]
+    anchors = None
+    if m == _lib.RS_TTA_PROBS:
+        out = torch.empty((n, c, h, w), device=probs.device, dtype=torch.float32)
+    elif m == _lib.RS_TTA_QUANTIZE:
+        out = torch.empty((n, h - 2 * overlap, w - 2 * overlap) + ((c - 1,) if c > 2 else ()), device=probs.device, dtype=torch.uint8)
+        anchors = _dev(_anchors(probs.device), "anchors", torch.float64)
+    else:
+        out = torch.empty((n, h, w), device=probs.device, dtype=torch.uint8)
+    rc = _lib.lib().rs_tta_merge(_dev(probs, "probs"), (ctypes.c_int * v)(*op_list), v, m, anchors, int(overlap),
+                                 _dev(out, "out", out.dtype), n, c, h, w, _stream())
+    check(rc, "rs_tta_merge")
+    return out
+
+
 def maxpool2d(x, k, stride, pad, want_argmax=False, out_dtype=None):
     """``out_dtype`` (default: x.dtype): torch.bfloat16 on an fp32 input is the precision boundary of the bf16 path."""
 

@@ -18,7 +18,7 @@ import torch
 from torch.utils.data import DataLoader
 from tqdm import tqdm
 
-from robosat_amd import launch, png
+from robosat_amd import launch, ops, png
 from robosat_amd.bands import bands_from_config, split_per_source
 from robosat_amd.colors import continuous_palette_for_color
 from robosat_amd.config import check_num_classes, load_config
@@ -45,6 +45,10 @@ def add_parser(subparser):
     # extension (multi-band models, BASELINE configs[4]): one more slippy-map directory per further entry of the dataset's
     # `[common] image_dirs` (e.g. the infrared tiles), same z/x/y as `tiles`
     parser.add_argument("--extra_tiles", type=str, nargs="*", default=[], help="directories with the further image bands")
+    # extension: dihedral test-time augmentation (UNet.predict_quantized): the network runs on V flipped / rotated views of every
+    # tile and their probabilities are averaged; V = 2 / 4 / 8, and so V times the work and the activation memory of a batch
+    parser.add_argument("--tta", choices=["none", "hflip", "flips", "d4"], default="none",
+                        help="test-time augmentation: average the probabilities over flipped / rotated views (d4: square tiles)")
     parser.set_defaults(func=main)
 
 
@@ -53,6 +57,9 @@ def argv_from_args(args):
 
     argv = ["predict", "--batch_size", str(args.batch_size), "--checkpoint", args.checkpoint, "--overlap", str(args.overlap),
             "--tile_size", str(args.tile_size), "--workers", str(args.workers), "--model", args.model, "--dataset", args.dataset]
+    tta = getattr(args, "tta", "none")
+    if tta != "none":
+        argv += ["--tta", tta]
     extra = list(getattr(args, "extra_tiles", None) or [])
     # (positionals first: `--extra_tiles` takes any number of values and would swallow them)
     return argv + [args.tiles, args.probs] + (["--extra_tiles"] + extra if extra else [])
@@ -135,6 +142,13 @@ def main(args):
     # network, softmax, the un-buffer crop and the 8-bit quantisation all run on the GPU and one byte per pixel comes
     # back.  ROBOSAT_PREDICT_HOST_PIPELINE=1 keeps the reference's host-side steps (same bytes; the parity tests compare).
     host_pipeline = os.environ.get("ROBOSAT_PREDICT_HOST_PIPELINE", "0") == "1"
+    tta = getattr(args, "tta", "none")
+    if host_pipeline and tta != "none":
+        sys.exit("Error: --tta {} runs on the device-side pipeline only; unset ROBOSAT_PREDICT_HOST_PIPELINE".format(tta))
+    try:
+        ops.tta_ops(tta, args.tile_size + 2 * args.overlap, args.tile_size + 2 * args.overlap)
+    except ValueError as err:
+        sys.exit("Error: {}".format(err))
     if host_pipeline:
         transforms = [Compose([ConvertImageMode(mode=md), ImageToTensor(), Normalize(mean=m, std=s)])
                       for md, m, s in zip(bands.modes, split_per_source(bands, mean), split_per_source(bands, std))]
@@ -213,7 +227,7 @@ def main(args):
             submit(tiles, quantized)
             lap("writers")
             continue
-        q_dev = net.predict_quantized(images.to(device, non_blocking=True), overlap=args.overlap, mean=mean, std=std)
+        q_dev = net.predict_quantized(images.to(device, non_blocking=True), overlap=args.overlap, mean=mean, std=std, tta=tta)
         slot = step & 1
         if staging[slot] is None or staging[slot].shape[1:] != q_dev.shape[1:] or staging[slot].shape[0] < q_dev.shape[0]:
             staging[slot] = torch.empty(q_dev.shape, dtype=q_dev.dtype, pin_memory=True)

@@ -39,13 +39,15 @@ def add_parser(subparser):
     parser.add_argument("--tile_size", type=int, default=512, help="tile size for slippy map tiles")
     parser.add_argument("--host", type=str, default="127.0.0.1", help="host to serve on")
     parser.add_argument("--port", type=int, default=5000, help="port to serve on")
+    parser.add_argument("--tta", choices=["none", "hflip", "flips", "d4"], default="none",
+                        help="test-time augmentation: argmax of the probabilities averaged over flipped / rotated views")
     parser.set_defaults(func=main)
 
 
 class Predictor:
     """Reference ``serve.py:135-192``: loads a (``module.``-prefixed) checkpoint once, segments one image per call."""
 
-    def __init__(self, checkpoint, model, dataset):
+    def __init__(self, checkpoint, model, dataset, tta="none"):
         cuda = model["common"]["cuda"]
         assert torch.cuda.is_available() or not cuda, "cuda is available when requested"
         if not cuda:
@@ -55,6 +57,7 @@ class Predictor:
         self.checkpoint = checkpoint
         self.model = model
         self.dataset = dataset
+        self.tta = tta  # (UNet.predict_classes: "none" = argmax of the logits, else of the merged view probabilities)
         # the band layout of the dataset config (default: one RGB image, ImageNet statistics -- serve.py:152-153); a served
         # tile is ONE image, so a multi-band model needs a single 4-band source (`image_modes = ["RGBA"]`)
         self.bands = bands_from_config(dataset, model)
@@ -69,7 +72,7 @@ class Predictor:
         mean, std = self.bands.mean, self.bands.std
         pixels = np.array(image.convert(self.bands.modes[0]), dtype=np.uint8)
         u8 = torch.from_numpy(pixels if pixels.ndim == 3 else pixels[:, :, None]).unsqueeze(0)
-        mask = self.net.predict_classes(u8.to(self.device, non_blocking=True), mean=mean, std=std)[0].cpu().numpy()
+        mask = self.net.predict_classes(u8.to(self.device, non_blocking=True), mean=mean, std=std, tta=self.tta)[0].cpu().numpy()
         mask = Image.fromarray(mask, mode="P")
         mask.putpalette(self.palette)
         return mask
@@ -141,5 +144,5 @@ def main(args):
     global size, tiles, predictor
     size = args.tile_size
     tiles = args.url
-    predictor = Predictor(args.checkpoint, model, dataset)
+    predictor = Predictor(args.checkpoint, model, dataset, tta=getattr(args, "tta", "none"))
     make_app().run(host=args.host, port=args.port, threaded=False)  # one request at a time on the GPU, as the reference

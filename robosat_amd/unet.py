@@ -462,13 +462,14 @@ class UNet(nn.Module):
         return st
 
     @staticmethod
-    def _want_graph(x):
-        """Graphs for the latency regime (a few tiles per call); ROBOSAT_GRAPHS=0|1 overrides."""
+    def _want_graph(x, views=1):
+        """Graphs for the latency regime (a few tiles per call; ``views``: the network batch is N * views tiles);
+        ROBOSAT_GRAPHS=0|1 overrides."""
 
         forced = os.environ.get("ROBOSAT_GRAPHS")
         if forced is not None:
             return forced == "1"
-        return x.shape[0] * x.shape[1] * x.shape[2] <= 2 * 512 * 512
+        return x.shape[0] * views * x.shape[1] * x.shape[2] <= 2 * 512 * 512
 
     # -- forward ------------------------------------------------------------------------------------------------
 
@@ -494,22 +495,36 @@ class UNet(nn.Module):
         return self._forward_eval(x, softmax=False)
 
     @torch.no_grad()
-    def predict_probs(self, x):
-        """softmax(forward(x), dim=1) with the softmax fused into the last kernel (tools/predict.py:84-87)."""
+    def predict_probs(self, x, tta="none"):
+        """softmax(forward(x), dim=1) with the softmax fused into the last kernel (tools/predict.py:84-87).
+
+        ``tta`` ("none", "hflip", "flips", "d4"; ``ops.TTA_MODES``): dihedral test-time augmentation -- the network runs on the V
+        flipped / rotated views of every image and the V probabilities of a pixel are averaged back in the image's frame (sorted
+        fp32 sum, exactly equivariant; ``rs_tta_merge``).  Memory: V times the activations of the N-image batch."""
 
         size = x.size()
         assert size[-1] % 32 == 0 and size[-2] % 32 == 0, "image resolution has to be divisible by 32 for resnet"
         assert not self.training, "predict_probs is an eval-mode call"
-        return self._forward_eval(x, softmax=True)
+        if tta == "none":
+            return self._forward_eval(x, softmax=True)
+        op_list = ops.tta_ops(tta, size[-2], size[-1])
+        if not x.is_cuda:
+            raise RuntimeError("robosat_amd.UNet runs on the MI355X only (got a {} tensor); there is no CPU fallback".format(x.device))
+        assert x.size(1) == self.in_channels
+        x4 = ops.tta_fan_out_f32(x.detach().float().contiguous(), op_list, self.compute_dtype)
+        return ops.tta_merge(self._forward_eval(None, softmax=True, x4=x4), op_list, "probs")
 
     @torch.no_grad()
-    def predict_quantized(self, images_u8, overlap=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    def predict_quantized(self, images_u8, overlap=0, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), tta="none"):
         """The whole device side of ``rs predict`` for a batch of decoded tiles:
         uint8 HWC ``[N,H,W,C]`` in -> ToTensor + Normalize -> U-Net -> softmax -> crop of the ``overlap`` border ->
         ``np.digitize(p_foreground, np.linspace(0,1,256)).astype(uint8)`` out, ``[N,H-2*overlap,W-2*overlap]`` uint8:
         exactly the bytes the reference writes into its probability PNGs (tools/predict.py:71-103), 1 byte per pixel each
         way over PCIe instead of 12 in / 8 out.  Models with more than two classes (which the reference's predict tool
-        asserts away) return ``[N,H',W',C-1]``: the same encoding for every non-background class."""
+        asserts away) return ``[N,H',W',C-1]``: the same encoding for every non-background class.
+
+        ``tta`` (see ``predict_probs``): the tiles go up once; the views are made, and their probabilities merged and quantised,
+        on the device.  Memory: V times the activations of the N-tile batch."""
 
         assert not self.training, "predict_quantized is an eval-mode call"
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.size(3) == self.in_channels
@@ -517,23 +532,34 @@ class UNet(nn.Module):
         if not images_u8.is_cuda:
             raise RuntimeError("robosat_amd.UNet runs on the MI355X only (got a {} tensor); there is no CPU fallback".format(images_u8.device))
         mean, std = list(mean)[:self.in_channels], list(std)[:self.in_channels]
+        if tta != "none":
+            op_list = ops.tta_ops(tta, images_u8.size(1), images_u8.size(2))
 
-        def run(u8):
-            x4 = ops.u8_to_nhwc4_norm(u8, mean, std)
-            if self.compute_dtype == torch.bfloat16:
-                x4 = x4.to(torch.bfloat16)  # (device-side cast of the 4-channel image; the stem then runs in bf16)
-            return self._forward_eval(None, softmax=False, x4=x4, quantize_overlap=overlap)
+            def run(u8):
+                x4 = ops.tta_fan_out_u8(u8, mean, std, op_list, self.compute_dtype)
+                return ops.tta_merge(self._forward_eval(None, softmax=True, x4=x4), op_list, "quantize", overlap)
+        else:
+            op_list = [0]
+
+            def run(u8):
+                x4 = ops.u8_to_nhwc4_norm(u8, mean, std)
+                if self.compute_dtype == torch.bfloat16:
+                    x4 = x4.to(torch.bfloat16)  # (device-side cast of the 4-channel image; the stem then runs in bf16)
+                return self._forward_eval(None, softmax=False, x4=x4, quantize_overlap=overlap)
 
         images_u8 = images_u8.contiguous()
-        if self._want_graph(images_u8):
-            return self._graph_replay(("quantized", overlap, tuple(mean), tuple(std)), run, images_u8)
+        if self._want_graph(images_u8, len(op_list)):
+            return self._graph_replay(("quantized", overlap, tuple(mean), tuple(std), tta), run, images_u8)
         return run(images_u8)
 
     @torch.no_grad()
-    def predict_classes(self, images_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    def predict_classes(self, images_u8, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), tta="none"):
         """The device side of ``rs serve``'s ``Predictor.segment`` (reference tools/serve.py:149-164): uint8 HWC tiles
         ``[N,H,W,C]`` in -> ToTensor + Normalize -> U-Net -> ``argmax`` over the class logits -> uint8 ``[N,H,W]`` class
-        indices out (``self.final`` and the argmax are one kernel; the logits never reach HBM)."""
+        indices out (``self.final`` and the argmax are one kernel; the logits never reach HBM).
+
+        ``tta`` (see ``predict_probs``): the class is the first maximum of the merged PROBABILITIES (without TTA: of the logits).
+        Memory: V times the activations of the N-tile batch."""
 
         assert not self.training, "predict_classes is an eval-mode call"
         assert images_u8.dtype == torch.uint8 and images_u8.dim() == 4 and images_u8.size(3) == self.in_channels
@@ -541,16 +567,24 @@ class UNet(nn.Module):
         if not images_u8.is_cuda:
             raise RuntimeError("robosat_amd.UNet runs on the MI355X only (got a {} tensor); there is no CPU fallback".format(images_u8.device))
         mean, std = list(mean)[:self.in_channels], list(std)[:self.in_channels]
+        if tta != "none":
+            op_list = ops.tta_ops(tta, images_u8.size(1), images_u8.size(2))
 
-        def run(u8):
-            x4 = ops.u8_to_nhwc4_norm(u8, mean, std)
-            if self.compute_dtype == torch.bfloat16:
-                x4 = x4.to(torch.bfloat16)
-            return self._forward_eval(None, softmax=False, x4=x4, argmax=True)
+            def run(u8):
+                x4 = ops.tta_fan_out_u8(u8, mean, std, op_list, self.compute_dtype)
+                return ops.tta_merge(self._forward_eval(None, softmax=True, x4=x4), op_list, "argmax")
+        else:
+            op_list = [0]
+
+            def run(u8):
+                x4 = ops.u8_to_nhwc4_norm(u8, mean, std)
+                if self.compute_dtype == torch.bfloat16:
+                    x4 = x4.to(torch.bfloat16)
+                return self._forward_eval(None, softmax=False, x4=x4, argmax=True)
 
         images_u8 = images_u8.contiguous()
-        if self._want_graph(images_u8):
-            return self._graph_replay(("classes", tuple(mean), tuple(std)), run, images_u8)
+        if self._want_graph(images_u8, len(op_list)):
+            return self._graph_replay(("classes", tuple(mean), tuple(std), tta), run, images_u8)
         return run(images_u8)
 
     def _forward_eval(self, x, softmax, x4=None, quantize_overlap=None, argmax=False):
