@@ -568,6 +568,46 @@ int rs_softvote_masks(const uint8_t* q, const double* weights, const double* anc
 int rs_augment_tiles(const uint8_t* images, const uint8_t* masks, const int32_t* index, const int32_t* op, const float* mean,
                      const float* std, float* out_images, int64_t* out_masks, int N, int S, int C, rs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * `rs features` (robosat/tools/features.py, robosat/features/core.py): the raster stages on the device
+ * (csrc/features.hip).  Batched over B tiles of equal H x W, 1 <= H, W <= 4096, B <= 65535,
+ * B*H*W < 2^29 (so the edge count, at most 4 per pixel, fits the int32 counter); RS_EINVAL otherwise.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* disc(eps): eps x eps 0/1 matrix, r = c = eps / 2; row i (dy = i - r) has dx = rint(c * sqrt((r*r - dy*dy) / (r*r))) and
+ * columns max(c - dx, 0) .. min(c + dx + 1, eps) - 1 set (OpenCV's documented MORPH_ELLIPSE); S = {(i - r, j - c)} its offsets.
+ * erode(m)[p] = AND over s in S of m[p + s], outside the tile 1; dilate(m)[p] = OR over s in S of m[p - s], outside 0 (the
+ * reflected set: open(m) <= m <= close(m) and both idempotent for even eps too, where OpenCV anchors both at the same corner).
+ * rs_features_clean: out = close(open(images == index)) as 0/1 bytes [B][H][W]; open = dilate(erode) with disc(eps_open),
+ * close = erode(dilate) with disc(eps_close); eps 0 or 1 = identity, eps <= 64.  dx_open / dx_close: HOST arrays of eps ints, the
+ * rows' dx above.  form 1: bit-planes resident in LDS, one workgroup per tile (needs rs_features_clean_form(H, W) == 1, i.e. two
+ * planes of H * ceil(W/32) words within 160 KB); form 2: planes in `workspace` (rs_features_clean_workspace_bytes; may be NULL
+ * for form 1), one launch per pass; form 0: the library's choice (form 2: profiles/features).  Both forms give the same bytes. */
+int rs_features_clean_form(int H, int W);
+long rs_features_clean_workspace_bytes(int B, int H, int W);
+int rs_features_clean(const uint8_t* images, uint8_t* out, void* workspace, int B, int H, int W, int index, int eps_open,
+                      const int32_t* dx_open, int eps_close, const int32_t* dx_close, int form, rs_stream_t stream);
+
+/* 4-connected components of masks != 0: labels [B][H][W] int32, background 0, a component's label = 1 + min(y * W + x) over its
+ * pixels (canonical: independent of the order the device worked in).  Lock-free union-find; no workgroup waits for another and
+ * every loop is bounded by H*W.  *err (int32 in device memory, zeroed by the caller) is set non-zero should a bound run out. */
+int rs_features_label(const uint8_t* masks, int32_t* labels, int32_t* err, int B, int H, int W, rs_stream_t stream);
+
+/* Component table: one row [tile, label, area, x0, y0, x1, y1] (pixel count, inclusive bounding box) per component with
+ * area >= min_area, in no particular order.  counters (int32 [2], device): [0] = components found, [1] = rows kept; rows are
+ * written only below `capacity` (call again with capacity >= counters[0] if it was exceeded).  slotmap: int32 [B][H][W]
+ * scratch; raw: int32 [capacity][6] scratch; table: int32 [capacity][7]. */
+int rs_features_components(const int32_t* labels, int32_t* slotmap, int32_t* raw, int32_t* table, int32_t* counters,
+                           long capacity, int B, int H, int W, int min_area, rs_stream_t stream);
+
+/* Boundary edges of the components listed in `table` (`rows` rows as above): a pixel (x, y) of label L emits one directed unit
+ * edge per 4-neighbour whose label is not L (outside the tile counts), walking round the pixel with the pixel on the right --
+ * dir 0 top (x,y)->(x+1,y), 1 right (x+1,y)->(x+1,y+1), 2 bottom (x+1,y+1)->(x,y+1), 3 left (x,y+1)->(x,y).  Rows
+ * [tile, label, x, y, dir] int32 in no particular order; *counter (int32, device) = number of edges, rows written only below
+ * `capacity` (capacity 0, edges NULL: count only).  keep: B*H*W bytes of scratch. */
+int rs_features_edges(const int32_t* labels, const int32_t* table, long rows, uint8_t* keep, int32_t* edges, long capacity,
+                      int32_t* counter, int B, int H, int W, rs_stream_t stream);
+
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ROBOSAT_HIP_LIB") or os.path.join(_HERE, "librobosat_hip.so")
 
 RS_EINVAL = -22
-ABI_VERSION = 23
+ABI_VERSION = 24
 RS_F32, RS_BF16 = 0, 1
 RS_TTA_IN_U8, RS_TTA_IN_F32 = 0, 1
 RS_TTA_PROBS, RS_TTA_QUANTIZE, RS_TTA_ARGMAX = 0, 1, 2
@@ -151,6 +151,13 @@ SIGNATURES = {
     "rs_label_histogram_u8": (c_int, [P, c_long, P, P]),
     "rs_softvote_masks": (c_int, [P, P, P, P, c_int, c_long, c_int, P]),
     "rs_augment_tiles": (c_int, [P, P, P, P, POINTER(c_float), POINTER(c_float), P, P, c_int, c_int, c_int, P]),
+    # rs features: raster stages (csrc/features.hip)
+    "rs_features_clean_form": (c_int, [c_int, c_int]),
+    "rs_features_clean_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "rs_features_clean": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, POINTER(c_int32), c_int, POINTER(c_int32), c_int, P]),
+    "rs_features_label": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "rs_features_components": (c_int, [P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
+    "rs_features_edges": (c_int, [P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),
 }
 
 _lib = None

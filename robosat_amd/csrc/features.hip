@@ -1,0 +1,473 @@
+// `rs features` on the device: the raster half of robosat/tools/features.py + robosat/features/core.py (class select, morphological
+// open / close with a disc, 4-connected components, boundary edges).  Integer work, LDS / HBM bound.  Definitions: include/robosat_hip.h.
+//
+//   rs_features_clean       mask bytes -> bit-planes (one __ballot packs a wave's 64 pixels) -> erode, dilate, dilate, erode -> 0/1 bytes.
+//                           A disc is a stack of horizontal runs: a pass ANDs (ORs) funnel-shifted words of the eps rows around a word.
+//                           LDS form: one block per tile, both planes resident, no HBM between the passes.  HBM form: one launch per pass
+//                           (the default: a batch of 16 tiles fills 16 CUs in the LDS form and all of them in this one).
+//                           Both run the same morph_word() on the same bits.
+//   rs_features_label       union-find over the pixel grid with atomicMin (lock-free; every loop counted against H*W), then flatten:
+//                           the root of a component is its smallest y*W+x, so label = root + 1 is canonical.
+//   rs_features_components  roots -> slots, area / bounding box per slot by integer atomics, min_area filter, compaction.
+//   rs_features_edges       directed unit boundary edges of the kept components, compacted by one atomic per wave.
+#include "common.h"
+
+namespace {
+
+constexpr int kMaxEps = 64;                  // a run reaches at most 32 bits to either side: one neighbouring word
+constexpr int kLdsBytes = 160 * 1024;        // gfx950 LDS per workgroup
+constexpr int kCleanThreads = 1024;
+
+struct Disc {
+  int eps;
+  signed char lo[kMaxEps], hi[kMaxEps];  // row i (dy = i - eps/2): offsets lo..hi set
+};
+
+struct CleanArgs {
+  const uint8_t* images;
+  uint8_t* out;
+  uint32_t* ws;  // HBM form: [B][2][H][Wd]
+  int B, H, W, Wd, index;
+  Disc open, close;
+};
+
+// One output word of erode (ERODE: AND over s of m[p + s], outside = 1) or dilate (OR over s of m[p - s], outside = 0).
+// `src`: plane [H][Wd] whose bits beyond W are 0.
+template <bool ERODE>
+__device__ __forceinline__ uint32_t morph_word(const uint32_t* src, const Disc& d, int y, int wx, int H, int W, int Wd) {
+  const uint32_t pad = ERODE ? 0xffffffffu : 0u;
+  const int r = d.eps >> 1;
+  const int tail = W & 31;
+  const uint32_t valid_last = tail ? ((1u << tail) - 1u) : 0xffffffffu;
+  uint32_t acc = pad;
+  for (int i = 0; i < d.eps; ++i) {
+    const int yy = ERODE ? y + (i - r) : y - (i - r);
+    const int lo = ERODE ? d.lo[i] : -d.hi[i], hi = ERODE ? d.hi[i] : -d.lo[i];
+    uint32_t prev = pad, cur = pad, next = pad;
+    if (yy >= 0 && yy < H) {
+      const uint32_t* row = src + (long)yy * Wd;
+      cur = row[wx];
+      if (ERODE && wx == Wd - 1) cur |= ~valid_last;
+      if (wx > 0) prev = row[wx - 1];
+      if (wx + 1 < Wd) {
+        next = row[wx + 1];
+        if (ERODE && wx + 1 == Wd - 1) next |= ~valid_last;
+      }
+    }
+    for (int o = lo; o <= hi; ++o) {
+      // bits x + o, x = 0..31
+      uint32_t v;
+      if (o == 0)
+        v = cur;
+      else if (o > 0)
+        v = o == 32 ? next : __funnelshift_r(cur, next, o);
+      else
+        v = o == -32 ? prev : __funnelshift_r(prev, cur, 32 + o);
+      acc = ERODE ? (acc & v) : (acc | v);
+    }
+  }
+  if (wx == Wd - 1) acc &= valid_last;
+  return acc;
+}
+
+// mask = (image == index) packed 32 pixels per word, bits beyond W zero.  Wave-uniform loop: every lane reaches the ballot.
+__device__ __forceinline__ void select_pack(const uint8_t* img, uint32_t* plane, int H, int W, int Wd, int index, int wave, int nwaves,
+                                            int lane) {
+  const int chunks = (W + 63) >> 6;
+  for (int item = wave; item < H * chunks; item += nwaves) {
+    const int y = item / chunks, ch = item - y * chunks;
+    const int x = ch * 64 + lane;
+    const bool fg = x < W && img[(long)y * W + x] == (uint8_t)index;
+    const unsigned long long m = __ballot(fg);
+    if (lane == 0) plane[(long)y * Wd + ch * 2] = (uint32_t)m;
+    if (lane == 32 && ch * 2 + 1 < Wd) plane[(long)y * Wd + ch * 2 + 1] = (uint32_t)(m >> 32);
+  }
+}
+
+__global__ __launch_bounds__(kCleanThreads) void clean_lds_kernel(const CleanArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t planes[];
+  const int H = a.H, W = a.W, Wd = a.Wd, words = H * Wd;
+  uint32_t* p0 = planes;
+  uint32_t* p1 = planes + words;
+  const long HW = (long)H * W;
+  const uint8_t* img = a.images + (long)blockIdx.x * HW;
+  select_pack(img, p0, H, W, Wd, a.index, threadIdx.x >> 6, kCleanThreads >> 6, threadIdx.x & 63);
+  rs_lds_writes_done();
+  __syncthreads();
+  uint32_t* src = p0;
+  uint32_t* dst = p1;
+  for (int pass = 0; pass < 4; ++pass) {  // erode, dilate (open), dilate, erode (close)
+    const Disc& d = pass < 2 ? a.open : a.close;
+    if (d.eps <= 1) continue;  // (uniform)
+    const bool erode = pass == 0 || pass == 3;
+    for (int i = threadIdx.x; i < words; i += kCleanThreads) {
+      const int y = i / Wd, wx = i - y * Wd;
+      dst[i] = erode ? morph_word<true>(src, d, y, wx, H, W, Wd) : morph_word<false>(src, d, y, wx, H, W, Wd);
+    }
+    rs_lds_writes_done();
+    __syncthreads();
+    uint32_t* t = src;
+    src = dst;
+    dst = t;
+  }
+  uint8_t* out = a.out + (long)blockIdx.x * HW;
+  for (long p = threadIdx.x; p < HW; p += kCleanThreads) {
+    const int y = (int)(p / W), x = (int)(p - (long)y * W);
+    out[p] = (uint8_t)((src[y * Wd + (x >> 5)] >> (x & 31)) & 1u);
+  }
+}
+
+// HBM form: planes in global memory, one launch per stage.
+__global__ __launch_bounds__(256) void clean_select_kernel(const CleanArgs a) {
+  const int tile = blockIdx.y;
+  const long words = (long)a.H * a.Wd;
+  select_pack(a.images + (long)tile * a.H * a.W, a.ws + (long)tile * 2 * words, a.H, a.W, a.Wd, a.index,
+              blockIdx.x * 4 + (threadIdx.x >> 6), gridDim.x * 4, threadIdx.x & 63);
+}
+
+template <bool ERODE>
+__global__ __launch_bounds__(256) void clean_pass_kernel(const CleanArgs a, const Disc d, int from) {
+  const int tile = blockIdx.y;
+  const long words = (long)a.H * a.Wd;
+  const uint32_t* src = a.ws + ((long)tile * 2 + from) * words;
+  uint32_t* dst = a.ws + ((long)tile * 2 + (from ^ 1)) * words;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= words) return;
+  const int y = (int)(i / a.Wd), wx = (int)(i - (long)y * a.Wd);
+  dst[i] = morph_word<ERODE>(src, d, y, wx, a.H, a.W, a.Wd);
+}
+
+__global__ __launch_bounds__(256) void clean_unpack_kernel(const CleanArgs a, int from) {
+  const int tile = blockIdx.y;
+  const long HW = (long)a.H * a.W;
+  const uint32_t* src = a.ws + ((long)tile * 2 + from) * (long)a.H * a.Wd;
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= HW) return;
+  const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
+  a.out[tile * HW + p] = (uint8_t)((src[(long)y * a.Wd + (x >> 5)] >> (x & 31)) & 1u);
+}
+
+bool make_disc(int eps, const int32_t* dx, Disc* d) {
+  d->eps = eps;
+  if (eps < 0 || eps > kMaxEps) return false;
+  if (eps > 1 && !dx) return false;
+  const int c = eps / 2;
+  for (int i = 0; i < eps && eps > 1; ++i) {
+    if (dx[i] < 0 || dx[i] > c) return false;
+    const int lo = dx[i] < c ? dx[i] : c, hi = dx[i] < eps - 1 - c ? dx[i] : eps - 1 - c;
+    d->lo[i] = (signed char)-lo;
+    d->hi[i] = (signed char)hi;
+  }
+  return true;
+}
+
+// ---- labelling -------------------------------------------------------------------------------------------------------
+// parent[p] = 1 + index of a pixel of the same component with a smaller or equal index (background 0); a root has parent[p] == p + 1.
+// Links only ever decrease, so a chain from p has at most p + 1 <= H*W steps: that is the bound of every loop below.  A loop that runs
+// out of its bound raises *err (the host turns it into an exception) instead of going on.
+
+__device__ __forceinline__ int uf_find(int* L, int p, int bound, int* err) {
+  int cur = p;
+  for (int it = 0; it <= bound; ++it) {
+    const int par = __hip_atomic_load(&L[cur], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - 1;
+    if (par == cur) {
+      if (cur != p) atomicMin(&L[p], cur + 1);  // compression: the root is an ancestor, and smaller
+      return cur;
+    }
+    cur = par;
+  }
+  atomicOr(err, 1);
+  return cur;
+}
+
+__device__ __forceinline__ void uf_union(int* L, int a, int b, int bound, int* err) {
+  for (int it = 0; it <= bound; ++it) {
+    a = uf_find(L, a, bound, err);
+    b = uf_find(L, b, bound, err);
+    if (a == b) return;
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicMin(&L[a], b + 1) - 1;  // a > b: hang root a under b
+    if (old == a) return;                        // a was still a root: linked
+    a = old;                                     // somebody linked a first: go on from where it points
+  }
+  atomicOr(err, 2);
+}
+
+// parent = start of the pixel's horizontal run inside its 64-pixel chunk (one ballot per chunk): rows are linked without a single atomic.
+__global__ __launch_bounds__(256) void label_init_kernel(const uint8_t* __restrict__ m, int* __restrict__ L, int B, int H, int W) {
+  const int lane = threadIdx.x & 63;
+  const int chunks = (W + 63) >> 6;
+  const long items = (long)B * H * chunks;
+  for (long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * 4) {
+    const long row = item / chunks;  // tile * H + y
+    const int ch = (int)(item - row * chunks);
+    const int y = (int)(row % H);
+    const int x = ch * 64 + lane;
+    const bool fg = x < W && m[row * W + x] != 0;
+    const unsigned long long mask = __ballot(fg);
+    if (x < W) {
+      const unsigned long long below = ~mask & ((1ull << lane) - 1ull);  // background pixels of the chunk left of this lane
+      const int start = below ? 64 - __clzll((long long)below) : 0;
+      L[row * W + x] = fg ? y * W + ch * 64 + start + 1 : 0;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void label_merge_kernel(const uint8_t* __restrict__ m, int* L, int* err, int B, int H, int W) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)B * HW) return;
+  const long tile = g / HW;
+  const int p = (int)(g - tile * HW);
+  const uint8_t* mt = m + tile * HW;
+  if (!mt[p]) return;
+  int* Lt = L + tile * HW;
+  const int y = p / W, x = p - y * W;
+  const bool left = x > 0 && mt[p - 1];
+  if (left && (x & 63) == 0) uf_union(Lt, p, p - 1, (int)HW, err);
+  // (up is redundant where left and up-left are both set: the pixel to the left makes the same link)
+  if (y > 0 && mt[p - W] && !(left && mt[p - W - 1])) uf_union(Lt, p, p - W, (int)HW, err);
+}
+
+__global__ __launch_bounds__(256) void label_flatten_kernel(int* L, int* err, int B, int H, int W) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)B * HW) return;
+  const long tile = g / HW;
+  const int p = (int)(g - tile * HW);
+  int* Lt = L + tile * HW;
+  if (Lt[p] == 0) return;
+  const int root = uf_find(Lt, p, (int)HW, err);
+  atomicMin(&Lt[p], root + 1);
+}
+
+// ---- component table ---------------------------------------------------------------------------------------------------
+// raw rows: [label, area, x0, y0, x1, y1]; table rows: [tile, label, area, x0, y0, x1, y1] (bounding box inclusive).
+// counters[0] = roots found, counters[1] = components kept: both counted past `capacity`, written only below it.
+
+__global__ __launch_bounds__(256) void comp_roots_kernel(const int* __restrict__ L, int* slotmap, int* raw, int* counters, long capacity,
+                                                         int B, int H, int W) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)B * HW) return;
+  const int p = (int)(g % HW);
+  if (L[g] != p + 1) return;
+  const int slot = atomicAdd(&counters[0], 1);
+  slotmap[g] = slot;
+  if (slot < capacity) {
+    int* r = raw + (long)slot * 6;
+    r[0] = p + 1;
+    r[1] = 0;
+    r[2] = W;
+    r[3] = H;
+    r[4] = -1;
+    r[5] = -1;
+  }
+}
+
+// One set of atomics per horizontal run of a label inside a wave's 64 consecutive pixels, not per pixel (a blob's pixels all hit the six
+// ints of one row: per pixel that serialised to 1.4 ms for a 512 x 512 x 16 batch).  A lane heads a run where the lane before it
+// (__shfl_up) is another label, another row or another wave; the run ends at the next head or background lane (one ballot).
+__global__ __launch_bounds__(256) void comp_stats_kernel(const int* __restrict__ L, const int* __restrict__ slotmap, int* raw,
+                                                         long capacity, int B, int H, int W) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool in = g < (long)B * HW;  // (no early return: every lane reaches the shuffle and the ballot)
+  const int lab = in ? L[g] : 0;
+  const long tile = in ? g / HW : 0;
+  const int p = (int)(g - tile * HW);
+  const int y = p / W, x = p - y * W;
+  const int before = __shfl_up(lab, 1, 64);
+  const bool head = lab != 0 && (lane == 0 || x == 0 || before != lab);
+  const unsigned long long ends = __ballot(head || lab == 0);
+  if (!head) return;
+  const unsigned long long above = lane == 63 ? 0ull : ends & ~((2ull << lane) - 1ull);
+  const int len = (above ? __ffsll((long long)above) - 1 : 64) - lane;  // the run stays in this row: x == 0 is a head
+  const int slot = slotmap[tile * HW + lab - 1];
+  if (slot >= capacity) return;
+  int* r = raw + (long)slot * 6;
+  atomicAdd(&r[1], len);
+  atomicMin(&r[2], x);
+  atomicMin(&r[3], y);
+  atomicMax(&r[4], x + len - 1);
+  atomicMax(&r[5], y);
+}
+
+__global__ __launch_bounds__(256) void comp_filter_kernel(const int* __restrict__ L, const int* __restrict__ slotmap,
+                                                          const int* __restrict__ raw, int* table, int* counters, long capacity, int B,
+                                                          int H, int W, int min_area) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)B * HW) return;
+  const int p = (int)(g % HW);
+  if (L[g] != p + 1) return;
+  const int slot = slotmap[g];
+  if (slot >= capacity) return;
+  const int* r = raw + (long)slot * 6;
+  if (r[1] < min_area) return;
+  const int k = atomicAdd(&counters[1], 1);
+  if (k >= capacity) return;
+  int* t = table + (long)k * 7;
+  t[0] = (int)(g / HW);
+#pragma unroll
+  for (int j = 0; j < 6; ++j) t[1 + j] = r[j];
+}
+
+// ---- boundary edges ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void edges_mark_kernel(const int* __restrict__ table, long rows, uint8_t* keep, int B, long HW) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows) return;
+  const int tile = table[i * 7], lab = table[i * 7 + 1];
+  if (tile >= 0 && tile < B && lab >= 1 && lab <= HW) keep[(long)tile * HW + lab - 1] = 1;
+}
+
+// Walking round the pixel with the pixel on the right: 0 top (x,y)->(x+1,y), 1 right, 2 bottom, 3 left.  Rows [tile, label, x, y, dir].
+// *counter counts every edge; rows are written only below `capacity` (a first call with capacity 0 sizes the list).
+__global__ __launch_bounds__(256) void edges_emit_kernel(const int* __restrict__ L, const uint8_t* __restrict__ keep, int* edges,
+                                                         long capacity, unsigned int* counter, int B, int H, int W) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int lab = 0, x = 0, y = 0, tile = 0;
+  unsigned int dirs = 0;
+  if (g < (long)B * HW) {
+    tile = (int)(g / HW);
+    const int p = (int)(g - (long)tile * HW);
+    lab = L[g];
+    if (lab && keep[(long)tile * HW + lab - 1]) {
+      y = p / W;
+      x = p - y * W;
+      if (y == 0 || L[g - W] != lab) dirs |= 1u;
+      if (x == W - 1 || L[g + 1] != lab) dirs |= 2u;
+      if (y == H - 1 || L[g + W] != lab) dirs |= 4u;
+      if (x == 0 || L[g - 1] != lab) dirs |= 8u;
+    }
+  }
+  const int n = __popc(dirs);
+  int incl = n;  // inclusive prefix sum over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  const int total = __shfl(incl, 63, 64);
+  if (total == 0) return;  // (uniform)
+  unsigned int base = 0;
+  if (lane == 63) base = atomicAdd(counter, (unsigned int)total);
+  base = __shfl(base, 63, 64);
+  long k = (long)base + incl - n;
+  for (int d = 0; d < 4; ++d)
+    if (dirs & (1u << d)) {
+      if (k < capacity) {
+        int* e = edges + k * 5;
+        e[0] = tile;
+        e[1] = lab;
+        e[2] = x;
+        e[3] = y;
+        e[4] = d;
+      }
+      ++k;
+    }
+}
+
+// (B rides in gridDim.y; 4 edges per pixel at the very most stay below 2^31 in the int32 edge counter)
+bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)B * H * W < (1l << 29); }
+
+}  // namespace
+
+extern "C" int rs_features_clean_form(int H, int W) {
+  if (H <= 0 || W <= 0) return RS_EINVAL;
+  const long plane = (long)H * ((W + 31) / 32) * 4;
+  return 2 * plane <= kLdsBytes ? 1 : 2;
+}
+
+extern "C" long rs_features_clean_workspace_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return RS_EINVAL;
+  return (long)B * 2 * H * ((W + 31) / 32) * 4;
+}
+
+extern "C" int rs_features_clean(const uint8_t* images, uint8_t* out, void* workspace, int B, int H, int W, int index, int eps_open,
+                                 const int32_t* dx_open, int eps_close, const int32_t* dx_close, int form, rs_stream_t stream) {
+  if (!images || !out || !shape_ok(B, H, W) || index < 0 || index > 255 || form < 0 || form > 2) return RS_EINVAL;
+  CleanArgs a;
+  if (!make_disc(eps_open, dx_open, &a.open) || !make_disc(eps_close, dx_close, &a.close)) return RS_EINVAL;
+  a.images = images;
+  a.out = out;
+  a.ws = static_cast<uint32_t*>(workspace);
+  a.B = B, a.H = H, a.W = W, a.Wd = (W + 31) / 32, a.index = index;
+  const int fits = rs_features_clean_form(H, W);
+  if (form == 0) form = 2;  // measured at 512 x 512, batch 16: 0.12 ms through HBM on every CU against 1.2 ms on 16 LDS-resident workgroups
+  if (form == 1 && fits != 1) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long words = (long)H * a.Wd;
+  if (form == 1) {
+    const int lds = (int)(2 * words * 4);
+    if (lds > 64 * 1024) {
+      const hipError_t e = hipFuncSetAttribute((const void*)clean_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+      if (e != hipSuccess) return (int)e;
+    }
+    clean_lds_kernel<<<B, kCleanThreads, lds, s>>>(a);
+    return RS_LAUNCH_RESULT();
+  }
+  if (!workspace) return RS_EINVAL;
+  const int chunks = (W + 63) / 64;
+  const long items = (long)H * chunks;
+  clean_select_kernel<<<dim3(rs_cdiv(items, 4) < 1024 ? rs_cdiv(items, 4) : 1024, B), 256, 0, s>>>(a);
+  int from = 0;
+  const dim3 grid(rs_cdiv(words, 256), B);
+  for (int pass = 0; pass < 4; ++pass) {
+    const Disc& d = pass < 2 ? a.open : a.close;
+    if (d.eps <= 1) continue;
+    if (pass == 0 || pass == 3)
+      clean_pass_kernel<true><<<grid, 256, 0, s>>>(a, d, from);
+    else
+      clean_pass_kernel<false><<<grid, 256, 0, s>>>(a, d, from);
+    from ^= 1;
+  }
+  clean_unpack_kernel<<<dim3(rs_cdiv((long)H * W, 256), B), 256, 0, s>>>(a, from);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_label(const uint8_t* masks, int32_t* labels, int32_t* err, int B, int H, int W, rs_stream_t stream) {
+  if (!masks || !labels || !err || !shape_ok(B, H, W)) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)B * H * W;
+  const long items = (long)B * H * ((W + 63) / 64);
+  label_init_kernel<<<rs_cdiv(items, 4) < 8192 ? rs_cdiv(items, 4) : 8192, 256, 0, s>>>(masks, labels, B, H, W);
+  label_merge_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(masks, labels, err, B, H, W);
+  label_flatten_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(labels, err, B, H, W);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_components(const int32_t* labels, int32_t* slotmap, int32_t* raw, int32_t* table, int32_t* counters,
+                                      long capacity, int B, int H, int W, int min_area, rs_stream_t stream) {
+  if (!labels || !slotmap || !counters || capacity < 0 || (capacity > 0 && (!raw || !table)) || !shape_ok(B, H, W)) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)B * H * W;
+  const int grid = rs_cdiv(P, 256);
+  const hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  comp_roots_kernel<<<grid, 256, 0, s>>>(labels, slotmap, raw, counters, capacity, B, H, W);
+  comp_stats_kernel<<<grid, 256, 0, s>>>(labels, slotmap, raw, capacity, B, H, W);
+  comp_filter_kernel<<<grid, 256, 0, s>>>(labels, slotmap, raw, table, counters, capacity, B, H, W, min_area);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_edges(const int32_t* labels, const int32_t* table, long rows, uint8_t* keep, int32_t* edges, long capacity,
+                                 int32_t* counter, int B, int H, int W, rs_stream_t stream) {
+  if (!labels || !keep || !counter || rows < 0 || (rows > 0 && !table) || capacity < 0 || (capacity > 0 && !edges) || !shape_ok(B, H, W))
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)B * H * W;
+  hipError_t e = hipMemsetAsync(keep, 0, P, s);
+  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (rows > 0) edges_mark_kernel<<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, B, (long)H * W);
+  edges_emit_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(labels, keep, edges, capacity, reinterpret_cast<unsigned int*>(counter), B, H, W);
+  return RS_LAUNCH_RESULT();
+}

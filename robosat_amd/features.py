@@ -1,0 +1,220 @@
+"""Host half of ``rs features``: boundary edges -> rings -> simplified, georeferenced GeoJSON polygons (numpy + stdlib only;
+the reference uses OpenCV contours, shapely and geojson: ``robosat/features/core.py``, ``robosat/features/parking.py``).
+
+Vertices are pixel corners, integer (x, y) in [0, W] x [0, H], y down.  An edge row is ``(tile, label, x, y, dir)``: the
+pixel (x, y) of component ``label`` walked round with the pixel on the right -- dir 0 top (x,y)->(x+1,y), 1 right
+(x+1,y)->(x+1,y+1), 2 bottom (x+1,y+1)->(x,y+1), 3 left (x,y+1)->(x,y).  With that orientation the shoelace area of a
+component's outer ring is positive, its holes' negative, and the areas of its rings sum to its pixel count."""
+
+import json
+import sys
+
+import numpy as np
+
+from robosat_amd.tiles import pixel_to_location
+
+_SX = np.array([0, 1, 1, 0], dtype=np.int64)  # start corner of an edge, relative to its pixel
+_SY = np.array([0, 0, 1, 1], dtype=np.int64)
+_DX = np.array([1, 0, -1, 0], dtype=np.int64)  # heading
+_DY = np.array([0, 1, 0, -1], dtype=np.int64)
+
+
+def signed_area(ring):
+    """Shoelace area of an open ring [[x, y], ...] (positive for the outer rings ``link_rings`` returns); exact for integers."""
+
+    ring = np.asarray(ring)
+    x, y = ring[:, 0], ring[:, 1]
+    twice = np.sum(x * np.roll(y, -1) - np.roll(x, -1) * y)
+    return twice / 2 if twice % 2 else twice // 2
+
+
+def _rotate_to_smallest(ring):
+    start = np.lexsort((ring[:, 1], ring[:, 0]))[0]
+    return np.roll(ring, -start, axis=0)
+
+
+def link_rings(edges, turns=(3, 0, 1)):
+    """Edge rows int [E, 5] in any order -> ``{(tile, label): [ring, ...]}``; a ring is an int64 array [k, 2] of unit-step
+    vertices, not closed, started at its lexicographically smallest (x, y); the component's outer ring first, then its holes
+    ordered by their first vertex.
+
+    Edges of one label link head to tail.  Where a vertex has two outgoing edges of the label (two of its pixels meeting
+    only at that corner) the walk takes the LEFT turn, onto the diagonally opposite pixel's edge: rings then never touch
+    themselves, and every component has exactly one ring of positive area.  ``turns`` is that preference (left, straight, right as
+    dir + 3, + 0, + 1); the tests pass the right turn first to show what it does."""
+
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 5)
+    n = len(e)
+    if n == 0:
+        return {}
+    tile, label, x, y, d = e.T
+    assert tile.min() >= 0 and tile.max() < 1024 and label.min() >= 1 and label.max() <= 1 << 24, "tile < 1024, label <= 2^24"
+    assert x.min() >= 0 and y.min() >= 0 and max(x.max(), y.max()) < 4096 and d.min() >= 0 and d.max() <= 3
+    sx, sy = x + _SX[d], y + _SY[d]
+    ex, ey = sx + _DX[d], sy + _DY[d]
+    group = tile << 25 | label
+
+    def key(g, vx, vy, direction):
+        return ((g << 26 | vy << 13 | vx) << 2) | direction
+
+    out_key = key(group, sx, sy, d)
+    order = np.argsort(out_key, kind="stable")
+    sorted_keys = out_key[order]
+    assert n == 1 or (np.diff(sorted_keys) > 0).all(), "duplicate edges"
+    nxt = np.full(n, -1, dtype=np.int64)
+    for turn in turns:  # left, straight, right
+        want = key(group, ex, ey, (d + turn) & 3)
+        pos = np.minimum(np.searchsorted(sorted_keys, want), n - 1)
+        hit = (sorted_keys[pos] == want) & (nxt < 0)
+        nxt[hit] = order[pos[hit]]
+    assert (nxt >= 0).all(), "an edge without a successor: the edge list is not the boundary of a label image"
+
+    nxt_l, order_l = nxt.tolist(), order.tolist()
+    seen = bytearray(n)
+    rings = {}
+    for start in order_l:
+        if seen[start]:
+            continue
+        idx = []
+        cur = start
+        while not seen[cur]:
+            seen[cur] = 1
+            idx.append(cur)
+            cur = nxt_l[cur]
+        assert cur == start, "edges do not close into a ring"
+        idx = np.array(idx)
+        ring = _rotate_to_smallest(np.stack([sx[idx], sy[idx]], axis=1))
+        rings.setdefault((int(tile[start]), int(label[start])), []).append(ring)
+    for key_, group_rings in rings.items():
+        group_rings.sort(key=lambda r: (signed_area(r) < 0, int(r[0, 0]), int(r[0, 1])))
+    return rings
+
+
+def drop_collinear(ring):
+    """The ring without the vertices at which it does not turn."""
+
+    ring = np.asarray(ring)
+    a, b = ring - np.roll(ring, 1, axis=0), np.roll(ring, -1, axis=0) - ring
+    turn = a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]
+    return ring[turn != 0]
+
+
+def perimeter(ring):
+    ring = np.asarray(ring, dtype=np.float64)
+    return float(np.sqrt(((np.roll(ring, -1, axis=0) - ring) ** 2).sum(axis=1)).sum())
+
+
+def _line_distance(points, a, b):
+    ab = b - a
+    norm = np.hypot(ab[0], ab[1])
+    if norm == 0:
+        return np.hypot(points[:, 0] - a[0], points[:, 1] - a[1])
+    return np.abs(ab[0] * (points[:, 1] - a[1]) - ab[1] * (points[:, 0] - a[0])) / norm
+
+
+def simplify_ring(ring, simplify):
+    """Collinear vertices dropped, then (simplify > 0) Douglas-Peucker with epsilon = simplify * perimeter of the ring
+    (``robosat/features/core.py:123``) in its closed-ring form: the ring is started at its lexicographically smallest vertex
+    v0 and split at the vertex farthest from v0 (the first such), and each half is reduced as an open line, keeping a vertex
+    where the largest distance to the chord exceeds epsilon.  Returns an open ring, possibly with fewer than 3 vertices."""
+
+    ring = drop_collinear(ring)
+    if simplify <= 0 or len(ring) < 3:
+        return ring
+    ring = _rotate_to_smallest(ring)
+    epsilon = simplify * perimeter(ring)
+    pts = np.concatenate([ring, ring[:1]]).astype(np.float64)
+    n = len(ring)
+    far = int(np.argmax(np.hypot(pts[:n, 0] - pts[0, 0], pts[:n, 1] - pts[0, 1])))
+    keep = np.zeros(n + 1, dtype=bool)
+    keep[[0, far, n]] = True
+    stack = [(0, far), (far, n)]
+    while stack:
+        lo, hi = stack.pop()
+        if hi - lo < 2:
+            continue
+        dist = _line_distance(pts[lo + 1:hi], pts[lo], pts[hi])
+        k = int(np.argmax(dist))
+        if dist[k] > epsilon:
+            mid = lo + 1 + k
+            keep[mid] = True
+            stack += [(lo, mid), (mid, hi)]
+    keep[n] = False
+    if far == 0 or not np.hypot(*(pts[far] - pts[0])) > epsilon:  # the whole ring lies within epsilon of one point
+        return ring[:1]
+    return ring[keep[:n]]
+
+
+def polygon_is_valid(rings):
+    """False where any two segments of the polygon's rings cross properly (their interiors meet in one point).  Plain
+    O(n^2) orientation tests, exact for integer vertices."""
+
+    seg_a, seg_b = [], []
+    for ring in rings:
+        ring = np.asarray(ring, dtype=np.int64)
+        seg_a.append(ring)
+        seg_b.append(np.roll(ring, -1, axis=0))
+    a, b = np.concatenate(seg_a), np.concatenate(seg_b)
+
+    def orient(p, q, r):  # sign of (q - p) x (r - p), broadcast
+        return np.sign((q[..., 0] - p[..., 0]) * (r[..., 1] - p[..., 1]) - (q[..., 1] - p[..., 1]) * (r[..., 0] - p[..., 0]))
+
+    for start in range(0, len(a), 256):
+        p, q = a[start:start + 256, None, :], b[start:start + 256, None, :]
+        r, s = a[None, :, :], b[None, :, :]
+        if ((orient(p, q, r) * orient(p, q, s) < 0) & (orient(r, s, p) * orient(r, s, q) < 0)).any():
+            return False
+    return True
+
+
+def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr):
+    """Edge rows + component table rows (tile, label, area, ...) of one batch -> GeoJSON features.  ``tiles[i]`` is the
+    ``Tile`` of batch index i, ``shape`` = (H, W).  Rings are simplified, checked, reversed to RFC 7946 winding (outer ring
+    counter-clockwise, holes clockwise in lon / lat), closed and georeferenced from pixel corners.  Plain GeoJSON Feature
+    dicts, ordered by (batch index, label)."""
+
+    h, w = shape
+    area = {(int(r[0]), int(r[1])): int(r[2]) for r in np.asarray(table).reshape(-1, 7)}
+    features = []
+    for (index, label), rings in sorted(link_rings(edges).items()):
+        tile = tiles[index]
+        outer = simplify_ring(rings[0], simplify)
+        if len(outer) < 3:
+            print("Warning: simplified feature no longer valid polygon, skipping", file=warn)
+            continue
+        kept = [outer] + [r for r in (simplify_ring(hole, simplify) for hole in rings[1:]) if len(r) >= 3]
+        if simplify > 0 and not polygon_is_valid(kept):
+            print("Warning: extracted feature is not valid, skipping", file=warn)
+            continue
+        coordinates = []
+        for ring in kept:
+            ring = ring[::-1]  # y points down in the tile and up on the map
+            closed = [pixel_to_location(tile, int(px) / w, int(py) / h) for px, py in ring]
+            coordinates.append([[lon, lat] for lon, lat in closed + closed[:1]])
+        features.append({
+            "type": "Feature",
+            "geometry": {"type": "Polygon", "coordinates": coordinates},
+            "properties": {"tile": [int(tile.x), int(tile.y), int(tile.z)], "area_px": area[(index, label)]},
+        })
+    return features
+
+
+class FeatureWriter:
+    """Collects features and writes one FeatureCollection ordered by (z, x, y, label): two runs over the same masks give
+    byte-identical files (floats are printed by ``repr``).  The features of a tile arrive in label order from one
+    ``featurize`` call, so a stable sort by the tile is that order."""
+
+    def __init__(self):
+        self.features = []
+
+    def add(self, features):
+        self.features.extend(features)
+
+    def save(self, out):
+        def by_tile(feature):
+            x, y, z = feature["properties"]["tile"]
+            return z, x, y
+
+        collection = {"type": "FeatureCollection", "features": sorted(self.features, key=by_tile)}
+        with open(out, "w") as fp:
+            json.dump(collection, fp)

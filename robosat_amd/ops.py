@@ -1414,3 +1414,128 @@ def augment_tiles(images, masks, index, op, mean, std):
                                      _dev(om, "out_masks", torch.int64), n, s, c, _stream())
     check(rc, "rs_augment_tiles")
     return out, om
+
+
+# ---- rs features: raster stages (csrc/features.hip; definitions in include/robosat_hip.h) --------------------------------
+CLEAN_AUTO, CLEAN_LDS, CLEAN_HBM = 0, 1, 2
+
+
+def disc_rows(eps):
+    """Per-row half-widths dx of ``disc(eps)`` (OpenCV's documented MORPH_ELLIPSE, eps x eps): r = c = eps // 2, row i has
+    dy = i - r, dx = rint(c * sqrt((r*r - dy*dy) / (r*r))) and columns max(c - dx, 0) .. min(c + dx + 1, eps) - 1 set."""
+
+    import math
+
+    r = c = eps // 2
+    rows = []
+    for i in range(eps):
+        dy = i - r
+        rows.append(int(round(c * math.sqrt((r * r - dy * dy) / (r * r)))) if r else 0)  # (round: half to even, as rint)
+    return rows
+
+
+def disc(eps):
+    """``disc(eps)`` as an eps x eps uint8 0/1 numpy matrix (what ``getStructuringElement(MORPH_ELLIPSE, (eps, eps))`` documents)."""
+
+    import numpy as np
+
+    k = np.zeros((eps, eps), dtype=np.uint8)
+    c = eps // 2
+    for i, dx in enumerate(disc_rows(eps)):
+        k[i, max(c - dx, 0):min(c + dx + 1, eps)] = 1
+    return k
+
+
+def _disc_arg(eps):
+    if eps < 0 or eps > 64:
+        raise ValueError("robosat_amd: disc diameter must be in 0..64, got {}".format(eps))
+    return (ctypes.c_int32 * max(eps, 1))(*(disc_rows(eps) or [0]))
+
+
+def clean_form(h, w):
+    """CLEAN_LDS where a tile's two bit-planes fit the 160 KB LDS, else CLEAN_HBM."""
+
+    return _lib.lib().rs_features_clean_form(h, w)
+
+
+def clean_masks(images_u8, index, eps_open, eps_close, form=CLEAN_AUTO):
+    """uint8 [B, H, W] class-index masks -> uint8 0/1 [B, H, W]: close(open(images == index)) with discs of diameter
+    eps_open (``--denoise``) and eps_close (``--grow``)."""
+
+    b, h, w = images_u8.shape
+    out = torch.empty_like(images_u8)
+    lib = _lib.lib()
+    ws = None
+    if form != CLEAN_LDS:  # (CLEAN_AUTO is the HBM form: profiles/features)
+        ws = torch.empty(lib.rs_features_clean_workspace_bytes(b, h, w), device=images_u8.device, dtype=torch.uint8)
+    rc = lib.rs_features_clean(_dev(images_u8, "images", torch.uint8), _dev(out, "out", torch.uint8), _dev(ws, "workspace", torch.uint8),
+                               b, h, w, index, eps_open, _disc_arg(eps_open), eps_close, _disc_arg(eps_close), form, _stream())
+    check(rc, "rs_features_clean")
+    return out
+
+
+def label_components(masks):
+    """uint8 [B, H, W] (non-zero = foreground) -> int32 [B, H, W]: 4-connected components, label = 1 + min(y * W + x) of the
+    component, background 0."""
+
+    b, h, w = masks.shape
+    labels = torch.empty((b, h, w), device=masks.device, dtype=torch.int32)
+    err = torch.zeros(1, device=masks.device, dtype=torch.int32)
+    rc = _lib.lib().rs_features_label(_dev(masks, "masks", torch.uint8), _dev(labels, "labels", torch.int32), _dev(err, "err", torch.int32),
+                                      b, h, w, _stream())
+    check(rc, "rs_features_label")
+    if int(err.item()):
+        raise RuntimeError("rs_features_label: a union-find loop ran out of its H*W bound (code {})".format(int(err.item())))
+    return labels
+
+
+def component_table(labels, min_area=0):
+    """int32 [B, H, W] canonical labels -> int32 [N, 7] rows (tile, label, area, x0, y0, x1, y1) of the components with
+    area >= min_area, sorted by (tile, label)."""
+
+    b, h, w = labels.shape
+    dev = labels.device
+    slotmap = torch.empty((b, h, w), device=dev, dtype=torch.int32)
+    counters = torch.empty(2, device=dev, dtype=torch.int32)
+    capacity = 1 << 16
+    for _ in range(2):  # (the second pass has the exact capacity)
+        raw = torch.empty((capacity, 6), device=dev, dtype=torch.int32)
+        table = torch.empty((capacity, 7), device=dev, dtype=torch.int32)
+        rc = _lib.lib().rs_features_components(_dev(labels, "labels", torch.int32), _dev(slotmap, "slotmap", torch.int32),
+                                               _dev(raw, "raw", torch.int32), _dev(table, "table", torch.int32),
+                                               _dev(counters, "counters", torch.int32), capacity, b, h, w, int(min_area), _stream())
+        check(rc, "rs_features_components")
+        found, kept = counters.tolist()
+        if found <= capacity:
+            break
+        capacity = found
+    else:
+        raise RuntimeError("rs_features_components: {} components do not fit a table of {}".format(found, capacity))
+    table = table[:kept]
+    order = torch.argsort(table[:, 0].to(torch.int64) * (h * w + 1) + table[:, 1].to(torch.int64))
+    return table[order].contiguous()
+
+
+def boundary_edges(labels, table):
+    """Directed unit boundary edges of the components in ``table``: int32 [E, 5] rows (tile, label, x, y, dir), in the
+    order the device wrote them (sort on the host)."""
+
+    b, h, w = labels.shape
+    dev = labels.device
+    keep = torch.empty(b * h * w, device=dev, dtype=torch.uint8)
+    counter = torch.empty(1, device=dev, dtype=torch.int32)
+    table = table.contiguous()
+
+    def run(edges, capacity):
+        rc = _lib.lib().rs_features_edges(_dev(labels, "labels", torch.int32), _dev(table, "table", torch.int32) if len(table) else None,
+                                          len(table), _dev(keep, "keep", torch.uint8), _dev(edges, "edges", torch.int32), capacity,
+                                          _dev(counter, "counter", torch.int32), b, h, w, _stream())
+        check(rc, "rs_features_edges")
+        return int(counter.item())
+
+    n = run(None, 0)
+    edges = torch.empty((n, 5), device=dev, dtype=torch.int32)
+    if n:
+        got = run(edges, n)
+        assert got == n, (got, n)
+    return edges

@@ -79,3 +79,31 @@ def buffer_tile_image(tile, tiles, overlap, tile_size, nodata=0, opener=None, mo
             else:
                 composite.paste(piece.crop(box=(sx, sy, sx + w, sy + h)), box=(tx, ty, tx + w, ty + h))
     return composite
+
+
+def tile_bounds(tile):
+    """``(west, south, east, north)`` of a web-mercator tile in degrees, float64 (what ``mercantile.bounds`` returns):
+    west = x / 2^z * 360 - 180, north = degrees(atan(sinh(pi * (1 - 2 y / 2^z)))), east / south from x + 1 / y + 1."""
+
+    import math
+
+    n = 2.0 ** int(tile.z)
+
+    def lon(x):
+        return x / n * 360.0 - 180.0
+
+    def lat(y):
+        return math.degrees(math.atan(math.sinh(math.pi * (1.0 - 2.0 * y / n))))
+
+    return lon(tile.x), lat(tile.y + 1), lon(tile.x + 1), lat(tile.y)
+
+
+def pixel_to_location(tile, dx, dy):
+    """``(lon, lat)`` of the relative offset (dx, dy) in [0, 1]^2 of a tile, dy measured DOWN from the tile's north edge
+    (image rows): lon = lerp(west, east, dx), lat = lerp(north, south, dy).  Latitude is interpolated linearly inside the
+    tile, the reference's choice (``robosat/tiles.py:19-42``); callers pass pixel corners divided by the tile size."""
+
+    assert 0 <= dx <= 1, "x offset is in [0, 1]"
+    assert 0 <= dy <= 1, "y offset is in [0, 1]"
+    west, south, east, north = tile_bounds(tile)
+    return west + dx * (east - west), north + dy * (south - north)
