@@ -10,7 +10,7 @@
 // block combines its row lanes through LDS), stage 2 combines the splits -- deterministic, no atomics.
 #include <atomic>
 
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(256) void bn_reduce_finalize_kernel(const float* __
     __hip_atomic_store(out + ((long)blockIdx.y * 2 + 1) * C + c, s1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (set < 0) return;  // (more channel groups than counters: the host launches the finalize kernel behind this one)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  rs_dma_wait();  // (this wave's stores have gone out)
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned int* ctr = g_bn_arrivals + set * 128 + blockIdx.x;

@@ -10,6 +10,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16_t;
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // Four consecutive activations as fp32, whatever the storage type: fp32 = one 16-byte access, bf16 = one 8-byte
 // access (+ v_cvt_pk_bf16_f32, round to nearest even, on the way out).  All arithmetic stays fp32.

@@ -31,7 +31,6 @@ constexpr int EB_STAGE = EB_BM * EB_SROW;
 constexpr int EB_RED = 4 * 2 * EB_BN * 4;          // [wave][sum | sum of squares][cout] floats
 constexpr int EB_NG = EB_BM / 16;                  // epilogue groups per tile: 16 rows x 16 pieces of 16 bytes (8 couts)
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void eb_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -54,9 +53,9 @@ __global__ __launch_bounds__(512, 2) void conv1x1_ew_bf16_stats_kernel(const Con
     const int wm = wave >> 1, wn = wave & 1;
     const int ra = lane >> 2, pp = lane & 3;
     const int gp = pp ^ ((ra >> 2) & 3);
-    const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rb_lds_addr(smem));
-    const __amdgpu_buffer_rsrc_t rsrcw = rb_make_rsrc(p.wgt, (long)p.Cout * K * 2);
-    __amdgpu_buffer_rsrc_t rsrca = rb_make_rsrc(p.src1, 0);
+    const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
+    const __amdgpu_buffer_rsrc_t rsrcw = rs_dma_rsrc<kDmaClamp>(p.wgt, (long)p.Cout * K * 2);
+    __amdgpu_buffer_rsrc_t rsrca = rs_dma_rsrc<kDmaClamp>(p.src1, 0);
     int f_seq = 0, f_kc = 0, f_b = 0;  // fetch cursor: item, chunk of it, ring buffer
     int voff[4];                       // two pixel-row instructions (relative to the item's first row), two filter-row instructions
     auto fetch_item = [&]() __attribute__((always_inline)) {
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_ew_bf16_stats_kernel(const Con
       const int mt = __builtin_amdgcn_readfirstlane(it / ntiles);
       const int nt = it - mt * ntiles;
       const int m0 = mt * EB_BM, n0 = nt * EB_BN;
-      rsrca = rb_make_rsrc(p.src1 + (long)m0 * K, (long)(p.M - m0) * K * 2);  // (rows past M are past the descriptor: zeros)
+      rsrca = rs_dma_rsrc<kDmaClamp>(p.src1 + (long)m0 * K, (long)(p.M - m0) * K * 2);  // (rows past M are past the descriptor: zeros)
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         voff[j] = (16 * (wave + 4 * j) + ra) * (K * 2) + gp * 16;
@@ -73,8 +72,8 @@ __global__ __launch_bounds__(512, 2) void conv1x1_ew_bf16_stats_kernel(const Con
     };
     auto issue = [&](int j) __attribute__((always_inline)) {  // j compile-time: instruction wave + 4 j of the chunk's 16
       const unsigned int dst = lds0 + f_b * EB_BUF + (wave + 4 * j) * 1024;
-      if (j < 2) rb_dma16s(rsrca, dst, voff[j], f_kc * EB_ROWB);
-      else rb_dma16s(rsrcw, dst, voff[j], f_kc * EB_ROWB);
+      if (j < 2) rs_dma16(rsrca, dst, voff[j], f_kc * EB_ROWB);
+      else rs_dma16(rsrcw, dst, voff[j], f_kc * EB_ROWB);
     };
     auto advance = [&]() __attribute__((always_inline)) {
       f_b = f_b == EB_RING - 1 ? 0 : f_b + 1;
@@ -114,10 +113,10 @@ __global__ __launch_bounds__(512, 2) void conv1x1_ew_bf16_stats_kernel(const Con
       for (int kc = 0; kc < nk; ++kc, ++g) {
         // chunk g has landed when at most the younger chunks' instructions of this wave are outstanding (4 per chunk)
         const int younger = total - 1 - g;
-        if (younger >= 3) rb_dma_wait_n<12>();
-        else if (younger == 2) rb_dma_wait_n<8>();
-        else if (younger == 1) rb_dma_wait_n<4>();
-        else rb_dma_wait();
+        if (younger >= 3) rs_dma_wait_n<12>();
+        else if (younger == 2) rs_dma_wait_n<8>();
+        else if (younger == 1) rs_dma_wait_n<4>();
+        else rs_dma_wait();
         eb_barrier();  // chunk g is in buffer c_b; the buffer chunk g - 1 was read from is free again
         const bool more = g + EB_RING - 1 < total;
         if (more && f_kc == 0) fetch_item();
@@ -168,7 +167,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_ew_bf16_stats_kernel(const Con
     }
     eb_barrier();  // publishes the last tile's staging
     eb_barrier();  // (the epilogue waves' partial sums)
-    rb_dma_wait();
+    rs_dma_wait();
   } else {
     // ================================================ epilogue waves =================================================
     const int e = tid - 256;

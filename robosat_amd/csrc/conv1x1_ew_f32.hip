@@ -19,7 +19,7 @@
 // K order, MFMA operand order and the epilogue's arithmetic are those of the generic kernel's 64-byte-row variants.
 //
 // STATUS: measurement candidate, reached only with RS_CONV1X1_EW=1 in the environment (conv_igemm_dma.hip).
-#define RS_CONV_INSTANTIATE  // (the LDS-DMA helpers and ConvArgsT of the header; no kernel of it is instantiated here)
+#define RS_CONV_INSTANTIATE  // (kDmaClamp, the small helpers and ConvArgsT of the header; no kernel of it is instantiated here)
 #include "conv_igemm_dma_kernel.h"
 
 namespace {
@@ -51,9 +51,9 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ew_f32_kernel(const ConvArgsT<
     const int wm = wave >> 1, wn = wave & 1;
     const int ra = lane >> 2, pp = lane & 3;
     const int gp = pp ^ ((ra >> 2) & 3);  // the 16-byte piece this lane fetches (swizzle on the SOURCE address: the LDS image is lane-linear)
-    const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rb_lds_addr(smem));
-    const __amdgpu_buffer_rsrc_t rsrcw = rb_make_rsrc(p.wgt, (long)p.Cout * K * 4);
-    __amdgpu_buffer_rsrc_t rsrca = rb_make_rsrc(p.src1, 0);
+    const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
+    const __amdgpu_buffer_rsrc_t rsrcw = rs_dma_rsrc<kDmaClamp>(p.wgt, (long)p.Cout * K * 4);
+    __amdgpu_buffer_rsrc_t rsrca = rs_dma_rsrc<kDmaClamp>(p.src1, 0);
     // fetch cursor (wave-uniform): item f_seq, chunk f_kc of it, global chunk f_g (buffer f_g & 1)
     int f_seq = 0, f_kc = 0, f_g = 0;
     int voff[3];  // this lane's byte offsets: two pixel-row instructions (relative to the item's first row), one filter-row instruction
@@ -62,15 +62,15 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ew_f32_kernel(const ConvArgsT<
       const int mt = __builtin_amdgcn_readfirstlane(it / ntiles);
       const int nt = it - mt * ntiles;
       const int m0 = mt * EW_BM, n0 = nt * EW_BN;
-      rsrca = rb_make_rsrc(p.src1 + (long)m0 * K, (long)(p.M - m0) * K * 4);  // (rows past M are past the descriptor: zeros)
+      rsrca = rs_dma_rsrc<kDmaClamp>(p.src1 + (long)m0 * K, (long)(p.M - m0) * K * 4);  // (rows past M are past the descriptor: zeros)
 #pragma unroll
       for (int j = 0; j < 2; ++j) voff[j] = (16 * (wave + 4 * j) + ra) * (K * 4) + gp * 16;
       voff[2] = (n0 + 16 * wave + ra) * (K * 4) + gp * 16;
     };
     auto issue = [&](int j) __attribute__((always_inline)) {  // j compile-time: instruction wave + 4 j of the chunk's 12
       const unsigned int dst = lds0 + (f_g & 1) * EW_BUF + (wave + 4 * j) * 1024;
-      if (j < 2) rb_dma16s(rsrca, dst, voff[j], f_kc * EW_ROWB);
-      else rb_dma16s(rsrcw, dst, voff[j], f_kc * EW_ROWB);
+      if (j < 2) rs_dma16(rsrca, dst, voff[j], f_kc * EW_ROWB);
+      else rs_dma16(rsrcw, dst, voff[j], f_kc * EW_ROWB);
     };
     auto advance = [&]() __attribute__((always_inline)) {
       ++f_g;
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ew_f32_kernel(const ConvArgsT<
     int g = 0;
     for (int seq = 0; seq < nitems; ++seq) {
       for (int kc = 0; kc < nk; ++kc, ++g) {
-        rb_dma_wait();
+        rs_dma_wait();
         ew_barrier();  // chunk g is in buffer g & 1; buffer (g + 1) & 1 is free again
         const bool more = g + 1 < total;
         if (more && f_kc == 0) fetch_item();
@@ -154,7 +154,7 @@ __global__ __launch_bounds__(512, 4) void conv1x1_ew_f32_kernel(const ConvArgsT<
       }
     }
     ew_barrier();  // publishes the last tile's staging
-    rb_dma_wait();
+    rs_dma_wait();
   } else {
     // ================================================ epilogue waves =================================================
     const int e = tid - 256;

@@ -22,7 +22,7 @@
 // Two things: the 128 x 64 sub-tile's main loop runs at ~75 % of the matrix cores where the generic 128 x 128 tile reaches ~95 % (the
 // finding of conv1x1_ew_f32 again: half the MFMAs per barrier and per fetched byte), and the epilogue traffic is NOT hidden -- stores
 // and loads count in the one vmcnt the LDS-DMA wait in front of every barrier drains, so each step waits for the step's store.
-#define RS_CONV_INSTANTIATE  // (the LDS-DMA helpers and ConvArgsT of the header; no kernel of it is instantiated here)
+#define RS_CONV_INSTANTIATE  // (kDmaClamp, the small helpers and ConvArgsT of the header; no kernel of it is instantiated here)
 #include "conv_igemm_dma_kernel.h"
 
 namespace {
@@ -48,9 +48,9 @@ __global__ __launch_bounds__(256, 4) void conv1x1_np_f32_kernel(const ConvArgsT<
   const int wm = wave >> 1, wn = wave & 1;
   const int ra = lane >> 2, pp = lane & 3;
   const int gp = pp ^ ((ra >> 2) & 3);  // the 16-byte piece this lane fetches (swizzle on the SOURCE address: the LDS image is lane-linear)
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rb_lds_addr(smem));
-  const __amdgpu_buffer_rsrc_t rsrcw = rb_make_rsrc(p.wgt, (long)p.Cout * K * 4);
-  __amdgpu_buffer_rsrc_t rsrca = rb_make_rsrc(p.src1, 0);
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
+  const __amdgpu_buffer_rsrc_t rsrcw = rs_dma_rsrc<kDmaClamp>(p.wgt, (long)p.Cout * K * 4);
+  __amdgpu_buffer_rsrc_t rsrca = rs_dma_rsrc<kDmaClamp>(p.src1, 0);
   // fetch cursor (wave-uniform): item f_seq, chunk f_kc of it, global chunk f_g (buffer f_g & 1)
   int f_seq = 0, f_kc = 0, f_g = 0;
   int voff[3];  // this lane's byte offsets: two pixel-row instructions (relative to the item's first row), one filter-row instruction
@@ -59,15 +59,15 @@ __global__ __launch_bounds__(256, 4) void conv1x1_np_f32_kernel(const ConvArgsT<
     const int mt = __builtin_amdgcn_readfirstlane(it / ntiles);
     const int nt = it - mt * ntiles;
     const int m0 = mt * NP_BM, n0 = nt * NP_BN;
-    rsrca = rb_make_rsrc(p.src1 + (long)m0 * K, (long)(p.M - m0) * K * 4);  // (rows past M are past the descriptor: zeros)
+    rsrca = rs_dma_rsrc<kDmaClamp>(p.src1 + (long)m0 * K, (long)(p.M - m0) * K * 4);  // (rows past M are past the descriptor: zeros)
 #pragma unroll
     for (int j = 0; j < 2; ++j) voff[j] = (16 * (wave + 4 * j) + ra) * (K * 4) + gp * 16;
     voff[2] = (n0 + 16 * wave + ra) * (K * 4) + gp * 16;
   };
   auto issue = [&](int j) __attribute__((always_inline)) {  // j compile-time: instruction wave + 4 j of the chunk's 12
     const unsigned int dst = lds0 + (f_g & 1) * NP_BUF + (wave + 4 * j) * 1024;
-    if (j < 2) rb_dma16s(rsrca, dst, voff[j], f_kc * NP_ROWB);
-    else rb_dma16s(rsrcw, dst, voff[j], f_kc * NP_ROWB);
+    if (j < 2) rs_dma16(rsrca, dst, voff[j], f_kc * NP_ROWB);
+    else rs_dma16(rsrcw, dst, voff[j], f_kc * NP_ROWB);
   };
   auto advance = [&]() __attribute__((always_inline)) {
     ++f_g;
@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256, 4) void conv1x1_np_f32_kernel(const ConvArgsT<
     for (; kc < nk; ++kc) step(std::integral_constant<int, NP_NQ + 1>());
     // (K < 144: fewer than nine chunk steps -- the quads the steps did not reach are finished here; nk >= 2 is the launcher's rule)
     if (seq > 0 && nk <= NP_NQ) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      rs_dma_wait();
       rb_for_each([&](auto jc) __attribute__((always_inline)) {
         constexpr int J = decltype(jc)::value;
         if (J >= nk - 1) {
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256, 4) void conv1x1_np_f32_kernel(const ConvArgsT<
       finish(J);
     }, std::make_integer_sequence<int, NP_NQ>());
   }
-  rb_dma_wait();
+  rs_dma_wait();
 }
 
 }  // namespace

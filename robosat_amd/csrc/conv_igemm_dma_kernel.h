@@ -8,7 +8,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "lds_dma.h"
 
 enum { EPI_EVAL = 0, EPI_STATS = 1, EPI_BWD = 2 };
 constexpr int kMaxK = 4;  // filter height / width up to 4 (the 4x4 stride-2 data gradient of an upsampled 3x3)
@@ -88,8 +88,6 @@ __attribute__((visibility("hidden"))) int rs_conv1x1_ew_bf16_stats_launch(const 
 #ifdef RS_CONV_INSTANTIATE  // ---- kernel + launcher body: only in the instantiating translation units --------------------
 namespace {
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 // 16 bytes of activations <-> fp32 lanes
 template <typename T>
 struct Piece;
@@ -140,47 +138,17 @@ __device__ __forceinline__ void mma16(f32x16& acc, const u32x4 a, const u32x4 b,
   for (int t = 0; t < 4; ++t) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[t], fb[t], acc, 0, 0, 0);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rb_make_rsrc(const void* base, long bytes) {
-  // (clipped below kDmaOOB: every offset the kernels form is < 2^31, and the out-of-range sentinel must stay out of range)
-  const unsigned int n = bytes > 0xFFFE0000L ? 0xFFFE0000u : (unsigned int)(bytes < 0 ? 0 : bytes);
-  // The inputs are wave-uniform (kernel arguments and blockIdx arithmetic) but 64-bit multiplies, integer divisions and
-  // the clamp above run on the VALU: hipcc then carries the descriptor in VGPRs and only sometimes moves it back (it did not
-  // once a select between two descriptors was itself lowered to v_cndmask: "invalid operand" in the LDS-DMA asm, whose
-  // SRSRC must be SGPRs).  readfirstlane on the descriptor's INPUTS makes the uniformity provable (cdna_hip_programming.md T20).
-  const unsigned long b = (unsigned long)base;
-  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
-  const unsigned int nn = __builtin_amdgcn_readfirstlane(n);
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long)hi << 32) | lo), 0, (int)nn, 0x00020000);
-}
-
-// One LDS-DMA wave instruction (buffer_load_dwordx4 ... lds): lane l's 16 bytes at buffer offset `voff` + `soff` land at
-// LDS byte `lds_dst` + 16*l (lds_dst wave-uniform, in M0); an out-of-range offset => zeros (scripts/probes/probe_glds.hip).
-// Inline asm on purpose: through the builtin hipcc cannot tell that the DMA's destination (the OTHER pipeline buffer) is
-// disjoint from the fragment reads that follow and drains the queue (s_waitcnt vmcnt(0)) before the first ds_read of
-// every chunk.  As asm the copy is invisible to its counters, so the kernel waits itself (rb_dma_wait) ahead of the
-// barrier that publishes the buffer.
-// `soff` is a wave-uniform byte offset added to the address (the SOFFSET operand): the per-lane offsets of a
-// (tap, source) stay in registers and the K loop advances through the channels with one SGPR.  kDmaOOB + soff is out of
-// range for every rsrc rb_make_rsrc builds (zeros land in the LDS): the per-lane offset of a padding / past-the-end row.
-// m0 is declared clobbered rather than saved and restored (two SALU per piece, eight pieces per chunk per wave): the
-// compiler itself only touches m0 for M0-operand LDS builtins and dynamically indexed register arrays, and this file has
-// neither (every register array is indexed by unrolled constants) -- check `grep m0` of the ISA after touching the kernel.
+// Out-of-range sentinel of this header's kernels (and of the kernels that borrow its helpers): the per-lane offset of a
+// padding / past-the-end row, for which the LDS-DMA writes zeros.  Every descriptor is built with num_records clipped to
+// kDmaClamp, BELOW the sentinel (every offset the kernels form is < 2^31).  The call sites add a wave-uniform `soff` to it
+// (rs_dma16's SOFFSET: a channel offset inside one pixel row, or a (tap, chunk) offset inside one filter row -- far below
+// 64 KiB): there are 64 KiB between clamp and sentinel and between sentinel and 2^32, so kDmaOOB + soff neither wraps
+// nor comes into range of any such descriptor.
+constexpr unsigned int kDmaClamp = 0xFFFE0000u;
 constexpr int kDmaOOB = (int)0xFFFF0000u;
-__device__ __forceinline__ void rb_dma16s(__amdgpu_buffer_rsrc_t r, unsigned int lds_dst, int voff, int soff) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %2, %3 offen lds"
-      :
-      : "v"(voff), "s"(lds_dst), "s"(r), "s"(soff)
-      : "memory", "m0");
-}
+static_assert((unsigned int)kDmaOOB > kDmaClamp && (unsigned int)kDmaOOB - kDmaClamp == 0x10000u && 0u - (unsigned int)kDmaOOB == 0x10000u,
+              "the sentinel is out of range for every descriptor, with 64 KiB for soff on either side");
 
-__device__ __forceinline__ void rb_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void rb_dma_wait_n() {  // all but the N youngest of this wave's DMA instructions have landed
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 // f(std::integral_constant<int, 0>()), f(<1>), ...: an unrolled loop whose index is a constant EXPRESSION (the counted
 // s_waitcnt immediates of the halo forms depend on the tap)
 template <class F, int... I>
@@ -195,10 +163,6 @@ constexpr int halo_pieces_at_tap(int t, int ntap, int njh) {
   for (int j = 0; j < njh; ++j) n += halo_tap_of_piece(j, ntap, njh) == t ? 1 : 0;
   return n;
 }
-__device__ __forceinline__ unsigned int rb_lds_addr(const void* p) {
-  return (unsigned int)(unsigned long)(__attribute__((address_space(3))) const void*)p;
-}
-
 
 // (second launch bound = waves per SIMD the LDS footprint admits, capped at 4: the register allocation must not be what
 // limits the blocks per CU of the short-K layers, whose co-resident blocks are what hides a block's DMA round trips)
@@ -340,10 +304,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
 
   const long img1 = (long)p.Hs * p.Ws * p.C1;
   const long img2 = (long)p.Hs * p.Ws * p.C2;
-  const __amdgpu_buffer_rsrc_t rsrc1 = rb_make_rsrc(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * ES);
-  const __amdgpu_buffer_rsrc_t rsrc2 = rb_make_rsrc(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * ES);
+  const __amdgpu_buffer_rsrc_t rsrc1 = rs_dma_rsrc<kDmaClamp>(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * ES);
+  const __amdgpu_buffer_rsrc_t rsrc2 = rs_dma_rsrc<kDmaClamp>(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * ES);
   const __amdgpu_buffer_rsrc_t rsrcw =
-      rb_make_rsrc(p.wgt + (long)(2 * py + px) * p.Cout * p.Kw, (long)p.Cout * p.Kw * ES);  // phase weights follow each other
+      rs_dma_rsrc<kDmaClamp>(p.wgt + (long)(2 * py + px) * p.Cout * p.Kw, (long)p.Cout * p.Kw * ES);  // phase weights follow each other
 
   // ---- LDS-DMA roles.  Instruction ii = wave + 4j copies 1 KiB = RI whole rows: ii < IA pixel rows RI*ii.., else
   //      weight rows RI*(ii-IA)...  Lane l: row ra = l / CPR of the instruction, 16-byte position pp = l % CPR, which
@@ -351,7 +315,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   const int ra = lane / CPR, pp = lane % CPR;
   const int fsw = ROWB == 128 ? ((4 * (wave & 1) + (ra >> 1)) & 7) : ((ra >> 2) & 3);  // f(RI*ii + ra): ii = wave (mod 2)
   const int gp = pp ^ fsw;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rb_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   constexpr int NIA = IA / NW;  // this wave's pieces j < NIA copy pixel rows, the others weight rows
   int wrow[NI];                 // byte offset of this lane's piece in weight row (n0 + RI*jj + ra), chunk 0
 #pragma unroll
@@ -400,9 +364,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   auto issue_piece = [&](int j) __attribute__((always_inline)) {  // j: compile-time after unrolling
     const int ii = wave + NW * j;  // wave-uniform; IA % NW == 0, so the role depends on j alone
     if (j < NIA) {
-      rb_dma16s(frs, fL + ii * 1024, pbase[j], fsa);
+      rs_dma16(frs, fL + ii * 1024, pbase[j], fsa);
     } else if ((IB % NW) == 0 || ii < IA + IB) {
-      rb_dma16s(rsrcw, fL + ii * 1024, wrow[j], fsb);
+      rs_dma16(rsrcw, fL + ii * 1024, wrow[j], fsb);
     }
   };
 
@@ -450,7 +414,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   // made hipcc keep the 64 accumulator registers of the two arms apart (64 v_mov per chunk).
   auto chunk = [&](int kc, auto fetch_tag) __attribute__((always_inline)) {
     constexpr bool FETCH = decltype(fetch_tag)::value;
-    rb_dma_wait();
+    rs_dma_wait();
     __syncthreads();
     if (FETCH) begin_chunk((kc + 1) % NBUF);  // refills the buffer chunk kc-1 was read from
     const unsigned char* L = smem + (kc % NBUF) * BUF;
@@ -542,13 +506,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
       const int first = g.c0 < p.C1 ? 1 : 0;
       const int v = g.live ? (first ? ho1[j] : ho2[j]) : kDmaOOB;
       const int ii = wave + NW * j;  // (wave-uniform) instructions past the halo's last row write their zeros to the scratch KiB
-      rb_dma16s(first ? rsrc1 : rsrc2, lds0 + (ii < NHI ? buf * HALOB + ii * 1024 : HSCRATCH), v, (first ? g.c0 : g.c0 - p.C1) * ES);
+      rs_dma16(first ? rsrc1 : rsrc2, lds0 + (ii < NHI ? buf * HALOB + ii * 1024 : HSCRATCH), v, (first ? g.c0 : g.c0 - p.C1) * ES);
     };
     auto issue_w = [&](int j, int slot, const Grp& g, int tap) __attribute__((always_inline)) {  // tap: compile-time
       // weight tap of (group, tap): 3x3 -> tap; phase -> tap (the parity's own 2x2 block: rsrcw starts there);
       // DG4 -> (2r + 1 - pa) * 4 + 2s + 1 - pb
       const int tau = HALO == HALO_DG4 ? (2 * (tap >> 1) + 1 - g.pa) * 4 + 2 * (tap & 1) + 1 - g.pb : tap;
-      rb_dma16s(rsrcw, lds0 + HBOFF + slot * BSLOT + (wave + NW * j) * 1024, g.live ? hwrow[j] : kDmaOOB, (tau * ctot + g.c0) * ES);
+      rs_dma16(rsrcw, lds0 + HBOFF + slot * BSLOT + (wave + NW * j) * 1024, g.live ? hwrow[j] : kDmaOOB, (tau * ctot + g.c0) * ES);
     };
     // fragment addressing: A = halo rows of the lane's pixel (patch row wm*RPT + tm, column l31) shifted by the tap,
     // swizzle key of THAT row; B as in the implicit-GEMM form
@@ -606,7 +570,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
     if (HALO == HALO_DG4) halo_pix(nxt.pa, nxt.pb);  // (the pieces issued during group q fetch group q + 1)
     constexpr int NMMA = KS * TM * TN;
     u32x4 fa[2][TM], fb[2][TN];
-    rb_dma_wait_n<NBW>();  // halo 0 and the weights of steps 0 and 1 have landed (step 2's may still fly)
+    rs_dma_wait_n<NBW>();  // halo 0 and the weights of steps 0 and 1 have landed (step 2's may still fly)
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
     rd(0, 0, 0, 0, fa[0], fb[0], 0);  // first fragments of step 0
@@ -627,7 +591,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
             __builtin_amdgcn_sched_barrier(0);
             // in flight after this wait: what the previous step issued (NBW weight pieces + its halo pieces)
             if constexpr (KO != 1) {
-              rb_dma_wait_n<NBW + halo_pieces_at_tap(tprev, HNT, NJH)>();
+              rs_dma_wait_n<NBW + halo_pieces_at_tap(tprev, HNT, NJH)>();
 #ifdef RS_HALO_FENCED_BARRIER
               __syncthreads();
 #else
@@ -695,7 +659,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
       nxt = group(q + 2);
       if (HALO == HALO_DG4) halo_pix(nxt.pa, nxt.pb);
     }
-    rb_dma_wait();  // the past-the-end pieces too: they write (zeros) into the buffers the epilogue stages through
+    rs_dma_wait();  // the past-the-end pieces too: they write (zeros) into the buffers the epilogue stages through
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();  // every wave is done with the pipeline buffers: the epilogue stages through them

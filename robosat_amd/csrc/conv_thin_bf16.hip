@@ -29,7 +29,7 @@
 //             the compiler's vmcnt bookkeeping and drain them).
 //
 // Traffic per launch = input once (x 1.2-1.4 halo overlap) + output once (+ the mask once).
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -45,34 +45,10 @@ struct ThinConvArgs {
   int ppx, ppi, total;  // patches per row of the base grid / per image / in all
 };
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tc_make_rsrc(const void* base, long bytes) {
-  const unsigned int n = bytes > 0x7FFF0000L ? 0x7FFF0000u : (unsigned int)(bytes < 0 ? 0 : bytes);
-  const unsigned long b = (unsigned long)base;  // (descriptor inputs made provably wave-uniform: cdna_hip_programming.md T20)
-  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long)hi << 32) | lo), 0,
-                                           (int)__builtin_amdgcn_readfirstlane(n), 0x00020000);
-}
-
-constexpr int kThinOOB = (int)0x80000000u;  // beyond every descriptor tc_make_rsrc builds: the DMA writes zeros
-
-// One LDS-DMA wave instruction: lane l's 16 bytes at buffer offset `voff` land at LDS byte `lds_dst` + 16*l (see rb_dma16s in
-// conv_igemm_dma_kernel.h for why this is inline asm and why m0 is a clobber).
-__device__ __forceinline__ void tc_dma16(__amdgpu_buffer_rsrc_t r, unsigned int lds_dst, int voff) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %2, 0 offen lds"
-      :
-      : "v"(voff), "s"(lds_dst), "s"(r)
-      : "memory", "m0");
-}
-__device__ __forceinline__ void tc_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned int tc_lds_addr(const void* p) {
-  return (unsigned int)(unsigned long)(__attribute__((address_space(3))) const void*)p;
-}
+// out-of-range sentinel (the DMA writes zeros) and the num_records clamp of every descriptor this file builds, below it
+constexpr unsigned int kThinClamp = 0x7FFF0000u;
+constexpr int kThinOOB = (int)0x80000000u;
+static_assert((unsigned int)kThinOOB > kThinClamp, "the sentinel is out of range for every descriptor");
 
 template <int MODE>
 struct ThinGeom;
@@ -91,11 +67,6 @@ struct ThinGeom<THIN_DG4> {  // base grid = output grid (half the resolution of 
   static constexpr int CIN = 32, COUT = 128, NTAP = 16, PH = 8, PW = 16, HALO_H = 18, HALO_W = 34;
   static constexpr int OUT_ROWS = 8, OUT_PX = 16;
 };
-
-template <int N>
-__device__ __forceinline__ void tc_dma_wait_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 template <int MODE>
 __global__ __launch_bounds__(512, 2) void conv_thin_bf16(const ThinConvArgs p) {
@@ -152,10 +123,10 @@ __global__ __launch_bounds__(512, 2) void conv_thin_bf16(const ThinConvArgs p) {
     for (int f = 0; f < NF; ++f) wf[f] = *reinterpret_cast<const u32x4*>(wbase + (f / KS) * CIN + (f % KS) * 16 + 8 * hi);
   }
 
-  const __amdgpu_buffer_rsrc_t rsrc = tc_make_rsrc(p.src, (long)p.N * p.Hs * p.Ws * ROWB);
-  const __amdgpu_buffer_rsrc_t rsrc_mask = tc_make_rsrc(p.mask ? (const void*)p.mask : (const void*)p.src,
+  const __amdgpu_buffer_rsrc_t rsrc = rs_dma_rsrc<kThinClamp>(p.src, (long)p.N * p.Hs * p.Ws * ROWB);
+  const __amdgpu_buffer_rsrc_t rsrc_mask = rs_dma_rsrc<kThinClamp>(p.mask ? (const void*)p.mask : (const void*)p.src,
                                                         p.mask ? (long)p.N * p.Ho * p.Wo * COUT * 2 : 0);
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(tc_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
 
   // patch -> (image, base-grid origin); halo origin in source coordinates, output origin
   struct Where {
@@ -183,7 +154,7 @@ __global__ __launch_bounds__(512, 2) void conv_thin_bf16(const ThinConvArgs p) {
     const int sy = hy0 + (c >> 10), sx = hx0 + ((c >> 4) & 63);
     const bool ok = w.live && c >= 0 && (unsigned)sy < (unsigned)p.Hs && (unsigned)sx < (unsigned)p.Ws;
     const int voff = ok ? (((w.n * p.Hs + sy) * p.Ws + sx) * ROWB + (c & 15) * 16) : kThinOOB;
-    tc_dma16(rsrc, lds0 + slot * HALOB + ii * 1024, voff);
+    rs_dma16(rsrc, lds0 + slot * HALOB + ii * 1024, voff);
   };
   // Mask piece j of this wave for the patch being computed: the output-shaped patch of `mask`, linear rows (OROWB bytes each)
   auto issue_mask = [&](int j, const Where& w) __attribute__((always_inline)) {
@@ -193,7 +164,7 @@ __global__ __launch_bounds__(512, 2) void conv_thin_bf16(const ThinConvArgs p) {
     const int oy = (MODE == THIN_PHASE ? 2 : 1) * w.by0 + row, ox = (MODE == THIN_PHASE ? 2 : 1) * w.bx0 + inrow / (COUT * 2);
     const bool ok = w.live && p.mask && oy < p.Ho && ox < p.Wo;
     const int voff = ok ? (((w.n * p.Ho + oy) * p.Wo + ox) * COUT * 2 + inrow % (COUT * 2)) : kThinOOB;
-    tc_dma16(rsrc_mask, lds0 + NB * HALOB + ii * 1024, voff);
+    rs_dma16(rsrc_mask, lds0 + NB * HALOB + ii * 1024, voff);
   };
 
   // ---- fragment addressing: sub-tile u = 2*half + t of this wave's role, lane pixel on the patch; halo row of tap (r, s) = baseR + r*HALO_W + s
@@ -238,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void conv_thin_bf16(const ThinConvArgs p) {
   for (int j = 0; j < NJ; ++j) issue_piece(j, 0, cur);
 #pragma unroll
   for (int j = 0; j < NJ; ++j) issue_piece(j, 1, nxt);
-  tc_dma_wait_n<NJ>();  // halo 0 (this wave's pieces) has landed; halo 1 may still fly
+  rs_dma_wait_n<NJ>();  // halo 0 (this wave's pieces) has landed; halo 1 may still fly
   int slot = 0;
   while (cur.live) {
     // Every wave waited for ITS pieces of this halo before it got here (above; below, ahead of the write-out): barrier A makes
@@ -318,7 +289,7 @@ __global__ __launch_bounds__(512, 2) void conv_thin_bf16(const ThinConvArgs p) {
     // All but this iteration's NJ halo pieces (halo i+2) have landed: halo i+1 (issued an iteration ago), this patch's
     // mask, and the previous patch's output stores.  The wait sits BEFORE the output stores on purpose: after them it
     // would wait for the stores as well (vmcnt counts them) -- one HBM write round trip per patch on the critical path.
-    tc_dma_wait_n<NJ>();
+    rs_dma_wait_n<NJ>();
     __syncthreads();  // barrier C: staging (and everybody's mask pieces) visible
 
     // ---- write out: the staged patch is OUT_ROWS rows of OROWB contiguous output bytes

@@ -30,15 +30,9 @@
 //            -- 16/36 of the multiply-adds -- and combine_phase_wgrad_f32_kernel adds the four G's that make up each
 //            filter tap (the fp32 twin of conv_wgrad_bf16.hip's phase form; round 4).
 #include "conv_wgrad_f32.h"
+#include "lds_dma.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_make_rsrc(const float* base, long bytes) {
-  const unsigned int n = bytes > 0xFFFFFFFEL ? 0xFFFFFFFEu : (unsigned int)(bytes < 0 ? 0 : bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)n, 0x00020000);
-}
 
 __device__ __forceinline__ f32x4 wg_buffer_load4(__amdgpu_buffer_rsrc_t r, int byte_off) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
@@ -98,9 +92,9 @@ __global__ __launch_bounds__(64 * WGM * WGN) void conv_wgrad_f32(const WgradArgs
   const int n_first = (int)rs_div((unsigned)m_first, p.div_howo);
   const long img = (long)p.Hs * p.Ws * Cs;
   const long dyimg = (long)p.Ho * p.Wo * p.Cout;
-  const __amdgpu_buffer_rsrc_t rsrc_dy = PHASE ? wg_make_rsrc(p.dy + n_first * dyimg, (long)(p.N - n_first) * dyimg * 4)
-                                               : wg_make_rsrc(p.dy + (long)m_first * p.Cout, ((long)p.M - m_first) * p.Cout * 4);
-  const __amdgpu_buffer_rsrc_t rsrc_x = wg_make_rsrc(src + n_first * img, (long)(p.N - n_first) * img * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_dy = PHASE ? rs_buf_rsrc<0xFFFFFFFEu>(p.dy + n_first * dyimg, (long)(p.N - n_first) * dyimg * 4)
+                                               : rs_buf_rsrc<0xFFFFFFFEu>(p.dy + (long)m_first * p.Cout, ((long)p.M - m_first) * p.Cout * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_buf_rsrc<0xFFFFFFFEu>(src + n_first * img, (long)(p.N - n_first) * img * 4);
   const int ush = p.ups ? 1 : 0;
   const int upar = p.ups == 2 ? 1 : 0;
 

@@ -29,7 +29,7 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -45,55 +45,7 @@ struct WgradArgsB {
   rs_fastdiv div_howo, div_wo;
 };
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wb_make_rsrc(const void* base, long bytes) {
-  const unsigned int n = bytes > 0xFFFFFFFEL ? 0xFFFFFFFEu : (unsigned int)(bytes < 0 ? 0 : bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)n, 0x00020000);
-}
-
-// One LDS-DMA wave instruction: lane l's 16 bytes at buffer offset `voff` land at LDS byte `lds_dst` + 16*l (lds_dst
-// wave-uniform, in M0).  Inline asm on purpose: through the builtin hipcc cannot tell that the DMA's LDS destination
-// (the OTHER pipeline buffer) is disjoint from the operand reads that follow and drains the queue (s_waitcnt vmcnt(0))
-// before the first ds_read of every chunk, serialising copy and MFMA.  As asm the copy is invisible to its counters, so
-// the kernel waits itself: wb_dma_wait() ahead of the barrier that publishes the buffer.
-// m0 is named as a clobber rather than saved/restored around every piece (see the note at rb_dma16s in
-// conv_igemm_dma.hip: nothing else in this file makes the compiler use m0).
-__device__ __forceinline__ void wb_dma16(__amdgpu_buffer_rsrc_t r, unsigned int lds_dst, int voff) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %2, 0 offen lds"
-      :
-      : "v"(voff), "s"(lds_dst), "s"(r)
-      : "memory", "m0");
-}
-
 __device__ unsigned int wb_zero_line[256];  // 1 KiB of zeros (a __device__ array is zero-initialised): DEAD == 1
-
-__device__ __forceinline__ void wb_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-__device__ __forceinline__ unsigned int wb_lds_addr(const void* p) {
-  return (unsigned int)(unsigned long)(__attribute__((address_space(3))) const void*)p;
-}
-
-__device__ __forceinline__ bf16x8 wb_tr_read8(const unsigned char* p0, const unsigned char* p1) {
-  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p1);
-  s16x8 v;
-  v[0] = lo[0];
-  v[1] = lo[1];
-  v[2] = lo[2];
-  v[3] = lo[3];
-  v[4] = hi[0];
-  v[5] = hi[1];
-  v[6] = hi[2];
-  v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 
 // PK = pixels per chunk: 64 (4 k-steps per barrier, 64 KB of LDS for the 128x128 tile: 2 blocks per CU) or 32 (2 k-steps,
 // half the LDS: 4 blocks per CU -- the short reductions of the small layers)
@@ -184,9 +136,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
   const long img = (long)p.Hs * p.Ws * Cs;
   const long dimg = (long)p.Ho * p.Wo * p.Cout;
   const __amdgpu_buffer_rsrc_t rsrc_dy =
-      PHASE ? wb_make_rsrc(p.dy + n_first * dimg, (long)(p.N - n_first) * dimg * 2)
-            : wb_make_rsrc(p.dy + (long)m_first * p.Cout, ((long)p.M - m_first) * p.Cout * 2);
-  const __amdgpu_buffer_rsrc_t rsrc_x = wb_make_rsrc(src + n_first * img, (long)(p.N - n_first) * img * 2);
+      PHASE ? rs_buf_rsrc<0xFFFFFFFEu>(p.dy + n_first * dimg, (long)(p.N - n_first) * dimg * 2)
+            : rs_buf_rsrc<0xFFFFFFFEu>(p.dy + (long)m_first * p.Cout, ((long)p.M - m_first) * p.Cout * 2);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_buf_rsrc<0xFFFFFFFEu>(src + n_first * img, (long)(p.N - n_first) * img * 2);
   const int ush = p.ups ? 1 : 0;
   const int upar = p.ups == 2 ? 1 : 0;
 
@@ -232,14 +184,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
   const int colb = (cs + gpb * 8) * 2;
   const int cout2 = p.Cout * 2, cs2 = Cs * 2;
 
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(wb_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   // Per chunk: first the byte offsets of all of this wave's pieces (one LDS round trip for the gather tables), then the
   // pieces themselves -- in the steady state BETWEEN the MFMAs of the previous chunk (an LDS-DMA instruction costs its
   // wave 60-180 cycles of issue; a burst at the top of the chunk puts that on every wave's critical path at once).
   int voff[NI];
   unsigned int fL = lds0;
   bool fdead = false;  // (wave-uniform) the chunk being fetched lies past the split
-  const __amdgpu_buffer_rsrc_t rsrc_zero = wb_make_rsrc(wb_zero_line, 1024);
+  const __amdgpu_buffer_rsrc_t rsrc_zero = rs_buf_rsrc<0xFFFFFFFEu>(wb_zero_line, 1024);
   // (`live` = false, RING > 2 only: a chunk past the block's range -- its pieces are still issued, out of range (zeros into a
   // buffer nobody reads), so that every wave issues the same number of DMA instructions per step: what the counted waits rely on)
   auto prepare_dma = [&](int chunk, int buf, int which, bool live = true) __attribute__((always_inline)) {
@@ -268,10 +220,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
   };
   auto issue_piece = [&](int j) __attribute__((always_inline)) {
     const int ii = wave + NW * j;
-    if (DEAD == 1 && fdead) wb_dma16(rsrc_zero, NW * j < IA ? fL + ii * 1024 : fL + ABYTES + (ii - IA) * 1024, voff[j]);
-    else if (DEAD == 2 && fdead) wb_dma16(rsrc_dy, lds0 + SCRATCH, voff[j]);
-    else if (NW * j < IA) wb_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
-    else wb_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
+    if (DEAD == 1 && fdead) rs_dma16(rsrc_zero, NW * j < IA ? fL + ii * 1024 : fL + ABYTES + (ii - IA) * 1024, voff[j]);
+    else if (DEAD == 2 && fdead) rs_dma16(rsrc_dy, lds0 + SCRATCH, voff[j]);
+    else if (NW * j < IA) rs_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
+    else rs_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
   };
 
   f32x16 acc[TM][TN];
@@ -310,10 +262,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
       bf16x8 fa[TM], fb[TN];
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
-        fa[tm] = wb_tr_read8(L + aoff[tm][0] + (16 * s) * ROWA, L + aoff[tm][1] + (16 * s) * ROWA);
+        fa[tm] = rs_tr_read8(L + aoff[tm][0] + (16 * s) * ROWA, L + aoff[tm][1] + (16 * s) * ROWA);
 #pragma unroll
       for (int tn = 0; tn < TN; ++tn)
-        fb[tn] = wb_tr_read8(L + boff[tn][0] + (16 * s) * ROWB_, L + boff[tn][1] + (16 * s) * ROWB_);
+        fb[tn] = rs_tr_read8(L + boff[tn][0] + (16 * s) * ROWB_, L + boff[tn][1] + (16 * s) * ROWB_);
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -345,8 +297,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
       }
       int slot = 0;  // ring slot of the chunk being multiplied
       for (int c = chunk0; c < chunk1; ++c) {
-        if (c + 1 < chunk1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");  // chunk c landed, chunk c + 1 may still fly
-        else wb_dma_wait();
+        if (c + 1 < chunk1) rs_dma_wait_n<NI>();  // chunk c landed, chunk c + 1 may still fly
+        else rs_dma_wait();
         __syncthreads();
         const int s2 = slot == 0 ? RING - 1 : slot - 1;
         if (c + 2 < chunk1) {
@@ -376,14 +328,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
         for (int q = 0; q < NI; ++q) issue_piece(q);
       }
       if (LATE) {  // chunk0 retired, and a barrier behind that wait, before the loop's first read
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RING - 2) * NI) : "memory");
+        rs_dma_wait_n<(RING - 2) * NI>();
         __syncthreads();
       }
       int slot = 0;  // ring slot of the chunk being multiplied
       for (int c = chunk0; c < chunk1; ++c) {
         // RING = 3: chunk c has landed when at most the pieces of the chunk behind it are still in flight; the barrier publishes
         // everybody's share and frees the slot chunk c - 1 was read from: chunk c + RING - 1 streams into it between the MFMAs
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LOOPWAIT) : "memory");
+        rs_dma_wait_n<LOOPWAIT>();
         __syncthreads();
         const int s2 = slot == 0 ? RING - 1 : slot - 1;
         prepare_dma(c + RING - 1, s2, s2, c + RING - 1 < chunk1);
@@ -391,7 +343,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
         fill_table(c + RING, slot);  // (this slot's table was read by prepare_dma RING - 1 iterations ago)
         slot = slot == RING - 1 ? 0 : slot + 1;
       }
-      wb_dma_wait();  // (the out-of-range pieces of the last steps)
+      rs_dma_wait();  // (the out-of-range pieces of the last steps)
     }
   } else if (chunk0 < chunk1) {
     fill_table(chunk0, 0);
@@ -400,7 +352,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
     prepare_dma(chunk0, 0, 0);
 #pragma unroll
     for (int q = 0; q < NI; ++q) issue_piece(q);
-    wb_dma_wait();
+    rs_dma_wait();
     __syncthreads();
     int c = chunk0;
     for (; c + 1 < chunk1; ++c) {  // steady state: chunk c+1 streams into the other buffer between chunk c's MFMAs
@@ -409,7 +361,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN > 4 || RING > 2) ? 1 : 2
       prepare_dma(c + 1, (it + 1) & 1, (it + 1) & 1);
       chunk_mma(smem + (it & 1) * BUF, std::true_type());
       fill_table(c + 2, it & 1);
-      wb_dma_wait();  // this wave's share of chunk c+1 has landed; the barrier publishes everybody's
+      rs_dma_wait();  // this wave's share of chunk c+1 has landed; the barrier publishes everybody's
       __syncthreads();
     }
     chunk_mma(smem + ((c - chunk0) & 1) * BUF, std::false_type());
@@ -493,8 +445,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_phase4_bf16(const WgradArgs
   const int n_first = (int)rs_div((unsigned)m_first, p.div_howo);
   const long img = (long)p.Hs * p.Ws * Cs;
   const long dimg = (long)p.Ho * p.Wo * p.Cout;
-  const __amdgpu_buffer_rsrc_t rsrc_dy = wb_make_rsrc(p.dy + n_first * dimg, (long)(p.N - n_first) * dimg * 2);
-  const __amdgpu_buffer_rsrc_t rsrc_x = wb_make_rsrc(src + n_first * img, (long)(p.N - n_first) * img * 2);
+  const __amdgpu_buffer_rsrc_t rsrc_dy = rs_buf_rsrc<0xFFFFFFFEu>(p.dy + n_first * dimg, (long)(p.N - n_first) * dimg * 2);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_buf_rsrc<0xFFFFFFFEu>(src + n_first * img, (long)(p.N - n_first) * img * 2);
 
   // pixel m = source pixel (n, a, b): dz row (2a + py, 2b + px); source row of offset (r, s): (a - (1 - py) + r, b - (1 - px) + s)
   auto fill_table = [&](int chunk, int which) __attribute__((always_inline)) {
@@ -527,7 +479,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_phase4_bf16(const WgradArgs
   const int cola = (co0 + gp * 8) * 2;
   const int colb = (cs + gp * 8) * 2;
   const int cout2 = p.Cout * 2, cs2 = Cs * 2;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(wb_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   int voff[NI];
   unsigned int fL = lds0;
   // (`live` = 0: a chunk past the block's range -- its five pieces are still issued, out of range (zeros into a buffer nobody
@@ -544,8 +496,8 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_phase4_bf16(const WgradArgs
     }
   };
   auto issue_piece = [&](int j) __attribute__((always_inline)) {  // j: compile-time after unrolling
-    if (j == 0) wb_dma16(rsrc_dy, fL + wave * 1024, voff[0]);
-    else wb_dma16(rsrc_x, fL + j * TBYTES + wave * 1024, voff[j]);
+    if (j == 0) rs_dma16(rsrc_dy, fL + wave * 1024, voff[0]);
+    else rs_dma16(rsrc_x, fL + j * TBYTES + wave * 1024, voff[j]);
   };
 
   f32x16 acc[NOFF][TM];
@@ -577,10 +529,10 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_phase4_bf16(const WgradArgs
     for (int s = 0; s < NS; ++s) {
       bf16x8 fa[TM], fb[NOFF];
 #pragma unroll
-      for (int tm = 0; tm < TM; ++tm) fa[tm] = wb_tr_read8(L + aoff[tm][0] + (16 * s) * ROW, L + aoff[tm][1] + (16 * s) * ROW);
+      for (int tm = 0; tm < TM; ++tm) fa[tm] = rs_tr_read8(L + aoff[tm][0] + (16 * s) * ROW, L + aoff[tm][1] + (16 * s) * ROW);
 #pragma unroll
       for (int o = 0; o < NOFF; ++o)
-        fb[o] = wb_tr_read8(L + boff[0] + o * TBYTES + (16 * s) * ROW, L + boff[1] + o * TBYTES + (16 * s) * ROW);
+        fb[o] = rs_tr_read8(L + boff[0] + o * TBYTES + (16 * s) * ROW, L + boff[1] + o * TBYTES + (16 * s) * ROW);
 #pragma unroll
       for (int o = 0; o < NOFF; ++o)
 #pragma unroll
@@ -607,7 +559,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_phase4_bf16(const WgradArgs
     for (int c = chunk0; c < chunk1; ++c) {
       // chunk c has landed when at most the NI pieces of chunk c + 1 are still in flight; the barrier publishes everybody's
       // share and frees the slot chunk c - 1 was read from: chunk c + 2 streams into it between this chunk's MFMAs
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
+      rs_dma_wait_n<NI>();
       __syncthreads();
       const int s2 = slot == 0 ? 2 : slot - 1;  // (slot + 2) % 3
       prepare_dma(s2, s2, c + 2 < chunk1);
@@ -615,7 +567,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_phase4_bf16(const WgradArgs
       fill_table(c + 3, slot);  // (this slot's table was read by prepare_dma two iterations ago)
       slot = slot == 2 ? 0 : slot + 1;
     }
-    wb_dma_wait();  // (the out-of-range pieces of the last two steps)
+    rs_dma_wait();  // (the out-of-range pieces of the last two steps)
   }
 
   // D[i][j]: i = cout (tile-local) = (r&3) + 8*(r>>2) + 4*(lane>>5), j = cin (tile-local) = lane&31; offset o -> tap 4 * plane + o

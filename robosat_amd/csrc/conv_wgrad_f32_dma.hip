@@ -26,35 +26,9 @@
 #include <type_traits>
 
 #include "conv_wgrad_f32.h"
+#include "lds_dma.h"
 
 namespace {
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wd_make_rsrc(const void* base, long bytes) {
-  const unsigned int n = bytes > 0xFFFFFFFEL ? 0xFFFFFFFEu : (unsigned int)(bytes < 0 ? 0 : bytes);
-  // (the inputs are block-uniform, but 64-bit multiplies and divisions run on the VALU: readfirstlane makes the uniformity
-  // provable, the LDS-DMA asm needs its SRSRC in SGPRs -- see rb_make_rsrc in conv_igemm_dma_kernel.h)
-  const unsigned long b = (unsigned long)base;
-  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
-  const unsigned int nn = __builtin_amdgcn_readfirstlane(n);
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long)hi << 32) | lo), 0, (int)nn, 0x00020000);
-}
-
-// One LDS-DMA wave instruction: lane l's 16 bytes at buffer offset `voff` land at LDS byte `lds_dst` + 16*l (lds_dst
-// wave-uniform, in M0); an out-of-range offset writes zeros.  Inline asm for the reason given at wb_dma16 (conv_wgrad_bf16.hip):
-// the compiler must not drain the queue before the fragment reads of the OTHER buffer; the kernel waits itself.
-__device__ __forceinline__ void wd_dma16(__amdgpu_buffer_rsrc_t r, unsigned int lds_dst, int voff) {
-  asm volatile(
-      "s_mov_b32 m0, %1\n\t"
-      "s_nop 0\n\t"
-      "buffer_load_dwordx4 %0, %2, 0 offen lds"
-      :
-      : "v"(voff), "s"(lds_dst), "s"(r)
-      : "memory", "m0");
-}
-__device__ __forceinline__ void wd_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ unsigned int wd_lds_addr(const void* p) {
-  return (unsigned int)(unsigned long)(__attribute__((address_space(3))) const void*)p;
-}
 
 // PK = pixels per pipeline chunk (a plan chunk is 32 pixels).  Instantiated with 32: 16-pixel chunks -- half the LDS, four
 // blocks per CU instead of two -- were measured on every layer of the fp32 bs-8 step and change nothing (8.79 vs 8.74 ms
@@ -117,9 +91,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, PK == 16 ? 4 : 2) void conv_wgrad_f
   const long img = (long)p.Hs * p.Ws * Cs;
   const long dimg = (long)p.Ho * p.Wo * p.Cout;
   const __amdgpu_buffer_rsrc_t rsrc_dy =
-      PHASE ? wd_make_rsrc(p.dy + n_first * dimg, (long)(p.N - n_first) * dimg * 4)
-            : wd_make_rsrc(p.dy + (long)m_first * p.Cout, ((long)p.M - m_first) * p.Cout * 4);
-  const __amdgpu_buffer_rsrc_t rsrc_x = wd_make_rsrc(src + n_first * img, (long)(p.N - n_first) * img * 4);
+      PHASE ? rs_dma_rsrc<0xFFFFFFFEu>(p.dy + n_first * dimg, (long)(p.N - n_first) * dimg * 4)
+            : rs_dma_rsrc<0xFFFFFFFEu>(p.dy + (long)m_first * p.Cout, ((long)p.M - m_first) * p.Cout * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_dma_rsrc<0xFFFFFFFEu>(src + n_first * img, (long)(p.N - n_first) * img * 4);
   const int ush = p.ups ? 1 : 0;
   const int upar = p.ups == 2 ? 1 : 0;
 
@@ -157,7 +131,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, PK == 16 ? 4 : 2) void conv_wgrad_f
   const int colb = (cs + pp_b * 4) * 4;
   const int cout4 = p.Cout * 4, cs4 = Cs * 4;
 
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(wd_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   int voff[NI];
   unsigned int fL = lds0;
   auto prepare_dma = [&](int chunk, int buf, int which) __attribute__((always_inline)) {
@@ -184,8 +158,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, PK == 16 ? 4 : 2) void conv_wgrad_f
   };
   auto issue_piece = [&](int j) __attribute__((always_inline)) {
     const int ii = wave + NW * j;
-    if (NW * j < IA) wd_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
-    else wd_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
+    if (NW * j < IA) rs_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
+    else rs_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
   };
 
   f32x16 acc[TM][TN];
@@ -237,7 +211,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, PK == 16 ? 4 : 2) void conv_wgrad_f
     prepare_dma(chunk0, 0, 0);
 #pragma unroll
     for (int q = 0; q < NI; ++q) issue_piece(q);
-    wd_dma_wait();
+    rs_dma_wait();
     __syncthreads();
     int c = chunk0;
     for (; c + 1 < chunk1; ++c) {  // steady state: chunk c+1 streams into the other buffer between chunk c's MFMAs
@@ -246,7 +220,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, PK == 16 ? 4 : 2) void conv_wgrad_f
       prepare_dma(c + 1, (it + 1) & 1, (it + 1) & 1);
       chunk_mma(smem + (it & 1) * BUF, std::true_type());
       fill_table(c + 2, it & 1);
-      wd_dma_wait();  // this wave's share of chunk c+1 has landed; the barrier publishes everybody's
+      rs_dma_wait();  // this wave's share of chunk c+1 has landed; the barrier publishes everybody's
       __syncthreads();
     }
     chunk_mma(smem + ((c - chunk0) & 1) * BUF, std::false_type());

@@ -20,7 +20,7 @@
 //   wider layers (round 2): the grid's y / z dimensions walk 32-cout tiles and 128-cin slabs of a wider stride-1 3x3 layer
 //            (the encoder's conv2's: 64 -> 64 ... 512 -> 512), every block re-reading the patch's dy slice and halo slab; on
 //            layer1 (two cout tiles) that is 2.5x faster than nine tap-per-block passes, on the 128+ wide layers a wash.
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -33,31 +33,6 @@ struct ThinArgs {
   int ppr, ppi;       // patches per row / per image
   int total_patches, patches_per_block;
 };
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tb_make_rsrc(const void* base, long bytes) {
-  const unsigned int n = bytes > 0xFFFFFFFEL ? 0xFFFFFFFEu : (unsigned int)(bytes < 0 ? 0 : bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)n, 0x00020000);
-}
-
-__device__ __forceinline__ bf16x8 tb_tr_read8(const unsigned char* p0, const unsigned char* p1) {
-  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p1);
-  s16x8 v;
-  v[0] = lo[0];
-  v[1] = lo[1];
-  v[2] = lo[2];
-  v[3] = lo[3];
-  v[4] = hi[0];
-  v[5] = hi[1];
-  v[6] = hi[2];
-  v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 // CT = Cin / 32 (1, 2 or 4); UPS = 1: the input is read through the nearest-x2 upsample (source at half resolution)
 template <int CT, int UPS>
@@ -90,8 +65,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_thin_bf16(const ThinArgs p)
 
   const int co_base = blockIdx.y * 32, ci_base = blockIdx.z * CIN;
   const int dyrow = p.Cout * 2, xrow = p.Cin * 2;  // bytes per pixel in HBM
-  const __amdgpu_buffer_rsrc_t rsrc_dy = tb_make_rsrc(p.dy, (long)p.N * p.Ho * p.Wo * dyrow);
-  const __amdgpu_buffer_rsrc_t rsrc_x = tb_make_rsrc(p.src, (long)p.N * p.Hs * p.Ws * xrow);
+  const __amdgpu_buffer_rsrc_t rsrc_dy = rs_buf_rsrc<0xFFFFFFFEu>(p.dy, (long)p.N * p.Ho * p.Wo * dyrow);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_buf_rsrc<0xFFFFFFFEu>(p.src, (long)p.N * p.Hs * p.Ws * xrow);
 
   // ---- staging roles (fixed per thread): NH halo pieces + one dy piece -----------------------------------------
   int h_hy[NH], h_hx[NH], h_pc[NH], h_lds[NH];
@@ -189,12 +164,12 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_thin_bf16(const ThinArgs p)
       load_patch(pat + 1);  // zeros past the block's range
 #pragma unroll
       for (int si = 0; si < NS; ++si) {
-        const bf16x8 a = tb_tr_read8(L + aoff[si][0], L + aoff[si][1]);
+        const bf16x8 a = rs_tr_read8(L + aoff[si][0], L + aoff[si][1]);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx) {
-            const bf16x8 b = tb_tr_read8(L + yoff[si][ky] + xoff[0][kx], L + yoff[si][ky] + xoff[1][kx]);
+            const bf16x8 b = rs_tr_read8(L + yoff[si][ky] + xoff[0][kx], L + yoff[si][ky] + xoff[1][kx]);
             acc[ky * 3 + kx] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[ky * 3 + kx], 0, 0, 0);
           }
       }

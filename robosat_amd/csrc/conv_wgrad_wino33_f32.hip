@@ -16,7 +16,8 @@
 //           rows x 18 pixels instead of 8 x 16 -- next to two rows x 16 pixels of dy; LDS-DMA, gather table (-1 = zeros: padding,
 //           odd edges, the tail of a row), ring of three stages, as in conv_wgrad_wino_f32.hip.
 //   output  partial tiles [split][16][Cout][Cin]; rs_reduce_splits (fixed order), then wino33_wgrad_finish_kernel applies G^T . G.
-#include "conv_wgrad_wino_f32.h"
+#include "conv_wgrad_f32.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -72,8 +73,8 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
   if (chunk1 > p.nchunks) chunk1 = p.nchunks;
   const int n_first = (int)rs_div((unsigned)chunk0, p.div_tycx);
   const long img = (long)p.H * p.W;
-  const __amdgpu_buffer_rsrc_t rsrc_dy = ww_make_rsrc(p.dy + n_first * img * p.Cout, (long)(p.N - n_first) * img * p.Cout * 4);
-  const __amdgpu_buffer_rsrc_t rsrc_x = ww_make_rsrc(p.src + n_first * img * p.Cin, (long)(p.N - n_first) * img * p.Cin * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_dy = rs_dma_rsrc<0xFFFFFFFEu>(p.dy + n_first * img * p.Cout, (long)(p.N - n_first) * img * p.Cout * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_dma_rsrc<0xFFFFFFFEu>(p.src + n_first * img * p.Cin, (long)(p.N - n_first) * img * p.Cin * 4);
 
   auto fill_table = [&](int chunk, int which) __attribute__((always_inline)) {
     if (tid < NT) {
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
   const int ra_b = lane / PPB, pp_b = lane % PPB;
   const int cola = (co0 + pp_a * 4) * 4, colb = (ci0 + pp_b * 4) * 4;
   const int cout4 = p.Cout * 4, cin4 = p.Cin * 4;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(ww_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   int voff[NI];
   unsigned int fL = lds0;
   auto prepare_dma = [&](int buf, int which) __attribute__((always_inline)) {
@@ -122,8 +123,8 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
   };
   auto issue_piece = [&](int j) __attribute__((always_inline)) {
     const int ii = wave + NW * j;
-    if (ii < IA) ww_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
-    else if (ii < IA + IB) ww_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
+    if (ii < IA) rs_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
+    else if (ii < IA + IB) rs_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
   };
 
   f32x16 acc[8];
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
         for (int q = 0; q < NI; ++q) issue_piece(q);
       }
     }
-    ww_dma_wait();
+    rs_dma_wait();
     __syncthreads();
     int st = 0;
     for (int c = chunk0; c < chunk1; ++c) {
@@ -218,9 +219,9 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
       chunk_mma(smem + st * BUF, fetch);
       if (fetch) {
         fill_table(c + RING, st);
-        ww_dma_wait_but<(RING - 2) * NI>();
+        rs_dma_wait_n<(RING - 2) * NI>();
       } else {
-        ww_dma_wait();
+        rs_dma_wait();
       }
       __syncthreads();
       st = st == RING - 1 ? 0 : st + 1;

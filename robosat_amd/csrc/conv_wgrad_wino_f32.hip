@@ -21,11 +21,14 @@
 //                transforms them in registers and feeds the nine MFMAs of the k-step.
 //   output       partial tiles [split][parity][xi][Cout][Cin]; wino_wgrad_finish_kernel sums the splits in a fixed order, applies
 //                G^T . G and adds the (parity, tap) pairs that make up each 3x3 filter tap (combine_phase_wgrad_f32_kernel's rule).
-#include "conv_wgrad_wino_f32.h"
+#include "conv_wgrad_f32.h"
+#include "lds_dma.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kWwPK = 8;  // tiles per chunk of the four-wave blocks (the plan counts chunks of this size; the eight-wave block takes two at a time)
 
 struct WinoWgradArgs {
   const float* dz;    // [N][2 Hs][2 Ws][Cout]
@@ -95,8 +98,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
   const int Ho = 2 * p.Hs, Wo = 2 * p.Ws;
   const int n_first = (int)rs_div((unsigned)(chunk0 * PK), p.div_tytx);
   const long img = (long)p.Hs * p.Ws * Cs, dimg = (long)Ho * Wo * p.Cout;
-  const __amdgpu_buffer_rsrc_t rsrc_dz = ww_make_rsrc(p.dz + n_first * dimg, (long)(p.N - n_first) * dimg * 4);
-  const __amdgpu_buffer_rsrc_t rsrc_x = ww_make_rsrc(src + n_first * img, (long)(p.N - n_first) * img * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_dz = rs_dma_rsrc<0xFFFFFFFEu>(p.dz + n_first * dimg, (long)(p.N - n_first) * dimg * 4);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_dma_rsrc<0xFFFFFFFEu>(src + n_first * img, (long)(p.N - n_first) * img * 4);
 
   auto fill_table = [&](int chunk, int which) __attribute__((always_inline)) {
     if (tid < NT) {
@@ -129,7 +132,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
   const int ra_b = lane / PPB, pp_b = lane % PPB;
   const int cola = (co0 + pp_a * 4) * 4, colb = (cs + pp_b * 4) * 4;
   const int cout4 = p.Cout * 4, cs4 = Cs * 4;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(ww_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   int voff[NI];
   unsigned int fL = lds0;
   auto prepare_dma = [&](int buf, int which) __attribute__((always_inline)) {
@@ -151,8 +154,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
 #if defined(RS_WW_KO) && (RS_WW_KO & 1)
     return;  // (knock-out build: no DMA in the steady state -- wrong results by construction)
 #endif
-    if (ii < IA) ww_dma16(rsrc_dz, fL + ii * 1024, voff[j]);
-    else if (ii < IA + IB) ww_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
+    if (ii < IA) rs_dma16(rsrc_dz, fL + ii * 1024, voff[j]);
+    else if (ii < IA + IB) rs_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
   };
 
   f32x16 acc[9];
@@ -242,7 +245,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
         for (int q = 0; q < NI; ++q) issue_piece(q);
       }
     }
-    ww_dma_wait();
+    rs_dma_wait();
     __syncthreads();
     int st = 0;  // (c - chunk0) % RING
     for (int c = chunk0; c < chunk1; ++c) {
@@ -252,9 +255,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
       chunk_mma(smem + st * BUF, fetch);
       if (fetch) {
         fill_table(c + RING, st);
-        ww_dma_wait_but<(RING - 2) * NI>();
+        rs_dma_wait_n<(RING - 2) * NI>();
       } else {
-        ww_dma_wait();
+        rs_dma_wait();
       }
       __syncthreads();
       st = st == RING - 1 ? 0 : st + 1;

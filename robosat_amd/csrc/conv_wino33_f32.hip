@@ -20,7 +20,7 @@
 //   store  = A^T M A (+ the eval-mode BatchNorm's scale / shift, ReLU) from registers: 4 consecutive couts per lane.
 // Only the EVAL epilogue exists (predict, serve): the train-mode forward needs the raw output + BatchNorm partial sums and
 // stays on the generic kernel.  Chosen by layer geometry (>= 8 tiles per image side, i.e. H, W >= 15), never by batch size.
-#define RS_CONV_INSTANTIATE  // (for the LDS-DMA helpers of the header; no kernel of it is instantiated here)
+#define RS_CONV_INSTANTIATE  // (for kDmaOOB / kDmaClamp and the small helpers of the header; no kernel of it is instantiated here)
 #include "conv_igemm_dma_kernel.h"
 #include "final_head.h"
 
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   const int ntiles = ((p.nsub + SB - 1) / SB) * p.ncb;
   const int first = rs_xcd_remap(blockIdx.x, gridDim.x);
   const int nitems = (ntiles - first + (int)gridDim.x - 1) / (int)gridDim.x;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rb_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   const long img = (long)p.H * p.W * p.Cin;
 
   auto decode = [&](int it, int& mblk, int& nblk) __attribute__((always_inline)) {
@@ -157,13 +157,13 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   const int ra = lane >> 2, pp = lane & 3;
   int doff[NI];
   int f_seq = 0, f_kc = 0, f_g = 0;
-  __amdgpu_buffer_rsrc_t rsrc = rb_make_rsrc(p.src, 0);
-  const __amdgpu_buffer_rsrc_t rsrcu = rb_make_rsrc(p.u, (long)16 * p.Cout * p.Cin * 4);
+  __amdgpu_buffer_rsrc_t rsrc = rs_dma_rsrc<kDmaClamp>(p.src, 0);
+  const __amdgpu_buffer_rsrc_t rsrcu = rs_dma_rsrc<kDmaClamp>(p.u, (long)16 * p.Cout * p.Cin * 4);
   auto fetch_item = [&]() __attribute__((always_inline)) {
     int mblk, nblk;
     decode(first + f_seq * (int)gridDim.x, mblk, nblk);
     const int nfirst = __builtin_amdgcn_readfirstlane((mblk * SB) / per_img);
-    rsrc = rb_make_rsrc(p.src + nfirst * img, (long)(p.N - nfirst) * img * 4);
+    rsrc = rs_dma_rsrc<kDmaClamp>(p.src + nfirst * img, (long)(p.N - nfirst) * img * 4);
     const int* tab = tabs + (f_seq & 1) * AROWS_PAD;
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
@@ -186,8 +186,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
     const int fs = f_kc * KC * 4;
     interleave([&](int j) __attribute__((always_inline)) {
       const int ii = wave + NW * j;  // wave-uniform
-      if (ii < IA) rb_dma16s(rsrc, fL + ii * 1024, doff[j], fs);
-      else if (ii < IA + IB) rb_dma16s(rsrcu, fL + ii * 1024, doff[j], fs);
+      if (ii < IA) rs_dma16(rsrc, fL + ii * 1024, doff[j], fs);
+      else if (ii < IA + IB) rs_dma16(rsrcu, fL + ii * 1024, doff[j], fs);
     });
     ++f_g;
     if (!past && ++f_kc == nk) {
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
     for (int x = 0; x < 16; ++x) acc[x] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int kc = 0; kc < nk; ++kc, ++g) {
-      rb_dma_wait();
+      rs_dma_wait();
       __syncthreads();
       if (HEAD && kc == 0 && seq > 0) finish_head();  // (behind this barrier the other cout group's partial logits are in LDS)
       if (STATS && kc == 0 && seq > 0) finish_stats();
@@ -504,7 +504,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
     __syncthreads();
     if (nitems > 0) finish_stats();
   }
-  rb_dma_wait();  // (the re-issued pieces of the last chunk: landed before this block's LDS is handed to the next one)
+  rs_dma_wait();  // (the re-issued pieces of the last chunk: landed before this block's LDS is handed to the next one)
 }
 
 // U = G g G^T per (cout, cin): KRSC [Cout][3][3][Cin] -> [16][Cout][Cin]

@@ -44,7 +44,7 @@
 // (profiles/r03/wino_variants.txt): 32x32x2 MFMAs with 144 accumulator registers at one wave per SIMD (104 TFLOP/s executed
 // on dec3), the same with two dedicated DMA-producer waves and persistent blocks (101), with wave pairs splitting each
 // chunk's channels and an LDS reduction at the end (110), this one (116); front-loading the DMA pieces: no change.
-#define RS_CONV_INSTANTIATE  // (for the LDS-DMA helpers of the header; no kernel of it is instantiated here)
+#define RS_CONV_INSTANTIATE  // (for kDmaOOB / kDmaClamp and the small helpers of the header; no kernel of it is instantiated here)
 #include "conv_igemm_dma_kernel.h"
 
 namespace {
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   auto item_of = [&](int seq) __attribute__((always_inline)) {  // the (m block, cout block, parity) index of the block's unit `seq`
     return DG ? (((first + (seq >> 2) * (int)gridDim.x) << 2) | (seq & 3)) : first + seq * (int)gridDim.x;
   };
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rb_lds_addr(smem));
+  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   const long img1 = (long)p.Hs * p.Ws * p.C1 * (DG ? 4 : 1), img2 = (long)p.Hs * p.Ws * p.C2;  // (DG: dz images are 2 Hs x 2 Ws)
 
   // item -> (parity, m block, cout block)
@@ -177,14 +177,14 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   const int ra = lane >> 2, pp = lane & 3;
   int doff[NI];
   int f_seq = 0, f_kc = 0, f_g = 0;  // item / chunk / global chunk being fetched
-  __amdgpu_buffer_rsrc_t rsrc1 = rb_make_rsrc(p.src1, 0), rsrc2 = rsrc1, rsrcu = rsrc1;
+  __amdgpu_buffer_rsrc_t rsrc1 = rs_dma_rsrc<kDmaClamp>(p.src1, 0), rsrc2 = rsrc1, rsrcu = rsrc1;
   auto fetch_item = [&]() __attribute__((always_inline)) {  // f_seq changed: descriptors and filter offsets of the new item
     int py, px, mblk, nblk;
     decode(item_of(f_seq), py, px, mblk, nblk);
     const int nfirst = __builtin_amdgcn_readfirstlane((mblk * SB) / per_img);
-    rsrc1 = rb_make_rsrc(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * 4);
-    rsrc2 = rb_make_rsrc(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * 4);
-    rsrcu = rb_make_rsrc(p.u + (long)(2 * py + px) * 9 * p.Cout * Cin, (long)9 * p.Cout * Cin * 4);
+    rsrc1 = rs_dma_rsrc<kDmaClamp>(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * 4);
+    rsrc2 = rs_dma_rsrc<kDmaClamp>(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * 4);
+    rsrcu = rs_dma_rsrc<kDmaClamp>(p.u + (long)(2 * py + px) * 9 * p.Cout * Cin, (long)9 * p.Cout * Cin * 4);
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int ii = wave + NW * j;
@@ -223,10 +223,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
     interleave([&](int j) __attribute__((always_inline)) {
       const int ii = wave + NW * j;  // wave-uniform
       if (ii < IA) {
-        if (src_first) rb_dma16s(rsrc1, fL + ii * 1024, doff[j], fsa);
-        else rb_dma16s(rsrc2, fL + ii * 1024, doff[j], fsa);
+        if (src_first) rs_dma16(rsrc1, fL + ii * 1024, doff[j], fsa);
+        else rs_dma16(rsrc2, fL + ii * 1024, doff[j], fsa);
       } else if (ii < IA + IB) {
-        rb_dma16s(rsrcu, fL + ii * 1024, doff[j], fsu);
+        rs_dma16(rsrcu, fL + ii * 1024, doff[j], fsu);
       }
     });
     ++f_g;
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
     const int x = q / (4 * NM), k = (q / NM) % 4, m = q % NM;
     acc[x][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(Bq[x][m][k], V[x][k], acc[x][m], 0, 0, 0);
   };
-  rb_dma_wait();
+  rs_dma_wait();
   __syncthreads();  // chunk 0 is in stage 0
   chunk_head(smem, V, Bq[0], [](int) {}, std::integral_constant<int, 0>());
 
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
       // in item seq's last chunk -- a later one, since nk >= 2 (wino_plan)
       if (kc == 0 && seq + 1 < nitems) build_table(seq + 1);
       rs_lds_writes_done();  // (and every LDS read of stage g & 1 by this wave has returned: other waves refill it behind the barrier)
-      rb_dma_wait();
+      rs_dma_wait();
       __syncthreads();  // chunk g + 1 is in stage (g + 1) & 1; no wave reads stage g & 1 any more
       // tail: chunk g's last TAIL positions around chunk g + 1's head (past the block's last chunk: the re-issued pieces, unused)
       f32x4 Vn[9], B0[NM];
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
         }
     }
   }
-  rb_dma_wait();  // (the re-issued pieces of the last chunk: landed before this block's LDS is handed to the next one)
+  rs_dma_wait();  // (the re-issued pieces of the last chunk: landed before this block's LDS is handed to the next one)
 }
 
 // U = G g G^T per (parity, cout, cin): phase pack [4][Cout][2][2][Cin] -> [4][9][Cout][Cin]

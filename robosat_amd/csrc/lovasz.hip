@@ -198,7 +198,6 @@ __global__ __launch_bounds__(256) void radix_scatter_kernel(const uint32_t* __re
   // one table read + one 8-byte store per element.  Rounds 1-4 counted first (an atomic per element), matched again in the
   // second sweep and read + updated the running counters there: ~8 scattered LDS operations per element against ~4 now
   // (scattered = bank conflicts by construction: SQ_LDS_BANK_CONFLICT was 64 % of this kernel's LDS cycles).  Same output.
-  typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
   constexpr int WCH = CHUNK / 4;       // elements per wave
   constexpr int NB = WCH / 64;         // batches of 64 per wave
   __shared__ u32x2 lkv[CHUNK];         // the tile, sorted by digit: (key, value)

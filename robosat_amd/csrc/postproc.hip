@@ -47,7 +47,6 @@ __global__ __launch_bounds__(256) void label_histogram_kernel(const uint8_t* __r
   __syncthreads();
   unsigned int* h = hist[threadIdx.x >> 6];
   const long nvec = n / 16;
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   const u32x4* v = reinterpret_cast<const u32x4*>(labels);
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (long)gridDim.x * blockDim.x) {
     const u32x4 q = v[i];

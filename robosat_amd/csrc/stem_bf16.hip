@@ -12,35 +12,9 @@
 //             ds_read_b64_tr_b16 every 4-lane set addresses one pixel ROW of the 4x16 block and every lane of the set
 //             its own TAP (the 8 bytes it reads are one input pixel = 4 channels), so the hardware transpose delivers
 //             [pixel k][(kx, ci)] without ever materialising an im2col row.
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
-
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sb_make_rsrc(const void* base, long bytes) {
-  const unsigned int n = bytes > 0xFFFFFFFEL ? 0xFFFFFFFEu : (unsigned int)(bytes < 0 ? 0 : bytes);
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)n, 0x00020000);
-}
-
-__device__ __forceinline__ bf16x8 sb_tr_read8(const unsigned char* p0, const unsigned char* p1) {
-  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_ptr)p1);
-  s16x8 v;
-  v[0] = lo[0];
-  v[1] = lo[1];
-  v[2] = lo[2];
-  v[3] = lo[3];
-  v[4] = hi[0];
-  v[5] = hi[1];
-  v[6] = hi[2];
-  v[7] = hi[3];
-  return __builtin_bit_cast(bf16x8, v);
-}
 
 // ---------------------------------------------------------------------------------------------------------------------
 // forward
@@ -84,7 +58,7 @@ __global__ __launch_bounds__(256, 2) void stem_fwd_bf16_kernel(const StemFwdArgs
     *reinterpret_cast<u32x4*>(wl + r * FWROW + c * 16) = *reinterpret_cast<const u32x4*>(p.w + (long)r * 224 + c * 8);
   }
 
-  const __amdgpu_buffer_rsrc_t rsrc = sb_make_rsrc(p.x, (long)p.N * p.H * p.W * 8);
+  const __amdgpu_buffer_rsrc_t rsrc = rs_buf_rsrc<0xFFFFFFFEu>(p.x, (long)p.N * p.H * p.W * 8);
   int h_y[FNP], h_x[FNP];
 #pragma unroll
   for (int j = 0; j < FNP; ++j) {
@@ -213,8 +187,8 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_bf16_kernel(const StemWgrad
   int pat1 = pat0 + p.patches_per_block;
   if (pat1 > p.total_patches) pat1 = p.total_patches;
 
-  const __amdgpu_buffer_rsrc_t rsrc_x = sb_make_rsrc(p.x, (long)p.N * p.H * p.W * 8);
-  const __amdgpu_buffer_rsrc_t rsrc_dy = sb_make_rsrc(p.dy, (long)p.N * p.Ho * p.Wo * 128);
+  const __amdgpu_buffer_rsrc_t rsrc_x = rs_buf_rsrc<0xFFFFFFFEu>(p.x, (long)p.N * p.H * p.W * 8);
+  const __amdgpu_buffer_rsrc_t rsrc_dy = rs_buf_rsrc<0xFFFFFFFEu>(p.dy, (long)p.N * p.Ho * p.Wo * 128);
   int h_y[WNP], h_x[WNP];
 #pragma unroll
   for (int j = 0; j < WNP; ++j) {
@@ -304,15 +278,15 @@ __global__ __launch_bounds__(256, 2) void stem_wgrad_bf16_kernel(const StemWgrad
         // k-step s covers pixels 16s..16s+15 = patch rows 2s, 2s+1
         bf16x8 a[2];
 #pragma unroll
-        for (int tm = 0; tm < 2; ++tm) a[tm] = sb_tr_read8(L + aoff[tm][0] + s * 2048, L + aoff[tm][1] + s * 2048);
+        for (int tm = 0; tm < 2; ++tm) a[tm] = rs_tr_read8(L + aoff[tm][0] + s * 2048, L + aoff[tm][1] + s * 2048);
         const int rowb = (4 * s) * WROW;  // halo row of patch row 2s is 2*(2s) = 4s
         {
-          const bf16x8 b = sb_tr_read8(L + rowb + ky0 * WROW + boff[0], L + rowb + ky0 * WROW + boff[1]);
+          const bf16x8 b = rs_tr_read8(L + rowb + ky0 * WROW + boff[0], L + rowb + ky0 * WROW + boff[1]);
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm) acc[0][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm], b, acc[0][tm], 0, 0, 0);
         }
         if (ky1 < 7) {  // wave-uniform
-          const bf16x8 b = sb_tr_read8(L + rowb + ky1 * WROW + boff[0], L + rowb + ky1 * WROW + boff[1]);
+          const bf16x8 b = rs_tr_read8(L + rowb + ky1 * WROW + boff[0], L + rowb + ky1 * WROW + boff[1]);
 #pragma unroll
           for (int tm = 0; tm < 2; ++tm) acc[1][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[tm], b, acc[1][tm], 0, 0, 0);
         }

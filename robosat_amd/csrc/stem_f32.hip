@@ -28,7 +28,7 @@
 // scripts/debug/stem_trace.py): a tile is 9 700 cycles of MFMAs + 2 200 of everything else, and the CU's two blocks ALTERNATE rather than
 // overlap -- a block's VALU work (epilogue arithmetic, fetch addresses) crawls while the other block's waves stream MFMAs on the same
 // SIMDs (its LDS traffic and barriers do not); s_setprio, s_sleep between MFMA pairs and a staggered start changed nothing.
-#include "common.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -84,14 +84,6 @@ __host__ __device__ constexpr int stem_imm(int t) {
   using G = Geom<CIN>;
   const Tap k = stem_tap<CIN>(t, 0);
   return ((k.r * 2 + (k.s & 1)) * XI + (k.s >> 1)) * G::PS + k.c;
-}
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t stem_rsrc(const float* base, long bytes) {
-  const unsigned int n = bytes > 0x7FFFFFF0L ? 0x7FFFFFF0u : (unsigned int)(bytes < 0 ? 0 : bytes);
-  const unsigned long b = (unsigned long)base;
-  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
-  return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long)hi << 32) | lo), 0,
-                                           (int)__builtin_amdgcn_readfirstlane(n), 0x00020000);
 }
 
 template <int CIN>
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(256, CIN == 3 ? 2 : 1) void stem_conv_f32(const Ste
   // fetch under `if (tile + 1 < t1)` makes pf a merge of old and new values, hipcc then loads into temporaries and copies, and the copies
   // wait for the loads right where they were issued: the strip's round trip ended up in front of every tile's MFMAs.)
   auto fetch = [&](int n, int oy, int tx, bool live) __attribute__((always_inline)) {
-    const __amdgpu_buffer_rsrc_t rs = stem_rsrc(p.x + n * img, live ? img * 4 : 0);
+    const __amdgpu_buffer_rsrc_t rs = rs_dma_rsrc<0x7FFFFFF0u>(p.x + n * img, live ? img * 4 : 0);
     const int iy0 = 2 * oy - 3, ix0 = 2 * tx * SBM - 3;
     const int base = (iy0 * p.W + ix0) * 16;
 #pragma unroll
