@@ -13,8 +13,6 @@ Backward structure (no tensor is ever upsampled or concatenated in memory, in ei
     ``torch.cat`` split + the ReLU masks into one pass.
 """
 
-import os
-
 import torch
 
 from . import ops
@@ -30,7 +28,7 @@ def _side_stream(device):
 
     if torch.device(device).type != "cuda":
         return None  # (host tensors -- the 8-rank gloo test of the arena / reducer bookkeeping, tests/dp_worker.py: no streams to order)
-    if os.environ.get("ROBOSAT_WGRAD_STREAM", "1") == "0":  # measurement knob: serial backward (clean per-kernel timings)
+    if not ops.switch("ROBOSAT_WGRAD_STREAM"):  # measurement knob: serial backward (clean per-kernel timings)
         return torch.cuda.current_stream(device)
     s = _SIDE.get(device)
     if s is None:
@@ -193,7 +191,7 @@ def _conv_bn(bn, src, w, stride=1, pad=0, residual=None, relu=True, conv=None):
     run the Winograd F(2x2, 3x3) form with the same statistics epilogue (4/9 of the multiply-adds)."""
 
     if (conv is not None and src.dtype == torch.float32 and stride == 1 and pad == 1 and ops.wino33_ok(src, conv.cout)
-            and os.environ.get("ROBOSAT_WINO33_STATS", "1") != "0"):
+            and ops.switch("ROBOSAT_WINO33_STATS")):
         y, partial = ops.conv2d_wino33_bnstats(src, conv.wino33())
     else:
         y, partial = ops.conv2d_bnstats(src, w, stride=stride, pad=pad)
@@ -287,7 +285,7 @@ def _forward(net, x, tape, backward=False):
     dec2 = up(net.dec2, enc2, dec1)
     dec3 = up(net.dec3, enc1, dec2)
     dec4 = up(net.dec4, dec3)
-    if dt == torch.float32 and ops.wino33_ok(dec4, net.dec5.block.cout) and os.environ.get("ROBOSAT_WINO33_BWD", "1") != "0":
+    if dt == torch.float32 and ops.wino33_ok(dec4, net.dec5.block.cout) and ops.switch("ROBOSAT_WINO33_BWD"):
         dec5 = ops.conv2d_wino33(dec4, net.dec5.block.wino33(), relu=True)  # (as the eval forward runs it)
     else:
         dec5 = ops.conv2d(dec4, net.dec5.block.krsc(dt), pad=1, relu=True)
@@ -414,7 +412,7 @@ def _backward(net, tape, dlogits, arena):
         arena.wgrad(lambda: ops.conv2d_wgrad(dy2, rec["z1"], 3, 3, stride=blk.stride, pad=1, out=w2), dy2, rec["z1"])
         h1, w1_ = rec["z1"].shape[1], rec["z1"].shape[2]
         if (blk.conv2.stride == 2 and blk.conv2.k == 3 and blk.conv2.padding == 1 and h1 == 2 * dy2.shape[1] and w1_ == 2 * dy2.shape[2]
-                and os.environ.get("ROBOSAT_S2_DGRAD", "1") != "0" and os.environ.get("ROBOSAT_S2_DGRAD_3X3", "1") != "0"):
+                and ops.switch("ROBOSAT_S2_DGRAD") and ops.switch("ROBOSAT_S2_DGRAD_3X3")):
             # 3x3 / stride 2: on each input parity the gradient is a 2x2 convolution over dy -- the phase form's geometry (16, in the
             # fp32 Winograd form 9, multiply-adds per four pixels against the zero-insertion launch's 36); BatchNorm's reductions
             # then take their own pass (bn_bwd) instead of riding in that launch's epilogue
@@ -441,7 +439,7 @@ def _backward(net, tape, dlogits, arena):
             wdn = arena.conv(dconv)
             arena.wgrad(lambda: ops.conv2d_wgrad(dyd, h, 1, 1, stride=blk.stride, out=wdn), dyd, h)
             if (extra is not None and dconv.k == 1 and dconv.stride == 2 and dconv.padding == 0 and hw_in[0] % 2 == 0 and hw_in[1] % 2 == 0
-                    and os.environ.get("ROBOSAT_S2_DGRAD", "1") != "0"):
+                    and ops.switch("ROBOSAT_S2_DGRAD")):
                 # 1x1 / stride 2: the transposed product on the low-resolution grid, added onto the even positions of the skip
                 # branch's gradient in place (as a zero-insertion convolution three of four GEMM rows are zeros)
                 res = ops.scatter_add_stride2(ops.conv2d(dyd, dconv.dgrad_weight(dyd.dtype)), extra)

@@ -198,9 +198,7 @@ __global__ __launch_bounds__(512, 2) void bottleneck_tail_f32(const TailArgs p) 
 }  // namespace
 
 static int tail_launch(const TailArgs& a, bool chain, hipStream_t s) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  const int cus = rs_cu_count();
   const int want = (a.nsub + 7) / 8;
   const int grid = want < cus ? want : cus;
   if (chain) bottleneck_tail_f32<true><<<grid, 512, 0, s>>>(a);

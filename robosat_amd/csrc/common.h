@@ -161,6 +161,18 @@ __device__ __forceinline__ double rs_wave_sum(double v) {
 
 static inline int rs_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Compute units of the device that is current at the FIRST call (256 if the query fails), cached for the process: the persistent
+// kernels size their grids by it.
+inline int rs_cu_count() {
+  static const int n = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;
+    return cus;
+  }();
+  return n;
+}
+
 // Division of a 31-bit unsigned by a runtime-constant divisor with one mul-hi (Granlund-Montgomery round-up
 // method): q = (umulhi(n, mul) + n) >> shift, exact for 0 <= n < 2^31 and 1 <= d < 2^31.
 struct rs_fastdiv {

@@ -259,9 +259,7 @@ int rs_conv1x1_ew_bf16_stats_ok(const rs_conv_desc* d) {
 }
 
 int rs_conv1x1_ew_bf16_stats_launch(const ConvArgsT<bf16_t>& a, hipStream_t s) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  const int cus = rs_cu_count();
   const long items = (long)rs_cdiv(a.M, EB_BM) * (a.Cout / EB_BN);
   if (items <= 0 || items >= (1L << 31) || !a.stats) return RS_EINVAL;
   const int grid = (int)(items < cus ? items : cus);

@@ -250,9 +250,7 @@ int rs_conv1x1_ew_f32_ok(const rs_conv_desc* d) {
 }
 
 int rs_conv1x1_ew_f32_launch(const ConvArgsT<float>& a, hipStream_t s) {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  const int cus = rs_cu_count();
   const long items = (long)rs_cdiv(a.M, EW_BM) * (a.Cout / EW_BN);
   if (items <= 0 || items >= (1L << 31)) return RS_EINVAL;
   const int grid = (int)(items < 2L * cus ? items : 2L * cus);

@@ -534,16 +534,6 @@ __global__ void pack_wino33_weight_kernel(const float* __restrict__ w, float* __
   }
 }
 
-int w33_cus() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
 // 0: cannot run; 1: can and should; (there is no "can but should not": the form needs >= 8 tiles per image side to run at all)
 int w33_plan(const rs_conv_desc* d, int* cgroups) {
   if (!d || d->N <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->C1 < 32 || (d->C1 % 16) || d->C2 != 0 || d->Cout <= 0 || (d->Cout % 16)) return 0;
@@ -616,7 +606,7 @@ extern "C" int rs_conv2d_fwd_wino33(const rs_conv_desc* d, const float* src, con
   const int sb = 16 * (8 / cgn) / (kPB * kPB);
   const long items = (long)rs_cdiv(a.nsub, sb) * a.ncb;
   if (items >= (1L << 31)) return RS_EINVAL;
-  const int grid = (int)(items < w33_cus() ? items : w33_cus());
+  const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
   if (cgn == 2) conv_wino33_f32_kernel<4, 2><<<grid, 512, 0, s>>>(a);
   else conv_wino33_f32_kernel<8, 1><<<grid, 512, 0, s>>>(a);
@@ -663,7 +653,7 @@ extern "C" int rs_conv2d_fwd_wino33_head(const rs_conv_desc* d, const float* src
   a.mask_bits = nullptr;
   const long items = a.nsub;
   if (items >= (1L << 31)) return RS_EINVAL;
-  const int grid = (int)(items < w33_cus() ? items : w33_cus());
+  const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
   if (mode <= 1) conv_wino33_f32_kernel<4, 2, 1><<<grid, 512, 0, s>>>(a);
   else if (mode == 2) conv_wino33_f32_kernel<4, 2, 2><<<grid, 512, 0, s>>>(a);
@@ -710,7 +700,7 @@ extern "C" int rs_conv2d_fwd_wino33_stats(const rs_conv_desc* d, const float* sr
   const int sb = 16 * (8 / cgn) / (kPB * kPB);
   const long items = (long)rs_cdiv(a.nsub, sb) * a.ncb;
   if (items >= (1L << 31)) return RS_EINVAL;
-  const int grid = (int)(items < w33_cus() ? items : w33_cus());
+  const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
   if (cgn == 2) conv_wino33_f32_kernel<4, 2, 4><<<grid, 512, 0, s>>>(a);
   else conv_wino33_f32_kernel<8, 1, 4><<<grid, 512, 0, s>>>(a);
@@ -761,7 +751,7 @@ extern "C" int rs_conv2d_dgrad_wino33(const rs_conv_desc* d, const float* dy, co
   const int sb = 16 * (8 / cgn) / (kPB * kPB);
   const long items = (long)rs_cdiv(a.nsub, sb) * a.ncb;
   if (items >= (1L << 31)) return RS_EINVAL;
-  const int grid = (int)(items < w33_cus() ? items : w33_cus());
+  const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
   conv_wino33_f32_kernel<4, 2, 5><<<grid, 512, 0, s>>>(a);
   return RS_LAUNCH_RESULT();

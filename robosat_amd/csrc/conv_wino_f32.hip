@@ -481,16 +481,6 @@ __global__ void pack_wino_dgrad_weight_kernel(const float* __restrict__ wd, floa
   for (int x = 0; x < 9; ++x) u[(((long)ph * 9 + x) * Cin + ci) * Cout + co] = v[x];
 }
 
-int wino_cus() {
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;
-    return cus;
-  }();
-  return n;
-}
-
 bool wino_wide() {  // (A/B knob while the wide block is being measured: ROBOSAT_WINO_WIDE=0 keeps 64 tiles x 64 couts)
   return rs_knobs().wino_wide != 0;
 }
@@ -532,7 +522,7 @@ bool wino_plan(const rs_conv_desc* d, WinoPlan* pl) {
   pl->wide = false;
   if (pl->pb == 8 && pl->wgn == 2 && wino_wide()) {
     const long nsub = (long)d->N * rs_cdiv(ty, 8) * rs_cdiv(tx, 8);
-    pl->wide = (nsub + 1) / 2 * (d->Cout / 64) * 4 >= 2L * wino_cus();
+    pl->wide = (nsub + 1) / 2 * (d->Cout / 64) * 4 >= 2L * rs_cu_count();
     if (pl->wide) pl->sb = 2;
   }
   return true;
@@ -588,7 +578,7 @@ extern "C" int rs_conv2d_fwd_phase_wino(const rs_conv_desc* d, const float* src1
   const long items = (long)rs_cdiv(a.nsub, pl.sb) * a.ncb * 4;
   if (items >= (1L << 31)) return RS_EINVAL;
   // persistent: one block per CU (its LDS stages fill the CU), items dealt round-robin
-  const int grid = (int)(items < wino_cus() ? items : wino_cus());
+  const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
   if (pl.wide) conv_wino_f32_kernel<8, 8, 1, 4><<<grid, 512, 0, s>>>(a);  // 128 tiles x 64 couts
   else if (pl.pb == 8 && pl.wgn == 2) conv_wino_f32_kernel<8, 4, 2><<<grid, 512, 0, s>>>(a);
@@ -666,11 +656,11 @@ extern "C" int rs_conv2d_dgrad_phase_wino(const rs_conv_desc* d, const float* dz
   a.relu = 0;
   // (the wide block where that leaves two OUTPUT items per CU: there is no parity factor in the item count here)
   bool wide = false;
-  if (wino_wide()) wide = (long)((a.nsub + 1) / 2) * a.ncb >= 2L * wino_cus();
+  if (wino_wide()) wide = (long)((a.nsub + 1) / 2) * a.ncb >= 2L * rs_cu_count();
   const int sb = wide ? 2 : 1;
   const long items = (long)rs_cdiv(a.nsub, sb) * a.ncb;
   if (items >= (1L << 29)) return RS_EINVAL;
-  const int grid = (int)(items < wino_cus() ? items : wino_cus());
+  const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
   if (wide) conv_wino_f32_kernel<8, 8, 1, 4, true><<<grid, 512, 0, s>>>(a);
   else conv_wino_f32_kernel<8, 4, 2, 2, true><<<grid, 512, 0, s>>>(a);

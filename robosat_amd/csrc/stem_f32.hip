@@ -318,9 +318,7 @@ __attribute__((visibility("hidden"))) int rs_stem_f32_launch(const rs_conv_desc*
   const long ntile = (long)d->N * d->Ho * a.tpr;
   if (ntile <= 0 || ntile >= (1L << 31)) return RS_EINVAL;
   a.ntile = (int)ntile;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  const int cus = rs_cu_count();
   const long want = bands == 3 ? 2L * cus : cus;  // resident blocks: the LDS admits two (RGB) / one per CU
   const int grid = (int)(ntile < want ? ntile : want);
   if (bands == 3)

@@ -17,13 +17,20 @@ BF16 = torch.bfloat16
 
 
 def _dt(t):
-    """dtype code of an activation tensor for the ``*_dt`` entry points."""
+    """dtype code of an activation tensor (or of a dtype) for the ``*_dt`` entry points."""
 
-    if t.dtype == torch.float32:
+    dtype = getattr(t, "dtype", t)
+    if dtype == torch.float32:
         return RS_F32
-    if t.dtype == torch.bfloat16:
+    if dtype == torch.bfloat16:
         return RS_BF16
-    raise TypeError("robosat_amd: activations are fp32 or bf16, got {}".format(t.dtype))
+    raise TypeError("robosat_amd: activations are fp32 or bf16, got {}".format(dtype))
+
+
+def _esize(t):
+    """Bytes per element of an fp32 / bf16 tensor (or dtype)."""
+
+    return 2 if getattr(t, "dtype", t) == BF16 else 4
 
 
 def _dev(t, name, dtype=torch.float32):
@@ -42,16 +49,77 @@ def _stream():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-# When set to a list, every conv launch is bracketed by HIP events on the launch stream and
-# (kernel name, algorithmic flops, start event, end event) is appended: bench.py's roofline leg.
+def _call(name, *args):
+    """Calls the entry point ``name`` and checks its status under that same name (for the entry points that return one)."""
+
+    rc = getattr(_lib.lib(), name)(*args)
+    if rc:
+        check(rc, name)
+
+
+# Kernel-selection switches of the Python side, read from the environment at every call (the tests and bench.py flip them
+# mid-process): unset = on, "0" = off, anything else = on.  (The library's own measurement switches: csrc/knobs.hip.)
+SWITCHES = {
+    "ROBOSAT_WINOGRAD": "fp32 Winograd forward forms (DecoderBlock, stride-1 3x3); off: the generic phase / implicit-GEMM kernels",
+    "ROBOSAT_WINO_DGRAD": "Winograd data gradient of the fp32 DecoderBlock; off: the 4x4 / stride-2 kernel",
+    "ROBOSAT_WINO33_STATS": "train-mode fp32 conv3x3 -> BatchNorm front half in the Winograd form; off: conv2d_bnstats",
+    "ROBOSAT_WINO33_BWD": "Winograd data gradient of the fp32 stride-1 3x3 convolutions; off: the generic kernel",
+    "ROBOSAT_FUSED_HEAD": "dec5 + self.final in one launch; off: two launches",
+    "ROBOSAT_TAIL_FUSE": "layer1's fused Bottleneck tail and its wave 1x1 kernel; off: the generic 1x1 convolutions",
+    "ROBOSAT_S2_DGRAD": "stride-2 data gradients in compact form (3x3: phase form, 1x1: scatter-add); off: zero-insertion convolutions",
+    "ROBOSAT_S2_DGRAD_3X3": "the 3x3 half of ROBOSAT_S2_DGRAD alone",
+    "ROBOSAT_WGRAD_STREAM": "weight gradients on a side stream; off: serial backward (clean per-kernel timings)",
+}
+
+
+def switch(name):
+    """Whether the kernel-selection switch ``name`` (a key of ``SWITCHES``) is on."""
+
+    if name not in SWITCHES:
+        raise KeyError("robosat_amd: unknown switch {!r}: one of {}".format(name, ", ".join(SWITCHES)))
+    return os.environ.get(name, "1") != "0"
+
+
+# When set to a list, every conv launch is bracketed by HIP events on the launch stream and the 7-tuple
+# (kernel name, algorithmic flops, shape, start event, end event, bytes, executed flops) is appended: bench.py's roofline leg.
 PROFILE = None
 
 
-def _record(name, flops, shape, ev0, ev1, nbytes, executed=None):
+def _start():
+    """Opens the roofline bracket of a launch: None when ``PROFILE`` is off, else the two events, the first recorded on the
+    current stream.  A wrapper calls it right before the launch and, when it got events, ``_stop`` right after it, then ``_record``."""
+
+    if PROFILE is None:
+        return None
+    ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev[0].record()
+    return ev
+
+
+def _stop(ev):
+    ev[1].record()
+
+
+def _record(ev, name, flops, shape, nbytes, executed=None):
     """One roofline record: ALGORITHMIC flops / bytes of the launch (reference shapes) and the flops
     the kernel actually executes (smaller for the phase-form decoder kernels: 4/9)."""
 
-    PROFILE.append((name, flops, shape, ev0, ev1, nbytes, flops if executed is None else executed))
+    PROFILE.append((name, flops, shape, ev[0], ev[1], nbytes, flops if executed is None else executed))
+
+
+def _shape(d):
+    """The launch-shape tuple of a roofline record: (Cin, Cout, k, stride, ups, Ho, Wo)."""
+
+    return (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo)
+
+
+def _partial(rows_fn, d, device, *args):
+    """The fp32 buffer [rows, 2, Cout] of a statistics epilogue's per-tile partial sums; ``rows_fn`` answers how many tiles."""
+
+    rows = getattr(_lib.lib(), rows_fn)(ctypes.byref(d), *args)
+    if rows <= 0:
+        raise ValueError("{}: invalid arguments".format(rows_fn))
+    return torch.empty((rows, 2, d.Cout), device=device, dtype=torch.float32)
 
 
 def conv_flops(d):
@@ -108,22 +176,17 @@ def conv2d(src1, weight, src2=None, ups=0, stride=1, pad=0, scale=None, shift=No
         assert residual.shape == out.shape
     if relu_mask is not None:
         assert relu_mask.shape == out.shape
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    fn = _lib.lib().rs_conv2d_fwd_bf16 if bf else _lib.lib().rs_conv2d_fwd
-    rc = fn(
-        ctypes.byref(d), _dev(src1, "src1", act), _dev(src2, "src2", act), _dev(weight, "weight", act), _dev(scale, "scale"),
-        _dev(shift, "shift"), _dev(residual, "residual", act), _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream(),
-    )
-    check(rc, "rs_conv2d_fwd_bf16" if bf else "rs_conv2d_fwd")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_conv2d_fwd_bf16" if bf else "rs_conv2d_fwd", ctypes.byref(d), _dev(src1, "src1", act), _dev(src2, "src2", act),
+          _dev(weight, "weight", act), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act),
+          _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
+    if ev:
+        _stop(ev)
         name = conv_tile_name(d, bf, plain=relu_mask is None)
         if alg_scale != 1.0 and not name.startswith(("conv_thin", "conv_halo")):  # phase-form data gradient: 16 taps at source resolution stand for 9 at the upsampled one
             name = name.replace("<", "<dgrad4x4,")
-        _record(name, conv_flops(d) * alg_scale, (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
-                conv_bytes(d, 2 if bf else 4, (residual is not None) + (relu_mask is not None)), conv_flops(d))
+        _record(ev, name, conv_flops(d) * alg_scale, _shape(d),
+                conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)), conv_flops(d))
     return out
 
 
@@ -134,24 +197,15 @@ def conv2d_bnstats(src1, weight, src2=None, ups=0, stride=1, pad=0):
 
     d = conv_desc(src1, weight, src2, ups, stride, pad, False, 0, None)
     act = src1.dtype
-    lib = _lib.lib()
     out = torch.empty((d.N, d.Ho, d.Wo, d.Cout), device=src1.device, dtype=act)
-    rows = lib.rs_conv2d_bnstats_rows_dt(ctypes.byref(d), _dt(src1))
-    if rows <= 0:
-        raise ValueError("rs_conv2d_bnstats_rows: invalid arguments")
-    partial = torch.empty((rows, 2, d.Cout), device=src1.device, dtype=torch.float32)
+    partial = _partial("rs_conv2d_bnstats_rows_dt", d, src1.device, _dt(src1))
     assert weight.shape[3] == d.C1 + d.C2
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.rs_conv2d_fwd_bnstats_dt(ctypes.byref(d), _dt(src1), _dev(src1, "src1", act), _dev(src2, "src2", act),
-                                      _dev(weight, "weight", act), _dev(out, "out", act), _dev(partial, "partial"), _stream())
-    check(rc, "rs_conv2d_fwd_bnstats_dt")
-    if PROFILE is not None:
-        ev1.record()
-        bf = act == BF16
-        _record(conv_tile_name(d, bf, plain=False), conv_flops(d), (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
-                        conv_bytes(d, 2 if bf else 4))
+    ev = _start()
+    _call("rs_conv2d_fwd_bnstats_dt", ctypes.byref(d), _dt(src1), _dev(src1, "src1", act), _dev(src2, "src2", act),
+          _dev(weight, "weight", act), _dev(out, "out", act), _dev(partial, "partial"), _stream())
+    if ev:
+        _stop(ev)
+        _record(ev, conv_tile_name(d, act == BF16, plain=False), conv_flops(d), _shape(d), conv_bytes(d, _esize(act)))
     return out, partial
 
 
@@ -164,35 +218,24 @@ def conv2d_dgrad_bnstats(dy, wd, out_hw, bn_y, bn_mean, bn_invstd, ups=0, pad=0,
 
     d = conv_desc(dy, wd, None, ups, stride, pad, False, 0, out_hw)
     act = dy.dtype
-    lib = _lib.lib()
     out = torch.empty((d.N, d.Ho, d.Wo, d.Cout), device=dy.device, dtype=act)
     assert bn_y.shape == out.shape
-    rows = lib.rs_conv2d_bnstats_rows_dt(ctypes.byref(d), _dt(dy))
-    if rows <= 0:
-        raise ValueError("rs_conv2d_bnstats_rows: invalid arguments")
-    partial = torch.empty((rows, 2, d.Cout), device=dy.device, dtype=torch.float32)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
+    partial = _partial("rs_conv2d_bnstats_rows_dt", d, dy.device, _dt(dy))
+    ev = _start()
     if relu_mask_bits is not None:
         assert relu_mask_bits.numel() * 8 == out.numel(), "one mask bit per output element"
-        rc = lib.rs_conv2d_dgrad_bnstats_bits_dt(
-            ctypes.byref(d), _dt(dy), _dev(dy, "dy", act), _dev(wd, "weight", act), _dev(residual, "residual", act),
-            _dev(relu_mask_bits, "relu_mask_bits", torch.uint8), _dev(bn_y, "bn_y", act), _dev(bn_mean, "bn_mean"),
-            _dev(bn_invstd, "bn_invstd"), _dev(out, "out", act), _dev(partial, "partial"), _stream())
-        check(rc, "rs_conv2d_dgrad_bnstats_bits_dt")
+        _call("rs_conv2d_dgrad_bnstats_bits_dt", ctypes.byref(d), _dt(dy), _dev(dy, "dy", act), _dev(wd, "weight", act),
+              _dev(residual, "residual", act), _dev(relu_mask_bits, "relu_mask_bits", torch.uint8), _dev(bn_y, "bn_y", act),
+              _dev(bn_mean, "bn_mean"), _dev(bn_invstd, "bn_invstd"), _dev(out, "out", act), _dev(partial, "partial"), _stream())
     else:
-        rc = lib.rs_conv2d_dgrad_bnstats_dt(
-            ctypes.byref(d), _dt(dy), _dev(dy, "dy", act), _dev(wd, "weight", act), _dev(residual, "residual", act),
-            _dev(relu_mask, "relu_mask", act), _dev(bn_y, "bn_y", act), _dev(bn_mean, "bn_mean"), _dev(bn_invstd, "bn_invstd"),
-            _dev(out, "out", act), _dev(partial, "partial"), _stream())
-        check(rc, "rs_conv2d_dgrad_bnstats_dt")
-    if PROFILE is not None:
-        ev1.record()
-        bf = act == BF16
-        _record(conv_tile_name(d, bf, plain=False), conv_flops(d), (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
-                        conv_bytes(d, 2 if bf else 4, 1 + (residual is not None) + (relu_mask is not None))
-                        + (out.numel() // 8 if relu_mask_bits is not None else 0))
+        _call("rs_conv2d_dgrad_bnstats_dt", ctypes.byref(d), _dt(dy), _dev(dy, "dy", act), _dev(wd, "weight", act),
+              _dev(residual, "residual", act), _dev(relu_mask, "relu_mask", act), _dev(bn_y, "bn_y", act), _dev(bn_mean, "bn_mean"),
+              _dev(bn_invstd, "bn_invstd"), _dev(out, "out", act), _dev(partial, "partial"), _stream())
+    if ev:
+        _stop(ev)
+        _record(ev, conv_tile_name(d, act == BF16, plain=False), conv_flops(d), _shape(d),
+                conv_bytes(d, _esize(act), 1 + (residual is not None) + (relu_mask is not None))
+                + (out.numel() // 8 if relu_mask_bits is not None else 0))
     return out, partial
 
 
@@ -208,11 +251,9 @@ def bn_bwd_from_partials(g, y, mean, invstd, gamma, partial, dgamma=None, dbeta=
     if dbeta is None:
         dbeta = torch.empty(c, device=y.device, dtype=torch.float32)
     t = y.dtype
-    rc = _lib.lib().rs_bn_bwd_from_partials_dt(
-        _dev(g, "g", t), _dev(y, "y", t), _dev(mean, "mean"), _dev(invstd, "invstd"), _dev(gamma, "gamma"), _dev(dy, "dy", t),
-        _dev(dgamma, "dgamma"), _dev(dbeta, "dbeta"), _dev(partial, "partial"), partial.shape[0], _dt(y), m, c,
-        _workspace(64 * 2 * c * 8 + 3 * c * 4, y.device), _stream())
-    check(rc, "rs_bn_bwd_from_partials_dt")
+    _call("rs_bn_bwd_from_partials_dt", _dev(g, "g", t), _dev(y, "y", t), _dev(mean, "mean"), _dev(invstd, "invstd"), _dev(gamma, "gamma"),
+          _dev(dy, "dy", t), _dev(dgamma, "dgamma"), _dev(dbeta, "dbeta"), _dev(partial, "partial"), partial.shape[0], _dt(y), m, c,
+          _workspace(64 * 2 * c * 8 + 3 * c * 4, y.device), _stream())
     return dy, dgamma, dbeta
 
 
@@ -221,12 +262,10 @@ def bn_finalize_stats(partial, m, gamma, beta, eps, momentum, running_mean=None,
 
     rows, _, c = partial.shape
     mean, invstd, scale, shift = (torch.empty(c, device=partial.device, dtype=torch.float32) for _ in range(4))
-    rc = _lib.lib().rs_bn_finalize_stats(
-        _dev(partial, "partial"), rows, m, c, ctypes.c_float(eps), ctypes.c_float(momentum), _dev(gamma, "gamma"),
-        _dev(beta, "beta"), _dev(mean, "mean"), _dev(invstd, "invstd"), _dev(scale, "scale"), _dev(shift, "shift"),
-        _dev(running_mean, "running_mean"), _dev(running_var, "running_var"),
-        _dev(num_batches_tracked, "num_batches_tracked", torch.int64), _workspace(64 * 2 * c * 8, partial.device), _stream())
-    check(rc, "rs_bn_finalize_stats")
+    _call("rs_bn_finalize_stats", _dev(partial, "partial"), rows, m, c, ctypes.c_float(eps), ctypes.c_float(momentum), _dev(gamma, "gamma"),
+          _dev(beta, "beta"), _dev(mean, "mean"), _dev(invstd, "invstd"), _dev(scale, "scale"), _dev(shift, "shift"),
+          _dev(running_mean, "running_mean"), _dev(running_var, "running_var"),
+          _dev(num_batches_tracked, "num_batches_tracked", torch.int64), _workspace(64 * 2 * c * 8, partial.device), _stream())
     return mean, invstd, scale, shift
 
 
@@ -237,8 +276,7 @@ def pack_phase_weight(w_krsc, dtype=torch.float32):
     cout, kh, kw, cin = w_krsc.shape
     assert kh == 3 and kw == 3
     out = torch.empty((4, cout, 2, 2, cin), device=w_krsc.device, dtype=dtype)
-    check(_lib.lib().rs_pack_phase_weight_dt(_dev(w_krsc, "w"), _dev(out, "out", dtype), RS_BF16 if dtype == BF16 else RS_F32,
-                                             cout, cin, _stream()), "rs_pack_phase_weight_dt")
+    _call("rs_pack_phase_weight_dt", _dev(w_krsc, "w"), _dev(out, "out", dtype), _dt(dtype), cout, cin, _stream())
     return out
 
 
@@ -249,8 +287,7 @@ def pack_s2_dgrad_phase_weight(w_krsc, dtype=torch.float32):
     cout, kh, kw, cin = w_krsc.shape
     assert kh == 3 and kw == 3
     out = torch.empty((4, cin, 2, 2, cout), device=w_krsc.device, dtype=dtype)
-    check(_lib.lib().rs_pack_s2_dgrad_phase_weight_dt(_dev(w_krsc, "w"), _dev(out, "out", dtype), RS_BF16 if dtype == BF16 else RS_F32,
-                                                      cout, cin, _stream()), "rs_pack_s2_dgrad_phase_weight_dt")
+    _call("rs_pack_s2_dgrad_phase_weight_dt", _dev(w_krsc, "w"), _dev(out, "out", dtype), _dt(dtype), cout, cin, _stream())
     return out
 
 
@@ -263,9 +300,7 @@ def pack_dgrad_phase_weight(w_krsc, dtype=torch.float32):
     out = torch.empty((cin, 4, 4, cout), device=w_krsc.device, dtype=dtype)
     # two coalesced steps: LDS-tiled transpose to [Cin,3,3,Cout] (rs_pack_dgrad_weight), then the tap sums along Cout
     wt = pack_dgrad_weight(w_krsc, torch.float32)
-    check(_lib.lib().rs_combine_dgrad_phase_weight_dt(_dev(wt, "wt"), _dev(out, "out", dtype),
-                                                      RS_BF16 if dtype == BF16 else RS_F32, cout, cin, _stream()),
-          "rs_combine_dgrad_phase_weight_dt")
+    _call("rs_combine_dgrad_phase_weight_dt", _dev(wt, "wt"), _dev(out, "out", dtype), _dt(dtype), cout, cin, _stream())
     return out
 
 
@@ -278,22 +313,16 @@ def conv2d_split(src, weight, c1, stride=1, pad=0, out_hw=None, mask1=None, mask
     c2 = d.Cout - c1
     out1 = torch.empty((d.N, d.Ho, d.Wo, c1), device=src.device, dtype=act)
     out2 = torch.empty((d.N, d.Ho, d.Wo, c2), device=src.device, dtype=act)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv2d_fwd_split_dt(ctypes.byref(d), _dt(src), _dev(src, "src", act), _dev(weight, "weight", act),
-                                           _dev(out1, "out1", act), _dev(mask1, "mask1", act), _dev(out2, "out2", act),
-                                           _dev(mask2, "mask2", act), c1, _stream())
-    check(rc, "rs_conv2d_fwd_split_dt")
-    if PROFILE is not None:
-        ev1.record()
-        bf = act == BF16
-        name = conv_tile_name(d, bf, plain=False)
+    ev = _start()
+    _call("rs_conv2d_fwd_split_dt", ctypes.byref(d), _dt(src), _dev(src, "src", act), _dev(weight, "weight", act), _dev(out1, "out1", act),
+          _dev(mask1, "mask1", act), _dev(out2, "out2", act), _dev(mask2, "mask2", act), c1, _stream())
+    if ev:
+        _stop(ev)
+        name = conv_tile_name(d, act == BF16, plain=False)
         if alg_scale != 1.0 and not name.startswith("conv_halo"):
             name = name.replace("<", "<dgrad4x4,")
-        _record(name, conv_flops(d) * alg_scale, (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
-                conv_bytes(d, 2 if bf else 4, ((mask1 is not None) * c1 + (mask2 is not None) * (d.Cout - c1)) / d.Cout),
-                conv_flops(d))
+        _record(ev, name, conv_flops(d) * alg_scale, _shape(d),
+                conv_bytes(d, _esize(act), ((mask1 is not None) * c1 + (mask2 is not None) * (d.Cout - c1)) / d.Cout), conv_flops(d))
     return out1, out2
 
 
@@ -307,10 +336,20 @@ def cat_split_bwd(dcat, c1, c2=0, mask1=None, mask2=None, out1=None):
     acc = out1 is not None
     d1 = out1 if acc else torch.empty((n, h, w, c1), device=dcat.device, dtype=t)
     d2 = torch.empty((n, h, w, c2), device=dcat.device, dtype=t) if c2 else None
-    rc = _lib.lib().rs_cat_split_bwd_dt(_dev(dcat, "dcat", t), _dev(d1, "d1", t), _dev(d2, "d2", t), _dev(mask1, "mask1", t),
-                                        _dev(mask2, "mask2", t), _dt(dcat), n, h, w, c1, c2, int(acc), _stream())
-    check(rc, "rs_cat_split_bwd_dt")
+    _call("rs_cat_split_bwd_dt", _dev(dcat, "dcat", t), _dev(d1, "d1", t), _dev(d2, "d2", t), _dev(mask1, "mask1", t),
+          _dev(mask2, "mask2", t), _dt(dcat), n, h, w, c1, c2, int(acc), _stream())
     return d1, d2
+
+
+def _phase_desc(n, hs, ws, c1, c2, cout, relu=False):
+    """DecoderBlock: sources [n,hs,ws,c1(+c2)], nearest x2, 3x3 / pad 1 -> [n,2hs,2ws,cout]."""
+
+    return ConvDesc(n, hs, ws, c1, c2, 1, 3, 3, 1, 1, 2 * hs, 2 * ws, cout, int(relu), 0)
+
+
+def _conv33_desc(src, cout, relu):
+    n, h, w, c = src.shape
+    return ConvDesc(n, h, w, c, 0, 0, 3, 3, 1, 1, h, w, cout, int(relu), 0)
 
 
 def conv2d_phase(src1, weight_phase, src2=None, scale=None, shift=None, residual=None, relu=False, relu_mask=None):
@@ -326,29 +365,17 @@ def conv2d_phase(src1, weight_phase, src2=None, scale=None, shift=None, residual
         raise RuntimeError("Sizes of tensors must match except in dimension 1: skip {} vs decoder {}".format(
             tuple(src1.shape[:3]), tuple(src2.shape[:3])))
     act = src1.dtype
-    d = ConvDesc(n, hs, ws, c1, c2, 1, 3, 3, 1, 1, 2 * hs, 2 * ws, cout, int(relu), 0)
+    d = _phase_desc(n, hs, ws, c1, c2, cout, relu)
     out = torch.empty((n, 2 * hs, 2 * ws, cout), device=src1.device, dtype=act)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv2d_fwd_phase_dt(
-        ctypes.byref(d), _dt(src1), _dev(src1, "src1", act), _dev(src2, "src2", act), _dev(weight_phase, "weight", act),
-        _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act), _dev(relu_mask, "relu_mask", act),
-        _dev(out, "out", act), _stream())
-    check(rc, "rs_conv2d_fwd_phase_dt")
-    if PROFILE is not None:
-        ev1.record()
-        bf = act == BF16
-        _record(conv_tile_name(d, bf, phase=True), conv_flops(d),
-                (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
-                conv_bytes(d, 2 if bf else 4, (residual is not None) + (relu_mask is not None)), conv_flops(d) * 4.0 / 9.0)
+    ev = _start()
+    _call("rs_conv2d_fwd_phase_dt", ctypes.byref(d), _dt(src1), _dev(src1, "src1", act), _dev(src2, "src2", act),
+          _dev(weight_phase, "weight", act), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act),
+          _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
+    if ev:
+        _stop(ev)
+        _record(ev, conv_tile_name(d, act == BF16, phase=True), conv_flops(d), _shape(d),
+                conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)), conv_flops(d) * 4.0 / 9.0)
     return out
-
-
-def _phase_desc(src1, src2, cout, relu):
-    n, hs, ws, c1 = src1.shape
-    c2 = 0 if src2 is None else src2.shape[3]
-    return ConvDesc(n, hs, ws, c1, c2, 1, 3, 3, 1, 1, 2 * hs, 2 * ws, cout, int(relu), 0)
 
 
 def wino_ok(src1, src2, cout, force=False):
@@ -357,11 +384,10 @@ def wino_ok(src1, src2, cout, force=False):
     parity tests reach the kernel with small problems).  ROBOSAT_WINOGRAD=0 switches it off (A/B measurements: the generic
     phase kernel then runs every layer)."""
 
-    import os
-
-    if src1.dtype != torch.float32 or (not force and os.environ.get("ROBOSAT_WINOGRAD", "1") == "0"):
+    if src1.dtype != torch.float32 or not (force or switch("ROBOSAT_WINOGRAD")):
         return False
-    rc = _lib.lib().rs_conv2d_phase_wino_ok(ctypes.byref(_phase_desc(src1, src2, cout, False)))
+    d = _phase_desc(*src1.shape, 0 if src2 is None else src2.shape[3], cout)
+    rc = _lib.lib().rs_conv2d_phase_wino_ok(ctypes.byref(d))
     return rc != 0 if force else rc == 1
 
 
@@ -370,8 +396,7 @@ def pack_wino_phase_weight(weight_phase):
 
     _, cout, _, _, cin = weight_phase.shape
     u = torch.empty((4, 9, cout, cin), device=weight_phase.device, dtype=torch.float32)
-    check(_lib.lib().rs_pack_wino_phase_weight(_dev(weight_phase, "w_phase"), _dev(u, "u"), cout, cin, _stream()),
-          "rs_pack_wino_phase_weight")
+    _call("rs_pack_wino_phase_weight", _dev(weight_phase, "w_phase"), _dev(u, "u"), cout, cin, _stream())
     return u
 
 
@@ -386,20 +411,15 @@ def conv2d_phase_wino(src1, u, src2=None, relu=False):
     if src2 is not None and tuple(src2.shape[:3]) != (n, hs, ws):
         raise RuntimeError("Sizes of tensors must match except in dimension 1: skip {} vs decoder {}".format(
             tuple(src1.shape[:3]), tuple(src2.shape[:3])))
-    d = _phase_desc(src1, src2, cout, relu)
+    d = _phase_desc(n, hs, ws, c1, c2, cout, relu)
     out = torch.empty((n, 2 * hs, 2 * ws, cout), device=src1.device, dtype=torch.float32)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv2d_fwd_phase_wino(ctypes.byref(d), _dev(src1, "src1"), _dev(src2, "src2"), _dev(u, "u"), _dev(out, "out"),
-                                             _stream())
-    check(rc, "rs_conv2d_fwd_phase_wino")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_conv2d_fwd_phase_wino", ctypes.byref(d), _dev(src1, "src1"), _dev(src2, "src2"), _dev(u, "u"), _dev(out, "out"), _stream())
+    if ev:
+        _stop(ev)
         name = _lib.lib().rs_conv2d_phase_wino_name(ctypes.byref(d)).decode()
         # executed: 9 multiply-adds per 2x2 outputs of a parity = 1/4 of the reference-shape count (the phase form: 4/9)
-        _record(name, conv_flops(d), (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1, conv_bytes(d, 4),
-                conv_flops(d) * 0.25)
+        _record(ev, name, conv_flops(d), _shape(d), conv_bytes(d, 4), conv_flops(d) * 0.25)
     return out
 
 
@@ -407,12 +427,9 @@ def wino_dgrad_ok(n, hs, ws, c1, c2, cout):
     """Whether the fp32 DecoderBlock (sources [n,hs,ws,c1(+c2)] -> cout at 2 hs x 2 ws) can take its data gradient through the Winograd
     form (``rs_conv2d_dgrad_phase_wino_ok``: geometry only; ROBOSAT_WINO_DGRAD=0 keeps the 4x4 / stride-2 kernel for A/B runs)."""
 
-    import os
-
-    if os.environ.get("ROBOSAT_WINO_DGRAD", "1") == "0":
+    if not switch("ROBOSAT_WINO_DGRAD"):
         return False
-    d = ConvDesc(n, hs, ws, c1, c2, 1, 3, 3, 1, 1, 2 * hs, 2 * ws, cout, 0, 0)
-    return _lib.lib().rs_conv2d_dgrad_phase_wino_ok(ctypes.byref(d)) == 1
+    return _lib.lib().rs_conv2d_dgrad_phase_wino_ok(ctypes.byref(_phase_desc(n, hs, ws, c1, c2, cout))) == 1
 
 
 def pack_wino_dgrad_weight(wd4x4):
@@ -422,7 +439,7 @@ def pack_wino_dgrad_weight(wd4x4):
     cin, kh, kw, cout = wd4x4.shape
     assert kh == 4 and kw == 4 and wd4x4.dtype == torch.float32
     u = torch.empty((4, 9, cin, cout), device=wd4x4.device, dtype=torch.float32)
-    check(_lib.lib().rs_pack_wino_dgrad_weight(_dev(wd4x4, "wd"), _dev(u, "u"), cin, cout, _stream()), "rs_pack_wino_dgrad_weight")
+    _call("rs_pack_wino_dgrad_weight", _dev(wd4x4, "wd"), _dev(u, "u"), cin, cout, _stream())
     return u
 
 
@@ -433,8 +450,8 @@ def conv2d_dgrad_phase_wino(dz, u, c1, c2=0, mask1=None, mask2=None, split=False
 
     n, ho, wo, cout = dz.shape
     hs, ws = ho // 2, wo // 2
-    assert tuple(u.shape) == (4, 9, c1 + c2, cout) and dz.dtype == torch.float32
-    d = ConvDesc(n, hs, ws, c1, c2, 1, 3, 3, 1, 1, ho, wo, cout, 0, 0)
+    assert tuple(u.shape) == (4, 9, c1 + c2, cout) and dz.dtype == torch.float32 and (ho, wo) == (2 * hs, 2 * ws)
+    d = _phase_desc(n, hs, ws, c1, c2, cout)
     if split:
         out1 = torch.empty((n, hs, ws, c1), device=dz.device, dtype=torch.float32)
         out2 = torch.empty((n, hs, ws, c2), device=dz.device, dtype=torch.float32)
@@ -443,36 +460,27 @@ def conv2d_dgrad_phase_wino(dz, u, c1, c2=0, mask1=None, mask2=None, split=False
         assert mask2 is None
     for m, o in ((mask1, out1), (mask2, out2)):
         assert m is None or tuple(m.shape) == tuple(o.shape)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv2d_dgrad_phase_wino(ctypes.byref(d), _dev(dz, "dz"), _dev(u, "u"), _dev(out1, "out"), _dev(mask1, "mask"),
-                                               _dev(out2, "out2"), _dev(mask2, "mask2"), c1 if split else 0, _stream())
-    check(rc, "rs_conv2d_dgrad_phase_wino")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_conv2d_dgrad_phase_wino", ctypes.byref(d), _dev(dz, "dz"), _dev(u, "u"), _dev(out1, "out"), _dev(mask1, "mask"),
+          _dev(out2, "out2"), _dev(mask2, "mask2"), c1 if split else 0, _stream())
+    if ev:
+        _stop(ev)
         # algorithmic: the reference's 3x3 at the upsampled resolution; the 4x4 / stride-2 form executes 16 taps at source resolution,
         # this form 9/16 of those
         alg = 2.0 * n * ho * wo * cout * (c1 + c2) * 9
         ex4 = 2.0 * n * hs * ws * cout * (c1 + c2) * 16
         nbytes = 4 * (n * ho * wo * cout + 16 * cout * (c1 + c2) + n * hs * ws * (c1 + c2) * (1 + (mask1 is not None) * (c1 if split else c1 + c2) / (c1 + c2)
                                                                                             + (mask2 is not None) * c2 / (c1 + c2)))
-        _record(_lib.lib().rs_conv2d_dgrad_phase_wino_name(ctypes.byref(d)).decode(), alg, (cout, c1 + c2, 4, 2, 0, hs, ws), ev0, ev1, nbytes, ex4 * 9.0 / 16.0)
+        _record(ev, _lib.lib().rs_conv2d_dgrad_phase_wino_name(ctypes.byref(d)).decode(), alg, (cout, c1 + c2, 4, 2, 0, hs, ws), nbytes,
+                ex4 * 9.0 / 16.0)
     return out1, out2
-
-
-def _conv33_desc(src, cout, relu):
-    n, h, w, c = src.shape
-    return ConvDesc(n, h, w, c, 0, 0, 3, 3, 1, 1, h, w, cout, int(relu), 0)
 
 
 def wino33_ok(src, cout):
     """Whether the fp32 Winograd F(2x2, 3x3) kernel runs a stride-1 3x3 / pad-1 convolution of ``src`` to ``cout`` channels
     (``rs_conv2d_wino33_ok``: the layer's geometry only, never the batch size); ROBOSAT_WINOGRAD=0 switches it off."""
 
-    import os
-
-    if src.dtype != torch.float32 or os.environ.get("ROBOSAT_WINOGRAD", "1") == "0":
+    if src.dtype != torch.float32 or not switch("ROBOSAT_WINOGRAD"):
         return False
     return _lib.lib().rs_conv2d_wino33_ok(ctypes.byref(_conv33_desc(src, cout, False))) == 1
 
@@ -483,7 +491,7 @@ def pack_wino33_weight(w_krsc):
     cout, kh, kw, cin = w_krsc.shape
     assert kh == 3 and kw == 3
     u = torch.empty((16, cout, cin), device=w_krsc.device, dtype=torch.float32)
-    check(_lib.lib().rs_pack_wino33_weight(_dev(w_krsc, "w"), _dev(u, "u"), cout, cin, _stream()), "rs_pack_wino33_weight")
+    _call("rs_pack_wino33_weight", _dev(w_krsc, "w"), _dev(u, "u"), cout, cin, _stream())
     return u
 
 
@@ -496,16 +504,13 @@ def conv2d_wino33(src, u, scale=None, shift=None, relu=False):
     assert tuple(u.shape) == (16, cout, c)
     d = _conv33_desc(src, cout, relu)
     out = torch.empty((n, h, w, cout), device=src.device, dtype=torch.float32)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv2d_fwd_wino33(ctypes.byref(d), _dev(src, "src"), _dev(u, "u"), _dev(scale, "scale"), _dev(shift, "shift"),
-                                         _dev(out, "out"), _stream())
-    check(rc, "rs_conv2d_fwd_wino33")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_conv2d_fwd_wino33", ctypes.byref(d), _dev(src, "src"), _dev(u, "u"), _dev(scale, "scale"), _dev(shift, "shift"),
+          _dev(out, "out"), _stream())
+    if ev:
+        _stop(ev)
         name = _lib.lib().rs_conv2d_wino33_name(ctypes.byref(d)).decode()
-        _record(name, conv_flops(d), (d.C1, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1, conv_bytes(d, 4), conv_flops(d) * 4.0 / 9.0)
+        _record(ev, name, conv_flops(d), _shape(d), conv_bytes(d, 4), conv_flops(d) * 4.0 / 9.0)
     return out
 
 
@@ -518,20 +523,14 @@ def conv2d_wino33_bnstats(src, u):
     cout = u.shape[1]
     assert tuple(u.shape) == (16, cout, c) and src.dtype == torch.float32
     d = _conv33_desc(src, cout, False)
-    lib = _lib.lib()
-    rows = lib.rs_conv2d_wino33_stats_rows(ctypes.byref(d))
-    if rows <= 0:
-        raise ValueError("rs_conv2d_wino33_stats_rows: invalid arguments")
     out = torch.empty((n, h, w, cout), device=src.device, dtype=torch.float32)
-    partial = torch.empty((rows, 2, cout), device=src.device, dtype=torch.float32)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib.rs_conv2d_fwd_wino33_stats(ctypes.byref(d), _dev(src, "src"), _dev(u, "u"), _dev(out, "out"), _dev(partial, "partial"), _stream()),
-          "rs_conv2d_fwd_wino33_stats")
-    if PROFILE is not None:
-        ev1.record()
-        _record(lib.rs_conv2d_wino33_name(ctypes.byref(d)).decode().replace("<3x3,", "<3x3+stats,"), conv_flops(d), (d.C1, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
+    partial = _partial("rs_conv2d_wino33_stats_rows", d, src.device)
+    ev = _start()
+    _call("rs_conv2d_fwd_wino33_stats", ctypes.byref(d), _dev(src, "src"), _dev(u, "u"), _dev(out, "out"), _dev(partial, "partial"),
+          _stream())
+    if ev:
+        _stop(ev)
+        _record(ev, _lib.lib().rs_conv2d_wino33_name(ctypes.byref(d)).decode().replace("<3x3,", "<3x3+stats,"), conv_flops(d), _shape(d),
                 conv_bytes(d, 4), conv_flops(d) * 4.0 / 9.0)
     return out, partial
 
@@ -541,9 +540,7 @@ def wino33_dgrad_ok(dy, cout):
     (``rs_conv2d_dgrad_wino33``: ``wino33_ok`` on the gradient's convolution, cout % 32 == 0); ROBOSAT_WINO33_BWD=0 keeps the generic
     kernel (A/B runs)."""
 
-    import os
-
-    if os.environ.get("ROBOSAT_WINO33_BWD", "1") == "0" or cout % 32:
+    if not switch("ROBOSAT_WINO33_BWD") or cout % 32:
         return False
     return wino33_ok(dy, cout)
 
@@ -558,32 +555,24 @@ def conv2d_wino33_dgrad(dy, u, relu_mask=None, relu_mask_bits=None, bn=None):
     cout = u.shape[1]
     assert tuple(u.shape) == (16, cout, c) and dy.dtype == torch.float32
     d = _conv33_desc(dy, cout, False)
-    lib = _lib.lib()
     out = torch.empty((n, h, w, cout), device=dy.device, dtype=torch.float32)
     partial = None
     y = mean = invstd = None
     if bn is not None:
         y, mean, invstd = bn
         assert y.shape == out.shape
-        rows = lib.rs_conv2d_wino33_stats_rows(ctypes.byref(d))
-        if rows <= 0:
-            raise ValueError("rs_conv2d_wino33_stats_rows: invalid arguments")
-        partial = torch.empty((rows, 2, cout), device=dy.device, dtype=torch.float32)
+        partial = _partial("rs_conv2d_wino33_stats_rows", d, dy.device)
     if relu_mask is not None:
         assert relu_mask.shape == out.shape
     if relu_mask_bits is not None:
         assert relu_mask_bits.numel() * 8 == out.numel(), "one mask bit per output element"
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    check(lib.rs_conv2d_dgrad_wino33(ctypes.byref(d), _dev(dy, "dy"), _dev(u, "u"), _dev(relu_mask, "relu_mask"),
-                                     _dev(relu_mask_bits, "relu_mask_bits", torch.uint8), _dev(y, "bn_y"), _dev(mean, "bn_mean"),
-                                     _dev(invstd, "bn_invstd"), _dev(out, "out"), _dev(partial, "partial"), _stream()),
-          "rs_conv2d_dgrad_wino33")
-    if PROFILE is not None:
-        ev1.record()
-        _record(lib.rs_conv2d_wino33_name(ctypes.byref(d)).decode().replace("<3x3,", "<3x3+bwd,"), conv_flops(d),
-                (d.C1, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
+    ev = _start()
+    _call("rs_conv2d_dgrad_wino33", ctypes.byref(d), _dev(dy, "dy"), _dev(u, "u"), _dev(relu_mask, "relu_mask"),
+          _dev(relu_mask_bits, "relu_mask_bits", torch.uint8), _dev(y, "bn_y"), _dev(mean, "bn_mean"), _dev(invstd, "bn_invstd"),
+          _dev(out, "out"), _dev(partial, "partial"), _stream())
+    if ev:
+        _stop(ev)
+        _record(ev, _lib.lib().rs_conv2d_wino33_name(ctypes.byref(d)).decode().replace("<3x3,", "<3x3+bwd,"), conv_flops(d), _shape(d),
                 conv_bytes(d, 4, 1 + (relu_mask is not None) + (bn is not None)) + (out.numel() // 8 if relu_mask_bits is not None else 0),
                 conv_flops(d) * 4.0 / 9.0)
     return out, partial
@@ -593,9 +582,7 @@ def wino33_head_ok(src, cout, classes):
     """Whether dec5 + ``self.final`` run as one launch (``rs_conv2d_wino33_head_ok``: the Winograd 3x3 form on a 32-cout
     layer, <= 8 classes); ROBOSAT_FUSED_HEAD=0 keeps the two launches (A/B runs)."""
 
-    import os
-
-    if not wino33_ok(src, cout) or os.environ.get("ROBOSAT_FUSED_HEAD", "1") == "0":
+    if not wino33_ok(src, cout) or not switch("ROBOSAT_FUSED_HEAD"):
         return False
     return _lib.lib().rs_conv2d_wino33_head_ok(ctypes.byref(_conv33_desc(src, cout, True)), int(classes)) == 1
 
@@ -619,19 +606,16 @@ def conv2d_wino33_head(src, u, final_w, final_b, mode="logits", overlap=0, relu=
         anchors = _anchors(src.device)
     else:
         qout = torch.empty((n, h, w), device=src.device, dtype=torch.uint8)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv2d_fwd_wino33_head(
-        ctypes.byref(d), _dev(src, "src"), _dev(u, "u"), None, None, _dev(final_w, "final_w"), _dev(final_b, "final_b"), classes, m,
-        _dev(anchors, "anchors", torch.float64), int(overlap), _dev(out, "out"), _dev(qout, "qout", torch.uint8), _stream())
-    check(rc, "rs_conv2d_fwd_wino33_head")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_conv2d_fwd_wino33_head", ctypes.byref(d), _dev(src, "src"), _dev(u, "u"), None, None, _dev(final_w, "final_w"),
+          _dev(final_b, "final_b"), classes, m, _dev(anchors, "anchors", torch.float64), int(overlap), _dev(out, "out"),
+          _dev(qout, "qout", torch.uint8), _stream())
+    if ev:
+        _stop(ev)
         fl = conv_flops(d) + 2.0 * n * h * w * cout * classes  # (the 1x1 rides along: < 1 % of the launch)
         nbytes = 4 * (n * h * w * c + 9 * cout * c + classes * cout) + (4 * classes if m <= 1 else 1) * n * h * w
-        _record(_lib.lib().rs_conv2d_wino33_head_name().decode(), fl, (d.C1, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1,
-                nbytes, conv_flops(d) * 4.0 / 9.0 + 2.0 * n * h * w * cout * classes)
+        _record(ev, _lib.lib().rs_conv2d_wino33_head_name().decode(), fl, _shape(d), nbytes,
+                conv_flops(d) * 4.0 / 9.0 + 2.0 * n * h * w * cout * classes)
     return out if m <= 1 else qout
 
 
@@ -640,7 +624,7 @@ def bottleneck_tail_ok(x, w3, w1):
 
     m = x.numel() // x.shape[-1]
     return (x.dtype == torch.float32 and x.shape[-1] == 64 and tuple(w3.shape) == (256, 1, 1, 64) and tuple(w1.shape) == (64, 1, 1, 256)
-            and m % 32 == 0 and os.environ.get("ROBOSAT_TAIL_FUSE", "1") != "0")
+            and m % 32 == 0 and switch("ROBOSAT_TAIL_FUSE"))
 
 
 def bottleneck_tail(x, w3, scale3, shift3, identity, w1, scale1, shift1):
@@ -652,18 +636,15 @@ def bottleneck_tail(x, w3, scale3, shift3, identity, w1, scale1, shift1):
     assert identity.shape == (n, h, w, cm) and w1.shape[3] == cm
     out = torch.empty((n, h, w, cm), device=x.device, dtype=torch.float32)
     z = torch.empty((n, h, w, c2), device=x.device, dtype=torch.float32)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_bottleneck_tail_f32(_dev(x, "x"), _dev(w3, "w3"), _dev(scale3, "scale3"), _dev(shift3, "shift3"),
-                                           _dev(identity, "identity"), _dev(w1, "w1"), _dev(scale1, "scale1"), _dev(shift1, "shift1"),
-                                           _dev(out, "out"), _dev(z, "z"), n * h * w, c1, cm, c2, _stream())
-    check(rc, "rs_bottleneck_tail_f32")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_bottleneck_tail_f32", _dev(x, "x"), _dev(w3, "w3"), _dev(scale3, "scale3"), _dev(shift3, "shift3"),
+          _dev(identity, "identity"), _dev(w1, "w1"), _dev(scale1, "scale1"), _dev(shift1, "shift1"), _dev(out, "out"), _dev(z, "z"),
+          n * h * w, c1, cm, c2, _stream())
+    if ev:
+        _stop(ev)
         m = n * h * w
         fl = 2.0 * m * cm * (c1 + c2)
-        _record("bottleneck_tail_f32", fl, (c1, cm, 1, 1, 0, h, w), ev0, ev1, 4 * (m * (c1 + 2 * cm + c2) + cm * (c1 + c2)), fl)
+        _record(ev, "bottleneck_tail_f32", fl, (c1, cm, 1, 1, 0, h, w), 4 * (m * (c1 + 2 * cm + c2) + cm * (c1 + c2)), fl)
     return out, z
 
 
@@ -672,7 +653,7 @@ def conv1x1_wave_ok(x, w):
 
     m = x.numel() // x.shape[-1]
     return (x.dtype == torch.float32 and x.shape[-1] == 64 and tuple(w.shape) == (256, 1, 1, 64) and m % 32 == 0
-            and os.environ.get("ROBOSAT_TAIL_FUSE", "1") != "0")
+            and switch("ROBOSAT_TAIL_FUSE"))
 
 
 def conv1x1_wave(x, w, scale, shift, residual=None, relu=False):
@@ -683,17 +664,14 @@ def conv1x1_wave(x, w, scale, shift, residual=None, relu=False):
     out = torch.empty((n, h, wd, cout), device=x.device, dtype=torch.float32)
     if residual is not None:
         assert residual.shape == out.shape
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_conv1x1_wave_f32(_dev(x, "x"), _dev(w, "w"), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual"),
-                                        int(relu), _dev(out, "out"), n * h * wd, c1, cout, _stream())
-    check(rc, "rs_conv1x1_wave_f32")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_conv1x1_wave_f32", _dev(x, "x"), _dev(w, "w"), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual"),
+          int(relu), _dev(out, "out"), n * h * wd, c1, cout, _stream())
+    if ev:
+        _stop(ev)
         m = n * h * wd
         fl = 2.0 * m * cout * c1
-        _record("conv1x1_wave_f32", fl, (c1, cout, 1, 1, 0, h, wd), ev0, ev1, 4 * (m * (c1 + cout * (2 if residual is not None else 1)) + cout * c1), fl)
+        _record(ev, "conv1x1_wave_f32", fl, (c1, cout, 1, 1, 0, h, wd), 4 * (m * (c1 + cout * (2 if residual is not None else 1)) + cout * c1), fl)
     return out
 
 
@@ -707,7 +685,7 @@ def conv_tile_name(d, bf16=False, phase=False, plain=True):
         return lib.rs_conv2d_tile_name(lib.rs_conv2d_tile(ctypes.byref(d))).decode()
     tile, rowb = ctypes.c_int(0), ctypes.c_int(0)
     form = int(bool(phase)) | (0 if plain else 2)  # (the library answers for the epilogue kind: no knob is touched around the query)
-    check(lib.rs_conv2d_config(ctypes.byref(d), 2 if bf16 else 4, form, ctypes.byref(tile), ctypes.byref(rowb)), "rs_conv2d_config")
+    _call("rs_conv2d_config", ctypes.byref(d), 2 if bf16 else 4, form, ctypes.byref(tile), ctypes.byref(rowb))
     base = (lib.rs_conv2d_tile_name_bf16 if bf16 else lib.rs_conv2d_tile_name)(tile.value).decode()
     if tile.value == TILES["thin"]:  # conv_thin_bf16.hip: named by the form it computes
         return "{}<{}>".format(base, "phase" if phase else ("dgrad4x4" if d.kh == 4 else "3x3"))
@@ -730,11 +708,11 @@ class tuning:
         self.rowb = int(rowb)
 
     def __enter__(self):
-        check(_lib.lib().rs_conv2d_set_tuning(self.tile, self.rowb), "rs_conv2d_set_tuning")
+        _call("rs_conv2d_set_tuning", self.tile, self.rowb)
         return self
 
     def __exit__(self, *exc):
-        check(_lib.lib().rs_conv2d_set_tuning(-1, 0), "rs_conv2d_set_tuning")
+        _call("rs_conv2d_set_tuning", -1, 0)
         return False
 
 
@@ -761,11 +739,11 @@ class knob:
 
     def __enter__(self):
         self.old = get_knob(self.name)
-        check(_lib.lib().rs_set_knob(self.name.encode(), self.value), "rs_set_knob({})".format(self.name))
+        set_knob(self.name, self.value)
         return self
 
     def __exit__(self, *exc):
-        check(_lib.lib().rs_set_knob(self.name.encode(), self.old), "rs_set_knob({})".format(self.name))
+        set_knob(self.name, self.old)
         return False
 
 
@@ -773,7 +751,7 @@ def cast_bf16(t):
     """fp32 -> bf16 copy (round to nearest even); used for the per-step compute copies of the fp32 master weights."""
 
     out = torch.empty(t.shape, device=t.device, dtype=BF16)
-    check(_lib.lib().rs_cast_f32_to_bf16(_dev(t, "src"), _dev(out, "dst", BF16), t.numel(), _stream()), "rs_cast_f32_to_bf16")
+    _call("rs_cast_f32_to_bf16", _dev(t, "src"), _dev(out, "dst", BF16), t.numel(), _stream())
     return out
 
 
@@ -781,8 +759,7 @@ def cast_bf16_scaled(t, scale):
     """bf16(t * scale): a gradient bucket on its way to a bf16 exchange, already divided by the world size."""
 
     out = torch.empty(t.shape, device=t.device, dtype=BF16)
-    check(_lib.lib().rs_cast_f32_to_bf16_scaled(_dev(t, "src"), _dev(out, "dst", BF16), t.numel(), ctypes.c_float(scale), _stream()),
-          "rs_cast_f32_to_bf16_scaled")
+    _call("rs_cast_f32_to_bf16_scaled", _dev(t, "src"), _dev(out, "dst", BF16), t.numel(), ctypes.c_float(scale), _stream())
     return out
 
 
@@ -790,8 +767,8 @@ def cast_f32_scaled(src_bf16, dst_f32, scale):
     """dst (fp32, in place) = float(src bf16) * scale: the way back from a bf16 gradient exchange (``GradReducer``)."""
 
     assert src_bf16.numel() == dst_f32.numel()
-    check(_lib.lib().rs_cast_bf16_to_f32_scaled(_dev(src_bf16, "src", BF16), _dev(dst_f32, "dst"), src_bf16.numel(),
-                                                 ctypes.c_float(scale), _stream()), "rs_cast_bf16_to_f32_scaled")
+    _call("rs_cast_bf16_to_f32_scaled", _dev(src_bf16, "src", BF16), _dev(dst_f32, "dst"), src_bf16.numel(), ctypes.c_float(scale),
+          _stream())
     return dst_f32
 
 
@@ -830,8 +807,8 @@ class WeightPrep:
         self.ptrs = tuple(w.data_ptr() for w in self.weights)
 
     def run(self):
-        fn = _lib.lib().rs_weight_prep_bf16 if self.dtype == BF16 else _lib.lib().rs_weight_prep_f32
-        check(fn(_dev(self.table, "items", torch.uint8), len(self.weights), self.tiles, _stream()), "rs_weight_prep")
+        _call("rs_weight_prep_bf16" if self.dtype == BF16 else "rs_weight_prep_f32", _dev(self.table, "items", torch.uint8),
+              len(self.weights), self.tiles, _stream())
 
 
 def pack_stem_weight(w_krsc, dtype=torch.float32):
@@ -839,16 +816,15 @@ def pack_stem_weight(w_krsc, dtype=torch.float32):
 
     cout, kh, kw, cin = w_krsc.shape
     out = torch.empty((cout, kh, 8, 4), device=w_krsc.device, dtype=dtype)
-    fn = _lib.lib().rs_pack_stem_weight_bf16 if dtype == BF16 else _lib.lib().rs_pack_stem_weight
-    check(fn(_dev(w_krsc, "w"), _dev(out, "out", dtype), cout, kh, kw, cin, _stream()), "rs_pack_stem_weight")
+    _call("rs_pack_stem_weight_bf16" if dtype == BF16 else "rs_pack_stem_weight", _dev(w_krsc, "w"), _dev(out, "out", dtype), cout, kh, kw,
+          cin, _stream())
     return out
 
 
 def nchw_to_nhwc4(x, dtype=torch.float32):
     n, c, h, w = x.shape
     out = torch.empty((n, h, w, 4), device=x.device, dtype=dtype)
-    fn = _lib.lib().rs_nchw_to_nhwc4_bf16 if dtype == BF16 else _lib.lib().rs_nchw_to_nhwc4
-    check(fn(_dev(x, "x"), _dev(out, "out", dtype), n, c, h, w, _stream()), "rs_nchw_to_nhwc4")
+    _call("rs_nchw_to_nhwc4_bf16" if dtype == BF16 else "rs_nchw_to_nhwc4", _dev(x, "x"), _dev(out, "out", dtype), n, c, h, w, _stream())
     return out
 
 
@@ -857,16 +833,13 @@ def stem_conv_bf16(x4, w_packed, scale=None, shift=None, relu=False):
 
     n, h, w, _ = x4.shape
     out = torch.empty((n, h // 2, w // 2, 64), device=x4.device, dtype=BF16)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = _lib.lib().rs_stem_conv_fwd_bf16(_dev(x4, "x4", BF16), _dev(w_packed, "w", BF16), _dev(scale, "scale"),
-                                          _dev(shift, "shift"), _dev(out, "out", BF16), n, h, w, int(relu), _stream())
-    check(rc, "rs_stem_conv_fwd_bf16")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_stem_conv_fwd_bf16", _dev(x4, "x4", BF16), _dev(w_packed, "w", BF16), _dev(scale, "scale"), _dev(shift, "shift"),
+          _dev(out, "out", BF16), n, h, w, int(relu), _stream())
+    if ev:
+        _stop(ev)
         flops = 2.0 * n * 64 * 3 * 49 * (h // 2) * (w // 2)
-        _record("stem_conv_bf16", flops, (3, 64, 7, 2, 0, h // 2, w // 2), ev0, ev1, 2 * (x4.numel() + out.numel()))
+        _record(ev, "stem_conv_bf16", flops, (3, 64, 7, 2, 0, h // 2, w // 2), 2 * (x4.numel() + out.numel()))
     return out
 
 
@@ -894,16 +867,13 @@ def stem_conv_wgrad_bf16(dy, x4):
     n, h, w, _ = x4.shape
     lib = _lib.lib()
     dw = torch.empty((64, 7, 8, 4), device=dy.device, dtype=torch.float32)
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    rc = lib.rs_stem_conv_wgrad_bf16(_dev(dy, "dy", BF16), _dev(x4, "x4", BF16), _dev(dw, "dw"), n, h, w,
-                                     _workspace(lib.rs_stem_conv_wgrad_bf16_workspace_bytes(n, h, w), dy.device), _stream())
-    check(rc, "rs_stem_conv_wgrad_bf16")
-    if PROFILE is not None:
-        ev1.record()
+    ev = _start()
+    _call("rs_stem_conv_wgrad_bf16", _dev(dy, "dy", BF16), _dev(x4, "x4", BF16), _dev(dw, "dw"), n, h, w,
+          _workspace(lib.rs_stem_conv_wgrad_bf16_workspace_bytes(n, h, w), dy.device), _stream())
+    if ev:
+        _stop(ev)
         flops = 2.0 * n * 64 * 3 * 49 * (h // 2) * (w // 2)
-        _record("stem_wgrad_bf16", flops, (3, 64, 7, 2, 0, h // 2, w // 2), ev0, ev1, 2 * (x4.numel() + dy.numel()))
+        _record(ev, "stem_wgrad_bf16", flops, (3, 64, 7, 2, 0, h // 2, w // 2), 2 * (x4.numel() + dy.numel()))
     return dw
 
 
@@ -914,8 +884,7 @@ def u8_to_nhwc4_norm(img, mean, std):
     assert len(mean) == c and len(std) == c
     out = torch.empty((n, h, w, 4), device=img.device, dtype=torch.float32)
     fm, fs = (ctypes.c_float * c)(*mean), (ctypes.c_float * c)(*std)
-    check(_lib.lib().rs_u8_to_nhwc4_norm(_dev(img, "img", torch.uint8), _dev(out, "out"), fm, fs, n, h, w, c, _stream()),
-          "rs_u8_to_nhwc4_norm")
+    _call("rs_u8_to_nhwc4_norm", _dev(img, "img", torch.uint8), _dev(out, "out"), fm, fs, n, h, w, c, _stream())
     return out
 
 
@@ -941,10 +910,8 @@ def final_conv1x1_quantize(x, w, bias, overlap):
     c = w.shape[0]
     shape = (n, h - 2 * overlap, wd - 2 * overlap) + ((c - 1,) if c > 2 else ())
     out = torch.empty(shape, device=x.device, dtype=torch.uint8)
-    rc = _lib.lib().rs_final_conv1x1_quantize_dt(_dev(x, "x", x.dtype), _dt(x), _dev(w, "w"), _dev(bias, "bias"),
-                                                 _dev(_anchors(x.device), "anchors", torch.float64), _dev(out, "out", torch.uint8),
-                                                 n, h, wd, cin, c, overlap, _stream())
-    check(rc, "rs_final_conv1x1_quantize_dt")
+    _call("rs_final_conv1x1_quantize_dt", _dev(x, "x", x.dtype), _dt(x), _dev(w, "w"), _dev(bias, "bias"),
+          _dev(_anchors(x.device), "anchors", torch.float64), _dev(out, "out", torch.uint8), n, h, wd, cin, c, overlap, _stream())
     return out
 
 
@@ -953,9 +920,8 @@ def final_conv1x1_argmax(x, w, bias):
 
     n, h, wd, cin = x.shape
     out = torch.empty((n, h, wd), device=x.device, dtype=torch.uint8)
-    rc = _lib.lib().rs_final_conv1x1_argmax_dt(_dev(x, "x", x.dtype), _dt(x), _dev(w, "w"), _dev(bias, "bias"),
-                                               _dev(out, "out", torch.uint8), n, h, wd, cin, w.shape[0], _stream())
-    check(rc, "rs_final_conv1x1_argmax_dt")
+    _call("rs_final_conv1x1_argmax_dt", _dev(x, "x", x.dtype), _dt(x), _dev(w, "w"), _dev(bias, "bias"), _dev(out, "out", torch.uint8), n,
+          h, wd, cin, w.shape[0], _stream())
     return out
 
 
@@ -982,9 +948,8 @@ def _tta_fan_out(x, kind, mean, std, op_list, dtype, n, h, w, c):
     if mean is not None:
         assert len(mean) == c and len(std) == c
         fm, fs = (ctypes.c_float * c)(*mean), (ctypes.c_float * c)(*std)
-    rc = _lib.lib().rs_tta_fan_out(_dev(x, "x", x.dtype), kind, fm, fs, _dev(out, "out", dtype), RS_BF16 if dtype == BF16 else RS_F32,
-                                   (ctypes.c_int * v)(*op_list), v, n, h, w, c, _stream())
-    check(rc, "rs_tta_fan_out")
+    _call("rs_tta_fan_out", _dev(x, "x", x.dtype), kind, fm, fs, _dev(out, "out", dtype), _dt(dtype), (ctypes.c_int * v)(*op_list), v, n, h,
+          w, c, _stream())
     return out
 
 
@@ -1021,9 +986,8 @@ def tta_merge(probs, op_list, mode="probs", overlap=0):
         anchors = _dev(_anchors(probs.device), "anchors", torch.float64)
     else:
         out = torch.empty((n, h, w), device=probs.device, dtype=torch.uint8)
-    rc = _lib.lib().rs_tta_merge(_dev(probs, "probs"), (ctypes.c_int * v)(*op_list), v, m, anchors, int(overlap),
-                                 _dev(out, "out", out.dtype), n, c, h, w, _stream())
-    check(rc, "rs_tta_merge")
+    _call("rs_tta_merge", _dev(probs, "probs"), (ctypes.c_int * v)(*op_list), v, m, anchors, int(overlap), _dev(out, "out", out.dtype), n,
+          c, h, w, _stream())
     return out
 
 
@@ -1034,9 +998,8 @@ def maxpool2d(x, k, stride, pad, want_argmax=False, out_dtype=None):
     ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
     out = torch.empty((n, ho, wo, c), device=x.device, dtype=out_dtype or x.dtype)
     amax = torch.empty((n, ho, wo, c), device=x.device, dtype=torch.uint8) if want_argmax else None
-    rc = _lib.lib().rs_maxpool2d_fwd_dt(_dev(x, "x", x.dtype), _dt(x), _dev(out, "out", out.dtype), _dt(out),
-                                        _dev(amax, "argmax", torch.uint8), n, h, w, c, k, stride, pad, ho, wo, _stream())
-    check(rc, "rs_maxpool2d_fwd_dt")
+    _call("rs_maxpool2d_fwd_dt", _dev(x, "x", x.dtype), _dt(x), _dev(out, "out", out.dtype), _dt(out), _dev(amax, "argmax", torch.uint8), n,
+          h, w, c, k, stride, pad, ho, wo, _stream())
     return (out, amax) if want_argmax else out
 
 
@@ -1044,9 +1007,8 @@ def bn_fold(gamma, beta, mean, var, eps):
     c = gamma.numel()
     scale = torch.empty(c, device=gamma.device, dtype=torch.float32)
     shift = torch.empty(c, device=gamma.device, dtype=torch.float32)
-    rc = _lib.lib().rs_bn_fold(_dev(gamma, "gamma"), _dev(beta, "beta"), _dev(mean, "mean"), _dev(var, "var"),
-                               ctypes.c_float(eps), _dev(scale, "scale"), _dev(shift, "shift"), c, _stream())
-    check(rc, "rs_bn_fold")
+    _call("rs_bn_fold", _dev(gamma, "gamma"), _dev(beta, "beta"), _dev(mean, "mean"), _dev(var, "var"), ctypes.c_float(eps),
+          _dev(scale, "scale"), _dev(shift, "shift"), c, _stream())
     return scale, shift
 
 
@@ -1056,9 +1018,8 @@ def final_conv1x1(x, w, bias, softmax=False):
     n, h, wd, cin = x.shape
     c = w.shape[0]
     out = torch.empty((n, c, h, wd), device=x.device, dtype=torch.float32)
-    rc = _lib.lib().rs_final_conv1x1_dt(_dev(x, "x", x.dtype), _dt(x), _dev(w, "w"), _dev(bias, "bias"), _dev(out, "out"), n, h,
-                                        wd, cin, c, int(softmax), _stream())
-    check(rc, "rs_final_conv1x1_dt")
+    _call("rs_final_conv1x1_dt", _dev(x, "x", x.dtype), _dt(x), _dev(w, "w"), _dev(bias, "bias"), _dev(out, "out"), n, h, wd, cin, c,
+          int(softmax), _stream())
     return out
 
 
@@ -1088,8 +1049,8 @@ def pack_dgrad_weight(w_krsc, dtype=torch.float32):
 
     cout, kh, kw, cin = w_krsc.shape
     out = torch.empty((cin, kh, kw, cout), device=w_krsc.device, dtype=dtype)
-    fn = _lib.lib().rs_pack_dgrad_weight_bf16 if dtype == BF16 else _lib.lib().rs_pack_dgrad_weight
-    check(fn(_dev(w_krsc, "w"), _dev(out, "out", dtype), cout, kh, kw, cin, _stream()), "rs_pack_dgrad_weight")
+    _call("rs_pack_dgrad_weight_bf16" if dtype == BF16 else "rs_pack_dgrad_weight", _dev(w_krsc, "w"), _dev(out, "out", dtype), cout, kh,
+          kw, cin, _stream())
     return out
 
 
@@ -1098,8 +1059,7 @@ def unpack_stem_weight(packed, kw, cin, out=None):
     if out is None:
         out = torch.empty((cout, kh, kw, cin), device=packed.device, dtype=torch.float32)
     assert tuple(out.shape) == (cout, kh, kw, cin)
-    check(_lib.lib().rs_unpack_stem_weight(_dev(packed, "packed"), _dev(out, "out"), cout, kh, kw, cin, _stream()),
-          "rs_unpack_stem_weight")
+    _call("rs_unpack_stem_weight", _dev(packed, "packed"), _dev(out, "out"), cout, kh, kw, cin, _stream())
     return out
 
 
@@ -1117,17 +1077,12 @@ def conv2d_wgrad(dy, src1, kh, kw, src2=None, ups=0, stride=1, pad=0, stem=0, ou
     dw = out if out is not None else torch.empty(shape, device=dy.device, dtype=torch.float32)
     assert tuple(dw.shape) == shape
     wsb = (lib.rs_conv2d_wgrad_bf16_workspace_bytes if bf else lib.rs_conv2d_wgrad_workspace_bytes)(ctypes.byref(d))
-    if PROFILE is not None:
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record()
-    fn = lib.rs_conv2d_wgrad_bf16 if bf else lib.rs_conv2d_wgrad
-    rc = fn(ctypes.byref(d), _dev(dy, "dy", act), _dev(src1, "src1", act), _dev(src2, "src2", act), _dev(dw, "dw"),
-            _workspace(wsb, dy.device), _stream())
-    check(rc, "rs_conv2d_wgrad_bf16" if bf else "rs_conv2d_wgrad")
-    if PROFILE is not None:
-        ev1.record()
-        es = 2 if bf else 4
-        nbytes = es * (d.N * d.Ho * d.Wo * d.Cout + d.N * d.Hs * d.Ws * (4 if stem else d.C1 + d.C2)) + 4 * dw.numel()
+    ev = _start()
+    _call("rs_conv2d_wgrad_bf16" if bf else "rs_conv2d_wgrad", ctypes.byref(d), _dev(dy, "dy", act), _dev(src1, "src1", act),
+          _dev(src2, "src2", act), _dev(dw, "dw"), _workspace(wsb, dy.device), _stream())
+    if ev:
+        _stop(ev)
+        nbytes = _esize(act) * (d.N * d.Ho * d.Wo * d.Cout + d.N * d.Hs * d.Ws * (4 if stem else d.C1 + d.C2)) + 4 * dw.numel()
         form = lib.rs_conv2d_wgrad_bf16_form(ctypes.byref(d)) if bf else 0
         if not bf and not stem:
             # conv_wgrad.hip: 2 = the fp32 phase form of DecoderBlock (16 / 36 of the MACs), 3 = that in the Winograd domain (9 / 36),
@@ -1137,8 +1092,7 @@ def conv2d_wgrad(dy, src1, kh, kw, src2=None, ups=0, stride=1, pad=0, stem=0, ou
         name = wgrad_kernel_name(d, form) if bf else ("conv_wgrad_f32" if stem or get_knob("wgrad_f32_dma") == 0 else
                                                       "conv_wgrad_wino_f32" if form == 3 else "conv_wgrad_wino33_f32" if form == 4 else
                                                       "conv_wgrad_f32_dma")
-        _record(name, conv_flops(d), (d.C1 + d.C2, d.Cout, d.kh, d.stride, d.ups, d.Ho, d.Wo), ev0, ev1, nbytes,
-                conv_flops(d) * (0.25 if form == 3 else 4.0 / 9.0 if form in (2, 4) else 1.0))
+        _record(ev, name, conv_flops(d), _shape(d), nbytes, conv_flops(d) * (0.25 if form == 3 else 4.0 / 9.0 if form in (2, 4) else 1.0))
     return dw
 
 
@@ -1152,12 +1106,10 @@ def bn_train_stats(y, gamma, beta, eps, momentum, running_mean=None, running_var
     c = y.shape[-1]
     m = y.numel() // c
     mean, invstd, scale, shift = (torch.empty(c, device=y.device, dtype=torch.float32) for _ in range(4))
-    rc = _lib.lib().rs_bn_train_stats_dt(
-        _dev(y, "y", y.dtype), _dt(y), m, c, ctypes.c_float(eps), ctypes.c_float(momentum), _dev(gamma, "gamma"), _dev(beta, "beta"),
-        _dev(mean, "mean"), _dev(invstd, "invstd"), _dev(scale, "scale"), _dev(shift, "shift"),
-        _dev(running_mean, "running_mean"), _dev(running_var, "running_var"),
-        _dev(num_batches_tracked, "num_batches_tracked", torch.int64), _bn_ws(m, c, y.device), _stream())
-    check(rc, "rs_bn_train_stats")
+    _call("rs_bn_train_stats_dt", _dev(y, "y", y.dtype), _dt(y), m, c, ctypes.c_float(eps), ctypes.c_float(momentum), _dev(gamma, "gamma"),
+          _dev(beta, "beta"), _dev(mean, "mean"), _dev(invstd, "invstd"), _dev(scale, "scale"), _dev(shift, "shift"),
+          _dev(running_mean, "running_mean"), _dev(running_var, "running_var"),
+          _dev(num_batches_tracked, "num_batches_tracked", torch.int64), _bn_ws(m, c, y.device), _stream())
     return mean, invstd, scale, shift
 
 
@@ -1174,10 +1126,8 @@ def bn_apply(y, scale, shift, residual=None, relu=False, want_bits=False):
     c = y.shape[-1]
     out = torch.empty_like(y)
     bits = torch.empty(y.numel() // 8, device=y.device, dtype=torch.uint8) if want_bits else None
-    rc = _lib.lib().rs_bn_apply_bits_dt(_dev(y, "y", y.dtype), _dev(scale, "scale"), _dev(shift, "shift"),
-                                        _dev(residual, "residual", y.dtype), _dev(out, "out", y.dtype),
-                                        _dev(bits, "bits", torch.uint8), _dt(y), y.numel() // c, c, int(relu), _stream())
-    check(rc, "rs_bn_apply_bits_dt")
+    _call("rs_bn_apply_bits_dt", _dev(y, "y", y.dtype), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", y.dtype),
+          _dev(out, "out", y.dtype), _dev(bits, "bits", torch.uint8), _dt(y), y.numel() // c, c, int(relu), _stream())
     return (out, bits) if want_bits else out
 
 
@@ -1193,10 +1143,9 @@ def bn_bwd(dz, zmask, y, mean, invstd, gamma, want_masked=False, dgamma=None, db
     if dbeta is None:
         dbeta = torch.empty(c, device=y.device, dtype=torch.float32)
     t = y.dtype
-    rc = _lib.lib().rs_bn_bwd_dt(_dev(dz, "dz", t), _dev(zmask, "zmask", t), _dev(y, "y", t), _dev(mean, "mean"),
-                                 _dev(invstd, "invstd"), _dev(gamma, "gamma"), _dev(dy, "dy", t), _dev(dmasked, "dmasked", t),
-                                 _dev(dgamma, "dgamma"), _dev(dbeta, "dbeta"), _dt(y), m, c, _bn_ws(m, c, y.device), _stream())
-    check(rc, "rs_bn_bwd")
+    _call("rs_bn_bwd_dt", _dev(dz, "dz", t), _dev(zmask, "zmask", t), _dev(y, "y", t), _dev(mean, "mean"), _dev(invstd, "invstd"),
+          _dev(gamma, "gamma"), _dev(dy, "dy", t), _dev(dmasked, "dmasked", t), _dev(dgamma, "dgamma"), _dev(dbeta, "dbeta"), _dt(y), m, c,
+          _bn_ws(m, c, y.device), _stream())
     return (dy, dgamma, dbeta, dmasked) if want_masked else (dy, dgamma, dbeta)
 
 
@@ -1206,8 +1155,8 @@ def scatter_add_stride2(t, out):
 
     n, hs, ws, c = t.shape
     assert out.shape[0] == n and out.shape[3] == c and out.dtype == t.dtype and out.is_contiguous()
-    check(_lib.lib().rs_scatter_add_stride2_dt(_dev(t, "t", t.dtype), _dev(out, "out", t.dtype), _dt(t), n, hs, ws, out.shape[1], out.shape[2], c,
-                                               _stream()), "rs_scatter_add_stride2_dt")
+    _call("rs_scatter_add_stride2_dt", _dev(t, "t", t.dtype), _dev(out, "out", t.dtype), _dt(t), n, hs, ws, out.shape[1], out.shape[2], c,
+          _stream())
     return out
 
 
@@ -1220,10 +1169,8 @@ def maxpool2d_bwd(dy, argmax, in_shape, k, stride, pad, out=None, out_dtype=None
     acc = out is not None
     if out is None:
         out = torch.empty(in_shape, device=dy.device, dtype=out_dtype or dy.dtype)
-    rc = _lib.lib().rs_maxpool2d_bwd_dt(_dev(dy, "dy", dy.dtype), _dt(dy), _dev(argmax, "argmax", torch.uint8),
-                                        _dev(out, "dx", out.dtype), _dt(out), n, h, w, c, k, stride, pad, ho, wo, int(acc),
-                                        _stream())
-    check(rc, "rs_maxpool2d_bwd")
+    _call("rs_maxpool2d_bwd_dt", _dev(dy, "dy", dy.dtype), _dt(dy), _dev(argmax, "argmax", torch.uint8), _dev(out, "dx", out.dtype),
+          _dt(out), n, h, w, c, k, stride, pad, ho, wo, int(acc), _stream())
     return out
 
 
@@ -1237,9 +1184,8 @@ def upsample2x_bwd(dup, c1, c2=0, mask1=None, mask2=None, out1=None):
     t = dup.dtype
     d1 = out1 if acc else torch.empty((n, h, w, c1), device=dup.device, dtype=t)
     d2 = torch.empty((n, h, w, c2), device=dup.device, dtype=t) if c2 else None
-    rc = _lib.lib().rs_upsample2x_bwd_dt(_dev(dup, "dup", t), _dev(d1, "d1", t), _dev(d2, "d2", t), _dev(mask1, "mask1", t),
-                                         _dev(mask2, "mask2", t), _dt(dup), n, h, w, c1, c2, int(acc), _stream())
-    check(rc, "rs_upsample2x_bwd")
+    _call("rs_upsample2x_bwd_dt", _dev(dup, "dup", t), _dev(d1, "d1", t), _dev(d2, "d2", t), _dev(mask1, "mask1", t),
+          _dev(mask2, "mask2", t), _dt(dup), n, h, w, c1, c2, int(acc), _stream())
     return d1, d2
 
 
@@ -1255,9 +1201,8 @@ def final_conv1x1_bwd(x, w, dlogits, relu_mask=True, dw=None, db=None):
     if db is None:
         db = torch.empty(c, device=x.device, dtype=torch.float32)
     ws = _workspace(lib.rs_final_conv1x1_bwd_workspace_bytes(cin, c), x.device)
-    rc = lib.rs_final_conv1x1_bwd_dt(_dev(x, "x", x.dtype), _dev(w, "w"), _dev(dlogits, "dlogits"), _dev(dx, "dx", x.dtype),
-                                     _dev(dw, "dw"), _dev(db, "db"), _dt(x), n, h, wd, cin, c, int(relu_mask), ws, _stream())
-    check(rc, "rs_final_conv1x1_bwd")
+    _call("rs_final_conv1x1_bwd_dt", _dev(x, "x", x.dtype), _dev(w, "w"), _dev(dlogits, "dlogits"), _dev(dx, "dx", x.dtype), _dev(dw, "dw"),
+          _dev(db, "db"), _dt(x), n, h, wd, cin, c, int(relu_mask), ws, _stream())
     return dx, dw, db
 
 
@@ -1273,20 +1218,17 @@ def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0):
     lib = _lib.lib()
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     stats = torch.empty(2, device=logits.device, dtype=torch.float32)
-    rc = lib.rs_nll_loss_fwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
-                             _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma),
-                             _workspace(lib.rs_nll_loss_workspace_bytes(), logits.device), _stream())
-    check(rc, "rs_nll_loss_fwd")
+    _call("rs_nll_loss_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(loss, "loss"),
+          _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma), _workspace(lib.rs_nll_loss_workspace_bytes(), logits.device),
+          _stream())
     return loss, stats
 
 
 def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0):
     n, c, h, w = logits.shape
     dlogits = torch.empty_like(logits)
-    rc = _lib.lib().rs_nll_loss_bwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
-                                    _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w,
-                                    mode, ctypes.c_float(gamma), _stream())
-    check(rc, "rs_nll_loss_bwd")
+    _call("rs_nll_loss_bwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(stats, "stats"),
+          _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mode, ctypes.c_float(gamma), _stream())
     return dlogits
 
 
@@ -1295,20 +1237,16 @@ def miou_loss_fwd(logits, targets, weight):
     lib = _lib.lib()
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     stats = torch.empty(5 + 2 * n * c, device=logits.device, dtype=torch.float32)
-    rc = lib.rs_miou_loss_fwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
-                              _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w,
-                              _workspace(lib.rs_miou_loss_workspace_bytes(n, c), logits.device), _stream())
-    check(rc, "rs_miou_loss_fwd")
+    _call("rs_miou_loss_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(loss, "loss"),
+          _dev(stats, "stats"), n, c, h, w, _workspace(lib.rs_miou_loss_workspace_bytes(n, c), logits.device), _stream())
     return loss, stats
 
 
 def miou_loss_bwd(logits, targets, weight, stats, grad_out):
     n, c, h, w = logits.shape
     dlogits = torch.empty_like(logits)
-    rc = _lib.lib().rs_miou_loss_bwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
-                                     _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w,
-                                     _stream())
-    check(rc, "rs_miou_loss_bwd")
+    _call("rs_miou_loss_bwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(stats, "stats"),
+          _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, _stream())
     return dlogits
 
 
@@ -1319,10 +1257,8 @@ def lovasz_fwd(logits, targets, want_grad=True):
     lib = _lib.lib()
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     grad = torch.empty_like(logits) if want_grad else None
-    rc = lib.rs_lovasz_fwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"),
-                           _dev(grad, "grad"), n, c, h, w,
-                           _workspace(lib.rs_lovasz_workspace_bytes(n, c, h, w), logits.device), _stream())
-    check(rc, "rs_lovasz_fwd")
+    _call("rs_lovasz_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"), _dev(grad, "grad"), n, c, h,
+          w, _workspace(lib.rs_lovasz_workspace_bytes(n, c, h, w), logits.device), _stream())
     return loss, grad
 
 
@@ -1339,17 +1275,14 @@ def lovasz_softmax_fwd(logits, targets, per_image=True, classes="present", want_
     grad = torch.empty_like(logits) if want_grad else None
     probs = torch.empty_like(logits) if want_probs else None
     nbytes = lib.rs_lovasz_softmax_workspace_bytes(n, c, h, w, pi)
-    rc = lib.rs_lovasz_softmax_fwd(_dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"),
-                                   _dev(grad, "grad"), _dev(probs, "probs"), n, c, h, w, pi, 1 if classes == "all" else 0,
-                                   _workspace(nbytes, logits.device), _stream())
-    check(rc, "rs_lovasz_softmax_fwd")
+    _call("rs_lovasz_softmax_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"), _dev(grad, "grad"),
+          _dev(probs, "probs"), n, c, h, w, pi, 1 if classes == "all" else 0, _workspace(nbytes, logits.device), _stream())
     return loss, grad, probs
 
 
 def scale_by_scalar(src, scalar):
     out = torch.empty_like(src)
-    check(_lib.lib().rs_scale_by_scalar(_dev(src, "src"), _dev(scalar, "scalar"), _dev(out, "out"), src.numel(), _stream()),
-          "rs_scale_by_scalar")
+    _call("rs_scale_by_scalar", _dev(src, "src"), _dev(scalar, "scalar"), _dev(out, "out"), src.numel(), _stream())
     return out
 
 
@@ -1357,9 +1290,8 @@ def confusion_counts(scores, targets, counts):
     """counts (uint64-as-int64 [4] device tensor) += (tn, fn, fp, tp) of the whole batch (reference naming)."""
 
     n, c, h, w = scores.shape
-    rc = _lib.lib().rs_confusion_counts(_dev(scores, "scores"), _dev(targets, "targets", torch.int64),
-                                        _dev(counts, "counts", torch.int64), n, c, h, w, _stream())
-    check(rc, "rs_confusion_counts")
+    _call("rs_confusion_counts", _dev(scores, "scores"), _dev(targets, "targets", torch.int64), _dev(counts, "counts", torch.int64), n, c,
+          h, w, _stream())
     return counts
 
 
@@ -1368,18 +1300,15 @@ def confusion_matrix(scores, targets, counts):
 
     n, c, h, w = scores.shape
     assert counts.numel() == c * c
-    rc = _lib.lib().rs_confusion_matrix(_dev(scores, "scores"), _dev(targets, "targets", torch.int64),
-                                        _dev(counts, "counts", torch.int64), n, c, h, w, _stream())
-    check(rc, "rs_confusion_matrix")
+    _call("rs_confusion_matrix", _dev(scores, "scores"), _dev(targets, "targets", torch.int64), _dev(counts, "counts", torch.int64), n, c,
+          h, w, _stream())
     return counts
 
 
 def label_histogram_u8(labels, counts256):
     """counts256 (int64 [256] device tensor) += np.bincount(labels) of a uint8 device tensor (tools/weights.py:41-47)."""
 
-    rc = _lib.lib().rs_label_histogram_u8(_dev(labels, "labels", torch.uint8), labels.numel(), _dev(counts256, "counts", torch.int64),
-                                          _stream())
-    check(rc, "rs_label_histogram_u8")
+    _call("rs_label_histogram_u8", _dev(labels, "labels", torch.uint8), labels.numel(), _dev(counts256, "counts", torch.int64), _stream())
     return counts256
 
 
@@ -1392,10 +1321,8 @@ def softvote_masks(quantized, weights=None):
     k, p, cq = quantized.shape
     out = torch.empty(p, device=quantized.device, dtype=torch.uint8)
     wt = None if weights is None else torch.as_tensor(list(weights), dtype=torch.float64).to(quantized.device)
-    rc = _lib.lib().rs_softvote_masks(_dev(quantized, "quantized", torch.uint8), _dev(wt, "weights", torch.float64),
-                                      _dev(_anchors(quantized.device), "anchors", torch.float64), _dev(out, "out", torch.uint8),
-                                      k, p, cq + 1, _stream())
-    check(rc, "rs_softvote_masks")
+    _call("rs_softvote_masks", _dev(quantized, "quantized", torch.uint8), _dev(wt, "weights", torch.float64),
+          _dev(_anchors(quantized.device), "anchors", torch.float64), _dev(out, "out", torch.uint8), k, p, cq + 1, _stream())
     return out
 
 
@@ -1409,10 +1336,8 @@ def augment_tiles(images, masks, index, op, mean, std):
     out = torch.empty((n, c, s, s), device=images.device, dtype=torch.float32)
     om = torch.empty((n, s, s), device=images.device, dtype=torch.int64) if masks is not None else None
     fm, fs = (ctypes.c_float * c)(*mean), (ctypes.c_float * c)(*std)
-    rc = _lib.lib().rs_augment_tiles(_dev(images, "images", torch.uint8), _dev(masks, "masks", torch.uint8),
-                                     _dev(index, "index", torch.int32), _dev(op, "op", torch.int32), fm, fs, _dev(out, "out"),
-                                     _dev(om, "out_masks", torch.int64), n, s, c, _stream())
-    check(rc, "rs_augment_tiles")
+    _call("rs_augment_tiles", _dev(images, "images", torch.uint8), _dev(masks, "masks", torch.uint8), _dev(index, "index", torch.int32),
+          _dev(op, "op", torch.int32), fm, fs, _dev(out, "out"), _dev(om, "out_masks", torch.int64), n, s, c, _stream())
     return out, om
 
 
@@ -1468,9 +1393,8 @@ def clean_masks(images_u8, index, eps_open, eps_close, form=CLEAN_AUTO):
     ws = None
     if form != CLEAN_LDS:  # (CLEAN_AUTO is the HBM form: profiles/features)
         ws = torch.empty(lib.rs_features_clean_workspace_bytes(b, h, w), device=images_u8.device, dtype=torch.uint8)
-    rc = lib.rs_features_clean(_dev(images_u8, "images", torch.uint8), _dev(out, "out", torch.uint8), _dev(ws, "workspace", torch.uint8),
-                               b, h, w, index, eps_open, _disc_arg(eps_open), eps_close, _disc_arg(eps_close), form, _stream())
-    check(rc, "rs_features_clean")
+    _call("rs_features_clean", _dev(images_u8, "images", torch.uint8), _dev(out, "out", torch.uint8), _dev(ws, "workspace", torch.uint8), b,
+          h, w, index, eps_open, _disc_arg(eps_open), eps_close, _disc_arg(eps_close), form, _stream())
     return out
 
 
@@ -1481,9 +1405,8 @@ def label_components(masks):
     b, h, w = masks.shape
     labels = torch.empty((b, h, w), device=masks.device, dtype=torch.int32)
     err = torch.zeros(1, device=masks.device, dtype=torch.int32)
-    rc = _lib.lib().rs_features_label(_dev(masks, "masks", torch.uint8), _dev(labels, "labels", torch.int32), _dev(err, "err", torch.int32),
-                                      b, h, w, _stream())
-    check(rc, "rs_features_label")
+    _call("rs_features_label", _dev(masks, "masks", torch.uint8), _dev(labels, "labels", torch.int32), _dev(err, "err", torch.int32), b, h,
+          w, _stream())
     if int(err.item()):
         raise RuntimeError("rs_features_label: a union-find loop ran out of its H*W bound (code {})".format(int(err.item())))
     return labels
@@ -1501,10 +1424,9 @@ def component_table(labels, min_area=0):
     for _ in range(2):  # (the second pass has the exact capacity)
         raw = torch.empty((capacity, 6), device=dev, dtype=torch.int32)
         table = torch.empty((capacity, 7), device=dev, dtype=torch.int32)
-        rc = _lib.lib().rs_features_components(_dev(labels, "labels", torch.int32), _dev(slotmap, "slotmap", torch.int32),
-                                               _dev(raw, "raw", torch.int32), _dev(table, "table", torch.int32),
-                                               _dev(counters, "counters", torch.int32), capacity, b, h, w, int(min_area), _stream())
-        check(rc, "rs_features_components")
+        _call("rs_features_components", _dev(labels, "labels", torch.int32), _dev(slotmap, "slotmap", torch.int32),
+              _dev(raw, "raw", torch.int32), _dev(table, "table", torch.int32), _dev(counters, "counters", torch.int32), capacity, b, h, w,
+              int(min_area), _stream())
         found, kept = counters.tolist()
         if found <= capacity:
             break
@@ -1527,10 +1449,9 @@ def boundary_edges(labels, table):
     table = table.contiguous()
 
     def run(edges, capacity):
-        rc = _lib.lib().rs_features_edges(_dev(labels, "labels", torch.int32), _dev(table, "table", torch.int32) if len(table) else None,
-                                          len(table), _dev(keep, "keep", torch.uint8), _dev(edges, "edges", torch.int32), capacity,
-                                          _dev(counter, "counter", torch.int32), b, h, w, _stream())
-        check(rc, "rs_features_edges")
+        _call("rs_features_edges", _dev(labels, "labels", torch.int32), _dev(table, "table", torch.int32) if len(table) else None,
+              len(table), _dev(keep, "keep", torch.uint8), _dev(edges, "edges", torch.int32), capacity,
+              _dev(counter, "counter", torch.int32), b, h, w, _stream())
         return int(counter.item())
 
     n = run(None, 0)

@@ -12,6 +12,8 @@ from oracle import robosat_ref as R, seeded
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+SWITCH_DEFAULTS = ("ROBOSAT_TAIL_FUSE", "ROBOSAT_WINOGRAD", "ROBOSAT_WINO_DGRAD", "ROBOSAT_WINO33_STATS", "ROBOSAT_WINO33_BWD", "ROBOSAT_S2_DGRAD",
+                   "ROBOSAT_S2_DGRAD_3X3", "ROBOSAT_WGRAD_STREAM")
 
 
 @pytest.mark.parametrize("loss_name", ["CrossEntropy", "Lovasz"])
@@ -169,3 +171,68 @@ def test_graphed_train_step_is_the_eager_step(dtype, loss_name):
     assert a["steps"] == b["steps"] == {7.0}
     assert torch.equal(a["probs"], b["probs"])  # eval after graph replays reads the CURRENT weights (derived caches dropped)
     assert int(b["state"]["resnet.bn1.num_batches_tracked"]) == 7
+
+
+def test_kernel_selection_switches_select_the_other_kernels(monkeypatch):
+    """Every switch of ``ops.SWITCHES`` that the training step reads, set to "0", selects the other kernel: by the ``*_ok``
+    function's answer, or by the roofline records of one fp32 step (2 x 3 x 128 x 128).  (ROBOSAT_FUSED_HEAD:
+    test_gpu_tiles.py, ROBOSAT_TAIL_FUSE: test_gpu_ops.py.)"""
+    from robosat_amd import autograd, losses, ops
+    from robosat_amd.unet import UNet
+
+    with pytest.raises(KeyError):
+        ops.switch("ROBOSAT_NO_SUCH_SWITCH")
+    monkeypatch.setenv("ROBOSAT_WINOGRAD", "1")  # (anything but "0" is on)
+    assert ops.switch("ROBOSAT_WINOGRAD")
+
+    x33 = torch.zeros((2, 32, 32, 64), device=DEV)
+    for name in SWITCH_DEFAULTS:
+        monkeypatch.delenv(name, raising=False)
+    for name, probe in (("ROBOSAT_WINOGRAD", lambda: ops.wino33_ok(x33, 64)),
+                        ("ROBOSAT_WINO_DGRAD", lambda: ops.wino_dgrad_ok(2, 16, 16, 128, 0, 32)),
+                        ("ROBOSAT_WINO33_BWD", lambda: ops.wino33_dgrad_ok(x33, 64)),
+                        ("ROBOSAT_TAIL_FUSE", lambda: ops.conv1x1_wave_ok(x33, torch.zeros((256, 1, 1, 64), device=DEV))
+                         and ops.bottleneck_tail_ok(x33, torch.zeros((256, 1, 1, 64), device=DEV), torch.zeros((64, 1, 1, 256), device=DEV))),
+                        ("ROBOSAT_WGRAD_STREAM", lambda: autograd._side_stream(torch.device(DEV)) != torch.cuda.current_stream(DEV))):
+        assert probe(), name
+        monkeypatch.setenv(name, "0")
+        assert not probe(), name
+        monkeypatch.delenv(name)
+
+    net = UNet(2, pretrained=False)
+    net.load_state_dict(seeded.seeded_state_dict(R.UNetRef(2).state_dict(), 2))
+    net = net.to(DEV).train()
+    x = seeded.synthetic_images(2, 3, 128, 128, 2).to(DEV)
+    t = seeded.synthetic_targets(2, 2, 128, 128, 2).to(DEV)
+    crit = losses.CrossEntropyLoss2d(weight=torch.tensor([1.0, 2.0])).to(DEV)
+
+    def records(off=None):
+        if off is not None:
+            monkeypatch.setenv(off, "0")
+        ops.PROFILE = []
+        try:
+            net.zero_grad()
+            crit(net(x), t).backward()
+            torch.cuda.synchronize()
+            return [(r[0], r[2]) for r in ops.PROFILE]
+        finally:
+            ops.PROFILE = None
+            if off is not None:
+                monkeypatch.delenv(off)
+
+    def count(recs, what):
+        return sum(what in name for name, _ in recs)
+
+    def ups(recs):  # launches that read their input through the x2 upsample: the phase forms
+        return sum(shape[4] == 1 for _, shape in recs)
+
+    on = records()
+    assert count(on, "3x3+stats") > 0 and count(on, "3x3+bwd") > 0
+    assert count(records("ROBOSAT_WINO33_STATS"), "3x3+stats") == 0
+    assert count(records("ROBOSAT_WINO33_BWD"), "3x3+bwd") == 0
+    assert count(records("ROBOSAT_WINOGRAD"), "conv_wino_f32<3x3") == 0
+    # the 3x3 / stride-2 data gradients of layer2..4's first blocks run as phase forms; switched off they are plain convolutions
+    no33, no_s2 = records("ROBOSAT_S2_DGRAD_3X3"), records("ROBOSAT_S2_DGRAD")
+    assert ups(on) - ups(no33) == 3 and ups(no_s2) == ups(no33)
+    assert sorted(no_s2) != sorted(no33)  # (the 1x1 / stride-2 gradients: at the low resolution + scatter, or zero-insertion)
+    assert records() == on

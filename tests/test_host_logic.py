@@ -71,6 +71,46 @@ def test_library_exports_every_declared_symbol():
     assert handle.rs_abi_version() == _lib.ABI_VERSION
 
 
+def _c_class(ctype):
+    """Class of a C type as written in the header: pointer (any ``T*``, ``rs_stream_t``) / char* / int / long / float."""
+
+    t = " ".join(ctype.replace("const", " ").replace("*", " * ").split())
+    if t == "char *":
+        return "char*"
+    if t.endswith("*") or t == "rs_stream_t":
+        return "pointer"
+    assert t in ("int", "long", "float"), "a type this test has no class for: {!r}".format(ctype)
+    return t
+
+
+def _ctypes_class(t):
+    if t is ctypes.c_char_p:
+        return "char*"
+    if t is ctypes.c_void_p or isinstance(t, type) and issubclass(t, ctypes._Pointer):
+        return "pointer"
+    return {ctypes.c_int: "int", ctypes.c_long: "long", ctypes.c_float: "float"}[t]
+
+
+def test_ctypes_signatures_match_the_header_by_type():
+    """Every prototype of include/robosat_hip.h against its row of ``_lib.SIGNATURES``: return type and parameter list, by
+    class.  (A wrong row -- an ``int`` where the header says ``long``, a missing argument -- corrupts a call silently.)"""
+    from robosat_amd import _lib
+
+    header = open(os.path.join(ROOT, "include", "robosat_hip.h")).read()
+    header = re.sub(r"/\*.*?\*/", " ", re.sub(r"//[^\n]*", " ", header), flags=re.S)
+    protos = re.findall(r"^([A-Za-z_][\w \t]*?[\w*])[ \t]*\b(rs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header, flags=re.M)
+    assert len(protos) == len({name for _, name, _ in protos})
+    assert {name for _, name, _ in protos} == set(_lib.SIGNATURES)  # every declared entry point was parsed: none left over
+    for ret, name, params in protos:
+        params = [p.strip() for p in params.split(",")]
+        if params == ["void"]:
+            params = []
+        # a parameter is "<type> <identifier>": the type is what is left of the identifier
+        want = (_c_class(ret), [_c_class(re.sub(r"\w+$", "", p)) for p in params])
+        restype, argtypes = _lib.SIGNATURES[name]
+        assert (_ctypes_class(restype), [_ctypes_class(a) for a in argtypes]) == want, name
+
+
 def test_no_cpu_fallback():
     from robosat_amd.unet import UNet
 
