@@ -608,6 +608,42 @@ int rs_features_components(const int32_t* labels, int32_t* slotmap, int32_t* raw
 int rs_features_edges(const int32_t* labels, const int32_t* table, long rows, uint8_t* keep, int32_t* edges, long capacity,
                       int32_t* counter, int B, int H, int W, rs_stream_t stream);
 
+/* ---- stitched form: every tile of a call is part of one sparse raster (`rs features --stitch`) ----
+ * A call holds T tiles of equal H x W in slot order (the host sorts them by z, x, y); tile (x, y) covers mosaic pixels
+ * [x*W, (x+1)*W) x [y*H, (y+1)*H), and every pixel no present tile covers is "not the class" for every stage.  Two host tables
+ * describe the layout: nbr int32 [T][8], the slot of the neighbour to the NW, N, NE, W, E, SW, S, SE or -1 (an entry outside
+ * 0..T-1 reads as -1); origin int32 [T][2], the tile's (X, Y) offset in mosaic pixels from the call's smallest x and y.  The
+ * stages then give what the per-tile stages above give on that one large raster:
+ *
+ * halo (crop = 0): dst [T][H+2A][W+2A] = the tile with an apron of A pixels taken from its 8 neighbours, `fill` (0..255, a byte that
+ * is not the class) where a neighbour is absent; run the unchanged clean on it as T tiles of (H+2A) x (W+2A), then
+ * halo (crop = 1): dst [T][H][W] = the centres of src [T][H+2A][W+2A] (nbr may be NULL).  A = eps_open + eps_close (an eps of 0 or 1
+ * counting 0) is enough: an erode or dilate with disc(eps) reads at most eps/2 pixels away, so open then close reads at most
+ * 2*(eps_open/2) + 2*(eps_close/2) <= A pixels away, and the clean's "outside the tile = 1" rule, which is wrong only at the
+ * padded border, spoils apron pixels only.  RS_EINVAL for A > min(H, W) (one step in nbr must reach the whole apron), for H+2A or
+ * W+2A above 4096 and for T*(H+2A)*(W+2A) >= 2^29.
+ *
+ * stitch_labels: labels [T][H][W] as the per-tile labeller left them -> in place, the labels of the large raster in the global
+ * index space g = slot*H*W + y*W + x: components are joined across every right and down seam whose two tiles are present (never
+ * across a corner), and every pixel gets 1 + min(g) over its whole component: canonical, whatever order the device worked in.
+ * Same union-find as the labeller (lock-free, no workgroup waits, loops bounded by T*H*W, *err as there).
+ *
+ * components_stitched: rows [label, area, X0, Y0, X1, Y1], the area of the whole component against min_area, the box in mosaic
+ * pixels (inclusive); counters, capacity and scratch as in the per-tile call (slotmap int32 [T][H][W], raw [capacity][6],
+ * table [capacity][6]).
+ *
+ * edges_stitched: rows [label, X, Y, dir] in mosaic pixels of the components listed in `table` (rows of 6 as above).  The
+ * 4-neighbour across a seam is the facing pixel of the neighbour tile; an absent tile counts as outside; two pixels of one
+ * component either side of a seam emit nothing.  counter, capacity and keep as in the per-tile call. */
+int rs_features_halo(const uint8_t* src, uint8_t* dst, const int32_t* nbr, int T, int H, int W, int A, int fill, int crop,
+                     rs_stream_t stream);
+int rs_features_stitch_labels(int32_t* labels, const int32_t* nbr, int32_t* err, int T, int H, int W, rs_stream_t stream);
+int rs_features_components_stitched(const int32_t* labels, const int32_t* origin, int32_t* slotmap, int32_t* raw, int32_t* table,
+                                    int32_t* counters, long capacity, int T, int H, int W, int min_area, rs_stream_t stream);
+int rs_features_edges_stitched(const int32_t* labels, const int32_t* nbr, const int32_t* origin, const int32_t* table, long rows,
+                               uint8_t* keep, int32_t* edges, long capacity, int32_t* counter, int T, int H, int W,
+                               rs_stream_t stream);
+
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,10 @@ SIGNATURES = {
     "rs_features_label": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "rs_features_components": (c_int, [P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
     "rs_features_edges": (c_int, [P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),
+    "rs_features_halo": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "rs_features_stitch_labels": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "rs_features_components_stitched": (c_int, [P, P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
+    "rs_features_edges_stitched": (c_int, [P, P, P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),
 }
 
 _lib = None

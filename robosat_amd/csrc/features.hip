@@ -10,6 +10,10 @@
 //                           the root of a component is its smallest y*W+x, so label = root + 1 is canonical.
 //   rs_features_components  roots -> slots, area / bounding box per slot by integer atomics, min_area filter, compaction.
 //   rs_features_edges       directed unit boundary edges of the kept components, compacted by one atomic per wave.
+// Stitched form (all tiles of a zoom level as one sparse raster; tables nbr [T][8] and origin [T][2] from the host):
+//   rs_features_halo            tile + apron of A pixels from its 8 neighbours (A = reach of open + close), and the crop back.
+//   rs_features_stitch_labels   per-tile canonical labels -> global index space, unions across right / down seams, flatten.
+//   rs_features_components_stitched / rs_features_edges_stitched   the table and edge kernels with STITCH = true.
 #include "common.h"
 
 namespace {
@@ -248,13 +252,16 @@ __global__ __launch_bounds__(256) void label_flatten_kernel(int* L, int* err, in
 // ---- component table ---------------------------------------------------------------------------------------------------
 // raw rows: [label, area, x0, y0, x1, y1]; table rows: [tile, label, area, x0, y0, x1, y1] (bounding box inclusive).
 // counters[0] = roots found, counters[1] = components kept: both counted past `capacity`, written only below it.
+// STITCH: labels are global (1 + slot*H*W + y*W + x, a root has L[g] == g + 1), boxes in mosaic pixels (origin [B][2] = the
+// tile's x, y offset), table rows [label, area, X0, Y0, X1, Y1].
 
+template <bool STITCH>
 __global__ __launch_bounds__(256) void comp_roots_kernel(const int* __restrict__ L, int* slotmap, int* raw, int* counters, long capacity,
                                                          int B, int H, int W) {
   const long HW = (long)H * W;
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
   if (g >= (long)B * HW) return;
-  const int p = (int)(g % HW);
+  const int p = STITCH ? (int)g : (int)(g % HW);
   if (L[g] != p + 1) return;
   const int slot = atomicAdd(&counters[0], 1);
   slotmap[g] = slot;
@@ -262,8 +269,8 @@ __global__ __launch_bounds__(256) void comp_roots_kernel(const int* __restrict__
     int* r = raw + (long)slot * 6;
     r[0] = p + 1;
     r[1] = 0;
-    r[2] = W;
-    r[3] = H;
+    r[2] = STITCH ? 0x7fffffff : W;
+    r[3] = STITCH ? 0x7fffffff : H;
     r[4] = -1;
     r[5] = -1;
   }
@@ -272,8 +279,9 @@ __global__ __launch_bounds__(256) void comp_roots_kernel(const int* __restrict__
 // One set of atomics per horizontal run of a label inside a wave's 64 consecutive pixels, not per pixel (a blob's pixels all hit the six
 // ints of one row: per pixel that serialised to 1.4 ms for a 512 x 512 x 16 batch).  A lane heads a run where the lane before it
 // (__shfl_up) is another label, another row or another wave; the run ends at the next head or background lane (one ballot).
+template <bool STITCH>
 __global__ __launch_bounds__(256) void comp_stats_kernel(const int* __restrict__ L, const int* __restrict__ slotmap, int* raw,
-                                                         long capacity, int B, int H, int W) {
+                                                         long capacity, int B, int H, int W, const int* __restrict__ origin) {
   const long HW = (long)H * W;
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -288,23 +296,25 @@ __global__ __launch_bounds__(256) void comp_stats_kernel(const int* __restrict__
   if (!head) return;
   const unsigned long long above = lane == 63 ? 0ull : ends & ~((2ull << lane) - 1ull);
   const int len = (above ? __ffsll((long long)above) - 1 : 64) - lane;  // the run stays in this row: x == 0 is a head
-  const int slot = slotmap[tile * HW + lab - 1];
+  const int slot = slotmap[(STITCH ? 0 : tile * HW) + lab - 1];
   if (slot >= capacity) return;
   int* r = raw + (long)slot * 6;
+  const int X = STITCH ? x + origin[tile * 2] : x, Y = STITCH ? y + origin[tile * 2 + 1] : y;
   atomicAdd(&r[1], len);
-  atomicMin(&r[2], x);
-  atomicMin(&r[3], y);
-  atomicMax(&r[4], x + len - 1);
-  atomicMax(&r[5], y);
+  atomicMin(&r[2], X);
+  atomicMin(&r[3], Y);
+  atomicMax(&r[4], X + len - 1);
+  atomicMax(&r[5], Y);
 }
 
+template <bool STITCH>
 __global__ __launch_bounds__(256) void comp_filter_kernel(const int* __restrict__ L, const int* __restrict__ slotmap,
                                                           const int* __restrict__ raw, int* table, int* counters, long capacity, int B,
                                                           int H, int W, int min_area) {
   const long HW = (long)H * W;
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
   if (g >= (long)B * HW) return;
-  const int p = (int)(g % HW);
+  const int p = STITCH ? (int)g : (int)(g % HW);
   if (L[g] != p + 1) return;
   const int slot = slotmap[g];
   if (slot >= capacity) return;
@@ -312,24 +322,41 @@ __global__ __launch_bounds__(256) void comp_filter_kernel(const int* __restrict_
   if (r[1] < min_area) return;
   const int k = atomicAdd(&counters[1], 1);
   if (k >= capacity) return;
-  int* t = table + (long)k * 7;
-  t[0] = (int)(g / HW);
+  int* t = table + (long)k * (STITCH ? 6 : 7);
+  if (!STITCH) t[0] = (int)(g / HW);
 #pragma unroll
-  for (int j = 0; j < 6; ++j) t[1 + j] = r[j];
+  for (int j = 0; j < 6; ++j) t[(STITCH ? 0 : 1) + j] = r[j];
 }
 
 // ---- boundary edges ------------------------------------------------------------------------------------------------------
+template <bool STITCH>
 __global__ __launch_bounds__(256) void edges_mark_kernel(const int* __restrict__ table, long rows, uint8_t* keep, int B, long HW) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= rows) return;
+  if (STITCH) {
+    const int lab = table[i * 6];
+    if (lab >= 1 && lab <= B * HW) keep[lab - 1] = 1;
+    return;
+  }
   const int tile = table[i * 7], lab = table[i * 7 + 1];
   if (tile >= 0 && tile < B && lab >= 1 && lab <= HW) keep[(long)tile * HW + lab - 1] = 1;
 }
 
+// Slot of the tile at (dx, dy) from `tile` in the neighbour table (order NW N NE W E SW S SE), -1 where absent (or out of range).
+__device__ __forceinline__ int nbr_slot(const int* __restrict__ nbr, int tile, int dx, int dy, int T) {
+  const int k = (dy + 1) * 3 + (dx + 1);
+  const int n = nbr[(long)tile * 8 + (k > 4 ? k - 1 : k)];
+  return n >= 0 && n < T ? n : -1;
+}
+
 // Walking round the pixel with the pixel on the right: 0 top (x,y)->(x+1,y), 1 right, 2 bottom, 3 left.  Rows [tile, label, x, y, dir].
 // *counter counts every edge; rows are written only below `capacity` (a first call with capacity 0 sizes the list).
+// STITCH: global labels; the 4-neighbour across a seam is the facing pixel of the neighbour tile (absent = outside); rows
+// [label, X, Y, dir] in mosaic pixels.
+template <bool STITCH>
 __global__ __launch_bounds__(256) void edges_emit_kernel(const int* __restrict__ L, const uint8_t* __restrict__ keep, int* edges,
-                                                         long capacity, unsigned int* counter, int B, int H, int W) {
+                                                         long capacity, unsigned int* counter, int B, int H, int W,
+                                                         const int* __restrict__ nbr, const int* __restrict__ origin) {
   const long HW = (long)H * W;
   const long g = (long)blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
@@ -339,13 +366,29 @@ __global__ __launch_bounds__(256) void edges_emit_kernel(const int* __restrict__
     tile = (int)(g / HW);
     const int p = (int)(g - (long)tile * HW);
     lab = L[g];
-    if (lab && keep[(long)tile * HW + lab - 1]) {
+    if (lab && keep[(STITCH ? 0 : (long)tile * HW) + lab - 1]) {
       y = p / W;
       x = p - y * W;
-      if (y == 0 || L[g - W] != lab) dirs |= 1u;
-      if (x == W - 1 || L[g + 1] != lab) dirs |= 2u;
-      if (y == H - 1 || L[g + W] != lab) dirs |= 4u;
-      if (x == 0 || L[g - 1] != lab) dirs |= 8u;
+      if (STITCH) {
+        // (label across the seam: the facing pixel of the neighbour tile, 0 where there is none)
+        int up = 0, right = 0, down = 0, left = 0, n;
+        if (y > 0) up = L[g - W];
+        else if ((n = nbr_slot(nbr, tile, 0, -1, B)) >= 0) up = L[(long)n * HW + (long)(H - 1) * W + x];
+        if (x < W - 1) right = L[g + 1];
+        else if ((n = nbr_slot(nbr, tile, 1, 0, B)) >= 0) right = L[(long)n * HW + (long)y * W];
+        if (y < H - 1) down = L[g + W];
+        else if ((n = nbr_slot(nbr, tile, 0, 1, B)) >= 0) down = L[(long)n * HW + x];
+        if (x > 0) left = L[g - 1];
+        else if ((n = nbr_slot(nbr, tile, -1, 0, B)) >= 0) left = L[(long)n * HW + (long)y * W + W - 1];
+        dirs = (up != lab ? 1u : 0u) | (right != lab ? 2u : 0u) | (down != lab ? 4u : 0u) | (left != lab ? 8u : 0u);
+        x += origin[tile * 2];
+        y += origin[tile * 2 + 1];
+      } else {
+        if (y == 0 || L[g - W] != lab) dirs |= 1u;
+        if (x == W - 1 || L[g + 1] != lab) dirs |= 2u;
+        if (y == H - 1 || L[g + W] != lab) dirs |= 4u;
+        if (x == 0 || L[g - 1] != lab) dirs |= 8u;
+      }
     }
   }
   const int n = __popc(dirs);
@@ -364,19 +407,87 @@ __global__ __launch_bounds__(256) void edges_emit_kernel(const int* __restrict__
   for (int d = 0; d < 4; ++d)
     if (dirs & (1u << d)) {
       if (k < capacity) {
-        int* e = edges + k * 5;
-        e[0] = tile;
-        e[1] = lab;
-        e[2] = x;
-        e[3] = y;
-        e[4] = d;
+        int* e = edges + k * (STITCH ? 4 : 5);
+        if (!STITCH) *e++ = tile;
+        e[0] = lab;
+        e[1] = x;
+        e[2] = y;
+        e[3] = d;
       }
       ++k;
     }
 }
 
+// ---- stitching: all tiles of a call as one sparse raster ------------------------------------------------------------------
+// GATHER: dst [T][H+2A][W+2A] = the tile with an apron of A pixels from its 8 neighbours (`fill` where there is none);
+// !GATHER (crop): dst [T][H][W] = the centre of src [T][H+2A][W+2A].  A <= min(H, W): one step in the table reaches every apron pixel.
+template <bool GATHER>
+__global__ __launch_bounds__(256) void halo_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const int* __restrict__ nbr,
+                                                   int T, int H, int W, int A, int fill) {
+  const int Hp = H + 2 * A, Wp = W + 2 * A;
+  const long HW = (long)H * W, HWp = (long)Hp * Wp;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)T * (GATHER ? HWp : HW)) return;
+  if (!GATHER) {
+    const long tile = g / HW;
+    const int p = (int)(g - tile * HW);
+    const int y = p / W, x = p - y * W;
+    dst[g] = src[tile * HWp + (long)(y + A) * Wp + x + A];
+    return;
+  }
+  const int tile = (int)(g / HWp);
+  const int p = (int)(g - (long)tile * HWp);
+  int y = p / Wp - A, x = p % Wp - A;
+  const int dy = y < 0 ? -1 : y >= H ? 1 : 0, dx = x < 0 ? -1 : x >= W ? 1 : 0;
+  const int from = (dx | dy) ? nbr_slot(nbr, tile, dx, dy, T) : tile;
+  y -= dy * H;
+  x -= dx * W;
+  dst[g] = from >= 0 ? src[(long)from * HW + (long)y * W + x] : (uint8_t)fill;
+}
+
+// Per-tile canonical labels (1 + y*W + x of the tile's root) -> parents in the global index space slot*H*W + y*W + x: still a forest
+// whose links only decrease, now bounded by P = T*H*W, for the same uf_find / uf_union.
+__global__ __launch_bounds__(256) void stitch_global_kernel(int* L, long P, long HW) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= P) return;
+  const int l = L[g];
+  if (l) L[g] = (int)(g / HW * HW) + l;
+}
+
+// One thread per seam pixel: item < H the right seam (x = W-1 against the E tile's x = 0), else the down seam (y = H-1 against the S
+// tile's y = 0).  A pair whose predecessor along the seam is set on both sides too is already joined through it on either side.
+__global__ __launch_bounds__(256) void stitch_seam_kernel(int* L, const int* __restrict__ nbr, int* err, int T, int H, int W) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= (long)T * (H + W)) return;
+  const int tile = (int)(g / (H + W));
+  const int item = (int)(g - (long)tile * (H + W));
+  const bool right = item < H;
+  const int n = right ? nbr_slot(nbr, tile, 1, 0, T) : nbr_slot(nbr, tile, 0, 1, T);
+  if (n < 0) return;
+  const int i = right ? item : item - H;
+  const long step = right ? W : 1;
+  const long a = tile * HW + (right ? (long)i * W + W - 1 : (long)(H - 1) * W + i);
+  const long b = n * HW + (right ? (long)i * W : (long)i);
+  if (!L[a] || !L[b]) return;  // (a label is 0 or positive throughout: concurrent unions never change which)
+  if (i > 0 && L[a - step] && L[b - step]) return;
+  uf_union(L, (int)a, (int)b, (int)(T * HW), err);
+}
+
+__global__ __launch_bounds__(256) void stitch_flatten_kernel(int* L, int* err, long P) {
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= P) return;
+  if (L[g] == 0) return;
+  const int root = uf_find(L, (int)g, (int)P, err);
+  atomicMin(&L[g], root + 1);
+}
+
 // (B rides in gridDim.y; 4 edges per pixel at the very most stay below 2^31 in the int32 edge counter)
 bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)B * H * W < (1l << 29); }
+
+bool halo_ok(int T, int H, int W, int A) {
+  return A >= 0 && H > 0 && W > 0 && A <= (H < W ? H : W) && shape_ok(T, H, W) && shape_ok(T, H + 2 * A, W + 2 * A);
+}
 
 }  // namespace
 
@@ -452,9 +563,9 @@ extern "C" int rs_features_components(const int32_t* labels, int32_t* slotmap, i
   const int grid = rs_cdiv(P, 256);
   const hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), s);
   if (e != hipSuccess) return (int)e;
-  comp_roots_kernel<<<grid, 256, 0, s>>>(labels, slotmap, raw, counters, capacity, B, H, W);
-  comp_stats_kernel<<<grid, 256, 0, s>>>(labels, slotmap, raw, capacity, B, H, W);
-  comp_filter_kernel<<<grid, 256, 0, s>>>(labels, slotmap, raw, table, counters, capacity, B, H, W, min_area);
+  comp_roots_kernel<false><<<grid, 256, 0, s>>>(labels, slotmap, raw, counters, capacity, B, H, W);
+  comp_stats_kernel<false><<<grid, 256, 0, s>>>(labels, slotmap, raw, capacity, B, H, W, nullptr);
+  comp_filter_kernel<false><<<grid, 256, 0, s>>>(labels, slotmap, raw, table, counters, capacity, B, H, W, min_area);
   return RS_LAUNCH_RESULT();
 }
 
@@ -467,7 +578,61 @@ extern "C" int rs_features_edges(const int32_t* labels, const int32_t* table, lo
   hipError_t e = hipMemsetAsync(keep, 0, P, s);
   if (e == hipSuccess) e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
   if (e != hipSuccess) return (int)e;
-  if (rows > 0) edges_mark_kernel<<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, B, (long)H * W);
-  edges_emit_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(labels, keep, edges, capacity, reinterpret_cast<unsigned int*>(counter), B, H, W);
+  if (rows > 0) edges_mark_kernel<false><<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, B, (long)H * W);
+  edges_emit_kernel<false><<<rs_cdiv(P, 256), 256, 0, s>>>(labels, keep, edges, capacity, reinterpret_cast<unsigned int*>(counter), B, H, W,
+                                                            nullptr, nullptr);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_halo(const uint8_t* src, uint8_t* dst, const int32_t* nbr, int T, int H, int W, int A, int fill, int crop,
+                                rs_stream_t stream) {
+  if (!src || !dst || (!crop && !nbr) || !halo_ok(T, H, W, A) || fill < 0 || fill > 255) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  if (crop)
+    halo_kernel<false><<<rs_cdiv((long)T * H * W, 256), 256, 0, s>>>(src, dst, nbr, T, H, W, A, fill);
+  else
+    halo_kernel<true><<<rs_cdiv((long)T * (H + 2 * A) * (W + 2 * A), 256), 256, 0, s>>>(src, dst, nbr, T, H, W, A, fill);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_stitch_labels(int32_t* labels, const int32_t* nbr, int32_t* err, int T, int H, int W, rs_stream_t stream) {
+  if (!labels || !nbr || !err || !shape_ok(T, H, W)) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)T * H * W;
+  stitch_global_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(labels, P, (long)H * W);
+  stitch_seam_kernel<<<rs_cdiv((long)T * (H + W), 256), 256, 0, s>>>(labels, nbr, err, T, H, W);
+  stitch_flatten_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(labels, err, P);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_components_stitched(const int32_t* labels, const int32_t* origin, int32_t* slotmap, int32_t* raw, int32_t* table,
+                                               int32_t* counters, long capacity, int T, int H, int W, int min_area, rs_stream_t stream) {
+  if (!labels || !origin || !slotmap || !counters || capacity < 0 || (capacity > 0 && (!raw || !table)) || !shape_ok(T, H, W))
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)T * H * W;
+  const int grid = rs_cdiv(P, 256);
+  const hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  comp_roots_kernel<true><<<grid, 256, 0, s>>>(labels, slotmap, raw, counters, capacity, T, H, W);
+  comp_stats_kernel<true><<<grid, 256, 0, s>>>(labels, slotmap, raw, capacity, T, H, W, origin);
+  comp_filter_kernel<true><<<grid, 256, 0, s>>>(labels, slotmap, raw, table, counters, capacity, T, H, W, min_area);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_edges_stitched(const int32_t* labels, const int32_t* nbr, const int32_t* origin, const int32_t* table, long rows,
+                                          uint8_t* keep, int32_t* edges, long capacity, int32_t* counter, int T, int H, int W,
+                                          rs_stream_t stream) {
+  if (!labels || !nbr || !origin || !keep || !counter || rows < 0 || (rows > 0 && !table) || capacity < 0 || (capacity > 0 && !edges) ||
+      !shape_ok(T, H, W))
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)T * H * W;
+  hipError_t e = hipMemsetAsync(keep, 0, P, s);
+  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (rows > 0) edges_mark_kernel<true><<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, T, (long)H * W);
+  edges_emit_kernel<true><<<rs_cdiv(P, 256), 256, 0, s>>>(labels, keep, edges, capacity, reinterpret_cast<unsigned int*>(counter), T, H, W,
+                                                           nbr, origin);
   return RS_LAUNCH_RESULT();
 }

@@ -11,7 +11,7 @@ import sys
 
 import numpy as np
 
-from robosat_amd.tiles import pixel_to_location
+from robosat_amd.tiles import Tile, pixel_to_location, tile_bounds
 
 _SX = np.array([0, 1, 1, 0], dtype=np.int64)  # start corner of an edge, relative to its pixel
 _SY = np.array([0, 0, 1, 1], dtype=np.int64)
@@ -33,6 +33,51 @@ def _rotate_to_smallest(ring):
     return np.roll(ring, -start, axis=0)
 
 
+def _link(group, x, y, d, bits, turns):
+    """The linking itself: edges (pixel x, y, dir d) of int64 ``group`` ids, vertices below 2^bits -> [(first edge, ring), ...] in
+    the order of the sort key (group, y, x, dir) of each ring's smallest edge; ``(group << 2 * bits + 2)`` must fit an int64."""
+
+    n = len(group)
+    sx, sy = x + _SX[d], y + _SY[d]
+    ex, ey = sx + _DX[d], sy + _DY[d]
+
+    def key(g, vx, vy, direction):
+        return ((g << 2 * bits | vy << bits | vx) << 2) | direction
+
+    out_key = key(group, sx, sy, d)
+    order = np.argsort(out_key, kind="stable")
+    sorted_keys = out_key[order]
+    assert n == 1 or (np.diff(sorted_keys) > 0).all(), "duplicate edges"
+    nxt = np.full(n, -1, dtype=np.int64)
+    for turn in turns:  # left, straight, right
+        want = key(group, ex, ey, (d + turn) & 3)
+        pos = np.minimum(np.searchsorted(sorted_keys, want), n - 1)
+        hit = (sorted_keys[pos] == want) & (nxt < 0)
+        nxt[hit] = order[pos[hit]]
+    assert (nxt >= 0).all(), "an edge without a successor: the edge list is not the boundary of a label image"
+
+    nxt_l, order_l = nxt.tolist(), order.tolist()
+    seen = bytearray(n)
+    rings = []
+    for start in order_l:
+        if seen[start]:
+            continue
+        idx = []
+        cur = start
+        while not seen[cur]:
+            seen[cur] = 1
+            idx.append(cur)
+            cur = nxt_l[cur]
+        assert cur == start, "edges do not close into a ring"
+        idx = np.array(idx)
+        rings.append((start, _rotate_to_smallest(np.stack([sx[idx], sy[idx]], axis=1))))
+    return rings
+
+
+def _ring_order(ring):
+    return signed_area(ring) < 0, int(ring[0, 0]), int(ring[0, 1])
+
+
 def link_rings(edges, turns=(3, 0, 1)):
     """Edge rows int [E, 5] in any order -> ``{(tile, label): [ring, ...]}``; a ring is an int64 array [k, 2] of unit-step
     vertices, not closed, started at its lexicographically smallest (x, y); the component's outer ring first, then its holes
@@ -50,43 +95,46 @@ def link_rings(edges, turns=(3, 0, 1)):
     tile, label, x, y, d = e.T
     assert tile.min() >= 0 and tile.max() < 1024 and label.min() >= 1 and label.max() <= 1 << 24, "tile < 1024, label <= 2^24"
     assert x.min() >= 0 and y.min() >= 0 and max(x.max(), y.max()) < 4096 and d.min() >= 0 and d.max() <= 3
-    sx, sy = x + _SX[d], y + _SY[d]
-    ex, ey = sx + _DX[d], sy + _DY[d]
-    group = tile << 25 | label
-
-    def key(g, vx, vy, direction):
-        return ((g << 26 | vy << 13 | vx) << 2) | direction
-
-    out_key = key(group, sx, sy, d)
-    order = np.argsort(out_key, kind="stable")
-    sorted_keys = out_key[order]
-    assert n == 1 or (np.diff(sorted_keys) > 0).all(), "duplicate edges"
-    nxt = np.full(n, -1, dtype=np.int64)
-    for turn in turns:  # left, straight, right
-        want = key(group, ex, ey, (d + turn) & 3)
-        pos = np.minimum(np.searchsorted(sorted_keys, want), n - 1)
-        hit = (sorted_keys[pos] == want) & (nxt < 0)
-        nxt[hit] = order[pos[hit]]
-    assert (nxt >= 0).all(), "an edge without a successor: the edge list is not the boundary of a label image"
-
-    nxt_l, order_l = nxt.tolist(), order.tolist()
-    seen = bytearray(n)
     rings = {}
-    for start in order_l:
-        if seen[start]:
-            continue
-        idx = []
-        cur = start
-        while not seen[cur]:
-            seen[cur] = 1
-            idx.append(cur)
-            cur = nxt_l[cur]
-        assert cur == start, "edges do not close into a ring"
-        idx = np.array(idx)
-        ring = _rotate_to_smallest(np.stack([sx[idx], sy[idx]], axis=1))
+    for start, ring in _link(tile << 25 | label, x, y, d, 13, turns):
         rings.setdefault((int(tile[start]), int(label[start])), []).append(ring)
-    for key_, group_rings in rings.items():
-        group_rings.sort(key=lambda r: (signed_area(r) < 0, int(r[0, 0]), int(r[0, 1])))
+    for group_rings in rings.values():
+        group_rings.sort(key=_ring_order)
+    return rings
+
+
+MOSAIC_SIDE = 1 << 16  # pixels per side a stitched component may span (17-bit vertex coordinates in the linking key)
+MOSAIC_COMPONENTS = 1 << 27  # components per call (the rest of the 63 key bits)
+
+
+def link_rings_mosaic(edges, turns=(3, 0, 1)):
+    """``link_rings`` for stitched edge rows int [E, 4] = (label, X, Y, dir) in mosaic pixels -> ``{label: [ring, ...]}`` with
+    the rings in mosaic pixels.  Labels (up to 2^29) are ranked densely and every component is linked relative to the corner
+    of its own bounding box, so what must fit the key is a component's extent (at most 2^16 pixels a side, whatever the
+    mosaic's) and the number of components (below 2^27); beyond either: ValueError."""
+
+    e = np.asarray(edges, dtype=np.int64).reshape(-1, 4)
+    if len(e) == 0:
+        return {}
+    label, x, y, d = e.T
+    if label.min() < 1 or x.min() < 0 or y.min() < 0 or d.min() < 0 or d.max() > 3:
+        raise ValueError("edge rows are (label >= 1, X >= 0, Y >= 0, dir 0..3)")
+    labels, rank = np.unique(label, return_inverse=True)
+    rank = rank.reshape(-1).astype(np.int64)
+    if len(labels) >= MOSAIC_COMPONENTS:
+        raise ValueError("{} components in one call: ring linking takes fewer than 2^27".format(len(labels)))
+    x0 = np.full(len(labels), np.iinfo(np.int64).max)
+    y0 = x0.copy()
+    np.minimum.at(x0, rank, x)
+    np.minimum.at(y0, rank, y)
+    rx, ry = x - x0[rank], y - y0[rank]
+    if max(rx.max(), ry.max()) >= MOSAIC_SIDE:
+        raise ValueError("a stitched component spans {} pixels: ring linking takes at most 2^16 a side".format(int(max(rx.max(), ry.max())) + 1))
+    rings = {}
+    for start, ring in _link(rank, rx, ry, d, 17, turns):
+        rings.setdefault(int(label[start]), []).append(ring + np.array([x0[rank[start]], y0[rank[start]]]))
+    for group_rings in rings.values():
+        group_rings.sort(key=_ring_order)
     return rings
 
 
@@ -218,3 +266,131 @@ class FeatureWriter:
         collection = {"type": "FeatureCollection", "features": sorted(self.features, key=by_tile)}
         with open(out, "w") as fp:
             json.dump(collection, fp)
+
+
+# ---- rs features --stitch: the tiles of a zoom level as one sparse raster -------------------------------------------------
+NEIGHBOURS = ((-1, -1), (0, -1), (1, -1), (-1, 0), (1, 0), (-1, 1), (0, 1), (1, 1))  # (dx, dy) of NW N NE W E SW S SE
+CALL_PIXELS = (1 << 29) - 1  # the library takes T*H*W < 2^29 per call
+CALL_TILES = 65535
+
+
+def group_clusters(tiles):
+    """Tiles -> their 8-connected clusters within each zoom level (the halo crosses diagonals): a list of lists of ``Tile``,
+    each sorted by (z, x, y), the clusters ordered by their first tile."""
+
+    todo = {Tile(int(t.x), int(t.y), int(t.z)) for t in tiles}
+    clusters = []
+    for seed in sorted(todo, key=lambda t: (t.z, t.x, t.y)):
+        if seed not in todo:
+            continue
+        todo.discard(seed)
+        cluster, stack = [], [seed]
+        while stack:
+            t = stack.pop()
+            cluster.append(t)
+            for dx, dy in NEIGHBOURS:
+                n = Tile(t.x + dx, t.y + dy, t.z)
+                if n in todo:
+                    todo.discard(n)
+                    stack.append(n)
+        clusters.append(sorted(cluster, key=lambda t: (t.z, t.x, t.y)))
+    return clusters
+
+
+def pack_clusters(clusters, tile_pixels, side=4096, limit=CALL_PIXELS, max_tiles=CALL_TILES):
+    """Whole clusters of one zoom level -> calls (lists of tiles sorted by (z, x, y)), greedily in order, never splitting a
+    cluster: a call holds at most ``limit`` pixels at ``tile_pixels`` per tile (the padded tile where there is an apron), at
+    most ``max_tiles`` tiles, and spans less than 2^31 mosaic pixels (``side`` = the longer tile side).  A single cluster
+    beyond that: ValueError."""
+
+    span = ((1 << 31) - 1) // side
+
+    def fits(tiles):
+        xs, ys = [t.x for t in tiles], [t.y for t in tiles]
+        return (len(tiles) * tile_pixels <= limit and len(tiles) <= max_tiles and max(xs) - min(xs) < span and max(ys) - min(ys) < span
+                and len({t.z for t in tiles}) == 1)
+
+    calls, current = [], []
+    for cluster in clusters:
+        if not fits(cluster):
+            raise ValueError("a cluster of {} connected tiles ({} pixels each) around {}/{}/{} exceeds one device call ({} pixels, {} "
+                             "tiles) and cannot be split".format(len(cluster), tile_pixels, cluster[0].z, cluster[0].x, cluster[0].y, limit,
+                                                                 max_tiles))
+        if current and not fits(current + cluster):
+            calls.append(current)
+            current = []
+        current = current + cluster
+    if current:
+        calls.append(current)
+    return [sorted(call, key=lambda t: (t.z, t.x, t.y)) for call in calls]
+
+
+def stitch_tables(tiles, shape):
+    """The tiles of one call, sorted by (z, x, y) (a tile's slot is its position) -> (nbr int32 [T, 8]: the slot of each
+    neighbour in ``NEIGHBOURS`` order or -1; origin int32 [T, 2]: the tile's (X, Y) in mosaic pixels from the call's smallest x
+    and y; (x_min, y_min) in tiles)."""
+
+    h, w = shape
+    assert list(tiles) == sorted(tiles, key=lambda t: (t.z, t.x, t.y)) and len({t.z for t in tiles}) == 1, "one zoom level, sorted"
+    slot = {(t.x, t.y): i for i, t in enumerate(tiles)}
+    assert len(slot) == len(tiles), "duplicate tiles"
+    x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
+    nbr = np.array([[slot.get((t.x + dx, t.y + dy), -1) for dx, dy in NEIGHBOURS] for t in tiles], dtype=np.int32).reshape(-1, 8)
+    origin = np.array([[(t.x - x_min) * w, (t.y - y_min) * h] for t in tiles], dtype=np.int64).reshape(-1, 2)
+    assert origin.max() + max(h, w) < 1 << 31, "the call spans 2^31 mosaic pixels"
+    return nbr, origin.astype(np.int32), (x_min, y_min)
+
+
+def mosaic_location(z, gx, gy, shape):
+    """``(lon, lat)`` of the pixel corner (gx, gy) of zoom level z's whole raster (gx = tile x * W + pixel x), through the tile it
+    falls in: ``pixel_to_location`` there, except that a corner on the tile's east / south edge takes that edge's own
+    longitude / latitude.  A tile's east edge is computed as its neighbour's west edge is, so a vertex on a seam gets the same
+    floats from either tile."""
+
+    h, w = shape
+    last = (1 << z) - 1
+    tile = Tile(min(gx // w, last), min(gy // h, last), z)
+    return tile_vertex_location(tile, gx - tile.x * w, gy - tile.y * h, shape)
+
+
+def tile_vertex_location(tile, px, py, shape):
+    h, w = shape
+    west, south, east, north = tile_bounds(tile)
+    lon, lat = pixel_to_location(tile, px / w, py / h)
+    return east if px == w else lon, south if py == h else lat
+
+
+def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, georeference=True):
+    """``featurize`` for one stitched call: edge rows (label, X, Y, dir) + table rows (label, area, X0, Y0, X1, Y1) in
+    mosaic pixels, ``tiles`` the call's tiles in slot order.  A feature's ``tile`` is the tile holding its canonical pixel (the
+    one its label names: label - 1 = slot * H * W + y * W + x), ``area_px`` the area of the whole component; features come in
+    label order, which is (slot, label).  ``georeference=False`` leaves the vertices as mosaic pixel corners [X, Y]."""
+
+    h, w = shape
+    x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
+    area = {int(r[0]): int(r[1]) for r in np.asarray(table).reshape(-1, 6)}
+    features = []
+    for label, rings in sorted(link_rings_mosaic(edges).items()):
+        tile = tiles[(label - 1) // (h * w)]
+        outer = simplify_ring(rings[0], simplify)
+        if len(outer) < 3:
+            print("Warning: simplified feature no longer valid polygon, skipping", file=warn)
+            continue
+        kept = [outer] + [r for r in (simplify_ring(hole, simplify) for hole in rings[1:]) if len(r) >= 3]
+        if simplify > 0 and not polygon_is_valid(kept):
+            print("Warning: extracted feature is not valid, skipping", file=warn)
+            continue
+        coordinates = []
+        for ring in kept:
+            ring = ring[::-1]  # y points down in the raster and up on the map
+            if georeference:
+                closed = [list(mosaic_location(tile.z, x_min * w + int(px), y_min * h + int(py), shape)) for px, py in ring]
+            else:
+                closed = [[int(px), int(py)] for px, py in ring]
+            coordinates.append(closed + closed[:1])
+        features.append({
+            "type": "Feature",
+            "geometry": {"type": "Polygon", "coordinates": coordinates},
+            "properties": {"tile": [int(tile.x), int(tile.y), int(tile.z)], "area_px": area[label], "stitched": True},
+        })
+    return features

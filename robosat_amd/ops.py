@@ -1460,3 +1460,121 @@ def boundary_edges(labels, table):
         got = run(edges, n)
         assert got == n, (got, n)
     return edges
+
+
+# ---- rs features --stitch: the tiles of a call as one sparse raster (tables from robosat_amd.features.stitch_tables) ----------
+def halo_apron(eps_open, eps_close):
+    """Apron A of ``gather_halo`` for these discs: the reach of open followed by close (an eps of 0 or 1 is the identity)."""
+
+    return (eps_open if eps_open > 1 else 0) + (eps_close if eps_close > 1 else 0)
+
+
+def _halo(src, nbr, apron, fill, crop):
+    t, hs, ws = src.shape
+    h, w = (hs - 2 * apron, ws - 2 * apron) if crop else (hs, ws)
+    if apron < 0 or h <= 0 or w <= 0 or apron > min(h, w):
+        raise ValueError("robosat_amd: an apron of {} does not fit tiles of {}x{} (at most min(H, W))".format(apron, h, w))
+    out = torch.empty((t, h, w) if crop else (t, h + 2 * apron, w + 2 * apron), device=src.device, dtype=torch.uint8)
+    _call("rs_features_halo", _dev(src, "src", torch.uint8), _dev(out, "out", torch.uint8), _dev(nbr, "nbr", torch.int32), t, h, w, apron,
+          fill, int(crop), _stream())
+    return out
+
+
+def gather_halo(images_u8, nbr, apron, fill=0):
+    """uint8 [T, H, W] tiles + int32 [T, 8] neighbour slots -> uint8 [T, H + 2A, W + 2A]: every tile with an apron of A pixels
+    from its 8 neighbours, ``fill`` where there is none."""
+
+    assert nbr.shape == (images_u8.shape[0], 8), "nbr is [T, 8]"
+    return _halo(images_u8, nbr, apron, fill, False)
+
+
+def crop_halo(padded_u8, apron):
+    """uint8 [T, H + 2A, W + 2A] -> the centres, uint8 [T, H, W]."""
+
+    return _halo(padded_u8, None, apron, 0, True)
+
+
+def clean_masks_stitched(images_u8, nbr, index, eps_open, eps_close):
+    """``clean_masks`` of the one raster the tiles form: gather the apron, clean the padded tiles, crop."""
+
+    apron = halo_apron(eps_open, eps_close)
+    if apron == 0:
+        return clean_masks(images_u8, index, eps_open, eps_close)
+    padded = gather_halo(images_u8, nbr, apron, fill=255 if index == 0 else 0)  # (a byte that is not the class)
+    return crop_halo(clean_masks(padded, index, eps_open, eps_close), apron)
+
+
+def stitch_labels(labels, nbr, inplace=False):
+    """Per-tile canonical labels int32 [T, H, W] (``label_components``) -> the labels of the whole raster (a new tensor unless
+    ``inplace``): components joined across the seams of present 4-neighbour tiles, label = 1 + min(slot * H * W + y * W + x)."""
+
+    t, h, w = labels.shape
+    assert nbr.shape == (t, 8), "nbr is [T, 8]"
+    out = labels if inplace else labels.clone()
+    err = torch.zeros(1, device=labels.device, dtype=torch.int32)
+    _call("rs_features_stitch_labels", _dev(out, "labels", torch.int32), _dev(nbr, "nbr", torch.int32), _dev(err, "err", torch.int32), t, h,
+          w, _stream())
+    if int(err.item()):
+        raise RuntimeError("rs_features_stitch_labels: a union-find loop ran out of its T*H*W bound (code {})".format(int(err.item())))
+    return out
+
+
+def component_table_stitched(labels, origin, min_area=0):
+    """Stitched labels int32 [T, H, W] + int32 [T, 2] tile origins -> int32 [N, 6] rows (label, area, X0, Y0, X1, Y1) in mosaic
+    pixels of the components whose whole area is >= min_area, sorted by label."""
+
+    t, h, w = labels.shape
+    assert origin.shape == (t, 2), "origin is [T, 2]"
+    dev = labels.device
+    slotmap = torch.empty((t, h, w), device=dev, dtype=torch.int32)
+    counters = torch.empty(2, device=dev, dtype=torch.int32)
+    capacity = 1 << 16
+    for _ in range(2):  # (the second pass has the exact capacity)
+        raw = torch.empty((capacity, 6), device=dev, dtype=torch.int32)
+        table = torch.empty((capacity, 6), device=dev, dtype=torch.int32)
+        _call("rs_features_components_stitched", _dev(labels, "labels", torch.int32), _dev(origin, "origin", torch.int32),
+              _dev(slotmap, "slotmap", torch.int32), _dev(raw, "raw", torch.int32), _dev(table, "table", torch.int32),
+              _dev(counters, "counters", torch.int32), capacity, t, h, w, int(min_area), _stream())
+        found, kept = counters.tolist()
+        if found <= capacity:
+            break
+        capacity = found
+    else:
+        raise RuntimeError("rs_features_components_stitched: {} components do not fit a table of {}".format(found, capacity))
+    table = table[:kept]
+    return table[torch.argsort(table[:, 0])].contiguous()
+
+
+def boundary_edges_stitched(labels, nbr, origin, table):
+    """Directed unit boundary edges of the components in ``table`` (``component_table_stitched``): int32 [E, 4] rows
+    (label, X, Y, dir) in mosaic pixels, in the order the device wrote them."""
+
+    t, h, w = labels.shape
+    assert nbr.shape == (t, 8) and origin.shape == (t, 2)
+    dev = labels.device
+    keep = torch.empty(t * h * w, device=dev, dtype=torch.uint8)
+    counter = torch.empty(1, device=dev, dtype=torch.int32)
+    table = table.contiguous()
+
+    def run(edges, capacity):
+        _call("rs_features_edges_stitched", _dev(labels, "labels", torch.int32), _dev(nbr, "nbr", torch.int32),
+              _dev(origin, "origin", torch.int32), _dev(table, "table", torch.int32) if len(table) else None, len(table),
+              _dev(keep, "keep", torch.uint8), _dev(edges, "edges", torch.int32), capacity, _dev(counter, "counter", torch.int32), t, h, w,
+              _stream())
+        return int(counter.item())
+
+    n = run(None, 0)
+    edges = torch.empty((n, 4), device=dev, dtype=torch.int32)
+    if n:
+        got = run(edges, n)
+        assert got == n, (got, n)
+    return edges
+
+
+def stitched_features(images_u8, nbr, origin, index, eps_open, eps_close, min_area=0):
+    """Every raster stage of ``rs features --stitch`` for one call: class-index tiles uint8 [T, H, W] with their neighbour and
+    origin tables -> (table int32 [N, 6], edges int32 [E, 4]) of the whole raster."""
+
+    labels = stitch_labels(label_components(clean_masks_stitched(images_u8, nbr, index, eps_open, eps_close)), nbr, inplace=True)
+    table = component_table_stitched(labels, origin, min_area)
+    return table, boundary_edges_stitched(labels, nbr, origin, table)

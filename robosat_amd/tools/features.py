@@ -2,6 +2,7 @@
 reference's arguments (``robosat/tools/features.py``) with its handler's thresholds as flags.  Class select, morphological
 open / close, connected components and boundary extraction run on the MI355X (``csrc/features.hip``); only the boundary
 edges come back to the host, which links them into rings, simplifies and georeferences them (``robosat_amd/features.py``).
+``--stitch`` treats the tiles of a zoom level as one sparse raster, so an object that crosses tile borders is one polygon.
 The stage definitions, and where they depart from OpenCV's, are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
@@ -14,7 +15,7 @@ from tqdm import tqdm
 
 from robosat_amd import ops
 from robosat_amd.config import load_config
-from robosat_amd.features import FeatureWriter, featurize
+from robosat_amd.features import FeatureWriter, featurize, featurize_stitched, group_clusters, pack_clusters, stitch_tables
 from robosat_amd.tiles import tiles_from_slippy_map
 
 
@@ -33,7 +34,43 @@ def add_parser(subparser):
     parser.add_argument("--simplify", type=float, default=0.01, help="Douglas-Peucker epsilon as a share of a ring's perimeter")
     parser.add_argument("--min_area", type=int, default=0, help="components with fewer pixels are dropped")
     parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
+    parser.add_argument("--stitch", action="store_true", help="treat the tiles of a zoom level as one raster: whole polygons across tile borders")
     parser.set_defaults(func=main)
+
+
+def _load(paths, device):
+    return torch.from_numpy(np.stack([np.array(Image.open(path).convert("P"), dtype=np.uint8) for path in paths])).to(device)
+
+
+def stitched(items, index, args, device, writer):
+    """``--stitch``: per zoom level, the 8-connected clusters of tiles packed whole into device calls."""
+
+    by_zoom = {}
+    for tile, path, shape in items:
+        by_zoom.setdefault(tile.z, []).append((tile, path, shape))
+    apron = ops.halo_apron(args.denoise, args.grow)
+    for z, group in sorted(by_zoom.items()):
+        shapes = sorted({shape for _, _, shape in group})
+        if len(shapes) > 1:
+            sys.exit("Error: --stitch needs tiles of one size per zoom level; zoom {} has {}".format(
+                z, ", ".join("{}x{}".format(h, w) for h, w in shapes)))
+        h, w = shape = shapes[0]
+        if apron > min(h, w) or max(h, w) + 2 * apron > 4096:
+            sys.exit("Error: --denoise {} + --grow {} need a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
+                     .format(args.denoise, args.grow, apron, h, w, min(h, w, (4096 - max(h, w)) // 2)))
+        paths = {tile: path for tile, path, _ in group}
+        try:
+            calls = pack_clusters(group_clusters(paths), (h + 2 * apron) * (w + 2 * apron), side=max(h, w))
+        except ValueError as exc:
+            sys.exit("Error: {}".format(exc))
+        for tiles in tqdm(calls, desc="Features z{} {}x{}".format(z, h, w), unit="call", ascii=True):
+            nbr, origin, _ = stitch_tables(tiles, shape)
+            table, edges = ops.stitched_features(_load([paths[t] for t in tiles], device), torch.from_numpy(nbr).to(device),
+                                                 torch.from_numpy(origin).to(device), index, args.denoise, args.grow, args.min_area)
+            try:
+                writer.add(featurize_stitched(edges.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify))
+            except ValueError as exc:
+                sys.exit("Error: {}".format(exc))
 
 
 def main(args):
@@ -57,12 +94,15 @@ def main(args):
         by_shape.setdefault((height, width), []).append((tile, path))
 
     writer = FeatureWriter()
+    if args.stitch:
+        stitched([(tile, path, shape) for shape, items in by_shape.items() for tile, path in items], index, args, device, writer)
+        by_shape = {}
     for shape, items in by_shape.items():  # tiles of one batch share a shape
         # (the library takes B*H*W < 2^29 per call, link_rings fewer than 1024 tiles)
         batch = max(1, min(args.batch_size, 1023, ((1 << 29) - 1) // (shape[0] * shape[1])))
         for start in tqdm(range(0, len(items), batch), desc="Features {}x{}".format(*shape), unit="batch", ascii=True):
             group = items[start:start + batch]
-            images = torch.from_numpy(np.stack([np.array(Image.open(path).convert("P"), dtype=np.uint8) for _, path in group])).to(device)
+            images = _load([path for _, path in group], device)
             labels = ops.label_components(ops.clean_masks(images, index, args.denoise, args.grow))
             table = ops.component_table(labels, args.min_area)
             edges = ops.boundary_edges(labels, table)

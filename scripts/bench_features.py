@@ -9,6 +9,10 @@
   forms    the morphology kernel's LDS-resident form against its through-HBM form
   cli      `./rs features` from PNGs on disk, with the host share (PNG decode, ring linking, JSON)
 
+  --stitch-leg   `rs features --stitch` against the per-tile path on one dataset, a dense 8 x 8 block of 512 x 512 tiles cut from one
+           blob raster (objects cross the seams): per stage and whole, written to profiles/features_stitch/bench_stitch.json
+           (`--stitch-leg --stage-loop N` only runs the stitched stages N times, for rocprofv3)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -24,6 +28,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "features", "bench_features.json")
 
 
 def blob_masks(batch, size, seed):
@@ -62,6 +67,98 @@ def spiral_mask(n):
             dy, dx = dx, -dy
         else:
             return m
+
+
+def block_tiles(n, size, seed):
+    """One (n * size)^2 class-index raster of ellipses of class 1 (about a tenth of it, the size of `blob_masks`' so many
+    cross a seam) with a little salt and pepper, cut into n x n tiles in slot order (x, then y)."""
+
+    rng = np.random.RandomState(seed)
+    side = n * size
+    image = np.zeros((side, side), dtype=np.uint8)
+    for _ in range(6 * n * n):
+        cy, cx = rng.randint(0, side, 2)
+        ry, rx = rng.randint(size // 16, size // 8, 2)
+        y0, y1, x0, x1 = max(cy - ry, 0), min(cy + ry + 1, side), max(cx - rx, 0), min(cx + rx + 1, side)
+        yy, xx = np.mgrid[y0:y1, x0:x1]
+        image[y0:y1, x0:x1][((yy - cy) / ry) ** 2 + ((xx - cx) / rx) ** 2 <= 1] = 1
+    image ^= (rng.rand(side, side) < 0.01).astype(np.uint8)
+    return np.stack([image[y * size:(y + 1) * size, x * size:(x + 1) * size] for x in range(n) for y in range(n)])
+
+
+def stitch_leg(args):
+    """The stitched path against the per-tile path on the same n x n block, stage by stage (device time by host clock around a
+    synchronize, as the other legs)."""
+
+    import torch
+
+    from robosat_amd import ops
+    from robosat_amd.features import stitch_tables
+    from robosat_amd.tiles import Tile
+
+    n, size, eps = args.block, args.size, args.eps
+    tiles = block_tiles(n, size, 0)
+    nbr, origin, _ = stitch_tables([Tile(x, y, 18) for x in range(n) for y in range(n)], (size, size))
+    dev, nbr, origin = torch.from_numpy(tiles).to("cuda:0"), torch.from_numpy(nbr).to("cuda:0"), torch.from_numpy(origin).to("cuda:0")
+    apron = ops.halo_apron(eps, eps)
+
+    def stitched():
+        table, edges = ops.stitched_features(dev, nbr, origin, 1, eps, eps, 0)
+        return table, edges.cpu()
+
+    def per_tile():
+        out = []
+        for start in range(0, len(tiles), args.batch):
+            labels = ops.label_components(ops.clean_masks(dev[start:start + args.batch], 1, eps, eps))
+            table = ops.component_table(labels, 0)
+            out.append((table, ops.boundary_edges(labels, table).cpu()))
+        return out
+
+    if args.stage_loop:
+        for _ in range(args.stage_loop):
+            stitched()
+        return
+
+    table, edges = stitched()
+    parts = per_tile()
+    padded = ops.gather_halo(dev, nbr, apron)
+    cleaned_padded = ops.clean_masks(padded, 1, eps, eps)
+    cleaned = ops.crop_halo(cleaned_padded, apron)
+    local = ops.label_components(cleaned)
+    labels = ops.stitch_labels(local, nbr)
+    alone = ops.clean_masks(dev, 1, eps, eps)
+    alone_labels = ops.label_components(alone)
+    alone_table = ops.component_table(alone_labels, 0)
+    r = args.repeat
+    result = {
+        "block": n, "size": size, "eps": eps, "apron": apron, "batch_per_tile": args.batch, "tiles": len(tiles),
+        "foreground": float((tiles == 1).mean()),
+        "stitched": {"components": int(len(table)), "edges": int(len(edges)), "ms": timed(stitched, r) * 1e3, "ms_split": {
+            "gather": timed(lambda: ops.gather_halo(dev, nbr, apron), r) * 1e3,
+            "clean_padded": timed(lambda: ops.clean_masks(padded, 1, eps, eps), r) * 1e3,
+            "crop": timed(lambda: ops.crop_halo(cleaned_padded, apron), r) * 1e3,
+            "label": timed(lambda: ops.label_components(cleaned), r) * 1e3,
+            "seam_union_flatten": timed(lambda: ops.stitch_labels(local, nbr), r) * 1e3,
+            "table": timed(lambda: ops.component_table_stitched(labels, origin, 0), r) * 1e3,
+            "edges": timed(lambda: ops.boundary_edges_stitched(labels, nbr, origin, table).cpu(), r) * 1e3}},
+        "per_tile": {"components": int(sum(len(t) for t, _ in parts)), "edges": int(sum(len(e) for _, e in parts)),
+                     "ms": timed(per_tile, r) * 1e3, "ms_split_one_call_of_all_tiles": {
+            "clean": timed(lambda: ops.clean_masks(dev, 1, eps, eps), r) * 1e3,
+            "label": timed(lambda: ops.label_components(alone), r) * 1e3,
+            "table": timed(lambda: ops.component_table(alone_labels, 0), r) * 1e3,
+            "edges": timed(lambda: ops.boundary_edges(alone_labels, alone_table).cpu(), r) * 1e3}},
+    }
+    split = result["stitched"]["ms_split"]
+    result["clean_ratio"] = {"measured": (split["gather"] + split["clean_padded"] + split["crop"])
+                             / result["per_tile"]["ms_split_one_call_of_all_tiles"]["clean"],
+                             "measured_clean_padded_alone": split["clean_padded"] / result["per_tile"]["ms_split_one_call_of_all_tiles"]["clean"],
+                             "model": ((size + 2 * apron) / size) ** 2}
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "features_stitch", "bench_stitch.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
 
 
 def device_stage(images, eps):
@@ -109,8 +206,12 @@ def main():
     ap.add_argument("--eps", type=int, default=20)
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--stage-loop", type=int, default=0)
-    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "features", "bench_features.json"))
+    ap.add_argument("--stitch-leg", action="store_true", help="only the stitched path against the per-tile path on an n x n block")
+    ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched leg's block")
+    ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
+    if args.stitch_leg:
+        return stitch_leg(args)
 
     import torch
 
