@@ -644,6 +644,42 @@ int rs_features_edges_stitched(const int32_t* labels, const int32_t* nbr, const 
                                uint8_t* keep, int32_t* edges, long capacity, int32_t* counter, int T, int H, int W,
                                rs_stream_t stream);
 
+/* ---- centerlines: skeleton and links (`rs features --geometry centerline`) ----
+ * Thinning is the Guo-Hall two-subiteration parallel algorithm (CACM 32(3), 1989).  With p2..p9 = the N, NE, E, SE, S, SW, W, NW
+ * neighbours of a set pixel p, a pixel outside the raster reading 0:
+ *   C  = (!p2 & (p3|p4)) + (!p4 & (p5|p6)) + (!p6 & (p7|p8)) + (!p8 & (p9|p2))
+ *   N1 = (p9|p2) + (p3|p4) + (p5|p6) + (p7|p8),  N2 = (p2|p3) + (p4|p5) + (p6|p7) + (p8|p9),  N = min(N1, N2)
+ *   m  = (p2|p3|!p5) & p4 in the first sub-iteration of a pair, (p6|p7|!p9) & p8 in the second
+ * and p is deleted iff C == 1, 2 <= N <= 3 and m == 0.  Every pixel of a sub-iteration is judged on the raster as it stood before
+ * that sub-iteration (two bit-planes, ping-pong; one launch per sub-iteration over all tiles, no workgroup waits for another), and
+ * pairs repeat until a whole pair deletes nothing: the skeleton is a pure function of the mask.  A pair on a converged raster is the
+ * identity.
+ *
+ * rs_features_thin: masks [B][H][W] (non-zero = set) -> `pairs` (1 .. 2^20) pairs of sub-iterations -> out [B][H][W] 0/1 bytes.
+ * workspace: rs_features_clean_workspace_bytes(B, H, W) bytes holding the two planes; with resume != 0 the call goes on from the
+ * planes an earlier call with the same workspace and shape left (masks is not read and may be NULL).  counters (int32 [2], device):
+ * [0] = pixels deleted since the last call with resume == 0, [1] = pixels deleted by this call's last pair: the host enqueues pairs
+ * in chunks and stops at counters[1] == 0, whatever the chunk size.  nbr NULL: each of the B tiles is a raster of its own.  nbr
+ * int32 [B][8] (the table of rs_features_halo): the tiles are one sparse raster -- the 8-neighbour of a border pixel across a seam or
+ * a corner is the facing pixel of the neighbouring tile, 0 where that tile is absent; the result is the definition above applied to
+ * that raster (read through nbr at every sub-iteration: thinning has no bounded reach, so no apron would do).  Any W works.
+ *
+ * rs_features_skeleton_links: the links of skeleton s [B][H][W] (0/1) under `labels` and `table` as rs_features_edges takes them
+ * (nbr and origin NULL: per tile, table rows of 7) or as rs_features_edges_stitched does (both given: table rows of 6).  From a
+ * set pixel (x, y): dir 0 E to (x+1, y) where set; dir 2 S to (x, y+1) where set; dir 1 SE to (x+1, y+1) where set and neither
+ * (x+1, y) nor (x, y+1) is; dir 3 SW to (x-1, y+1) where set and neither (x-1, y) nor (x, y+1) is (a diagonal link only where no
+ * orthogonal detour exists: staircase corners stay at degree 2).  The links' connected components are the skeleton's 8-connected
+ * components.  A link is emitted, once, by its first pixel where the component of either end is listed in `table`, under the first
+ * pixel's label where that is listed and the other's otherwise; a set pixel of a listed component with no set 8-neighbour (no link at
+ * either end) emits one row with dir -1.  Rows [tile, label, x, y, dir] (per tile) or [label, X, Y, dir] in mosaic pixels
+ * (stitched; a link across a seam is emitted by its first pixel like any other), at most 4 per pixel, in no particular order;
+ * counter, capacity and keep as in rs_features_edges. */
+int rs_features_thin(const uint8_t* masks, uint8_t* out, void* workspace, const int32_t* nbr, int32_t* counters, int B, int H, int W,
+                     int pairs, int resume, rs_stream_t stream);
+int rs_features_skeleton_links(const uint8_t* skeleton, const int32_t* labels, const int32_t* nbr, const int32_t* origin,
+                               const int32_t* table, long rows, uint8_t* keep, int32_t* links, long capacity, int32_t* counter, int B,
+                               int H, int W, rs_stream_t stream);
+
 
 #ifdef __cplusplus
 }

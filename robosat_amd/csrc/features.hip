@@ -482,6 +482,198 @@ __global__ __launch_bounds__(256) void stitch_flatten_kernel(int* L, int* err, l
   atomicMin(&L[g], root + 1);
 }
 
+// ---- thinning: Guo-Hall, two sub-iterations per pair (definitions: include/robosat_hip.h) ---------------------------------
+// Bit-planes as in the morphology: ws [B][2][H][Wd], 32 pixels per word, bits beyond W zero.  One thread per word judges its 32
+// pixels on plane `from` and writes plane `from ^ 1`: the eight neighbour words are the rows above and below and the words shifted
+// by one bit, the three sums of the rule are bit-sliced (a 4-term sum is two half-adders: x = the pairs' XORs, c = their ANDs).
+struct ThinArgs {
+  uint32_t* ws;
+  const int* nbr;  // STITCH: [B][8]
+  int B, H, W, Wd;
+};
+
+// Word wx of row y of the tile at (dx, dy) from `tile`, 0 where there is none (per tile: every other tile is none).
+template <bool STITCH>
+__device__ __forceinline__ uint32_t thin_word(const ThinArgs& a, int from, int tile, int dx, int dy, int y, int wx) {
+  int slot = tile;
+  if (dx | dy) {
+    if (!STITCH) return 0u;
+    slot = nbr_slot(a.nbr, tile, dx, dy, a.B);
+    if (slot < 0) return 0u;
+  }
+  return a.ws[((long)slot * 2 + from) * a.H * a.Wd + (long)y * a.Wd + wx];
+}
+
+// Row yy (-1 .. H: one beyond is the facing row of the tile above / below) at word wx: c = the pixels x, w = x - 1, e = x + 1.
+// The pixel left of word 0 is the W tile's last pixel, the pixel right of pixel W - 1 the E tile's first (for any W: it lands on
+// bit (W - 1) & 31 of e, which cur >> 1 leaves 0).  Bits beyond W of w hold no pixel: the caller masks with its own pixels.
+template <bool STITCH>
+__device__ __forceinline__ void thin_row(const ThinArgs& a, int from, int tile, int yy, int wx, uint32_t& w, uint32_t& c, uint32_t& e) {
+  const int dy = yy < 0 ? -1 : yy >= a.H ? 1 : 0;
+  const int y = yy - dy * a.H;
+  if (!STITCH && dy) {
+    w = c = e = 0u;
+    return;
+  }
+  c = thin_word<STITCH>(a, from, tile, 0, dy, y, wx);
+  const int last = (a.W - 1) & 31;
+  const uint32_t before = wx > 0 ? thin_word<STITCH>(a, from, tile, 0, dy, y, wx - 1) >> 31
+                                 : (thin_word<STITCH>(a, from, tile, -1, dy, y, a.Wd - 1) >> last) & 1u;
+  w = (c << 1) | before;
+  if (wx < a.Wd - 1)
+    e = (c >> 1) | (thin_word<STITCH>(a, from, tile, 0, dy, y, wx + 1) << 31);
+  else
+    e = (c >> 1) | ((thin_word<STITCH>(a, from, tile, 1, dy, y, 0) & 1u) << last);
+}
+
+// Exactly one / at least two / all four of four 1-bit terms, per bit.
+__device__ __forceinline__ void sum4(uint32_t t1, uint32_t t2, uint32_t t3, uint32_t t4, uint32_t& one, uint32_t& ge2, uint32_t& four) {
+  const uint32_t xa = t1 ^ t2, ca = t1 & t2, xb = t3 ^ t4, cb = t3 & t4;
+  one = (xa ^ xb) & ~(ca | cb);
+  ge2 = ca | cb | (xa & xb);
+  four = ca & cb;
+}
+
+// SECOND: the second sub-iteration of a pair.  total / last: int32 in device memory, the pixels deleted (one atomic per wave).
+template <bool STITCH, bool SECOND>
+__global__ __launch_bounds__(256) void thin_pass_kernel(const ThinArgs a, int from, int* total, int* last) {
+  const int tile = blockIdx.y;
+  const long words = (long)a.H * a.Wd;
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  uint32_t del = 0u;
+  if (i < words) {  // (no early return: every lane reaches the shuffles)
+    const int y = (int)(i / a.Wd), wx = (int)(i - (long)y * a.Wd);
+    uint32_t p9, p2, p3, p8, p, p4, p7, p6, p5;
+    thin_row<STITCH>(a, from, tile, y, wx, p8, p, p4);
+    if (p) {
+      thin_row<STITCH>(a, from, tile, y - 1, wx, p9, p2, p3);
+      thin_row<STITCH>(a, from, tile, y + 1, wx, p7, p6, p5);
+      uint32_t c1, n1, n1x, n2, n2x, unused;
+      sum4(~p2 & (p3 | p4), ~p4 & (p5 | p6), ~p6 & (p7 | p8), ~p8 & (p9 | p2), c1, unused, unused);
+      sum4(p9 | p2, p3 | p4, p5 | p6, p7 | p8, unused, n1, n1x);
+      sum4(p2 | p3, p4 | p5, p6 | p7, p8 | p9, unused, n2, n2x);
+      const uint32_t m = SECOND ? (p6 | p7 | ~p9) & p8 : (p2 | p3 | ~p5) & p4;
+      del = p & c1 & n1 & n2 & ~(n1x & n2x) & ~m;  // min(N1, N2) in 2..3: both >= 2, not both 4
+    }
+    a.ws[((long)tile * 2 + (from ^ 1)) * words + i] = p & ~del;
+  }
+  int n = __popc(del);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if (n && (threadIdx.x & 63) == 0) {
+    atomicAdd(total, n);
+    if (last) atomicAdd(last, n);
+  }
+}
+
+// masks != 0 -> plane 0 (one ballot per 64 pixels, as select_pack).
+__global__ __launch_bounds__(256) void thin_pack_kernel(const uint8_t* __restrict__ masks, const ThinArgs a) {
+  const int tile = blockIdx.y, lane = threadIdx.x & 63;
+  const uint8_t* img = masks + (long)tile * a.H * a.W;
+  uint32_t* plane = a.ws + (long)tile * 2 * a.H * a.Wd;
+  const int chunks = (a.W + 63) >> 6;
+  for (int item = blockIdx.x * 4 + (threadIdx.x >> 6); item < a.H * chunks; item += gridDim.x * 4) {  // (wave-uniform)
+    const int y = item / chunks, ch = item - y * chunks;
+    const int x = ch * 64 + lane;
+    const unsigned long long m = __ballot(x < a.W && img[(long)y * a.W + x] != 0);
+    if (lane == 0) plane[(long)y * a.Wd + ch * 2] = (uint32_t)m;
+    if (lane == 32 && ch * 2 + 1 < a.Wd) plane[(long)y * a.Wd + ch * 2 + 1] = (uint32_t)(m >> 32);
+  }
+}
+
+// ---- skeleton links ---------------------------------------------------------------------------------------------------------
+// Global index of pixel (x, y) of `tile`, x and y at most one beyond it: the facing pixel of the neighbour tile, -1 where none is.
+template <bool STITCH>
+__device__ __forceinline__ long pixel_at(const int* __restrict__ nbr, int tile, int x, int y, int B, int H, int W) {
+  const int dx = x < 0 ? -1 : x >= W ? 1 : 0, dy = y < 0 ? -1 : y >= H ? 1 : 0;
+  int slot = tile;
+  if (dx | dy) {
+    if (!STITCH) return -1;
+    slot = nbr_slot(nbr, tile, dx, dy, B);
+    if (slot < 0) return -1;
+  }
+  return (long)slot * H * W + (long)(y - dy * H) * W + (x - dx * W);
+}
+
+// Links of skeleton pixel p: 0 E, 2 S, 1 SE where neither E nor S is set, 3 SW where neither W nor S is set; a pixel without any
+// set 8-neighbour has no link at either end and emits one row with dir -1.  A link is emitted where either end's component is kept,
+// under the label of p's where that is kept, else of the other end's.  Rows and counter as edges_emit_kernel.
+template <bool STITCH>
+__global__ __launch_bounds__(256) void links_emit_kernel(const uint8_t* __restrict__ S, const int* __restrict__ L,
+                                                         const uint8_t* __restrict__ keep, int* links, long capacity, unsigned int* counter,
+                                                         int B, int H, int W, const int* __restrict__ nbr, const int* __restrict__ origin) {
+  const long HW = (long)H * W;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  int x = 0, y = 0, tile = 0;
+  int lab[5] = {0, 0, 0, 0, 0};  // label of the row for dir 0..3, [4]: the lone pixel
+  unsigned int dirs = 0;
+  if (g < (long)B * HW && S[g]) {
+    tile = (int)(g / HW);
+    const int p = (int)(g - (long)tile * HW);
+    y = p / W;
+    x = p - y * W;
+    const long base = STITCH ? 0 : (long)tile * HW, top = STITCH ? (long)B * HW : HW;
+    const int own = L[g];
+    const bool own_kept = own >= 1 && own <= top && keep[base + own - 1];
+    // E, SE, S, SW, W, NW, N, NE
+    const int ox[8] = {1, 1, 0, -1, -1, -1, 0, 1}, oy[8] = {0, 1, 1, 1, 0, -1, -1, -1};
+    long at[8];
+    unsigned int set = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      at[k] = pixel_at<STITCH>(nbr, tile, x + ox[k], y + oy[k], B, H, W);
+      if (at[k] >= 0 && S[at[k]]) set |= 1u << k;
+    }
+    const bool e = set & 1u, se = set & 2u, s = set & 4u, sw = set & 8u, w = set & 16u;
+    const unsigned int want = (e ? 1u : 0u) | (se && !e && !s ? 2u : 0u) | (s ? 4u : 0u) | (sw && !w && !s ? 8u : 0u);
+#pragma unroll
+    for (int d = 0; d < 4; ++d)
+      if (want & (1u << d)) {
+        const int other = L[at[d]];
+        const bool other_kept = other >= 1 && other <= top && keep[base + other - 1];
+        if (own_kept || other_kept) {
+          dirs |= 1u << d;
+          lab[d] = own_kept ? own : other;
+        }
+      }
+    if (!set && own_kept) {
+      dirs = 16u;
+      lab[4] = own;
+    }
+    if (STITCH) {
+      x += origin[tile * 2];
+      y += origin[tile * 2 + 1];
+    }
+  }
+  const int n = __popc(dirs);
+  int incl = n;  // inclusive prefix sum over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  const int total = __shfl(incl, 63, 64);
+  if (total == 0) return;  // (uniform)
+  unsigned int first = 0;
+  if (lane == 63) first = atomicAdd(counter, (unsigned int)total);
+  first = __shfl(first, 63, 64);
+  long k = (long)first + incl - n;
+#pragma unroll
+  for (int d = 0; d < 5; ++d)
+    if (dirs & (1u << d)) {
+      if (k < capacity) {
+        int* r = links + k * (STITCH ? 4 : 5);
+        if (!STITCH) *r++ = tile;
+        r[0] = lab[d];
+        r[1] = x;
+        r[2] = y;
+        r[3] = d < 4 ? d : -1;
+      }
+      ++k;
+    }
+}
+
 // (B rides in gridDim.y; 4 edges per pixel at the very most stay below 2^31 in the int32 edge counter)
 bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)B * H * W < (1l << 29); }
 
@@ -634,5 +826,62 @@ extern "C" int rs_features_edges_stitched(const int32_t* labels, const int32_t* 
   if (rows > 0) edges_mark_kernel<true><<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, T, (long)H * W);
   edges_emit_kernel<true><<<rs_cdiv(P, 256), 256, 0, s>>>(labels, keep, edges, capacity, reinterpret_cast<unsigned int*>(counter), T, H, W,
                                                            nbr, origin);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_thin(const uint8_t* masks, uint8_t* out, void* workspace, const int32_t* nbr, int32_t* counters, int B, int H,
+                                int W, int pairs, int resume, rs_stream_t stream) {
+  if ((!masks && !resume) || !out || !workspace || !counters || !shape_ok(B, H, W) || pairs < 1 || pairs > (1 << 20)) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  ThinArgs a;
+  a.ws = static_cast<uint32_t*>(workspace);
+  a.nbr = nbr;
+  a.B = B, a.H = H, a.W = W, a.Wd = (W + 31) / 32;
+  const long words = (long)H * a.Wd;
+  hipError_t e = hipMemsetAsync(counters + 1, 0, sizeof(int32_t), s);
+  if (e == hipSuccess && !resume) e = hipMemsetAsync(counters, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  if (!resume) {
+    const long items = (long)H * ((W + 63) / 64);
+    thin_pack_kernel<<<dim3(rs_cdiv(items, 4) < 1024 ? rs_cdiv(items, 4) : 1024, B), 256, 0, s>>>(masks, a);
+  }
+  const dim3 grid(rs_cdiv(words, 256), B);
+  for (int pair = 0; pair < pairs; ++pair) {  // (a pair leaves its result where it found its input: plane 0)
+    int* last = pair == pairs - 1 ? counters + 1 : nullptr;
+    if (nbr) {
+      thin_pass_kernel<true, false><<<grid, 256, 0, s>>>(a, 0, counters, last);
+      thin_pass_kernel<true, true><<<grid, 256, 0, s>>>(a, 1, counters, last);
+    } else {
+      thin_pass_kernel<false, false><<<grid, 256, 0, s>>>(a, 0, counters, last);
+      thin_pass_kernel<false, true><<<grid, 256, 0, s>>>(a, 1, counters, last);
+    }
+  }
+  CleanArgs u = {};
+  u.out = out;
+  u.ws = a.ws;
+  u.B = B, u.H = H, u.W = W, u.Wd = a.Wd;
+  clean_unpack_kernel<<<dim3(rs_cdiv((long)H * W, 256), B), 256, 0, s>>>(u, 0);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_skeleton_links(const uint8_t* skeleton, const int32_t* labels, const int32_t* nbr, const int32_t* origin,
+                                          const int32_t* table, long rows, uint8_t* keep, int32_t* links, long capacity, int32_t* counter,
+                                          int B, int H, int W, rs_stream_t stream) {
+  if (!skeleton || !labels || (nbr == nullptr) != (origin == nullptr) || !keep || !counter || rows < 0 || (rows > 0 && !table) ||
+      capacity < 0 || (capacity > 0 && !links) || !shape_ok(B, H, W))
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)B * H * W;
+  hipError_t e = hipMemsetAsync(keep, 0, P, s);
+  if (e == hipSuccess) e = hipMemsetAsync(counter, 0, sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  unsigned int* c = reinterpret_cast<unsigned int*>(counter);
+  if (nbr) {
+    if (rows > 0) edges_mark_kernel<true><<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, B, (long)H * W);
+    links_emit_kernel<true><<<rs_cdiv(P, 256), 256, 0, s>>>(skeleton, labels, keep, links, capacity, c, B, H, W, nbr, origin);
+  } else {
+    if (rows > 0) edges_mark_kernel<false><<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, B, (long)H * W);
+    links_emit_kernel<false><<<rs_cdiv(P, 256), 256, 0, s>>>(skeleton, labels, keep, links, capacity, c, B, H, W, nullptr, nullptr);
+  }
   return RS_LAUNCH_RESULT();
 }

@@ -4,7 +4,9 @@ the reference uses OpenCV contours, shapely and geojson: ``robosat/features/core
 Vertices are pixel corners, integer (x, y) in [0, W] x [0, H], y down.  An edge row is ``(tile, label, x, y, dir)``: the
 pixel (x, y) of component ``label`` walked round with the pixel on the right -- dir 0 top (x,y)->(x+1,y), 1 right
 (x+1,y)->(x+1,y+1), 2 bottom (x+1,y+1)->(x,y+1), 3 left (x,y+1)->(x,y).  With that orientation the shoelace area of a
-component's outer ring is positive, its holes' negative, and the areas of its rings sum to its pixel count."""
+component's outer ring is positive, its holes' negative, and the areas of its rings sum to its pixel count.
+
+``--geometry centerline`` has its own half at the end of the file: skeleton links -> lines -> pruned, simplified LineStrings."""
 
 import json
 import sys
@@ -393,4 +395,231 @@ def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stder
             "geometry": {"type": "Polygon", "coordinates": coordinates},
             "properties": {"tile": [int(tile.x), int(tile.y), int(tile.z)], "area_px": area[label], "stitched": True},
         })
+    return features
+
+
+# ---- rs features --geometry centerline: skeleton links -> lines ----------------------------------------------------------------
+# A link row is (tile, label, x, y, dir): skeleton pixel (x, y) joined to (x + 1, y) for dir 0 (E), (x + 1, y + 1) for 1 (SE),
+# (x, y + 1) for 2 (S), (x - 1, y + 1) for 3 (SW); dir -1 is a skeleton pixel without links.  Vertices are PIXELS (their centres
+# on the map), unlike the polygon half's corners.  A line is (tile, label, points int64 [k, 2]); it is closed where k > 1 and
+# its first point is its last.
+_LINK_STEP = ((1, 0), (1, 1), (0, 1), (-1, 1))
+
+
+def _link_key(a, b):
+    return (a, b) if a < b else (b, a)
+
+
+def link_lines(rows):
+    """Link rows int [N, 5] (or [N, 4] = (label, X, Y, dir) of a stitched call, taken as tile 0) in any order -> the lines of the
+    link graph, a list of (tile, label, points).  The degree of a pixel is the number of its links; pixels of degree != 2 are
+    nodes.  A line is a maximal chain of links whose interior pixels have degree 2: it runs from node to node (back to the same
+    node for a loop hanging on a junction), or it is a node-free cycle, closed, started at its lexicographically smallest (x, y)
+    and walked towards the smaller of that pixel's two neighbours.  A pixel without links is a line of one point.  The output is
+    canonical whatever the order of the rows: every line is the smaller of its two readings (an open line starts at its smaller
+    end), and the lines are sorted by (tile, points).  A line's label is the smallest label among its links' rows."""
+
+    r = np.asarray(rows, dtype=np.int64)
+    if r.ndim == 2 and r.shape[1] == 4:
+        r = np.concatenate([np.zeros((len(r), 1), dtype=np.int64), r], axis=1)
+    r = r.reshape(-1, 5)
+    by_tile = {}
+    for tile, label, x, y, d in r.tolist():
+        adj, labels, lone = by_tile.setdefault(tile, ({}, {}, {}))
+        a = (x, y)
+        if d < 0:
+            lone[a] = label
+            continue
+        assert d <= 3, "dir is -1..3"
+        b = (x + _LINK_STEP[d][0], y + _LINK_STEP[d][1])
+        key = _link_key(a, b)
+        assert key not in labels, "duplicate link"
+        labels[key] = label
+        adj.setdefault(a, set()).add(b)
+        adj.setdefault(b, set()).add(a)
+
+    lines = []
+    for tile in sorted(by_tile):
+        adj, labels, lone = by_tile[tile]
+        used = set()
+
+        def walk(a, b, stop):
+            points = [a, b]
+            used.add(_link_key(a, b))
+            while b != stop and len(adj[b]) == 2:
+                first, second = adj[b]
+                nxt = second if first == points[-2] else first
+                used.add(_link_key(b, nxt))
+                points.append(nxt)
+                b = nxt
+            return points
+
+        found = [[p] for p in lone if p not in adj]
+        for a in sorted(p for p in adj if len(adj[p]) != 2):
+            for b in sorted(adj[a]):
+                if _link_key(a, b) not in used:
+                    points = walk(a, b, None)
+                    found.append(min(points, points[::-1]))
+        for a in sorted(adj):  # what is left: cycles without a node
+            b = min(adj[a])
+            if _link_key(a, b) not in used:
+                found.append(walk(a, b, a))
+        for points in sorted(found):
+            if len(points) == 1:
+                label = lone[points[0]]
+            else:
+                label = min(labels[_link_key(a, b)] for a, b in zip(points, points[1:]))
+            lines.append((tile, label, np.array(points, dtype=np.int64).reshape(-1, 2)))
+    return lines
+
+
+def line_length(points):
+    """Length in pixels: a link counts 1 or sqrt(2)."""
+
+    d = np.diff(np.asarray(points, dtype=np.int64), axis=0)
+    return float(np.hypot(d[:, 0], d[:, 1]).sum())
+
+
+def _line_rows(lines):
+    """Lines -> the link rows they came from (each link under its line's label)."""
+
+    step = {s: d for d, s in enumerate(_LINK_STEP)}
+    rows = []
+    for tile, label, points in lines:
+        points = np.asarray(points).tolist()
+        if len(points) == 1:
+            rows.append((tile, label, points[0][0], points[0][1], -1))
+        for (ax, ay), (bx, by) in zip(points, points[1:]):
+            if (bx - ax, by - ay) not in step:
+                ax, ay, bx, by = bx, by, ax, ay
+            rows.append((tile, label, ax, ay, step[(bx - ax, by - ay)]))
+    return np.array(rows, dtype=np.int64).reshape(-1, 5)
+
+
+def prune_lines(lines, prune):
+    """Removes spurs from the lines of ``link_lines``.  A spur is an open line from an end of degree 1 to a junction (a pixel
+    where three or more line ends meet) whose length (``line_length``) is below ``prune``.  Removal goes in rounds.  In a round
+    every junction drops its spurs, shortest first (ties in the lines' canonical order), but keeps at least two of its line
+    ends; then the remaining links are linked afresh (``link_lines``: two lines left at a former junction become one), and the
+    next round looks at the new lines, until a round finds nothing to remove.  A line between two ends of degree 1, a line between
+    two junctions and a cycle are never spurs, and a junction never loses all its lines: no component vanishes or falls apart.
+    The result depends on the set of links alone, pruning it again changes nothing, and ``prune`` = 0 returns the lines as they
+    are."""
+
+    lines = list(lines)
+    while prune > 0:
+        ends = {}
+        for tile, _, points in lines:
+            if len(points) > 1:
+                for p in (points[0], points[-1]):
+                    key = (tile, int(p[0]), int(p[1]))
+                    ends[key] = ends.get(key, 0) + 1
+        spurs = {}
+        for i, (tile, _, points) in enumerate(lines):
+            if len(points) < 2:
+                continue
+            a, b = (tile, int(points[0][0]), int(points[0][1])), (tile, int(points[-1][0]), int(points[-1][1]))
+            if a == b:
+                continue
+            for end, junction in ((a, b), (b, a)):
+                if ends[end] == 1 and ends[junction] >= 3:
+                    length = line_length(points)
+                    if length < prune:
+                        spurs.setdefault(junction, []).append((length, points.tolist(), i))
+        drop = set()
+        for junction, candidates in spurs.items():
+            candidates.sort()
+            drop.update(i for _, _, i in candidates[:ends[junction] - 2])
+        if not drop:
+            break
+        lines = link_lines(_line_rows([line for i, line in enumerate(lines) if i not in drop]))
+    return lines
+
+
+def simplify_line(points, tolerance):
+    """Douglas-Peucker on a polyline [[x, y], ...] with ``tolerance`` in pixels: between two kept vertices the vertex farthest from
+    their chord is kept where that distance exceeds the tolerance.  Both ends are kept; a closed line (first point = last) keeps
+    its start vertex, the distance to the zero-length chord being the distance to that point.  Tolerance 0 drops only vertices
+    that lie on the chord of their kept neighbours."""
+
+    points = np.asarray(points)
+    n = len(points)
+    if n < 3:
+        return points
+    pts = points.astype(np.float64)
+    keep = np.zeros(n, dtype=bool)
+    keep[[0, n - 1]] = True
+    stack = [(0, n - 1)]
+    while stack:
+        lo, hi = stack.pop()
+        if hi - lo < 2:
+            continue
+        dist = _line_distance(pts[lo + 1:hi], pts[lo], pts[hi])
+        k = int(np.argmax(dist))
+        if dist[k] > tolerance:
+            mid = lo + 1 + k
+            keep[mid] = True
+            stack += [(lo, mid), (mid, hi)]
+    return points[keep]
+
+
+def _line_feature(tile, label, points, locate, area, prune_length, tolerance, stitched):
+    kept = simplify_line(points, tolerance)
+    coordinates = [list(locate(int(px), int(py))) for px, py in kept]
+    if len(coordinates) == 1:  # a skeleton of one pixel: a LineString takes two positions
+        coordinates = coordinates * 2
+    properties = {"tile": [int(tile.x), int(tile.y), int(tile.z)], "component": int(label), "length_px": round(prune_length, 3),
+                  "area_px": area}
+    if stitched:
+        properties["stitched"] = True
+    return {"type": "Feature", "geometry": {"type": "LineString", "coordinates": coordinates}, "properties": properties}
+
+
+def centerlines(links, table, tiles, shape, prune=20, tolerance=1.5):
+    """Link rows (tile, label, x, y, dir) + component table rows (tile, label, area, ...) of one batch -> one GeoJSON Feature per
+    line (``link_lines``, ``prune_lines``, ``simplify_line``): a LineString whose vertices are PIXEL CENTRES (x + 0.5, y + 0.5)
+    georeferenced in their tile; properties ``tile``, ``component`` (the label), ``length_px`` (before simplification) and
+    ``area_px`` (of the component).  Ordered by (batch index, points)."""
+
+    h, w = shape
+    area = {(int(r[0]), int(r[1])): int(r[2]) for r in np.asarray(table).reshape(-1, 7)}
+    features = []
+    for index, label, points in prune_lines(link_lines(np.asarray(links).reshape(-1, 5)), prune):
+        tile = tiles[index]
+
+        def locate(px, py, tile=tile):
+            return pixel_to_location(tile, (px + 0.5) / w, (py + 0.5) / h)
+
+        features.append(_line_feature(tile, label, points, locate, area[(index, label)], line_length(points), tolerance, False))
+    return features
+
+
+def mosaic_centre_location(z, gx, gy, shape):
+    """``(lon, lat)`` of the centre of pixel (gx, gy) of zoom level z's whole raster, through the tile it falls in (present or not):
+    the floats ``centerlines`` gives the same pixel from that tile's side."""
+
+    h, w = shape
+    tile = Tile(gx // w, gy // h, z)
+    return pixel_to_location(tile, (gx - tile.x * w + 0.5) / w, (gy - tile.y * h + 0.5) / h)
+
+
+def centerlines_stitched(links, table, tiles, shape, prune=20, tolerance=1.5, georeference=True):
+    """``centerlines`` for one stitched call: link rows (label, X, Y, dir) + table rows (label, area, ...) in mosaic pixels,
+    ``tiles`` the call's tiles in slot order.  A feature's ``tile`` is the tile holding its component's canonical pixel,
+    ``"stitched": true`` marks it; ordered by (label, points).  ``georeference=False`` leaves the vertices as mosaic pixels
+    [X, Y]."""
+
+    h, w = shape
+    x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
+    z = tiles[0].z
+    area = {int(r[0]): int(r[1]) for r in np.asarray(table).reshape(-1, 6)}
+
+    def locate(px, py):
+        return mosaic_centre_location(z, x_min * w + px, y_min * h + py, shape) if georeference else (px, py)
+
+    lines = prune_lines(link_lines(np.asarray(links).reshape(-1, 4)), prune)
+    features = []
+    for _, label, points in sorted(lines, key=lambda line: (line[1], line[2].tolist())):
+        tile = tiles[(label - 1) // (h * w)]
+        features.append(_line_feature(tile, label, points, locate, area[label], line_length(points), tolerance, True))
     return features

@@ -1578,3 +1578,78 @@ def stitched_features(images_u8, nbr, origin, index, eps_open, eps_close, min_ar
     labels = stitch_labels(label_components(clean_masks_stitched(images_u8, nbr, index, eps_open, eps_close)), nbr, inplace=True)
     table = component_table_stitched(labels, origin, min_area)
     return table, boundary_edges_stitched(labels, nbr, origin, table)
+
+
+# ---- rs features --geometry centerline: skeleton and links (definitions in include/robosat_hip.h) --------------------------------
+THIN_PAIRS = 16  # pairs of sub-iterations enqueued between two reads of the device's counter (profiles/features_centerline)
+
+
+def thin_masks(masks_u8, nbr=None, pairs=None, want_pairs=False):
+    """uint8 [B, H, W] (non-zero = set) -> uint8 0/1 [B, H, W]: the Guo-Hall skeleton of every tile, or with ``nbr`` int32 [B, 8]
+    of the one sparse raster the tiles form.  ``pairs`` pairs of sub-iterations (default ``THIN_PAIRS``) are enqueued per read of
+    the counter; the result does not depend on it.  ``want_pairs``: also the number of pairs that were run."""
+
+    b, h, w = masks_u8.shape
+    pairs = THIN_PAIRS if pairs is None else int(pairs)
+    if pairs < 1:
+        raise ValueError("robosat_amd: thinning enqueues at least one pair per chunk, got {}".format(pairs))
+    if nbr is not None:
+        assert nbr.shape == (b, 8), "nbr is [T, 8]"
+    dev = masks_u8.device
+    out = torch.empty_like(masks_u8)
+    masks, outp = _dev(masks_u8, "masks", torch.uint8), _dev(out, "out", torch.uint8)  # (a CPU tensor raises before anything is sized)
+    ws = torch.empty(max(_lib.lib().rs_features_clean_workspace_bytes(b, h, w), 1), device=dev, dtype=torch.uint8)
+    counters = torch.empty(2, device=dev, dtype=torch.int32)
+    done = 0
+    while True:
+        _call("rs_features_thin", masks, outp, _dev(ws, "workspace", torch.uint8), _dev(nbr, "nbr", torch.int32),
+              _dev(counters, "counters", torch.int32), b, h, w, pairs, int(done > 0), _stream())
+        done += pairs
+        if counters[1].item() == 0:
+            return (out, done) if want_pairs else out
+        if done > b * h * w:  # (every pair but the last deletes a pixel)
+            raise RuntimeError("rs_features_thin: no fixed point after {} pairs on {} pixels".format(done, b * h * w))
+
+
+def skeleton_links(skeleton, labels, table, nbr=None, origin=None):
+    """Links of the skeleton uint8 [B, H, W] under the labels and table of the mask it was thinned from: int32 [N, 5] rows
+    (tile, label, x, y, dir) with ``component_table``'s rows, or with ``nbr`` and ``origin`` int32 [N, 4] rows (label, X, Y, dir)
+    in mosaic pixels with ``component_table_stitched``'s.  dir 0 E, 1 SE, 2 S, 3 SW; -1 a pixel without links.  In the order the
+    device wrote them."""
+
+    b, h, w = labels.shape
+    if (nbr is None) != (origin is None):
+        raise ValueError("robosat_amd: nbr and origin come together")
+    assert skeleton.shape == labels.shape, "skeleton and labels are both [B, H, W]"
+    if nbr is not None:
+        assert nbr.shape == (b, 8) and origin.shape == (b, 2)
+    dev = labels.device
+    keep = torch.empty(b * h * w, device=dev, dtype=torch.uint8)
+    counter = torch.empty(1, device=dev, dtype=torch.int32)
+    table = table.contiguous()
+    width = 5 if nbr is None else 4
+    assert table.shape[1:] == (width + 2,), "table rows do not match the form"
+
+    def run(links, capacity):
+        _call("rs_features_skeleton_links", _dev(skeleton, "skeleton", torch.uint8), _dev(labels, "labels", torch.int32),
+              _dev(nbr, "nbr", torch.int32), _dev(origin, "origin", torch.int32), _dev(table, "table", torch.int32) if len(table) else None,
+              len(table), _dev(keep, "keep", torch.uint8), _dev(links, "links", torch.int32), capacity,
+              _dev(counter, "counter", torch.int32), b, h, w, _stream())
+        return int(counter.item())
+
+    n = run(None, 0)
+    links = torch.empty((n, width), device=dev, dtype=torch.int32)
+    if n:
+        got = run(links, n)
+        assert got == n, (got, n)
+    return links
+
+
+def stitched_centerlines(images_u8, nbr, origin, index, eps_open, eps_close, min_area=0):
+    """Every raster stage of ``rs features --geometry centerline --stitch`` for one call: class-index tiles uint8 [T, H, W] with
+    their neighbour and origin tables -> (table int32 [N, 6], links int32 [L, 4]) of the whole raster."""
+
+    cleaned = clean_masks_stitched(images_u8, nbr, index, eps_open, eps_close)
+    labels = stitch_labels(label_components(cleaned), nbr, inplace=True)
+    table = component_table_stitched(labels, origin, min_area)
+    return table, skeleton_links(thin_masks(cleaned, nbr), labels, table, nbr, origin)

@@ -3,6 +3,8 @@ reference's arguments (``robosat/tools/features.py``) with its handler's thresho
 open / close, connected components and boundary extraction run on the MI355X (``csrc/features.hip``); only the boundary
 edges come back to the host, which links them into rings, simplifies and georeferences them (``robosat_amd/features.py``).
 ``--stitch`` treats the tiles of a zoom level as one sparse raster, so an object that crosses tile borders is one polygon.
+``--geometry centerline`` gives LineStrings for linear classes such as roads: the cleaned mask is thinned to its skeleton on the
+device too, and the host links, prunes and simplifies the skeleton's lines.
 The stage definitions, and where they depart from OpenCV's, are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
@@ -15,7 +17,8 @@ from tqdm import tqdm
 
 from robosat_amd import ops
 from robosat_amd.config import load_config
-from robosat_amd.features import FeatureWriter, featurize, featurize_stitched, group_clusters, pack_clusters, stitch_tables
+from robosat_amd.features import (FeatureWriter, centerlines, centerlines_stitched, featurize, featurize_stitched, group_clusters,
+                                  pack_clusters, stitch_tables)
 from robosat_amd.tiles import tiles_from_slippy_map
 
 
@@ -31,10 +34,16 @@ def add_parser(subparser):
     parser.add_argument("out", type=str, help="path to GeoJSON file to store features in")
     parser.add_argument("--denoise", type=int, default=20, help="diameter in pixels of the disc the mask is opened with")
     parser.add_argument("--grow", type=int, default=20, help="diameter in pixels of the disc the mask is closed with")
-    parser.add_argument("--simplify", type=float, default=0.01, help="Douglas-Peucker epsilon as a share of a ring's perimeter")
+    parser.add_argument("--simplify", type=float, default=0.01, help="Douglas-Peucker epsilon as a share of a ring's perimeter (ignored with --geometry centerline: see --tolerance)")
     parser.add_argument("--min_area", type=int, default=0, help="components with fewer pixels are dropped")
     parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
     parser.add_argument("--stitch", action="store_true", help="treat the tiles of a zoom level as one raster: whole polygons across tile borders")
+    parser.add_argument("--geometry", type=str, default="polygon", choices=["polygon", "centerline"],
+                        help="polygon: the outline of every component; centerline: LineStrings along its skeleton (roads). Without "
+                        "--stitch a centerline stops about half the road's width short of every tile border (a 20-pixel road crossing a "
+                        "tile ends 9-10 pixels inside it), so roads want --stitch")
+    parser.add_argument("--prune", type=float, default=20, help="centerline: side branches shorter than this many pixels are removed")
+    parser.add_argument("--tolerance", type=float, default=1.5, help="centerline: Douglas-Peucker tolerance in pixels")
     parser.set_defaults(func=main)
 
 
@@ -65,10 +74,14 @@ def stitched(items, index, args, device, writer):
             sys.exit("Error: {}".format(exc))
         for tiles in tqdm(calls, desc="Features z{} {}x{}".format(z, h, w), unit="call", ascii=True):
             nbr, origin, _ = stitch_tables(tiles, shape)
-            table, edges = ops.stitched_features(_load([paths[t] for t in tiles], device), torch.from_numpy(nbr).to(device),
-                                                 torch.from_numpy(origin).to(device), index, args.denoise, args.grow, args.min_area)
+            stages = ops.stitched_centerlines if args.geometry == "centerline" else ops.stitched_features
+            table, rows = stages(_load([paths[t] for t in tiles], device), torch.from_numpy(nbr).to(device),
+                                 torch.from_numpy(origin).to(device), index, args.denoise, args.grow, args.min_area)
             try:
-                writer.add(featurize_stitched(edges.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify))
+                if args.geometry == "centerline":
+                    writer.add(centerlines_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.prune, args.tolerance))
+                else:
+                    writer.add(featurize_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify))
             except ValueError as exc:
                 sys.exit("Error: {}".format(exc))
 
@@ -80,6 +93,8 @@ def main(args):
     for name in ("denoise", "grow"):
         if not 0 <= getattr(args, name) <= 64:
             sys.exit("Error: --{} must be in 0..64".format(name))
+    if args.prune < 0 or args.tolerance < 0:
+        sys.exit("Error: --prune and --tolerance are lengths in pixels, not negative")
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
@@ -103,8 +118,14 @@ def main(args):
         for start in tqdm(range(0, len(items), batch), desc="Features {}x{}".format(*shape), unit="batch", ascii=True):
             group = items[start:start + batch]
             images = _load([path for _, path in group], device)
-            labels = ops.label_components(ops.clean_masks(images, index, args.denoise, args.grow))
+            cleaned = ops.clean_masks(images, index, args.denoise, args.grow)
+            labels = ops.label_components(cleaned)
             table = ops.component_table(labels, args.min_area)
+            if args.geometry == "centerline":
+                links = ops.skeleton_links(ops.thin_masks(cleaned), labels, table)
+                writer.add(centerlines(links.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.prune,
+                                       args.tolerance))
+                continue
             edges = ops.boundary_edges(labels, table)
             writer.add(featurize(edges.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.simplify))
     writer.save(args.out)

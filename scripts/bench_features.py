@@ -13,6 +13,11 @@
            blob raster (objects cross the seams): per stage and whole, written to profiles/features_stitch/bench_stitch.json
            (`--stitch-leg --stage-loop N` only runs the stitched stages N times, for rocprofv3)
 
+  --centerline-leg   `rs features --geometry centerline`: thinning and links on a synthetic road network (roads 21-24 pixels wide, so
+           the 20-pixel opening keeps them), 512 x 512, batch 16, and on the stitched 8 x 8 block cut from one such raster; the pair
+           count, the time at each candidate chunk size K, and the polygon path on the same masks, written to
+           profiles/features_centerline/bench_centerline.json (`--centerline-leg --stage-loop N`: the stages N times, for rocprofv3)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -161,6 +166,104 @@ def stitch_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+def road_raster(side, seed):
+    """One side x side class-index raster of straight roads of class 1, 21 to 24 pixels wide, at random places and angles: six
+    per 512 pixels of side (every road crosses the whole raster, so that keeps about a quarter of it road at any side)."""
+
+    rng = np.random.RandomState(seed)
+    image = np.zeros((side, side), dtype=np.uint8)
+    at = np.arange(side, dtype=np.float32)
+    for _ in range(max(2, 6 * side // 512)):
+        cy, cx, angle, width = rng.uniform(0, side), rng.uniform(0, side), rng.uniform(0, np.pi), rng.uniform(21, 24)
+        image[np.abs(((at - cx) * np.sin(angle))[None, :] - ((at - cy) * np.cos(angle))[:, None]) <= width / 2] = 1
+    return image
+
+
+def centerline_leg(args):
+    """Thinning and links beside the polygon path on the same road masks: one batch of tiles, and the stitched n x n block."""
+
+    import torch
+
+    from robosat_amd import ops
+    from robosat_amd.features import stitch_tables
+    from robosat_amd.tiles import Tile
+
+    n, size, eps, r = args.block, args.size, args.eps, args.repeat
+    batch = np.stack([road_raster(size, seed) for seed in range(args.batch)])
+    block = road_raster(n * size, 100)
+    tiles = np.stack([block[y * size:(y + 1) * size, x * size:(x + 1) * size] for x in range(n) for y in range(n)])
+    nbr, origin, _ = stitch_tables([Tile(x, y, 18) for x in range(n) for y in range(n)], (size, size))
+    dev, dev_tiles = torch.from_numpy(batch).to("cuda:0"), torch.from_numpy(tiles).to("cuda:0")
+    nbr, origin = torch.from_numpy(nbr).to("cuda:0"), torch.from_numpy(origin).to("cuda:0")
+
+    def per_tile():
+        cleaned = ops.clean_masks(dev, 1, eps, eps)
+        labels = ops.label_components(cleaned)
+        table = ops.component_table(labels, 0)
+        return table, ops.skeleton_links(ops.thin_masks(cleaned), labels, table).cpu()
+
+    def stitched():
+        table, links = ops.stitched_centerlines(dev_tiles, nbr, origin, 1, eps, eps, 0)
+        return table, links.cpu()
+
+    if args.stage_loop:
+        for _ in range(args.stage_loop):
+            per_tile()
+            stitched()
+        return
+
+    result = {"batch": args.batch, "size": size, "eps": eps, "block": n, "default_pairs_per_chunk": ops.THIN_PAIRS}
+    cleaned = ops.clean_masks(dev, 1, eps, eps)
+    labels = ops.label_components(cleaned)
+    table = ops.component_table(labels, 0)
+    skeleton, pairs = ops.thin_masks(cleaned, pairs=1, want_pairs=True)
+    links = ops.skeleton_links(skeleton, labels, table)
+    sec = timed(per_tile, r)
+    polygon = timed(lambda: device_stage(batch, eps), r)
+    result["per_tile"] = {
+        "foreground_cleaned": float(cleaned.float().mean()), "components": int(len(table)), "skeleton_pixels": int(skeleton.sum()),
+        "links": int(len(links)), "pairs": pairs, "ms_per_batch": sec * 1e3, "tiles_per_s": args.batch / sec,
+        "polygon_path_ms_per_batch": polygon * 1e3, "polygon_path_tiles_per_s": args.batch / polygon,
+        "ms_split": {"clean": timed(lambda: ops.clean_masks(dev, 1, eps, eps), r) * 1e3,
+                     "label": timed(lambda: ops.label_components(cleaned), r) * 1e3,
+                     "table": timed(lambda: ops.component_table(labels, 0), r) * 1e3,
+                     "thin": timed(lambda: ops.thin_masks(cleaned), r) * 1e3,
+                     "links": timed(lambda: ops.skeleton_links(skeleton, labels, table).cpu(), r) * 1e3},
+        "thin_ms_by_pairs_per_chunk": {str(k): timed(lambda: ops.thin_masks(cleaned, pairs=k), r) * 1e3 for k in (1, 2, 4, 8, 16, 32, 64)},
+    }
+    full = torch.ones((args.batch, size, size), dtype=torch.uint8, device="cuda:0")
+    _, full_pairs = ops.thin_masks(full, pairs=1, want_pairs=True)
+    result["full_tiles"] = {"pairs": full_pairs, "thin_ms_by_pairs_per_chunk": {
+        str(k): timed(lambda: ops.thin_masks(full, pairs=k), max(2, r // 4)) * 1e3 for k in (1, 4, 16, 64)}}
+
+    cleaned = ops.clean_masks_stitched(dev_tiles, nbr, 1, eps, eps)
+    labels = ops.stitch_labels(ops.label_components(cleaned), nbr)
+    table = ops.component_table_stitched(labels, origin, 0)
+    skeleton, pairs = ops.thin_masks(cleaned, nbr, pairs=1, want_pairs=True)
+    links = ops.skeleton_links(skeleton, labels, table, nbr, origin)
+    sec = timed(stitched, r)
+
+    def polygons():
+        table, edges = ops.stitched_features(dev_tiles, nbr, origin, 1, eps, eps, 0)
+        return edges.cpu()
+
+    polygon = timed(polygons, r)
+    result["stitched"] = {
+        "tiles": len(tiles), "components": int(len(table)), "skeleton_pixels": int(skeleton.sum()), "links": int(len(links)), "pairs": pairs,
+        "ms": sec * 1e3, "tiles_per_s": len(tiles) / sec, "polygon_path_ms": polygon * 1e3, "polygon_path_tiles_per_s": len(tiles) / polygon,
+        "ms_split": {"thin": timed(lambda: ops.thin_masks(cleaned, nbr), r) * 1e3,
+                     "thin_ignoring_seams": timed(lambda: ops.thin_masks(cleaned), r) * 1e3,
+                     "links": timed(lambda: ops.skeleton_links(skeleton, labels, table, nbr, origin).cpu(), r) * 1e3},
+        "thin_ms_by_pairs_per_chunk": {str(k): timed(lambda: ops.thin_masks(cleaned, nbr, pairs=k), r) * 1e3 for k in (1, 2, 4, 8, 16, 32, 64)},
+    }
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "features_centerline", "bench_centerline.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def device_stage(images, eps):
     import torch
 
@@ -207,11 +310,14 @@ def main():
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--stage-loop", type=int, default=0)
     ap.add_argument("--stitch-leg", action="store_true", help="only the stitched path against the per-tile path on an n x n block")
-    ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched leg's block")
+    ap.add_argument("--centerline-leg", action="store_true", help="only thinning and links, on a road network and on its n x n block")
+    ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched legs' block")
     ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
     if args.stitch_leg:
         return stitch_leg(args)
+    if args.centerline_leg:
+        return centerline_leg(args)
 
     import torch
 
