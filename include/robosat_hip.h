@@ -337,6 +337,24 @@ int rs_conv2d_fwd_phase_dt(const rs_conv_desc* d, int dtype, const void* src1, c
                            const float* scale, const float* shift, const void* residual, const void* relu_mask, void* out,
                            rs_stream_t stream);
 
+/* Split K (fp32, the 64x64 tile of the implicit-GEMM kernel, direct or phase form): a launch whose grid cannot fill the chip but
+ * whose K loop is long -- the 16x16 stage of the network -- runs as S slices of the K loop per output tile, S x the blocks; each block
+ * stores its raw fp32 accumulators to `ws` [S][rows][Cout] (rows = N*Ho*Wo; phase form: [4 parities][N*Hs*Ws]) and a second kernel,
+ * splitk_reduce_f32, sums the partials in the fixed order s = 0 .. S-1 and applies the epilogue of rs_conv2d_fwd (scale / shift,
+ * residual, ReLU; phase form: the scatter of parity rows to output pixels).  No atomics: bit-reproducible.  The slice bounds fall on
+ * 32-channel groups, so the sums do not depend on the K-chunk row size either.
+ * rs_conv2d_splitk: the S the dispatcher picks for `d` (`form` as for rs_conv2d_config: bit 0 = phase form, bit 1 = a launch with a
+ * ReLU mask / fused statistics, which never splits) and the K-chunk row size in *rowb: 0 = the launch stays unsplit (call
+ * rs_conv2d_fwd / rs_conv2d_fwd_phase_dt), S >= 1 = call rs_conv2d_fwd_splitk with a workspace of S * rows * Cout floats.  By rule S
+ * is a function of the layer's GEOMETRY only (Hs, Ws, channels, filter, stride), never of N: splitting changes the fp32 summation
+ * order, and a tile's output must not depend on the batch it travels in.  Knob "conv_splitk" (RS_CONV_SPLITK): -1 the rule, 0 never,
+ * S >= 1 every launch that can (1: one slice through the split path, bit-identical to the unsplit launch), for tests and A/B runs.
+ * rs_conv2d_fwd_splitk: `splits` must be what rs_conv2d_splitk answers for the same `d` and `form` (bit 0 only). */
+int rs_conv2d_splitk(const rs_conv_desc* d, int form, int* rowb);
+int rs_conv2d_fwd_splitk(const rs_conv_desc* d, int form, const float* src1, const float* src2, const float* weight,
+                         const float* scale, const float* shift, const float* residual, float* out, float* ws, int splits,
+                         rs_stream_t stream);
+
 /* DecoderBlock (unet.py:63-73) in fp32 as a Winograd F(2x2, 2x2) convolution on the phase form: each parity's 2x2
  * convolution on the source grid produces 2x2 blocks of outputs from 3x3 blocks of inputs with 9 multiplies instead of 16
  * (transforms with 0 / +-1 coefficients only): 9/16 of the phase form's MFMA work, 1/4 of the reference-shape count -- for

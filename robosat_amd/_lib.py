@@ -105,6 +105,8 @@ SIGNATURES = {
     "rs_pack_phase_weight_dt": (c_int, [P, P, c_int, c_int, c_int, P]),
     "rs_pack_s2_dgrad_phase_weight_dt": (c_int, [P, P, c_int, c_int, c_int, P]),
     "rs_conv2d_fwd_phase_dt": (c_int, [POINTER(ConvDesc), c_int, P, P, P, P, P, P, P, P, P]),
+    "rs_conv2d_splitk": (c_int, [POINTER(ConvDesc), c_int, POINTER(c_int)]),
+    "rs_conv2d_fwd_splitk": (c_int, [POINTER(ConvDesc), c_int, P, P, P, P, P, P, P, P, c_int, P]),
     "rs_conv2d_phase_wino_ok": (c_int, [POINTER(ConvDesc)]),
     "rs_conv2d_phase_wino_name": (c_char_p, [POINTER(ConvDesc)]),
     "rs_pack_wino_phase_weight": (c_int, [P, P, c_int, c_int, P]),

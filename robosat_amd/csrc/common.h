@@ -209,6 +209,7 @@ struct RsKnobs {
   int conv_halo = 1;           // RS_CONV_HALO: halo-once forms allowed (bf16)
   int conv_halo_min = 192;     // RS_CONV_HALO_MIN: ... for launches with at least this many blocks
   int conv_halo512 = -1;       // RS_CONV_HALO512: the 512-pixel patch: -1 by rule, 0 never, 1 wherever it can run
+  int conv_splitk = -1;        // RS_CONV_SPLITK: split K of the fp32 implicit GEMM (conv_igemm_dma.hip: pick_splitk): -1 by rule (geometry only), 0 never, S >= 1 that many slices wherever it can run
   int conv1x1_ew = -1;         // RS_CONV1X1_EW: conv1x1_ew_f32 -- -1 by rule (K <= 64), 0 never, 1 wherever it can run
   int conv1x1_np = 0;          // RS_CONV1X1_NP: conv1x1_np_f32 (fp32 1x1 with the epilogue between the next sub-tile's MFMAs): -1 by rule, 0 never, 1 wherever it can run
   int conv1x1_ew_bf16 = 0;     // RS_CONV1X1_EW_BF16: conv1x1_ew_bf16 (train-mode 1x1 forward) -- 0 never, 1 wherever it can run

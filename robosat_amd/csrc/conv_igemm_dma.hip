@@ -202,8 +202,75 @@ int pick_rowb(const rs_conv_desc* d, int es, bool phase4 = false, bool stats = f
   return 128;
 }
 
+// ---- split K (fp32, 64x64 tile) ------------------------------------------------------------------------------------------
+// How many slices of its K loop a launch runs as (0: it stays unsplit).  By rule -- knob conv_splitk = -1 -- a function of the
+// layer's GEOMETRY alone, never of N: the slices change the fp32 summation order, and a tile's output must not depend on the batch
+// it travels in.  The rule names the launches that were measured to win (profiles/splitk/ab_launch.txt): the
+// 16x16 stage, whose tiles per image are so few that no batch the network runs at fills the chip, with a long K loop.
+//   center (phase form, 2048 -> 256 on an 8x8 source: 16 tiles per image, K = 8192)   S = 4: 256 -> 1024 blocks at bs 16
+// `plain`: scale / shift / residual / ReLU epilogue only (the reduce kernel's); a forced tile other than 64x64 keeps the generic launch.
+constexpr int kMaxSplitK = 16;
+int pick_splitk(const rs_conv_desc* d, bool phase4, bool plain) {
+  const int knob = rs_knobs().conv_splitk;
+  const int ft = tuning().tile;
+  if (knob == 0 || !plain || (ft >= 0 && ft != T64x64)) return 0;
+  const long n32 = (long)(phase4 ? 4 : d->kh * d->kw) * (d->C1 + d->C2) / 32;  // 32-channel groups of the K loop: a slice holds >= 1
+  int s = knob;
+  if (knob < 0) {
+    const long tiles_per_image = (long)rs_cdiv(phase4 ? d->Hs * d->Ws : d->Ho * d->Wo, 64) * rs_cdiv(d->Cout, 64) * (phase4 ? 4 : 1);
+    s = (phase4 && tiles_per_image <= 16 && n32 >= 128) ? 4 : 0;
+  }
+  if (s > kMaxSplitK) s = kMaxSplitK;
+  return s > n32 ? (int)n32 : s;
+}
+
+// The second kernel of a split launch: out = epilogue(sum_s ws[s]) -- the partials in the fixed order s = 0 .. S-1 (no atomics: the
+// result is bit-reproducible), then what the EPI_EVAL epilogue of the kernel applies, in its order: scale / shift, residual, ReLU.
+// One 16-byte piece of couts per thread; row r of the workspace is problem row (parity, m) in the phase form, whose output pixel is
+// (n, 2a + py, 2b + px) for source pixel m = (n, a, b).
+__global__ __launch_bounds__(256) void splitk_reduce_f32(const float* __restrict__ ws, int S, long rows, int M, int Cout,
+                                                         const float* __restrict__ scale, const float* __restrict__ shift,
+                                                         const float* __restrict__ res, float* __restrict__ out, int relu, int phase,
+                                                         int HsWs, int Ws, int Ho, int Wo) {
+  const int cp = Cout >> 2;  // pieces per row
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows * cp) return;
+  const long r = i / cp;
+  const int col = (int)(i - r * cp) * 4;
+  const long slice = rows * Cout;
+  const float* src = ws + r * Cout + col;
+  f32x4 v = *reinterpret_cast<const f32x4*>(src);
+#pragma unroll 4
+  for (int s = 1; s < S; ++s) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(src + s * slice);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += t[e];
+  }
+  long opix = r;
+  if (phase) {
+    const int par = (int)(r / M), m = (int)(r - (long)par * M);
+    const int n = m / HsWs, rem = m - n * HsWs;
+    const int a = rem / Ws, b = rem - a * Ws;
+    opix = ((long)n * Ho + 2 * a + (par >> 1)) * Wo + 2 * b + (par & 1);
+  }
+  const long o = opix * Cout + col;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = v[e] * (scale ? scale[col + e] : 1.f) + (shift ? shift[col + e] : 0.f);
+  if (res) {
+    const f32x4 t = *reinterpret_cast<const f32x4*>(res + o);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += t[e];
+  }
+  if (relu) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+  }
+  *reinterpret_cast<f32x4*>(out + o) = v;
+}
+
 void launch(int rowb, bool phase4, int epi, int tile, int grid, hipStream_t s, const ConvArgsT<float>& a) {
-  if (phase4) rs_conv_launch_f32_phase_eval(tile, rowb, grid, s, a);
+  if (epi == EPI_SPLITK) (phase4 ? rs_conv_launch_f32_phase_splitk : rs_conv_launch_f32_plain_splitk)(tile, rowb, grid, s, a);
+  else if (phase4) rs_conv_launch_f32_phase_eval(tile, rowb, grid, s, a);
   else if (epi == EPI_STATS) rs_conv_launch_f32_plain_stats(tile, rowb, grid, s, a);
   else if (epi == EPI_BWD) rs_conv_launch_f32_plain_bwd(tile, rowb, grid, s, a);
   else rs_conv_launch_f32_plain_eval(tile, rowb, grid, s, a);
@@ -309,8 +376,10 @@ int conv_fwd(const rs_conv_desc* d, const void* src1, const void* src2, const vo
              const float* shift, const void* residual, const void* relu_mask, void* out, rs_stream_t stream,
              float* stats = nullptr, const void* bn_y = nullptr, const float* bn_mean = nullptr,
              const float* bn_invstd = nullptr, bool phase4 = false, void* out2 = nullptr, const void* mask2 = nullptr,
-             int csplit = 0, const unsigned char* mask_bits = nullptr) {
+             int csplit = 0, const unsigned char* mask_bits = nullptr, float* ws = nullptr, int splits = 0) {
   if (!valid(d) || !src1 || !weight || !out) return RS_EINVAL;
+  // split K: asked for with a workspace (rs_conv2d_fwd_splitk); `splits` is what pick_splitk answers for this launch
+  if (ws && (sizeof(T) != 4 || stats || relu_mask || out2 || mask_bits || splits < 1 || splits != pick_splitk(d, phase4, true))) return RS_EINVAL;
   if (mask_bits && (relu_mask || !bn_y || (d->Cout & 7))) return RS_EINVAL;  // (bits: data gradients into a BatchNorm only)
   if (out2 && (csplit <= 0 || csplit >= d->Cout || residual || stats)) return RS_EINVAL;
   if (phase4 && (!phase_ok(d) || stats)) return RS_EINVAL;
@@ -379,6 +448,10 @@ int conv_fwd(const rs_conv_desc* d, const void* src1, const void* src2, const vo
   a.Kw = a.nk * kc;
   a.relu = d->relu;
   a.tpx = a.tpi = 0;
+  if (ws) {  // (in the storage of stats / csplit, both unset here)
+    a.ws = ws;
+    a.ksplit = splits;
+  }
 
   // epilogue kind: forward with fused BatchNorm statistics takes no other epilogue input; the data gradient into a
   // BatchNorm takes residual / mask but no scale / shift / ReLU
@@ -390,6 +463,17 @@ int conv_fwd(const rs_conv_desc* d, const void* src1, const void* src2, const vo
     if (epi == EPI_BWD && (!bn_mean || !bn_invstd)) return RS_EINVAL;
   }
   if constexpr (sizeof(T) == 4) {
+    if (ws) {  // S slices of the K loop on the 64x64 tile, then the reduce kernel with the launch's epilogue
+      a.ntiles = rs_cdiv(d->Cout, 64);
+      const long rows = M * (phase4 ? 4 : 1);
+      const long grid = (long)rs_cdiv(M, 64) * a.ntiles * (phase4 ? 4 : 1) * splits;
+      if (grid >= (1L << 31) || rows * d->Cout / 4 >= (1L << 31) * 256) return RS_EINVAL;
+      hipStream_t s = (hipStream_t)stream;
+      launch(kc == kc128 ? 128 : 64, phase4, EPI_SPLITK, T64x64, (int)grid, s, a);
+      splitk_reduce_f32<<<(unsigned)rs_cdiv(rows * (d->Cout / 4), 256), 256, 0, s>>>(ws, splits, rows, (int)M, d->Cout, scale, shift, a.res, a.out, d->relu,
+                                                                                phase4 ? 1 : 0, d->Hs * d->Ws, d->Ws, d->Ho, d->Wo);
+      return RS_LAUNCH_RESULT();
+    }
     if (ew_f32_mode(d, phase4, epi == EPI_EVAL && !relu_mask && !out2 && !mask_bits)) return rs_conv1x1_ew_f32_launch(a, (hipStream_t)stream);
 #ifdef RS_EXP_BUILD  // (`make EXP=1`: measurement only -- parity yes, speed no: profiles/r06/np_1x1.txt)
     if (np_f32_mode(d, phase4, epi == EPI_EVAL && !relu_mask && !out2 && !mask_bits, residual != nullptr)) return rs_conv1x1_np_f32_launch(a, (hipStream_t)stream);
@@ -488,6 +572,22 @@ extern "C" int rs_conv2d_config(const rs_conv_desc* d, int es, int form, int* ti
   if (tile) *tile = pick_tile(d, phase4 != 0, es);
   if (rowb) *rowb = (can128 && pick_rowb(d, es, phase4 != 0) == 128) ? 128 : 64;
   return 0;
+}
+
+extern "C" int rs_conv2d_splitk(const rs_conv_desc* d, int form, int* rowb) {
+  if (form < 0 || form > 3) return RS_EINVAL;
+  const bool phase4 = (form & 1) != 0;
+  if (!valid(d) || (phase4 && !phase_ok(d))) return RS_EINVAL;
+  if (rowb) *rowb = pick_rowb(d, 4, phase4) == 128 ? 128 : 64;  // (fp32: C1, C2 % 32 == 0, so 128-byte rows are always possible)
+  return pick_splitk(d, phase4, (form & 2) == 0);
+}
+
+extern "C" int rs_conv2d_fwd_splitk(const rs_conv_desc* d, int form, const float* src1, const float* src2, const float* weight,
+                                    const float* scale, const float* shift, const float* residual, float* out, float* ws, int splits,
+                                    rs_stream_t stream) {
+  if (form < 0 || form > 1 || !ws || (d && d->stem)) return RS_EINVAL;
+  return conv_fwd<float>(d, src1, src2, weight, scale, shift, residual, nullptr, out, stream, nullptr, nullptr, nullptr, nullptr,
+                         form == 1, nullptr, nullptr, 0, nullptr, ws, splits);
 }
 
 // ---- phase form of the decoder convolutions ---------------------------------------------------------------------------

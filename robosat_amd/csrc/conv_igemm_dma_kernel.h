@@ -10,7 +10,7 @@
 
 #include "lds_dma.h"
 
-enum { EPI_EVAL = 0, EPI_STATS = 1, EPI_BWD = 2 };
+enum { EPI_EVAL = 0, EPI_STATS = 1, EPI_BWD = 2, EPI_SPLITK = 3 };
 constexpr int kMaxK = 4;  // filter height / width up to 4 (the 4x4 stride-2 data gradient of an upsampled 3x3)
 // (index 4 is the fp32 stem kernel of conv_igemm.hip: the two files share the index space of rs_conv2d_tile_name)
 // T256x256: 8-wave blocks, one per CU, bf16 only (see pick_tile); T256x128: 8 waves as 4 x 2 (64x64 wave tiles)
@@ -36,7 +36,14 @@ struct ConvArgsT {
   const T* res;
   const T* mask;
   T* out;
-  float* stats;  // optional [M tiles][2][Cout]: per-tile sum / sum of squares of the STORED output (train-mode BatchNorm)
+  // EPI_SPLITK (fp32): block (m, n, parity, s) walks the K-chunks [s * nk / ksplit, (s + 1) * nk / ksplit) -- the bounds fall on
+  // 32-channel groups whatever the chunk size -- and stores its raw accumulator tile to ws [ksplit][parities * M][Cout];
+  // splitk_reduce_f32 (conv_igemm_dma.hip) sums the partials and applies the epilogue.  `ws` and `ksplit` share the storage of
+  // `stats` and `csplit`, which such a launch never has: the argument block of every other launch is what it was.
+  union {
+    float* stats;  // optional [M tiles][2][Cout]: per-tile sum / sum of squares of the STORED output (train-mode BatchNorm)
+    float* ws;
+  };
   // optional (data-gradient launches, with stats): the output is g = d loss / d z of a BatchNorm layer (ReLU mask
   // applied); the partial rows then hold sum g and sum g * xhat, xhat = (bn_y - bn_mean) * bn_invstd: the two reductions
   // of BatchNorm's backward, which otherwise cost a separate pass over (dz, z, y)
@@ -51,7 +58,10 @@ struct ConvArgsT {
   // stride csplit, `mask`), couts [csplit, Cout) to `out2` (row stride Cout - csplit, `mask2`); csplit % BN == 0
   T* out2;
   const T* mask2;
-  int csplit;
+  union {
+    int csplit;
+    int ksplit;
+  };
   int N, Hs, Ws, C1, C2, Hv, Wv, ups;
   int kh, kw, stride, pad, Ho, Wo, Cout;
   int M, cpt, nk, Kw, relu, ntiles, ntaps, phase4;
@@ -66,6 +76,8 @@ RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_eval, float);
 RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_stats, float);
 RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_bwd, float);
 RS_CONV_LAUNCHER(rs_conv_launch_f32_phase_eval, float);
+RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_splitk, float);  // (the 64x64 tile only: `tile` is ignored)
+RS_CONV_LAUNCHER(rs_conv_launch_f32_phase_splitk, float);
 RS_CONV_LAUNCHER(rs_conv_launch_bf16_plain_eval, bf16_t);
 RS_CONV_LAUNCHER(rs_conv_launch_bf16_plain_stats, bf16_t);
 RS_CONV_LAUNCHER(rs_conv_launch_bf16_plain_bwd, bf16_t);
@@ -181,6 +193,7 @@ constexpr int conv_waves_per_simd(int nw, int bm, int bn, int rowb, int es, int 
 //   EPI_EVAL  : scale/shift, residual, ReLU, ReLU mask, two-destination store (predict, and every plain data gradient)
 //   EPI_STATS : raw output + per-tile BatchNorm partial sums (sum y, sum y^2): the train-mode forward
 //   EPI_BWD   : residual, ReLU mask, + partial sums (sum g, sum g * xhat) against bn_y: data gradient into a BatchNorm
+//   EPI_SPLITK: a slice of the K loop; the raw fp32 accumulators go to the workspace (ConvArgsT::ws), no epilogue operand
 // KO (measurement builds only, conv_halo_ko.hip; results are WRONG for KO != 0): knock-outs of the halo main loop that say
 // where its time goes -- 1: no waits / barriers, 2: no DMA, 3: no fragment reads (one set reused), 4: no MFMAs.
 template <typename T, int BM, int BN, int WGM, int WGN, int ROWB, bool PHASE, int EPI, int HALO = HALO_NONE, int KO = 0>
@@ -225,6 +238,9 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   static_assert(!HL || (sizeof(T) == 2 && NW == 8 && (IB % NW) == 0 && WM % 32 == 0 && HNT >= 4 && KS % 2 == 0 && (HALO == HALO_PHASE) == PHASE),
                 "halo forms: bf16, 8 waves, whole weight DMA instructions per wave");
   static_assert(MAINB + TABN * 4 <= 160 * 1024, "LDS");
+  constexpr bool SPLIT = EPI == EPI_SPLITK;
+  constexpr bool STATS = EPI == EPI_STATS || EPI == EPI_BWD;  // the epilogues with BatchNorm partial sums
+  static_assert(!SPLIT || (ES == 4 && !HL), "split K: the fp32 implicit-GEMM forms");
 
   __shared__ __attribute__((aligned(16))) unsigned char smem[MAINB + TABN * 4];
   int* taby = reinterpret_cast<int*>(smem + MAINB);  // [kh][BM]: ((n - nfirst)*Hs + iy) * Ws, or -1
@@ -246,6 +262,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
     py = (bid >> 1) & 1;
     px = bid & 1;
     bid >>= 2;
+  }
+  int ksl = 0;  // split K: this block's slice of the K loop (slices outermost: the blocks of a slice share its weights)
+  if constexpr (SPLIT) {
+    const int tps = (int)(gridDim.x >> (PHASE ? 2 : 0)) / p.ksplit;  // tiles per slice
+    ksl = bid / tps;
+    bid -= ksl * tps;
   }
   const int mt = bid / p.ntiles, nt = bid - mt * p.ntiles;
   const int m0 = mt * BM, n0 = nt * BN;
@@ -341,6 +363,20 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   // for the phase form -- same fabric traffic per launch (FETCH_SIZE), same time -- and dropped: its summation order
   // depends on the chunk size, which depends on the batch, and predictions must not.)
   int lr = 0, ls = 0, lc = 0, lk = 0;
+  int nkl = p.nk;  // chunks this block walks
+  if constexpr (SPLIT) {
+    // slice bounds in 32-channel groups (u32 = 1 for 32-channel chunks, 2 for 16-channel ones): the same K ranges, hence the
+    // same sums, with either chunk size
+    const int u32 = KC == 32 ? 1 : 2, n32 = p.nk / u32;
+    const int k0 = (int)((long)ksl * n32 / p.ksplit) * u32, k1 = (int)((long)(ksl + 1) * n32 / p.ksplit) * u32;
+    nkl = k1 - k0;
+    lk = k0;
+    const int tap = k0 / p.cpt;
+    lc = k0 - tap * p.cpt;
+    lr = tap / p.kw;
+    ls = tap - lr * p.kw;
+    if (lc != 0) load_tap(pbase, lr, ls, lc * KC < p.C1);  // (begin_chunk rebuilds the offsets only where a tap or a source begins)
+  }
   unsigned int fL = lds0;
   __amdgpu_buffer_rsrc_t frs = rsrc1;
   int fsa = 0, fsb = 0;
@@ -397,7 +433,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   //      first waits for ITS OWN DMA instructions of chunk k, the barrier publishes everybody's, and only then the buffer
   //      freed by chunk k-1 is refilled.
   if constexpr (!HL) {
-  if (p.nk > 0) {
+  if (nkl > 0) {
     begin_chunk(0);
 #pragma unroll
     for (int q = 0; q < NI; ++q) issue_piece(q);
@@ -439,8 +475,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   };
   if constexpr (!HL) {
     int kc = 0;
-    for (; kc < p.nk - 1; ++kc) chunk(kc, std::true_type());
-    for (; kc < p.nk; ++kc) chunk(kc, std::false_type());
+    for (; kc < nkl - 1; ++kc) chunk(kc, std::true_type());
+    for (; kc < nkl; ++kc) chunk(kc, std::false_type());
   } else {
     // ================================ halo-once main loop ===================================================================
     // K = K-groups q (a 128-byte channel chunk of one source plane; HALO_DG4: 4 planes x chunks, else the chunks of the
@@ -684,6 +720,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
     }
   }
   T* outp = p.out;  // destination of this block's couts (block-uniform: a tile never straddles csplit)
+  if constexpr (SPLIT) outp = p.ws;  // rows = (slice, parity, problem row m): see load_group
   const T* maskp = p.mask;
   int ostride = p.Cout, ocol = col;
   if (EPI == EPI_EVAL && p.out2) {
@@ -715,7 +752,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   constexpr int NIT = WN / (2 * EPP);  // rows per thread per pass = WGM*32 / RPI
   constexpr int G = (ES == 4 && EPI == EPI_BWD) ? 1 : 2;  // (up to 3 tensors x G x 4 registers of loads in flight per thread)
   static_assert(NIT * RPI == WGM * 32 && NIT % G == 0, "row groups tile the pass");
-  const bool has_res = EPI != EPI_STATS && p.res != nullptr, has_mask = EPI != EPI_STATS && maskp != nullptr;
+  const bool has_res = EPI != EPI_STATS && !SPLIT && p.res != nullptr, has_mask = EPI != EPI_STATS && !SPLIT && maskp != nullptr;
   const bool has_bits = EPI == EPI_BWD && p.mask_bits != nullptr;
   constexpr bool has_bny = EPI == EPI_BWD;
   auto load_group = [&](int tm, int g0, long (&o)[G], bool (&ok)[G], u32x4 (&rr_)[G], u32x4 (&rm_)[G], u32x4 (&ry_)[G])
@@ -726,7 +763,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
       const int row = (lrow >> 5) * WM + 32 * tm + (lrow & 31);  // tile row of pass-local row lrow
       const int opix = orow[row];
       ok[i] = opix >= 0 && cvalid;
-      o[i] = ok[i] ? (long)opix * ostride + ocol : 0;
+      if constexpr (SPLIT) o[i] = ok[i] ? (((long)ksl * (PHASE ? 4 : 1) + (2 * py + px)) * p.M + m0 + row) * p.Cout + col : 0;
+      else o[i] = ok[i] ? (long)opix * ostride + ocol : 0;
     }
     if (has_res) {
 #pragma unroll
@@ -794,7 +832,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
         }
       }
       if (ok[i]) Piece<T>::store(outp + o[i], v);
-      if constexpr (EPI != EPI_EVAL) {
+      if constexpr (STATS) {
         float w[EPP];
         Piece<T>::round(v, w);  // statistics of the values as stored (bf16-rounded on the bf16 path)
         const float keep = ok[i] ? 1.f : 0.f;
@@ -846,7 +884,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
       finish_group(g0, o, ok, rr_, rm_, ry_);
     }
   }
-  if constexpr (EPI != EPI_EVAL) {  // block reduction over the RPI row lanes -> one partial row per M tile
+  if constexpr (STATS) {  // block reduction over the RPI row lanes -> one partial row per M tile
     __syncthreads();
     float* r0 = lds;             // [RPI][BN]
     float* r1 = lds + RPI * BN;  // [RPI][BN]
@@ -885,6 +923,12 @@ void launch_rows(int tile, int grid, hipStream_t s, const ConvArgsT<T>& a) {
   }
 }
 
+// split K (EPI_SPLITK): the 64x64 tile -- the launches that want it are the ones too small to fill the chip with any other
+template <int ROWB, bool PHASE>
+void launch_splitk(int grid, hipStream_t s, const ConvArgsT<float>& a) {
+  conv_igemm_dma<float, 64, 64, 2, 2, ROWB, PHASE, EPI_SPLITK><<<grid, 256, 0, s>>>(a);
+}
+
 }  // namespace
 
 // halo-once forms: 8 waves as 4 x 2 over a 256-pixel patch (8 rows x 32) x BN couts with 128-byte rows (64-channel
@@ -902,5 +946,10 @@ void launch_halo(int bn, int grid, hipStream_t s, const ConvArgsT<bf16_t>& a) {
   void name(int tile, int rowb, int grid, hipStream_t s, const ConvArgsT<T>& a) {               \
     if (rowb == 128) launch_rows<T, 128, PHASE, EPI>(tile, grid, s, a);                         \
     else launch_rows<T, 64, PHASE, EPI>(tile, grid, s, a);                                      \
+  }
+#define RS_CONV_DEFINE_SPLITK_LAUNCHER(name, PHASE)                                              \
+  void name(int, int rowb, int grid, hipStream_t s, const ConvArgsT<float>& a) {                \
+    if (rowb == 128) launch_splitk<128, PHASE>(grid, s, a);                                     \
+    else launch_splitk<64, PHASE>(grid, s, a);                                                  \
   }
 #endif  // RS_CONV_INSTANTIATE

@@ -122,6 +122,37 @@ def _partial(rows_fn, d, device, *args):
     return torch.empty((rows, 2, d.Cout), device=device, dtype=torch.float32)
 
 
+def _splitk(d, device, phase=False, plain=True):
+    """Workspace of a split-K launch (``rs_conv2d_splitk``: the dispatcher's choice for the layer's geometry, fp32 only): the fp32
+    buffer [S, rows, Cout] of the slices' partial sums and the launch's K-chunk row size, or (None, 0) when the launch stays unsplit."""
+
+    rowb = ctypes.c_int(0)
+    s = _lib.lib().rs_conv2d_splitk(ctypes.byref(d), int(bool(phase)) | (0 if plain else 2), ctypes.byref(rowb))
+    if s < 0:
+        check(s, "rs_conv2d_splitk")
+    if s == 0:
+        return None, 0
+    return torch.empty((s, d.N * d.Ho * d.Wo, d.Cout), device=device, dtype=torch.float32), rowb.value
+
+
+def _splitk_name(ws, rowb, phase=False, split=False):
+    """Report name of a split-K launch: the 64x64 tile of the implicit-GEMM kernel it runs (the name the roofline tables group
+    it under); ``split``: with the number of slices, ``conv_igemm_f32<[phase,]64x64,r<row bytes>,k<S>>``."""
+
+    return "conv_igemm_f32<{}64x64,r{}{}>".format("phase," if phase else "", rowb, ",k{}".format(ws.shape[0]) if split else "")
+
+
+def conv_splitk_name(d, phase=False, plain=True):
+    """``conv_igemm_f32<[phase,]64x64,r<row bytes>,k<S>>`` when the fp32 launch ``d`` runs as S slices of its K loop
+    (``rs_conv2d_splitk``: by the layer's geometry, or knob ``conv_splitk``), else None.  Allocates nothing."""
+
+    rowb = ctypes.c_int(0)
+    s = _lib.lib().rs_conv2d_splitk(ctypes.byref(d), int(bool(phase)) | (0 if plain else 2), ctypes.byref(rowb))
+    if s < 0:
+        check(s, "rs_conv2d_splitk")
+    return "conv_igemm_f32<{}64x64,r{},k{}>".format("phase," if phase else "", rowb.value, s) if s else None
+
+
 def conv_flops(d):
     """Algorithmic FLOPs of one launch: 2*N*Cout*Cin*kh*kw*Ho*Wo on the reference's shapes."""
 
@@ -176,17 +207,23 @@ def conv2d(src1, weight, src2=None, ups=0, stride=1, pad=0, scale=None, shift=No
         assert residual.shape == out.shape
     if relu_mask is not None:
         assert relu_mask.shape == out.shape
+    ws, ws_rowb = (None, 0) if bf or stem else _splitk(d, src1.device, plain=relu_mask is None)
     ev = _start()
-    _call("rs_conv2d_fwd_bf16" if bf else "rs_conv2d_fwd", ctypes.byref(d), _dev(src1, "src1", act), _dev(src2, "src2", act),
-          _dev(weight, "weight", act), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act),
-          _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
+    if ws is not None:
+        _call("rs_conv2d_fwd_splitk", ctypes.byref(d), 0, _dev(src1, "src1"), _dev(src2, "src2"), _dev(weight, "weight"), _dev(scale, "scale"),
+              _dev(shift, "shift"), _dev(residual, "residual"), _dev(out, "out"), _dev(ws, "ws"), ws.shape[0], _stream())
+    else:
+        _call("rs_conv2d_fwd_bf16" if bf else "rs_conv2d_fwd", ctypes.byref(d), _dev(src1, "src1", act), _dev(src2, "src2", act),
+              _dev(weight, "weight", act), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act),
+              _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
     if ev:
         _stop(ev)
-        name = conv_tile_name(d, bf, plain=relu_mask is None)
+        name = conv_tile_name(d, bf, plain=relu_mask is None) if ws is None else _splitk_name(ws, ws_rowb)
         if alg_scale != 1.0 and not name.startswith(("conv_thin", "conv_halo")):  # phase-form data gradient: 16 taps at source resolution stand for 9 at the upsampled one
             name = name.replace("<", "<dgrad4x4,")
         _record(ev, name, conv_flops(d) * alg_scale, _shape(d),
-                conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)), conv_flops(d))
+                conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)) + (0 if ws is None else 8 * ws.numel()),
+                conv_flops(d))
     return out
 
 
@@ -367,14 +404,20 @@ def conv2d_phase(src1, weight_phase, src2=None, scale=None, shift=None, residual
     act = src1.dtype
     d = _phase_desc(n, hs, ws, c1, c2, cout, relu)
     out = torch.empty((n, 2 * hs, 2 * ws, cout), device=src1.device, dtype=act)
+    ws, ws_rowb = (None, 0) if act == BF16 else _splitk(d, src1.device, phase=True, plain=relu_mask is None)
     ev = _start()
-    _call("rs_conv2d_fwd_phase_dt", ctypes.byref(d), _dt(src1), _dev(src1, "src1", act), _dev(src2, "src2", act),
-          _dev(weight_phase, "weight", act), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act),
-          _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
+    if ws is not None:
+        _call("rs_conv2d_fwd_splitk", ctypes.byref(d), 1, _dev(src1, "src1"), _dev(src2, "src2"), _dev(weight_phase, "weight"),
+              _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual"), _dev(out, "out"), _dev(ws, "ws"), ws.shape[0], _stream())
+    else:
+        _call("rs_conv2d_fwd_phase_dt", ctypes.byref(d), _dt(src1), _dev(src1, "src1", act), _dev(src2, "src2", act),
+              _dev(weight_phase, "weight", act), _dev(scale, "scale"), _dev(shift, "shift"), _dev(residual, "residual", act),
+              _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
     if ev:
         _stop(ev)
-        _record(ev, conv_tile_name(d, act == BF16, phase=True), conv_flops(d), _shape(d),
-                conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)), conv_flops(d) * 4.0 / 9.0)
+        _record(ev, conv_tile_name(d, act == BF16, phase=True) if ws is None else _splitk_name(ws, ws_rowb, phase=True), conv_flops(d), _shape(d),
+                conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)) + (0 if ws is None else 8 * ws.numel()),
+                conv_flops(d) * 4.0 / 9.0)
     return out
 
 
