@@ -662,6 +662,23 @@ int rs_features_edges_stitched(const int32_t* labels, const int32_t* nbr, const 
                                uint8_t* keep, int32_t* edges, long capacity, int32_t* counter, int T, int H, int W,
                                rs_stream_t stream);
 
+/* ---- overlap table of two label rasters (`rs features --dedupe`) ----
+ * labels_a, labels_b: int32 [pixels] each, canonical labels as rs_features_label or rs_features_stitch_labels write them, 0 =
+ * background.  `group` = pixels per independent raster (H*W for per-tile labels, T*H*W for stitched ones; pixels % group == 0),
+ * raster = p / group.  One row [raster, label_a, label_b, count] int32 per distinct triple with at least one pixel p where
+ * labels_a[p] != 0 && labels_b[p] != 0; count = the number of such pixels; rows in no particular order, and, counts being
+ * integers, a pure function of the inputs once sorted.  The pairs are summed in an open-addressing hash table of
+ * S = max(16, the power of two >= 2 * capacity) slots in `workspace` (rs_features_overlaps_workspace_bytes(capacity) = 12 * S
+ * bytes, 8-byte aligned, zeroed by the call).  counters (int32 [2], device): [0] = distinct triples in the table, counted past
+ * `capacity`, rows written only below it; [1] != 0: a probe sequence ran out (the table is full, or 1024 slots in a row are) and
+ * pairs were left out.  The rows are complete iff counters[1] == 0 && counters[0] <= capacity.  With counters[1] == 0 alone
+ * counters[0] is the exact number of rows: call again with capacity >= counters[0]; with counters[1] != 0 call again with a several
+ * times larger capacity.  capacity 0 (rows may be NULL) only counts, in a table of 16 slots.  capacity <= 2^29, pixels < 2^29;
+ * RS_EINVAL otherwise.  No workgroup waits for another; the probe loop is bounded by min(S, 1024). */
+long rs_features_overlaps_workspace_bytes(long capacity);
+int rs_features_overlaps(const int32_t* labels_a, const int32_t* labels_b, void* workspace, int32_t* rows, long capacity,
+                         int32_t* counters, long pixels, long group, rs_stream_t stream);
+
 /* ---- centerlines: skeleton and links (`rs features --geometry centerline`) ----
  * Thinning is the Guo-Hall two-subiteration parallel algorithm (CACM 32(3), 1989).  With p2..p9 = the N, NE, E, SE, S, SW, W, NW
  * neighbours of a set pixel p, a pixel outside the raster reading 0:

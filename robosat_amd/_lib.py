@@ -164,6 +164,9 @@ SIGNATURES = {
     "rs_features_stitch_labels": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "rs_features_components_stitched": (c_int, [P, P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, P]),
     "rs_features_edges_stitched": (c_int, [P, P, P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),
+    # overlap table of two label rasters (rs features --dedupe)
+    "rs_features_overlaps_workspace_bytes": (c_long, [c_long]),
+    "rs_features_overlaps": (c_int, [P, P, P, P, c_long, P, c_long, c_long, P]),
     # centerlines: Guo-Hall thinning, skeleton links
     "rs_features_thin": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rs_features_skeleton_links": (c_int, [P, P, P, P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),

@@ -10,6 +10,8 @@
 //                           the root of a component is its smallest y*W+x, so label = root + 1 is canonical.
 //   rs_features_components  roots -> slots, area / bounding box per slot by integer atomics, min_area filter, compaction.
 //   rs_features_edges       directed unit boundary edges of the kept components, compacted by one atomic per wave.
+//   rs_features_overlaps    two label rasters -> (raster, label_a, label_b, shared pixels) through a hash table in global memory,
+//                           equal pairs merged per thread, per wave and per block first (`rs features --dedupe`).
 // Stitched form (all tiles of a zoom level as one sparse raster; tables nbr [T][8] and origin [T][2] from the host):
 //   rs_features_halo            tile + apron of A pixels from its 8 neighbours (A = reach of open + close), and the crop back.
 //   rs_features_stitch_labels   per-tile canonical labels -> global index space, unions across right / down seams, flatten.
@@ -674,6 +676,186 @@ __global__ __launch_bounds__(256) void links_emit_kernel(const uint8_t* __restri
     }
 }
 
+// ---- overlap table of two label rasters (`rs features --dedupe`) -------------------------------------------------------------
+// An open-addressing table in global memory: keys [S] uint64 = (raster * group + label_a) << 32 | label_b (never 0: label_a >= 1),
+// then counts [S] int32; S a power of two >= 2 * capacity, linear probing from a mixed hash.  A slot is claimed by a 64-bit
+// atomicCAS against 0 and counted by atomicAdd.  Masks are runs of one pair (a whole tile can be a single pair), so equal keys are
+// merged before the table sees them: a thread owns kOvRun consecutive pixels and merges equal neighbours; then, kOvRounds times,
+// the first lane of the wave that still holds a key broadcasts it, every lane hands over what it holds of that key, the wave sums
+// it (shuffles) and that one lane adds it; the first round also merges the block's four waves through LDS.  What is left after the
+// rounds (a wave over many small pairs) goes to the table per lane.
+constexpr int kOvRun = 4;  // (one 16-byte load per raster; the code below spells out four keys)
+constexpr int kOvRounds = 4;
+constexpr long kOvMinSlots = 16;
+constexpr int kOvMaxProbe = 1024;  // (at a load of 1/2 a probe sequence of a mixed hash is tens of slots at the very most)
+
+long overlap_slots(long capacity) {
+  long s = kOvMinSlots;
+  while (s < 2 * capacity) s <<= 1;
+  return s;
+}
+
+__device__ __forceinline__ unsigned long long ov_mix(unsigned long long k) {  // (the finaliser of splitmix64)
+  k ^= k >> 30;
+  k *= 0xbf58476d1ce4e5b9ull;
+  k ^= k >> 27;
+  k *= 0x94d049bb133111ebull;
+  return k ^ (k >> 31);
+}
+
+// counts[slot of key] += n.  The probe loop is bounded by `probes` <= S; a probe that runs out raises counters[1], and once it is
+// raised nobody probes any more (the rows of that call are void: the caller comes back with a larger table).
+__device__ __forceinline__ void ov_add(unsigned long long* keys, int* counts, int* counters, unsigned long long mask, int probes,
+                                       unsigned long long key, int n) {
+  if (__hip_atomic_load(&counters[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  unsigned long long i = ov_mix(key) & mask;
+  for (int it = 0; it < probes; ++it) {
+    unsigned long long cur = __hip_atomic_load(&keys[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (cur == 0ull) cur = atomicCAS(&keys[i], 0ull, key);  // (a slot never changes once it holds a key)
+    if (cur == 0ull || cur == key) {
+      atomicAdd(&counts[i], n);
+      return;
+    }
+    i = (i + 1) & mask;
+  }
+  atomicAdd(&counters[1], 1);
+}
+
+__global__ __launch_bounds__(256) void overlaps_count_kernel(const int* __restrict__ A, const int* __restrict__ B, unsigned long long* keys,
+                                                             int* counts, int* counters, unsigned long long mask, int probes, long pixels,
+                                                             long group, int vec) {
+  const long p0 = ((long)blockIdx.x * 256 + threadIdx.x) * kOvRun;
+  const int lane = threadIdx.x & 63;
+  int a[kOvRun], b[kOvRun];
+  if (vec && p0 + kOvRun <= pixels) {
+    const int4 va = *reinterpret_cast<const int4*>(A + p0), vb = *reinterpret_cast<const int4*>(B + p0);
+    a[0] = va.x, a[1] = va.y, a[2] = va.z, a[3] = va.w;
+    b[0] = vb.x, b[1] = vb.y, b[2] = vb.z, b[3] = vb.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < kOvRun; ++j) {
+      const bool in = p0 + j < pixels;
+      a[j] = in ? A[p0 + j] : 0;
+      b[j] = in ? B[p0 + j] : 0;
+    }
+  }
+  // (no early return: every lane reaches the ballots and shuffles below)
+  unsigned long long key[kOvRun];
+  int cnt[kOvRun];
+  const long r0 = p0 < pixels ? p0 / group : 0;
+  const bool one_raster = p0 + kOvRun <= (r0 + 1) * group;
+#pragma unroll
+  for (int j = 0; j < kOvRun; ++j) {
+    const long raster = one_raster ? r0 : (p0 + j) / group;
+    const bool both = a[j] != 0 && b[j] != 0;
+    key[j] = both ? (unsigned long long)(unsigned int)(raster * group + a[j]) << 32 | (unsigned int)b[j] : 0ull;
+    cnt[j] = both ? 1 : 0;
+  }
+#pragma unroll
+  for (int j = 1; j < kOvRun; ++j)
+    if (key[j] != 0ull && key[j] == key[j - 1]) {
+      cnt[j] += cnt[j - 1];
+      key[j - 1] = 0ull;
+    }
+  // round 0 also merges across the block's four waves through LDS (a tile that is one pair: one atomic per 1024 pixels)
+  __shared__ unsigned long long wave_key[4];
+  __shared__ int wave_cnt[4];
+  const int wave = threadIdx.x >> 6;
+  for (int round = 0; round < kOvRounds; ++round) {
+    const unsigned long long mine = key[0] ? key[0] : key[1] ? key[1] : key[2] ? key[2] : key[3];
+    const unsigned long long who = __ballot(mine != 0ull);
+    if (!who && round > 0) return;  // (uniform; round 0 goes on to the barrier)
+    const int leader = who ? __ffsll((long long)who) - 1 : 0;
+    const unsigned int hi = (unsigned int)__shfl((int)(mine >> 32), leader, 64), lo = (unsigned int)__shfl((int)mine, leader, 64);
+    const unsigned long long k = (unsigned long long)hi << 32 | lo;  // (0 where the wave holds nothing: matches no lane's key)
+    int n = 0;
+#pragma unroll
+    for (int j = 0; j < kOvRun; ++j)
+      if (k != 0ull && key[j] == k) {
+        n += cnt[j];
+        key[j] = 0ull;
+      }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    if (round == 0) {
+      if (lane == 0) {
+        wave_key[wave] = k;
+        wave_cnt[wave] = n;
+      }
+      rs_lds_writes_done();
+      __syncthreads();
+      if (!who) return;  // (uniform)
+      if (lane == leader) {  // the first wave of the block that holds k adds for all of them
+        bool first = true;
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+          if (wave_key[w] == k) {
+            first = first && w >= wave;
+            total += wave_cnt[w];
+          }
+        if (first) ov_add(keys, counts, counters, mask, probes, k, total);
+      }
+    } else if (lane == leader) {
+      ov_add(keys, counts, counters, mask, probes, k, n);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kOvRun; ++j)
+    if (key[j] != 0ull) ov_add(keys, counts, counters, mask, probes, key[j], cnt[j]);
+}
+
+// Slots in use -> rows [raster, label_a, label_b, count]: a block of 256 threads takes 256 * kOvRowsRun slots and draws its rows with
+// one atomic (one per wave serialised the waves of a large table on the one counter); counters[0] counts every slot in use.
+constexpr int kOvRowsRun = 8;
+
+__global__ __launch_bounds__(256) void overlaps_rows_kernel(const unsigned long long* __restrict__ keys, const int* __restrict__ counts,
+                                                            int* rows, long capacity, int* counters, long slots, long group) {
+  __shared__ int wave_total[4];
+  __shared__ int block_base;
+  const long first = (long)blockIdx.x * (256 * kOvRowsRun) + threadIdx.x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned long long key[kOvRowsRun];
+  int n = 0;
+#pragma unroll
+  for (int j = 0; j < kOvRowsRun; ++j) {
+    const long i = first + j * 256;
+    key[j] = i < slots ? keys[i] : 0ull;
+    n += key[j] != 0ull ? 1 : 0;
+  }
+  int incl = n;  // inclusive prefix sum over the wave
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int v = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += v;
+  }
+  if (lane == 63) wave_total[wave] = incl;
+  rs_lds_writes_done();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int total = wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
+    block_base = total ? atomicAdd(&counters[0], total) : 0;
+  }
+  rs_lds_writes_done();
+  __syncthreads();
+  long k = (long)block_base + incl - n;
+  for (int w = 0; w < wave; ++w) k += wave_total[w];
+#pragma unroll
+  for (int j = 0; j < kOvRowsRun; ++j) {
+    if (key[j] == 0ull) continue;
+    if (k < capacity) {
+      const long at = (long)(key[j] >> 32);  // raster * group + label_a, label_a in 1 .. group
+      const long raster = (at - 1) / group;
+      int* r = rows + k * 4;
+      r[0] = (int)raster;
+      r[1] = (int)(at - raster * group);
+      r[2] = (int)(unsigned int)key[j];
+      r[3] = counts[first + j * 256];
+    }
+    ++k;
+  }
+}
+
 // (B rides in gridDim.y; 4 edges per pixel at the very most stay below 2^31 in the int32 edge counter)
 bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)B * H * W < (1l << 29); }
 
@@ -883,5 +1065,30 @@ extern "C" int rs_features_skeleton_links(const uint8_t* skeleton, const int32_t
     if (rows > 0) edges_mark_kernel<false><<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, keep, B, (long)H * W);
     links_emit_kernel<false><<<rs_cdiv(P, 256), 256, 0, s>>>(skeleton, labels, keep, links, capacity, c, B, H, W, nullptr, nullptr);
   }
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" long rs_features_overlaps_workspace_bytes(long capacity) {
+  if (capacity < 0 || capacity > (1l << 29)) return RS_EINVAL;
+  return overlap_slots(capacity) * (long)(sizeof(unsigned long long) + sizeof(int32_t));
+}
+
+extern "C" int rs_features_overlaps(const int32_t* labels_a, const int32_t* labels_b, void* workspace, int32_t* rows, long capacity,
+                                    int32_t* counters, long pixels, long group, rs_stream_t stream) {
+  if (!labels_a || !labels_b || !workspace || ((uintptr_t)workspace & 7) || !counters || capacity < 0 || capacity > (1l << 29) ||
+      (capacity > 0 && !rows) || pixels <= 0 || pixels >= (1l << 29) || group <= 0 || pixels % group != 0)
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long slots = overlap_slots(capacity);
+  unsigned long long* keys = static_cast<unsigned long long*>(workspace);
+  int* counts = reinterpret_cast<int*>(keys + slots);
+  hipError_t e = hipMemsetAsync(workspace, 0, slots * (sizeof(unsigned long long) + sizeof(int32_t)), s);
+  if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), s);
+  if (e != hipSuccess) return (int)e;
+  const int vec = (((uintptr_t)labels_a | (uintptr_t)labels_b) & 15) == 0;
+  overlaps_count_kernel<<<rs_cdiv(pixels, 256 * kOvRun), 256, 0, s>>>(labels_a, labels_b, keys, counts, counters,
+                                                                       (unsigned long long)(slots - 1),
+                                                                       (int)(slots < kOvMaxProbe ? slots : kOvMaxProbe), pixels, group, vec);
+  overlaps_rows_kernel<<<rs_cdiv(slots, 256 * kOvRowsRun), 256, 0, s>>>(keys, counts, rows, capacity, counters, slots, group);
   return RS_LAUNCH_RESULT();
 }

@@ -217,11 +217,12 @@ def polygon_is_valid(rings):
     return True
 
 
-def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr):
+def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, iou=None):
     """Edge rows + component table rows (tile, label, area, ...) of one batch -> GeoJSON features.  ``tiles[i]`` is the
     ``Tile`` of batch index i, ``shape`` = (H, W).  Rings are simplified, checked, reversed to RFC 7946 winding (outer ring
     counter-clockwise, holes clockwise in lon / lat), closed and georeferenced from pixel corners.  Plain GeoJSON Feature
-    dicts, ordered by (batch index, label)."""
+    dicts, ordered by (batch index, label).  ``iou`` (``--dedupe``): {(batch index, label): float}, added as the property
+    ``iou``."""
 
     h, w = shape
     area = {(int(r[0]), int(r[1])): int(r[2]) for r in np.asarray(table).reshape(-1, 7)}
@@ -246,6 +247,8 @@ def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr):
             "geometry": {"type": "Polygon", "coordinates": coordinates},
             "properties": {"tile": [int(tile.x), int(tile.y), int(tile.z)], "area_px": area[(index, label)]},
         })
+        if iou is not None:
+            features[-1]["properties"]["iou"] = float(iou[(index, label)])
     return features
 
 
@@ -362,11 +365,12 @@ def tile_vertex_location(tile, px, py, shape):
     return east if px == w else lon, south if py == h else lat
 
 
-def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, georeference=True):
+def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, georeference=True, iou=None):
     """``featurize`` for one stitched call: edge rows (label, X, Y, dir) + table rows (label, area, X0, Y0, X1, Y1) in
     mosaic pixels, ``tiles`` the call's tiles in slot order.  A feature's ``tile`` is the tile holding its canonical pixel (the
     one its label names: label - 1 = slot * H * W + y * W + x), ``area_px`` the area of the whole component; features come in
-    label order, which is (slot, label).  ``georeference=False`` leaves the vertices as mosaic pixel corners [X, Y]."""
+    label order, which is (slot, label).  ``georeference=False`` leaves the vertices as mosaic pixel corners [X, Y].  ``iou``
+    (``--dedupe``): {label: float}, added as the property ``iou``."""
 
     h, w = shape
     x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
@@ -395,7 +399,54 @@ def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stder
             "geometry": {"type": "Polygon", "coordinates": coordinates},
             "properties": {"tile": [int(tile.x), int(tile.y), int(tile.z)], "area_px": area[label], "stitched": True},
         })
+        if iou is not None:
+            features[-1]["properties"]["iou"] = float(iou[label])
     return features
+
+
+# ---- rs features --dedupe: which predicted components the reference labels already map ---------------------------------------
+def dedupe_keep(table, ref_table, pairs, threshold):
+    """``robosat/tools/dedupe.py`` restated on rasters.  ``table``: rows of the predicted components, ``ref_table``: of the
+    reference's, both per tile (rows of 7: tile, label, area, ...) or both stitched (rows of 6: label, area, ...); ``pairs``: the
+    overlap table, rows (raster, label of the predicted, label of the reference, shared pixels), raster = the tile, or 0 for
+    stitched tables.  For a predicted component P, N(P) = the reference components that share a pixel with it,
+    inter = the pixels it shares with them and union = area(P) + sum of area(Q) over N(P) - inter.  P is kept iff N(P) is
+    empty (IoU 0.0) or ``inter < threshold * union`` (Python floats; strict, as the reference's ``iou(...) < threshold``).
+    Returns (keep bool [N], iou float64 [N]) in the order of ``table``'s rows."""
+
+    table, ref_table = np.asarray(table), np.asarray(ref_table)
+    if table.ndim != 2 or table.shape[1] not in (6, 7) or ref_table.ndim != 2 or ref_table.shape[1] != table.shape[1]:
+        raise ValueError("tables are [N, 7] (per tile) or [N, 6] (stitched), both alike; got {} and {}".format(table.shape, ref_table.shape))
+    per_tile = table.shape[1] == 7
+
+    def keys(raster, label):  # (tiles per call <= 65535, labels < 2^29)
+        return np.asarray(raster, dtype=np.int64) << 31 | np.asarray(label, dtype=np.int64)
+
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 4)
+    keep = np.ones(len(table), dtype=bool)
+    iou = np.zeros(len(table), dtype=np.float64)
+    if len(pairs) == 0 or len(table) == 0:
+        return keep, iou
+    # the reference's areas are looked up for the pairs alone: unopened reference masks can hold tens of thousands of components
+    ref_key = keys(ref_table[:, 0], ref_table[:, 1]) if per_tile else keys(0, ref_table[:, 0])
+    order = np.argsort(ref_key, kind="stable")
+    at = np.searchsorted(ref_key[order], keys(pairs[:, 0], pairs[:, 2]))
+    if len(order) == 0 or at.max() >= len(order) or (ref_key[order][at] != keys(pairs[:, 0], pairs[:, 2])).any():
+        raise ValueError("a pair names a reference component that is not in ref_table")
+    ref_area = ref_table[:, 2 if per_tile else 1].astype(np.int64)[order][at]
+    touched, group = np.unique(keys(pairs[:, 0], pairs[:, 1]), return_inverse=True)
+    inter, others = np.zeros(len(touched), dtype=np.int64), np.zeros(len(touched), dtype=np.int64)
+    np.add.at(inter, group.reshape(-1), pairs[:, 3])
+    np.add.at(others, group.reshape(-1), ref_area)
+    own = keys(table[:, 0], table[:, 1]) if per_tile else keys(0, table[:, 0])
+    hit = np.minimum(np.searchsorted(touched, own), len(touched) - 1)
+    area = table[:, 2 if per_tile else 1].tolist()
+    for i in np.nonzero(touched[hit] == own)[0].tolist():  # (plain Python numbers from here: the rule as it is written)
+        shared = int(inter[hit[i]])
+        union = area[i] + int(others[hit[i]]) - shared
+        keep[i] = shared < float(threshold) * union
+        iou[i] = shared / union
+    return keep, iou
 
 
 # ---- rs features --geometry centerline: skeleton links -> lines ----------------------------------------------------------------

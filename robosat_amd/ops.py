@@ -1623,6 +1623,50 @@ def stitched_features(images_u8, nbr, origin, index, eps_open, eps_close, min_ar
     return table, boundary_edges_stitched(labels, nbr, origin, table)
 
 
+# ---- rs features --dedupe: the overlap table of two label rasters (definitions in include/robosat_hip.h) ------------------------
+OVERLAP_CAPACITY = 1 << 16  # rows of the first call (a hash table of 2^17 slots, 1.5 MB)
+
+
+def overlap_table(labels_a, labels_b, stitched=False, capacity=None):
+    """Two int32 [B, H, W] label rasters (``label_components`` / ``stitch_labels``) -> int32 [N, 4] rows
+    (raster, label_a, label_b, count): one row per pair of components that share a pixel, ``count`` the pixels they share,
+    sorted lexicographically.  ``raster`` is the tile, or 0 throughout with ``stitched`` (labels of one raster of B tiles).
+    ``capacity``: the rows of the first call (default ``OVERLAP_CAPACITY``); a call that does not fit is repeated with the
+    number of rows it reported, or with 8 times the capacity where the hash table itself ran out."""
+
+    if labels_a.shape != labels_b.shape or labels_a.dim() != 3:
+        raise ValueError("robosat_amd: the label rasters are both [B, H, W], got {} and {}".format(tuple(labels_a.shape), tuple(labels_b.shape)))
+    if labels_a.device != labels_b.device:
+        raise ValueError("robosat_amd: the label rasters are on {} and {}".format(labels_a.device, labels_b.device))
+    b, h, w = labels_a.shape
+    pixels = b * h * w
+    group = pixels if stitched else h * w
+    a, bb = _dev(labels_a, "labels_a", torch.int32), _dev(labels_b, "labels_b", torch.int32)
+    dev = labels_a.device
+    capacity = OVERLAP_CAPACITY if capacity is None else int(capacity)
+    if capacity < 1:
+        raise ValueError("robosat_amd: capacity is at least 1, got {}".format(capacity))
+    lib = _lib.lib()
+    counters = torch.empty(2, device=dev, dtype=torch.int32)
+    while True:  # (capacity grows with every pass and a table of `pixels` rows holds every pair there can be)
+        capacity = min(capacity, max(pixels, 1))
+        ws = torch.empty(lib.rs_features_overlaps_workspace_bytes(capacity) // 8, device=dev, dtype=torch.int64)
+        rows = torch.empty((capacity, 4), device=dev, dtype=torch.int32)
+        _call("rs_features_overlaps", a, bb, _dev(ws, "workspace", torch.int64), _dev(rows, "rows", torch.int32), capacity,
+              _dev(counters, "counters", torch.int32), pixels, group, _stream())
+        found, lost = counters.tolist()
+        if not lost and found <= capacity:
+            break
+        if capacity >= pixels:
+            raise RuntimeError("rs_features_overlaps: {} rows (table full: {}) do not fit a table of {}".format(found, bool(lost), capacity))
+        capacity = capacity * 8 if lost else found
+    rows = rows[:found]
+    if found:
+        key = (rows[:, 0].to(torch.int64) * (group + 1) + rows[:, 1].to(torch.int64)) * (pixels + 1) + rows[:, 2].to(torch.int64)
+        rows = rows[torch.argsort(key)]
+    return rows.contiguous()
+
+
 # ---- rs features --geometry centerline: skeleton and links (definitions in include/robosat_hip.h) --------------------------------
 THIN_PAIRS = 16  # pairs of sub-iterations enqueued between two reads of the device's counter (profiles/features_centerline)
 

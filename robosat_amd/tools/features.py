@@ -5,9 +5,13 @@ edges come back to the host, which links them into rings, simplifies and georefe
 ``--stitch`` treats the tiles of a zoom level as one sparse raster, so an object that crosses tile borders is one polygon.
 ``--geometry centerline`` gives LineStrings for linear classes such as roads: the cleaned mask is thinned to its skeleton on the
 device too, and the host links, prunes and simplifies the skeleton's lines.
+``--dedupe DIR`` drops the polygons the reference labels in DIR already map (the reference's ``rs dedupe``, on rasters): both
+sides are labelled on the device, one kernel tabulates the pixels every pair of components shares, and a component whose
+intersection over union with the reference objects it touches reaches ``--dedupe_threshold`` is left out.
 The stage definitions, and where they depart from OpenCV's, are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
+import os
 import sys
 
 import numpy as np
@@ -17,8 +21,8 @@ from tqdm import tqdm
 
 from robosat_amd import ops
 from robosat_amd.config import load_config
-from robosat_amd.features import (FeatureWriter, centerlines, centerlines_stitched, featurize, featurize_stitched, group_clusters,
-                                  pack_clusters, stitch_tables)
+from robosat_amd.features import (FeatureWriter, centerlines, centerlines_stitched, dedupe_keep, featurize, featurize_stitched,
+                                  group_clusters, pack_clusters, stitch_tables)
 from robosat_amd.tiles import tiles_from_slippy_map
 
 
@@ -44,6 +48,15 @@ def add_parser(subparser):
                         "tile ends 9-10 pixels inside it), so roads want --stitch")
     parser.add_argument("--prune", type=float, default=20, help="centerline: side branches shorter than this many pixels are removed")
     parser.add_argument("--tolerance", type=float, default=1.5, help="centerline: Douglas-Peucker tolerance in pixels")
+    parser.add_argument("--dedupe", type=str, default=None, metavar="DIR",
+                        help="slippy map directory with class-index masks of what is already mapped (a dataset's labels, rasterized "
+                        "OpenStreetMap): polygons they cover are dropped, the rest gain the property iou. The reference pixels are "
+                        "taken as they are (no --denoise, --grow or --min_area) and only inside the tiles of the masks directory: a "
+                        "reference object that runs on into a tile without a mask counts with its pixels inside those tiles alone. "
+                        "A mask tile without a file in DIR has nothing mapped. With --stitch objects are compared whole across tile borders")
+    parser.add_argument("--dedupe_threshold", type=float, default=None, metavar="T",
+                        help="with --dedupe (required): a polygon is dropped where the pixels it shares with the reference objects it "
+                        "touches are at least T times the pixels of their union, 0 <= T <= 1")
     parser.set_defaults(func=main)
 
 
@@ -51,7 +64,51 @@ def _load(paths, device):
     return torch.from_numpy(np.stack([np.array(Image.open(path).convert("P"), dtype=np.uint8) for path in paths])).to(device)
 
 
-def stitched(items, index, args, device, writer):
+class Dedupe:
+    """``--dedupe``: the reference tiles of a batch or call, and the count of what was examined and dropped."""
+
+    def __init__(self, directory, threshold, index):
+        self.paths = {tile: path for tile, path in tiles_from_slippy_map(directory)}
+        self.threshold, self.index = threshold, index
+        self.examined = self.dropped = 0
+
+    def load(self, tiles, shape, device):
+        """uint8 [T, H, W] class-index tiles; a tile without a file is background (the class is never index 0)."""
+
+        planes = []
+        for tile in tiles:
+            path = self.paths.get(tile)
+            if path is None:
+                planes.append(np.zeros(shape, dtype=np.uint8))
+                continue
+            plane = np.array(Image.open(path).convert("P"), dtype=np.uint8)
+            if plane.shape != tuple(shape):
+                sys.exit("Error: {} is {}x{}; the mask tile {}/{}/{} is {}x{}".format(path, plane.shape[0], plane.shape[1], tile.z, tile.x,
+                                                                                    tile.y, shape[0], shape[1]))
+            planes.append(plane)
+        return torch.from_numpy(np.stack(planes)).to(device)
+
+    def filter(self, labels, table, reference_u8, nbr=None, origin=None):
+        """Labels and component table of the masks + the reference tiles (``load``) -> (the table's kept rows, {feature key: iou}
+        for ``featurize``).  With ``nbr`` and ``origin`` everything is stitched: labels, table and the reference."""
+
+        reference = ops.label_components(ops.clean_masks(reference_u8, self.index, 0, 0))  # (discs of 0: tile == index as it is)
+        if nbr is None:
+            ref_table = ops.component_table(reference, 0)
+        else:
+            reference = ops.stitch_labels(reference, nbr, inplace=True)
+            ref_table = ops.component_table_stitched(reference, origin, 0)
+        pairs = ops.overlap_table(labels, reference, stitched=nbr is not None)
+        rows = table.cpu().numpy()
+        keep, iou = dedupe_keep(rows, ref_table.cpu().numpy(), pairs.cpu().numpy(), self.threshold)
+        self.examined += len(keep)
+        self.dropped += int((~keep).sum())
+        kept = rows[keep]
+        keys = [(int(r[0]), int(r[1])) for r in kept] if nbr is None else [int(r[0]) for r in kept]
+        return table[torch.from_numpy(keep).to(table.device)].contiguous(), dict(zip(keys, iou[keep].tolist()))
+
+
+def stitched(items, index, args, device, writer, dedupe=None):
     """``--stitch``: per zoom level, the 8-connected clusters of tiles packed whole into device calls."""
 
     by_zoom = {}
@@ -74,14 +131,23 @@ def stitched(items, index, args, device, writer):
             sys.exit("Error: {}".format(exc))
         for tiles in tqdm(calls, desc="Features z{} {}x{}".format(z, h, w), unit="call", ascii=True):
             nbr, origin, _ = stitch_tables(tiles, shape)
-            stages = ops.stitched_centerlines if args.geometry == "centerline" else ops.stitched_features
-            table, rows = stages(_load([paths[t] for t in tiles], device), torch.from_numpy(nbr).to(device),
-                                 torch.from_numpy(origin).to(device), index, args.denoise, args.grow, args.min_area)
+            nbr, origin = torch.from_numpy(nbr).to(device), torch.from_numpy(origin).to(device)
+            images = _load([paths[t] for t in tiles], device)
+            iou = None
+            if dedupe is not None:  # (the stages of ops.stitched_features, with the reference between the table and the edges)
+                labels = ops.stitch_labels(ops.label_components(ops.clean_masks_stitched(images, nbr, index, args.denoise, args.grow)), nbr,
+                                           inplace=True)
+                table, iou = dedupe.filter(labels, ops.component_table_stitched(labels, origin, args.min_area),
+                                           dedupe.load(tiles, shape, device), nbr, origin)
+                rows = ops.boundary_edges_stitched(labels, nbr, origin, table)
+            else:
+                stages = ops.stitched_centerlines if args.geometry == "centerline" else ops.stitched_features
+                table, rows = stages(images, nbr, origin, index, args.denoise, args.grow, args.min_area)
             try:
                 if args.geometry == "centerline":
                     writer.add(centerlines_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.prune, args.tolerance))
                 else:
-                    writer.add(featurize_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify))
+                    writer.add(featurize_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify, iou=iou))
             except ValueError as exc:
                 sys.exit("Error: {}".format(exc))
 
@@ -95,10 +161,20 @@ def main(args):
             sys.exit("Error: --{} must be in 0..64".format(name))
     if args.prune < 0 or args.tolerance < 0:
         sys.exit("Error: --prune and --tolerance are lengths in pixels, not negative")
+    if (args.dedupe is None) != (args.dedupe_threshold is None):
+        sys.exit("Error: --dedupe and --dedupe_threshold come together")
+    if args.dedupe is not None:
+        if not 0 <= args.dedupe_threshold <= 1:  # (false for nan too)
+            sys.exit("Error: --dedupe_threshold is a share of the union's pixels, 0 <= T <= 1, got {}".format(args.dedupe_threshold))
+        if not os.path.isdir(args.dedupe):
+            sys.exit("Error: --dedupe {} is not a directory".format(args.dedupe))
+        if args.geometry == "centerline":
+            sys.exit("Error: --dedupe compares areas, which says nothing about lines: not with --geometry centerline")
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
     index = classes.index(args.type)
+    dedupe = Dedupe(args.dedupe, args.dedupe_threshold, index) if args.dedupe is not None else None
 
     by_shape = {}  # (H, W) -> [(tile, path)]: the header gives the size, a mask is decoded when its batch runs
     for tile, path in sorted(tiles_from_slippy_map(args.masks), key=lambda t: (t[0].z, t[0].x, t[0].y)):
@@ -110,7 +186,7 @@ def main(args):
 
     writer = FeatureWriter()
     if args.stitch:
-        stitched([(tile, path, shape) for shape, items in by_shape.items() for tile, path in items], index, args, device, writer)
+        stitched([(tile, path, shape) for shape, items in by_shape.items() for tile, path in items], index, args, device, writer, dedupe)
         by_shape = {}
     for shape, items in by_shape.items():  # tiles of one batch share a shape
         # (the library takes B*H*W < 2^29 per call, link_rings fewer than 1024 tiles)
@@ -126,6 +202,11 @@ def main(args):
                 writer.add(centerlines(links.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.prune,
                                        args.tolerance))
                 continue
+            iou = None
+            if dedupe is not None:
+                table, iou = dedupe.filter(labels, table, dedupe.load([tile for tile, _ in group], shape, device))
             edges = ops.boundary_edges(labels, table)
-            writer.add(featurize(edges.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.simplify))
+            writer.add(featurize(edges.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.simplify, iou=iou))
     writer.save(args.out)
+    if dedupe is not None:
+        print("Dedupe: {} components examined, {} dropped as already mapped".format(dedupe.examined, dedupe.dropped), file=sys.stderr)

@@ -18,6 +18,11 @@
            count, the time at each candidate chunk size K, and the polygon path on the same masks, written to
            profiles/features_centerline/bench_centerline.json (`--centerline-leg --stage-loop N`: the stages N times, for rocprofv3)
 
+  --dedupe-leg   `rs features --dedupe`: the polygon stages without and with the reference (its labelling, its table, the overlap
+           table, the host's rule) on the blob batch, the overlap table on the shapes that bound it (one pair per tile, one pair
+           per pixel) beside the labeller on the same tiles, and `./rs features` from disk without and with the flag, written to
+           profiles/features_dedupe/bench_dedupe.json (`--dedupe-leg --stage-loop N`: the stages N times, for rocprofv3)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -264,6 +269,109 @@ def centerline_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+def dedupe_leg(args):
+    """The polygon path with the reference between the table and the edges, beside the path without it."""
+
+    import torch
+
+    from robosat_amd import ops, png
+    from robosat_amd.colors import make_palette
+    from robosat_amd.features import dedupe_keep
+
+    size, eps, r, threshold = args.size, args.eps, args.repeat, 0.5
+    masks = blob_masks(args.batch, size, 0)
+    reference = np.roll(masks, (5, 7), axis=(1, 2))  # the same objects a little off ...
+    reference[1::2] = blob_masks(args.batch, size, 2)[1::2]  # ... and, in every other tile, others
+    dev, ref = torch.from_numpy(masks).to("cuda:0"), torch.from_numpy(reference).to("cuda:0")
+
+    def plain():
+        labels = ops.label_components(ops.clean_masks(dev, 1, eps, eps))
+        table = ops.component_table(labels, 0)
+        return table, ops.boundary_edges(labels, table).cpu()
+
+    def deduped():
+        labels = ops.label_components(ops.clean_masks(dev, 1, eps, eps))
+        table = ops.component_table(labels, 0)
+        ref_labels = ops.label_components(ops.clean_masks(ref, 1, 0, 0))
+        pairs = ops.overlap_table(labels, ref_labels)
+        keep, _ = dedupe_keep(table.cpu().numpy(), ops.component_table(ref_labels, 0).cpu().numpy(), pairs.cpu().numpy(), threshold)
+        table = table[torch.from_numpy(keep).to(table.device)].contiguous()
+        return table, ops.boundary_edges(labels, table).cpu(), pairs
+
+    full = torch.ones((args.batch, size, size), dtype=torch.uint8, device="cuda:0")
+    yy, xx = np.mgrid[:size, :size]
+    board = torch.from_numpy(np.repeat(((yy + xx) % 2 == 0)[None], args.batch, 0).astype(np.uint8)).to("cuda:0")
+    if args.stage_loop:
+        for masks_u8 in (full, board):
+            labels = ops.label_components(masks_u8)
+            for _ in range(args.stage_loop):
+                ops.overlap_table(labels, labels, capacity=1 << 23)
+        for _ in range(args.stage_loop):
+            deduped()
+        return
+
+    labels = ops.label_components(ops.clean_masks(dev, 1, eps, eps))
+    table = ops.component_table(labels, 0)
+    ref_labels = ops.label_components(ops.clean_masks(ref, 1, 0, 0))
+    ref_table = ops.component_table(ref_labels, 0)
+    kept, _, pairs = deduped()
+    t_np, r_np, p_np = table.cpu().numpy(), ref_table.cpu().numpy(), pairs.cpu().numpy()
+    t0 = time.perf_counter()
+    for _ in range(r):
+        dedupe_keep(t_np, r_np, p_np, threshold)
+    host = (time.perf_counter() - t0) / r
+    sec_plain, sec_dedupe = timed(plain, r), timed(deduped, r)
+    result = {"batch": args.batch, "size": size, "eps": eps, "threshold": threshold,
+              "components": int(len(table)), "reference_components": int(len(ref_table)), "pairs": int(len(pairs)), "kept": int(len(kept)),
+              "ms_per_batch": {"without": sec_plain * 1e3, "with": sec_dedupe * 1e3},
+              "ms_split": {"reference_select_and_label": timed(lambda: ops.label_components(ops.clean_masks(ref, 1, 0, 0)), r) * 1e3,
+                           "reference_table": timed(lambda: ops.component_table(ref_labels, 0), r) * 1e3,
+                           "overlap_table": timed(lambda: ops.overlap_table(labels, ref_labels), r) * 1e3,
+                           "dedupe_keep_host": host * 1e3},
+              "overlap_table_bounds": {}}
+    for name, masks_u8 in (("all_ones", full), ("checkerboard", board)):
+        hard = ops.label_components(masks_u8)
+        rows = ops.overlap_table(hard, hard, capacity=1 << 23)
+        result["overlap_table_bounds"][name] = {
+            "rows": int(len(rows)),
+            "overlap_table_ms_capacity_2p23": timed(lambda: ops.overlap_table(hard, hard, capacity=1 << 23), r) * 1e3,
+            "overlap_table_ms_default_capacity": timed(lambda: ops.overlap_table(hard, hard), r) * 1e3,
+            "label_components_ms": timed(lambda: ops.label_components(masks_u8), r) * 1e3}
+
+    with tempfile.TemporaryDirectory() as tmp:
+        count = 4 * args.batch
+        tiles = blob_masks(count, size, 1)
+        mapped = np.roll(tiles, (5, 7), axis=(1, 2))
+        mapped[1::2] = blob_masks(count, size, 3)[1::2]
+        for root, stack in (("masks", tiles), ("labels", mapped)):
+            for i, image in enumerate(stack):
+                os.makedirs(os.path.join(tmp, root, "18", str(69000 + i // 8)), exist_ok=True)
+                png.write_png(os.path.join(tmp, root, "18", str(69000 + i // 8), str(104000 + i % 8) + ".png"), image, "P",
+                              make_palette("denim", "orange"))
+        with open(os.path.join(tmp, "dataset.toml"), "w") as fp:
+            fp.write('[common]\nclasses = ["background", "parking"]\ncolors = ["denim", "orange"]\n')
+        env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+        cmd = [sys.executable, "-m", "robosat_amd.tools", "features", os.path.join(tmp, "masks"), "--type", "parking", "--dataset",
+               os.path.join(tmp, "dataset.toml"), os.path.join(tmp, "out.geojson"), "--batch_size", str(args.batch)]
+        result["cli"] = {"tiles": count, "note": "seconds includes interpreter start, torch import and library load"}
+        for name, extra in (("without", []), ("with", ["--dedupe", os.path.join(tmp, "labels"), "--dedupe_threshold", str(threshold)])):
+            subprocess.run(cmd + extra, env=env, cwd=ROOT, check=True, capture_output=True)  # (warm file cache)
+            t0 = time.perf_counter()
+            done = subprocess.run(cmd + extra, env=env, cwd=ROOT, check=True, capture_output=True, text=True)
+            result["cli"][name] = {"seconds": time.perf_counter() - t0}
+            with open(os.path.join(tmp, "out.geojson")) as fp:
+                result["cli"][name]["features"] = len(json.load(fp)["features"])
+            if extra:
+                result["cli"][name]["stderr_last_line"] = done.stderr.strip().splitlines()[-1]
+
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "features_dedupe", "bench_dedupe.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def device_stage(images, eps):
     import torch
 
@@ -311,6 +419,7 @@ def main():
     ap.add_argument("--stage-loop", type=int, default=0)
     ap.add_argument("--stitch-leg", action="store_true", help="only the stitched path against the per-tile path on an n x n block")
     ap.add_argument("--centerline-leg", action="store_true", help="only thinning and links, on a road network and on its n x n block")
+    ap.add_argument("--dedupe-leg", action="store_true", help="only rs features --dedupe: the stages with and without the reference")
     ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched legs' block")
     ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
@@ -318,6 +427,8 @@ def main():
         return stitch_leg(args)
     if args.centerline_leg:
         return centerline_leg(args)
+    if args.dedupe_leg:
+        return dedupe_leg(args)
 
     import torch
 
