@@ -715,6 +715,34 @@ int rs_features_skeleton_links(const uint8_t* skeleton, const int32_t* labels, c
                                const int32_t* table, long rows, uint8_t* keep, int32_t* links, long capacity, int32_t* counter, int B,
                                int H, int W, rs_stream_t stream);
 
+/* ---- road widths: capped squared Euclidean distance transform (`rs features --width`) ----
+ * rs_features_edt: masks m [B][H][W] (non-zero = set), a radius R in 1 .. 128 -> d2 [B][H][W] int32:
+ *   an unset pixel gives 0;
+ *   a set pixel p gives min(R*R, min over the unset pixels q of the same raster of |p - q|^2), in integer pixel units.
+ * Pixels outside the raster are NOT background: nothing is known there, so they are ignored, and a road that runs off the edge keeps
+ * its width up to the edge.  A set pixel with no unset pixel within R gives exactly R*R, which reads as "capped".  The cap bounds the
+ * reach, which is what makes the stitched form exact.
+ *
+ * nbr NULL: each of the B tiles is a raster of its own.  nbr int32 [B][8] (the table of rs_features_halo and rs_features_thin): the
+ * tiles are one sparse raster -- the result is the definition above on the tiles pasted into a canvas whose other pixels are
+ * "unknown" (neither set nor unset): unset pixels of present neighbour tiles count across seams and corners, absent tiles are ignored
+ * like the outside.  This needs R <= min(H, W), so that only the 8 neighbours matter: RS_EINVAL otherwise.
+ *
+ * Two launches over the decomposition
+ *   g(x, y)  = the horizontal distance from (x, y) to the nearest unset pixel of row y, capped at R (R where the row has none within
+ *              reach; unknown pixels are passed over; g <= 128 fits a byte),
+ *   d2(x, y) = min(R*R, min over |dy| <= R of g(x, y + dy)^2 + dy^2), rows outside the canvas skipped,
+ * which is exact because of the cap.  The row pass writes g [B][H][W] (a caller-provided byte plane) and looks into the W and E tiles;
+ * the column pass reads the N and S tiles' g.  g is only kept for the tiles that are there: column x of a row in an ABSENT N (S) tile is
+ * x + 1 + g of the last column of that row in the NW (SW) tile, or W - x + g of the first column in the NE (SE) tile, whichever is
+ * present and smaller -- unset pixels of a corner tile count although the tile between is unknown.  Integer only, no atomics, every
+ * output written by one thread: bit-reproducible.  Any W and H work (W not a multiple of 32 or 64, H < R and W < R per tile). */
+int rs_features_edt(const uint8_t* masks, const int32_t* nbr, uint8_t* g, int32_t* d2, int B, int H, int W, int R, rs_stream_t stream);
+
+/* Width of a line (host, robosat_amd/features.py: line_width): over the line's pixel chain after pruning and before simplification,
+ * the per-pixel width is 2*sqrt(d2) - 1; width_px = the median, width_min_px / width_max_px the extremes, rounded to 3 decimals;
+ * width_capped = true where any pixel of the chain has d2 == R*R (absent otherwise).  An axis-parallel road of odd width w gives
+ * exactly w, one of even width w - 1 (the skeleton runs on one of the two middle rows). */
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,8 @@ SIGNATURES = {
     # centerlines: Guo-Hall thinning, skeleton links
     "rs_features_thin": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rs_features_skeleton_links": (c_int, [P, P, P, P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),
+    # road widths: capped squared Euclidean distance transform (rs features --width)
+    "rs_features_edt": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

@@ -856,6 +856,105 @@ __global__ __launch_bounds__(256) void overlaps_rows_kernel(const unsigned long 
   }
 }
 
+// ---- capped squared Euclidean distance transform (`rs features --width`; definitions: include/robosat_hip.h) ------------------
+// Two launches.  Row pass: g = the horizontal distance to the nearest unset pixel of the row, capped at R (a byte).  Column pass:
+// d2 = min(R*R, min over dy of g(x, y + dy)^2 + dy^2).  Integers only, no atomics, every output written by exactly one thread.
+constexpr int kEdtMaxR = 128;
+constexpr int kEdtRows = 64;     // TH: rows of a column-pass strip
+constexpr int kEdtNoRow = 255;   // g of a row that is not there: 255^2 > kEdtMaxR^2, so it never wins against the cap
+
+// One wave per 64 columns of a row: a ballot of "unset" for the chunk and for ceil(R / 64) chunks either side, then count-leading /
+// trailing-zeros on those words.  A column left of 0 / right of W - 1 is the W / E tile's (STITCH), or is not there at all; what
+// lies more than one tile away is beyond R <= W.
+template <bool STITCH>
+__global__ __launch_bounds__(256) void edt_row_kernel(const uint8_t* __restrict__ m, const int* __restrict__ nbr, uint8_t* __restrict__ g,
+                                                      int B, int H, int W, int R) {
+  const int lane = threadIdx.x & 63;
+  const int chunks = (W + 63) >> 6;
+  const int side = (R + 63) >> 6;  // 1 or 2
+  const long HW = (long)H * W;
+  const long items = (long)B * H * chunks;
+  for (long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6); item < items; item += (long)gridDim.x * 4) {  // (wave-uniform)
+    const long row = item / chunks;  // tile * H + y
+    const int ch = (int)(item - row * chunks);
+    const int tile = (int)(row / H), y = (int)(row - (long)tile * H);
+    unsigned long long word[5];  // unset pixels of chunks ch - 2 .. ch + 2
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      word[k] = 0ull;
+      if (k - 2 < -side || k - 2 > side) continue;  // (uniform)
+      int x = (ch + k - 2) * 64 + lane;
+      const int dx = x < 0 ? -1 : x >= W ? 1 : 0;
+      x -= dx * W;
+      int slot = tile;
+      if (dx) slot = STITCH && x >= 0 && x < W ? nbr_slot(nbr, tile, dx, 0, B) : -1;
+      word[k] = __ballot(slot >= 0 && m[(long)slot * HW + (long)y * W + x] == 0);
+    }
+    const int x = ch * 64 + lane;
+    if (x < W) {  // (behind the ballots: every lane reaches them)
+      const unsigned long long below = word[2] & ((2ull << lane) - 1ull);  // (lane 63: 2 << 63 wraps to 0, 0 - 1 = all ones)
+      const unsigned long long above = word[2] & ~((1ull << lane) - 1ull);
+      int left = R, right = R;
+      if (below) left = lane - (63 - __clzll((long long)below));
+      else if (word[1]) left = lane + 1 + __clzll((long long)word[1]);
+      else if (word[0]) left = lane + 65 + __clzll((long long)word[0]);
+      if (above) right = __ffsll((long long)above) - 1 - lane;
+      else if (word[3]) right = 63 - lane + __ffsll((long long)word[3]);
+      else if (word[4]) right = 127 - lane + __ffsll((long long)word[4]);
+      const int d = left < right ? left : right;
+      g[row * W + x] = (uint8_t)(d < R ? d : R);
+    }
+  }
+}
+
+// g of rows yy (one tile up or down at most) at the strip's 64 columns, as the column pass stages it.  A row above / below the tile is
+// the N / S tile's (STITCH).  Where that tile is absent its pixels are unknown, not unset, but the unset pixels of the NW / NE
+// (SW / SE) tile still count: from column x the nearest one in that row is x + 1 + g of the W-side tile's last column away, or
+// W - x + g of the E-side tile's first column (their own row pass found nothing in the absent tile between).
+template <bool STITCH>
+__device__ __forceinline__ int edt_staged(const uint8_t* __restrict__ g, const int* __restrict__ nbr, int tile, int yy, int x, int B, int H,
+                                          int W) {
+  const int dy = yy < 0 ? -1 : yy >= H ? 1 : 0;
+  const int y = yy - dy * H;
+  const long HW = (long)H * W;
+  if (!dy) return g[(long)tile * HW + (long)y * W + x];
+  if (!STITCH || y < 0 || y >= H) return kEdtNoRow;
+  const int n = nbr_slot(nbr, tile, 0, dy, B);
+  if (n >= 0) return g[(long)n * HW + (long)y * W + x];
+  const int w = nbr_slot(nbr, tile, -1, dy, B), e = nbr_slot(nbr, tile, 1, dy, B);
+  int best = kEdtNoRow;
+  if (w >= 0) best = min(best, x + 1 + (int)g[(long)w * HW + (long)y * W + W - 1]);
+  if (e >= 0) best = min(best, W - x + (int)g[(long)e * HW + (long)y * W]);
+  return best;
+}
+
+// A block takes 64 columns x kEdtRows rows of one tile: it stages g of the rows y0 - R .. y0 + kEdtRows - 1 + R in LDS (at most
+// (64 + 256) * 64 bytes = 20 KB), then every lane owns a column (a wave reads 64 consecutive bytes: no bank conflict) and walks outward
+// in |dy| until dy * dy >= the best so far.  Columns beyond W are staged as kEdtNoRow and written nowhere.
+template <bool STITCH>
+__global__ __launch_bounds__(256) void edt_col_kernel(const uint8_t* __restrict__ g, const int* __restrict__ nbr, int* __restrict__ d2,
+                                                      int B, int H, int W, int R) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t staged[];  // [kEdtRows + 2R][64]
+  const int tile = blockIdx.z, y0 = blockIdx.y * kEdtRows, x0 = blockIdx.x * 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int rows = kEdtRows + 2 * R;
+  const int x = x0 + lane;
+  for (int r = wave; r < rows; r += 4) staged[r * 64 + lane] = (uint8_t)(x < W ? edt_staged<STITCH>(g, nbr, tile, y0 - R + r, x, B, H, W) : kEdtNoRow);
+  __syncthreads();
+  if (x >= W) return;
+  const int cap = R * R;
+  for (int ry = wave; ry < kEdtRows && y0 + ry < H; ry += 4) {
+    const uint8_t* at = staged + (ry + R) * 64 + lane;
+    const int own = at[0];
+    int best = min(cap, own * own);
+    for (int d = 1; d * d < best; ++d) {  // (best <= R * R: d stays below R, inside the staged rows)
+      const int up = at[-d * 64], down = at[d * 64];
+      best = min(best, min(up * up, down * down) + d * d);
+    }
+    d2[((long)tile * H + y0 + ry) * W + x] = best;
+  }
+}
+
 // (B rides in gridDim.y; 4 edges per pixel at the very most stay below 2^31 in the int32 edge counter)
 bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)B * H * W < (1l << 29); }
 
@@ -1090,5 +1189,24 @@ extern "C" int rs_features_overlaps(const int32_t* labels_a, const int32_t* labe
                                                                        (unsigned long long)(slots - 1),
                                                                        (int)(slots < kOvMaxProbe ? slots : kOvMaxProbe), pixels, group, vec);
   overlaps_rows_kernel<<<rs_cdiv(slots, 256 * kOvRowsRun), 256, 0, s>>>(keys, counts, rows, capacity, counters, slots, group);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_edt(const uint8_t* masks, const int32_t* nbr, uint8_t* g, int32_t* d2, int B, int H, int W, int R,
+                               rs_stream_t stream) {
+  if (!masks || !g || !d2 || !shape_ok(B, H, W) || R < 1 || R > kEdtMaxR) return RS_EINVAL;
+  if (nbr && R > (H < W ? H : W)) return RS_EINVAL;  // (one step in the table must reach every pixel within R)
+  hipStream_t s = (hipStream_t)stream;
+  const long items = (long)B * H * ((W + 63) / 64);
+  const int row_grid = rs_cdiv(items, 4) < 16384 ? rs_cdiv(items, 4) : 16384;
+  const dim3 col_grid(rs_cdiv(W, 64), rs_cdiv(H, kEdtRows), B);
+  const int lds = (kEdtRows + 2 * R) * 64;
+  if (nbr) {
+    edt_row_kernel<true><<<row_grid, 256, 0, s>>>(masks, nbr, g, B, H, W, R);
+    edt_col_kernel<true><<<col_grid, 256, lds, s>>>(g, nbr, d2, B, H, W, R);
+  } else {
+    edt_row_kernel<false><<<row_grid, 256, 0, s>>>(masks, nullptr, g, B, H, W, R);
+    edt_col_kernel<false><<<col_grid, 256, lds, s>>>(g, nullptr, d2, B, H, W, R);
+  }
   return RS_LAUNCH_RESULT();
 }

@@ -9,6 +9,7 @@ component's outer ring is positive, its holes' negative, and the areas of its ri
 ``--geometry centerline`` has its own half at the end of the file: skeleton links -> lines -> pruned, simplified LineStrings."""
 
 import json
+import math
 import sys
 
 import numpy as np
@@ -614,6 +615,52 @@ def simplify_line(points, tolerance):
     return points[keep]
 
 
+def line_width(d2_values, radius):
+    """The width properties of one line from the capped squared distances (``ops.distance_transform`` with ``radius``) at the pixels
+    of its chain, after pruning and before simplification.  The width at a pixel is ``2 * sqrt(d2) - 1``: the pixel itself plus what
+    lies either side of it up to the nearest non-road pixel.  ``width_px`` is the median over the chain (junction pixels read wide,
+    spur stubs narrow), ``width_min_px`` / ``width_max_px`` the extremes, all rounded to 3 decimals; ``width_capped`` is True where
+    any pixel sits at ``radius^2`` (no non-road pixel within reach: the true width is larger), and absent otherwise.  The estimator is
+    biased, knowingly: an axis-parallel road of odd width w gives exactly w, one of even width w - 1, its skeleton running on one of
+    the two middle rows."""
+
+    d2 = np.asarray(d2_values, dtype=np.int64).reshape(-1)
+    if len(d2) == 0 or d2.min() < 0 or d2.max() > radius * radius:
+        raise ValueError("a line has at least one pixel and its squared distances lie in 0..{}".format(radius * radius))
+    width = 2.0 * np.sqrt(d2.astype(np.float64)) - 1.0
+    properties = {"width_px": round(float(np.median(width)), 3), "width_min_px": round(float(width.min()), 3),
+                  "width_max_px": round(float(width.max()), 3)}
+    if (d2 == radius * radius).any():
+        properties["width_capped"] = True
+    return properties
+
+
+EARTH_RADIUS = 6378137.0  # metres, the sphere of the web mercator
+
+
+def ground_resolution(lat, z, width):
+    """Metres per pixel at latitude ``lat`` (degrees) in a zoom level ``z`` of tiles ``width`` pixels wide."""
+
+    return 2.0 * math.pi * EARTH_RADIUS * math.cos(math.radians(lat)) / (2 ** z * width)
+
+
+class Widths:
+    """The ``widths=`` of ``centerlines`` / ``centerlines_stitched``: ``sample(coords)`` takes int32 [N, 3] rows (slot, y, x) and
+    returns the N values of the batch's or call's distance transform there (one call per batch: two small transfers, no raster
+    comes back); ``radius`` is the transform's."""
+
+    def __init__(self, sample, radius):
+        self.sample, self.radius = sample, int(radius)
+
+    def of_lines(self, coords, lengths):
+        """Rows (slot, y, x) of all lines' chains, concatenated -> one ``line_width`` dict per line."""
+
+        values = np.asarray(self.sample(np.ascontiguousarray(coords, dtype=np.int32)), dtype=np.int64).reshape(-1)
+        assert len(values) == len(coords) == sum(lengths), "one value per chain pixel"
+        ends = np.cumsum(lengths)
+        return [line_width(values[end - n:end], self.radius) for n, end in zip(lengths, ends)]
+
+
 def _line_feature(tile, label, points, locate, area, prune_length, tolerance, stitched):
     kept = simplify_line(points, tolerance)
     coordinates = [list(locate(int(px), int(py))) for px, py in kept]
@@ -626,22 +673,38 @@ def _line_feature(tile, label, points, locate, area, prune_length, tolerance, st
     return {"type": "Feature", "geometry": {"type": "LineString", "coordinates": coordinates}, "properties": properties}
 
 
-def centerlines(links, table, tiles, shape, prune=20, tolerance=1.5):
+def _add_widths(feature, width, lat, z, tile_width):
+    """``line_width``'s properties and ``width_m`` = ``width_px`` times the ground resolution at ``lat``, the latitude of the centre
+    of the chain's middle pixel (index len // 2)."""
+
+    feature["properties"].update(width)
+    feature["properties"]["width_m"] = width["width_px"] * ground_resolution(lat, z, tile_width)
+
+
+def centerlines(links, table, tiles, shape, prune=20, tolerance=1.5, widths=None):
     """Link rows (tile, label, x, y, dir) + component table rows (tile, label, area, ...) of one batch -> one GeoJSON Feature per
     line (``link_lines``, ``prune_lines``, ``simplify_line``): a LineString whose vertices are PIXEL CENTRES (x + 0.5, y + 0.5)
     georeferenced in their tile; properties ``tile``, ``component`` (the label), ``length_px`` (before simplification) and
-    ``area_px`` (of the component).  Ordered by (batch index, points)."""
+    ``area_px`` (of the component).  Ordered by (batch index, points).  ``widths`` (``--width``): a ``Widths`` over the batch's
+    distance transform; every feature gains ``line_width``'s properties and ``width_m``."""
 
     h, w = shape
     area = {(int(r[0]), int(r[1])): int(r[2]) for r in np.asarray(table).reshape(-1, 7)}
+    lines = prune_lines(link_lines(np.asarray(links).reshape(-1, 5)), prune)
     features = []
-    for index, label, points in prune_lines(link_lines(np.asarray(links).reshape(-1, 5)), prune):
+    for index, label, points in lines:
         tile = tiles[index]
 
         def locate(px, py, tile=tile):
             return pixel_to_location(tile, (px + 0.5) / w, (py + 0.5) / h)
 
         features.append(_line_feature(tile, label, points, locate, area[(index, label)], line_length(points), tolerance, False))
+    if widths is not None and lines:
+        coords = np.concatenate([np.stack([np.full(len(p), index), p[:, 1], p[:, 0]], axis=1) for index, _, p in lines])
+        for feature, (index, _, points), width in zip(features, lines, widths.of_lines(coords, [len(p) for _, _, p in lines])):
+            px, py = points[len(points) // 2]
+            lat = pixel_to_location(tiles[index], (int(px) + 0.5) / w, (int(py) + 0.5) / h)[1]
+            _add_widths(feature, width, lat, tiles[index].z, w)
     return features
 
 
@@ -654,11 +717,28 @@ def mosaic_centre_location(z, gx, gy, shape):
     return pixel_to_location(tile, (gx - tile.x * w + 0.5) / w, (gy - tile.y * h + 0.5) / h)
 
 
-def centerlines_stitched(links, table, tiles, shape, prune=20, tolerance=1.5, georeference=True):
+def mosaic_slots(tiles, points, shape):
+    """Mosaic pixels int [N, 2] = (X, Y) of one stitched call -> int64 [N, 3] rows (slot, y, x) through the call's tiles (in slot
+    order); a pixel that no tile of the call covers: ValueError."""
+
+    h, w = shape
+    points = np.asarray(points, dtype=np.int64).reshape(-1, 2)
+    x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
+    nx, ny = max(t.x for t in tiles) - x_min + 1, max(t.y for t in tiles) - y_min + 1
+    slots = np.full(nx * ny, -1, dtype=np.int64)
+    slots[[(t.y - y_min) * nx + (t.x - x_min) for t in tiles]] = np.arange(len(tiles))
+    tx, ty = points[:, 0] // w, points[:, 1] // h
+    if len(points) and (tx.min() < 0 or ty.min() < 0 or tx.max() >= nx or ty.max() >= ny or (slots[ty * nx + tx] < 0).any()):
+        raise ValueError("a mosaic pixel outside the tiles of the call")
+    return np.stack([slots[ty * nx + tx], points[:, 1] - ty * h, points[:, 0] - tx * w], axis=1)
+
+
+def centerlines_stitched(links, table, tiles, shape, prune=20, tolerance=1.5, georeference=True, widths=None):
     """``centerlines`` for one stitched call: link rows (label, X, Y, dir) + table rows (label, area, ...) in mosaic pixels,
     ``tiles`` the call's tiles in slot order.  A feature's ``tile`` is the tile holding its component's canonical pixel,
     ``"stitched": true`` marks it; ordered by (label, points).  ``georeference=False`` leaves the vertices as mosaic pixels
-    [X, Y]."""
+    [X, Y].  ``widths``: as in ``centerlines``, over the call's distance transform (a chain's mosaic pixels go through
+    ``mosaic_slots``)."""
 
     h, w = shape
     x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
@@ -668,9 +748,15 @@ def centerlines_stitched(links, table, tiles, shape, prune=20, tolerance=1.5, ge
     def locate(px, py):
         return mosaic_centre_location(z, x_min * w + px, y_min * h + py, shape) if georeference else (px, py)
 
-    lines = prune_lines(link_lines(np.asarray(links).reshape(-1, 4)), prune)
+    lines = sorted(prune_lines(link_lines(np.asarray(links).reshape(-1, 4)), prune), key=lambda line: (line[1], line[2].tolist()))
     features = []
-    for _, label, points in sorted(lines, key=lambda line: (line[1], line[2].tolist())):
+    for _, label, points in lines:
         tile = tiles[(label - 1) // (h * w)]
         features.append(_line_feature(tile, label, points, locate, area[label], line_length(points), tolerance, True))
+    if widths is not None and lines:
+        coords = mosaic_slots(tiles, np.concatenate([p for _, _, p in lines]), shape)
+        for feature, (_, _, points), width in zip(features, lines, widths.of_lines(coords, [len(p) for _, _, p in lines])):
+            px, py = points[len(points) // 2]
+            lat = mosaic_centre_location(z, x_min * w + int(px), y_min * h + int(py), shape)[1]
+            _add_widths(feature, width, lat, z, w)
     return features

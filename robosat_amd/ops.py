@@ -1732,11 +1732,53 @@ def skeleton_links(skeleton, labels, table, nbr=None, origin=None):
     return links
 
 
-def stitched_centerlines(images_u8, nbr, origin, index, eps_open, eps_close, min_area=0):
+def stitched_centerlines(images_u8, nbr, origin, index, eps_open, eps_close, min_area=0, width_radius=None):
     """Every raster stage of ``rs features --geometry centerline --stitch`` for one call: class-index tiles uint8 [T, H, W] with
-    their neighbour and origin tables -> (table int32 [N, 6], links int32 [L, 4]) of the whole raster."""
+    their neighbour and origin tables -> (table int32 [N, 6], links int32 [L, 4]) of the whole raster.  ``width_radius`` (``--width``):
+    also ``distance_transform`` of the same cleaned mask with that radius, as a third result int32 [T, H, W]."""
 
     cleaned = clean_masks_stitched(images_u8, nbr, index, eps_open, eps_close)
     labels = stitch_labels(label_components(cleaned), nbr, inplace=True)
     table = component_table_stitched(labels, origin, min_area)
-    return table, skeleton_links(thin_masks(cleaned, nbr), labels, table, nbr, origin)
+    links = skeleton_links(thin_masks(cleaned, nbr), labels, table, nbr, origin)
+    if width_radius is None:
+        return table, links
+    return table, links, distance_transform(cleaned, width_radius, nbr)
+
+
+# ---- rs features --width: capped squared Euclidean distance transform (definitions in include/robosat_hip.h) ---------------------
+EDT_MAX_RADIUS = 128
+
+
+def distance_transform(masks_u8, radius, nbr=None):
+    """uint8 [B, H, W] (non-zero = set) -> int32 [B, H, W]: 0 at an unset pixel, at a set pixel min(radius^2, the squared distance
+    in pixels to the nearest unset pixel of its tile), or with ``nbr`` int32 [B, 8] of the one sparse raster the tiles form.  Outside
+    the raster (and in absent tiles) nothing is known: no distance comes from there.  ``radius`` in 1..128, with ``nbr`` at most
+    min(H, W); a pixel at ``radius^2`` has no unset pixel within reach."""
+
+    b, h, w = masks_u8.shape
+    radius = int(radius)
+    if not 1 <= radius <= EDT_MAX_RADIUS:
+        raise ValueError("robosat_amd: the distance transform's radius is in 1..{}, got {}".format(EDT_MAX_RADIUS, radius))
+    if nbr is not None:
+        assert nbr.shape == (b, 8), "nbr is [T, 8]"
+        if radius > min(h, w):
+            raise ValueError("robosat_amd: a radius of {} does not fit stitched tiles of {}x{} (at most min(H, W))".format(radius, h, w))
+    masks = _dev(masks_u8, "masks", torch.uint8)  # (a CPU tensor raises before anything is sized)
+    g = torch.empty_like(masks_u8)
+    d2 = torch.empty((b, h, w), device=masks_u8.device, dtype=torch.int32)
+    _call("rs_features_edt", masks, _dev(nbr, "nbr", torch.int32), _dev(g, "g", torch.uint8), _dev(d2, "d2", torch.int32), b, h, w, radius,
+          _stream())
+    return d2
+
+
+def sample_pixels(raster_i32, coords_i32):
+    """int32 [B, H, W] raster + int32 [N, 3] rows (slot, y, x) -> int32 [N]: the raster's values at those pixels, gathered on the
+    device (plain indexing: this is glue, the list is a few thousand skeleton pixels)."""
+
+    if not raster_i32.is_cuda or not coords_i32.is_cuda:
+        raise RuntimeError("robosat_amd: `raster` is on {} and `coords` on {} -- both live on the MI355X".format(raster_i32.device, coords_i32.device))
+    if raster_i32.dim() != 3 or raster_i32.dtype != torch.int32 or coords_i32.dim() != 2 or coords_i32.shape[1] != 3 or coords_i32.dtype != torch.int32:
+        raise ValueError("robosat_amd: sample_pixels takes an int32 [B, H, W] raster and int32 [N, 3] rows (slot, y, x)")
+    c = coords_i32.long()
+    return raster_i32[c[:, 0], c[:, 1], c[:, 2]]

@@ -5,6 +5,10 @@ edges come back to the host, which links them into rings, simplifies and georefe
 ``--stitch`` treats the tiles of a zoom level as one sparse raster, so an object that crosses tile borders is one polygon.
 ``--geometry centerline`` gives LineStrings for linear classes such as roads: the cleaned mask is thinned to its skeleton on the
 device too, and the host links, prunes and simplifies the skeleton's lines.
+``--width`` (with ``--geometry centerline``) gives every line its road's width: an exact Euclidean distance transform of the cleaned
+mask, capped at ``--max_width // 2 + 2`` pixels, runs on the device beside the thinning and is sampled along the pruned lines; a line
+gains ``width_px`` (the median of 2 * distance - 1 over its pixels), ``width_min_px``, ``width_max_px``, ``width_m`` and, where the
+road is wider than ``--max_width``, ``width_capped``.
 ``--dedupe DIR`` drops the polygons the reference labels in DIR already map (the reference's ``rs dedupe``, on rasters): both
 sides are labelled on the device, one kernel tabulates the pixels every pair of components shares, and a component whose
 intersection over union with the reference objects it touches reaches ``--dedupe_threshold`` is left out.
@@ -21,7 +25,7 @@ from tqdm import tqdm
 
 from robosat_amd import ops
 from robosat_amd.config import load_config
-from robosat_amd.features import (FeatureWriter, centerlines, centerlines_stitched, dedupe_keep, featurize, featurize_stitched,
+from robosat_amd.features import (FeatureWriter, Widths, centerlines, centerlines_stitched, dedupe_keep, featurize, featurize_stitched,
                                   group_clusters, pack_clusters, stitch_tables)
 from robosat_amd.tiles import tiles_from_slippy_map
 
@@ -45,9 +49,15 @@ def add_parser(subparser):
     parser.add_argument("--geometry", type=str, default="polygon", choices=["polygon", "centerline"],
                         help="polygon: the outline of every component; centerline: LineStrings along its skeleton (roads). Without "
                         "--stitch a centerline stops about half the road's width short of every tile border (a 20-pixel road crossing a "
-                        "tile ends 9-10 pixels inside it), so roads want --stitch")
+                        "tile ends 9-10 pixels inside it), so roads want --stitch. --width adds the road's width to every line")
     parser.add_argument("--prune", type=float, default=20, help="centerline: side branches shorter than this many pixels are removed")
     parser.add_argument("--tolerance", type=float, default=1.5, help="centerline: Douglas-Peucker tolerance in pixels")
+    parser.add_argument("--width", action="store_true",
+                        help="centerline: every line gains width_px, width_min_px, width_max_px and width_m, from a distance transform of "
+                        "the cleaned mask sampled along the line (the median over its pixels); an even width reads one pixel narrow")
+    parser.add_argument("--max_width", type=int, default=64, metavar="N",
+                        help="with --width: roads up to N pixels wide are measured (1..252); a wider one reads as its cap and is marked "
+                        "width_capped. With --stitch N // 2 + 2 pixels must fit the tile's smaller side")
     parser.add_argument("--dedupe", type=str, default=None, metavar="DIR",
                         help="slippy map directory with class-index masks of what is already mapped (a dataset's labels, rasterized "
                         "OpenStreetMap): polygons they cover are dropped, the rest gain the property iou. The reference pixels are "
@@ -108,6 +118,30 @@ class Dedupe:
         return table[torch.from_numpy(keep).to(table.device)].contiguous(), dict(zip(keys, iou[keep].tolist()))
 
 
+def width_radius(max_width):
+    """Radius of the distance transform that measures a road of ``max_width`` pixels uncapped."""
+
+    return max_width // 2 + 2
+
+
+def _sampler(d2):
+    """``Widths.sample`` over the raster ``d2`` on the device: the chain pixels go up, their values come back."""
+
+    def sample(coords):
+        return ops.sample_pixels(d2, torch.from_numpy(coords).to(d2.device)).cpu().numpy()
+
+    return sample
+
+
+def _tile_sizes(masks):
+    """(tile, path, (height, width)) from the PNG headers, one by one in the order (z, x, y): a mask is decoded when its batch runs."""
+
+    for tile, path in sorted(tiles_from_slippy_map(masks), key=lambda t: (t[0].z, t[0].x, t[0].y)):
+        with Image.open(path) as image:
+            width, height = image.size
+        yield tile, path, (height, width)
+
+
 def stitched(items, index, args, device, writer, dedupe=None):
     """``--stitch``: per zoom level, the 8-connected clusters of tiles packed whole into device calls."""
 
@@ -133,7 +167,7 @@ def stitched(items, index, args, device, writer, dedupe=None):
             nbr, origin, _ = stitch_tables(tiles, shape)
             nbr, origin = torch.from_numpy(nbr).to(device), torch.from_numpy(origin).to(device)
             images = _load([paths[t] for t in tiles], device)
-            iou = None
+            iou = widths = None
             if dedupe is not None:  # (the stages of ops.stitched_features, with the reference between the table and the edges)
                 labels = ops.stitch_labels(ops.label_components(ops.clean_masks_stitched(images, nbr, index, args.denoise, args.grow)), nbr,
                                            inplace=True)
@@ -141,11 +175,18 @@ def stitched(items, index, args, device, writer, dedupe=None):
                                            dedupe.load(tiles, shape, device), nbr, origin)
                 rows = ops.boundary_edges_stitched(labels, nbr, origin, table)
             else:
-                stages = ops.stitched_centerlines if args.geometry == "centerline" else ops.stitched_features
-                table, rows = stages(images, nbr, origin, index, args.denoise, args.grow, args.min_area)
+                if args.width:
+                    radius = width_radius(args.max_width)
+                    table, rows, d2 = ops.stitched_centerlines(images, nbr, origin, index, args.denoise, args.grow, args.min_area,
+                                                               width_radius=radius)
+                    widths = Widths(_sampler(d2), radius)
+                else:
+                    stages = ops.stitched_centerlines if args.geometry == "centerline" else ops.stitched_features
+                    table, rows = stages(images, nbr, origin, index, args.denoise, args.grow, args.min_area)
             try:
                 if args.geometry == "centerline":
-                    writer.add(centerlines_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.prune, args.tolerance))
+                    writer.add(centerlines_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.prune, args.tolerance,
+                                                    widths=widths))
                 else:
                     writer.add(featurize_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify, iou=iou))
             except ValueError as exc:
@@ -170,6 +211,17 @@ def main(args):
             sys.exit("Error: --dedupe {} is not a directory".format(args.dedupe))
         if args.geometry == "centerline":
             sys.exit("Error: --dedupe compares areas, which says nothing about lines: not with --geometry centerline")
+    if args.width:
+        if args.geometry != "centerline":
+            sys.exit("Error: --width measures along centerlines: only with --geometry centerline")
+        if not 1 <= args.max_width <= 252:
+            sys.exit("Error: --max_width must be in 1..252")
+        if args.stitch:  # (the tile sizes are in the PNG headers: no device needed to say this)
+            radius = width_radius(args.max_width)
+            for h, w in sorted({shape for _, _, shape in _tile_sizes(args.masks)}):
+                if radius > min(h, w):
+                    sys.exit("Error: --max_width {} needs a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
+                             .format(args.max_width, radius, h, w, min(h, w)))
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
@@ -177,9 +229,7 @@ def main(args):
     dedupe = Dedupe(args.dedupe, args.dedupe_threshold, index) if args.dedupe is not None else None
 
     by_shape = {}  # (H, W) -> [(tile, path)]: the header gives the size, a mask is decoded when its batch runs
-    for tile, path in sorted(tiles_from_slippy_map(args.masks), key=lambda t: (t[0].z, t[0].x, t[0].y)):
-        with Image.open(path) as image:
-            width, height = image.size
+    for tile, path, (height, width) in _tile_sizes(args.masks):
         if not (1 <= height <= 4096 and 1 <= width <= 4096):
             sys.exit("Error: {} is {}x{}; tiles are at most 4096x4096".format(path, height, width))
         by_shape.setdefault((height, width), []).append((tile, path))
@@ -199,8 +249,12 @@ def main(args):
             table = ops.component_table(labels, args.min_area)
             if args.geometry == "centerline":
                 links = ops.skeleton_links(ops.thin_masks(cleaned), labels, table)
+                widths = None
+                if args.width:  # (the same cleaned mask goes to the thinning and to the transform)
+                    radius = width_radius(args.max_width)
+                    widths = Widths(_sampler(ops.distance_transform(cleaned, radius)), radius)
                 writer.add(centerlines(links.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.prune,
-                                       args.tolerance))
+                                       args.tolerance, widths=widths))
                 continue
             iou = None
             if dedupe is not None:

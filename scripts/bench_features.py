@@ -23,6 +23,13 @@
            per pixel) beside the labeller on the same tiles, and `./rs features` from disk without and with the flag, written to
            profiles/features_dedupe/bench_dedupe.json (`--dedupe-leg --stage-loop N`: the stages N times, for rocprofv3)
 
+  --width-leg   `rs features --geometry centerline --width`: the distance transform beside the thinning it sits next to, the centerline
+           raster stages per batch without and with it, and scipy.ndimage.distance_transform_edt on the host for the same cleaned
+           masks; 16 tiles of 512 x 512 of tests/thin_ref.roads (22 pixels wide, so the 20-pixel opening keeps them) and a stitched
+           4 x 4 call cut from one such raster, written to profiles/features_width/bench_width.json (`--width-leg --stage-loop N`:
+           the stages N times, for rocprofv3; `--width-leg --without-only`: only the stages without the transform, which also runs
+           on a tree from before it, for the comparison with the parent commit)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -372,6 +379,96 @@ def dedupe_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+def width_leg(args):
+    """The distance transform beside the thinning, and the centerline stages per batch without and with it."""
+
+    import torch
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import thin_ref
+
+    from robosat_amd import ops
+    from robosat_amd.features import stitch_tables
+    from robosat_amd.tiles import Tile
+
+    n, size, eps, r, radius = args.width_block, args.size, args.eps, args.repeat, args.max_width // 2 + 2
+    batch = np.stack([thin_ref.roads(size, size, seed, count=6, width=22) for seed in range(args.batch)]).astype(np.uint8)
+    block = thin_ref.roads(n * size, n * size, 100, count=6 * n, width=22).astype(np.uint8)
+    tiles = np.stack([block[y * size:(y + 1) * size, x * size:(x + 1) * size] for x in range(n) for y in range(n)])
+    nbr, origin, _ = stitch_tables([Tile(x, y, 18) for x in range(n) for y in range(n)], (size, size))
+    dev, dev_tiles = torch.from_numpy(batch).to("cuda:0"), torch.from_numpy(tiles).to("cuda:0")
+    nbr, origin = torch.from_numpy(nbr).to("cuda:0"), torch.from_numpy(origin).to("cuda:0")
+
+    def per_tile(width):
+        cleaned = ops.clean_masks(dev, 1, eps, eps)
+        labels = ops.label_components(cleaned)
+        table = ops.component_table(labels, 0)
+        links = ops.skeleton_links(ops.thin_masks(cleaned), labels, table).cpu()
+        if width:  # (the skeleton's pixels stand in for the pruned chains: the same few thousand coordinates up, their values back)
+            d2 = ops.distance_transform(cleaned, radius)
+            at = links[:, [0, 3, 2]].to("cuda:0")
+            return links, ops.sample_pixels(d2, at).cpu()
+        return links
+
+    def stitched(width):
+        if not width:
+            return ops.stitched_centerlines(dev_tiles, nbr, origin, 1, eps, eps, 0)[1].cpu()
+        _, links, d2 = ops.stitched_centerlines(dev_tiles, nbr, origin, 1, eps, eps, 0, width_radius=radius)
+        links = links.cpu()
+        slot = torch.div(links[:, 1], size, rounding_mode="floor") * n + torch.div(links[:, 2], size, rounding_mode="floor")
+        at = torch.stack([slot, links[:, 2] % size, links[:, 1] % size], dim=1).to(torch.int32).to("cuda:0")
+        return links, ops.sample_pixels(d2, at).cpu()
+
+    if args.stage_loop:
+        for _ in range(args.stage_loop):
+            per_tile(not args.without_only)
+            stitched(not args.without_only)
+        return
+
+    result = {"batch": args.batch, "size": size, "eps": eps, "block": n, "max_width": args.max_width, "radius": radius, "repeat": r,
+              "per_tile": {}, "stitched": {"tiles": len(tiles)}}
+    # alternating, so that a drift of the machine shows in both
+    rounds = {"per_tile": {False: [], True: []}, "stitched": {False: [], True: []}}
+    for _ in range(3):
+        for width in ((False,) if args.without_only else (False, True)):
+            rounds["per_tile"][width].append(timed(lambda: per_tile(width), r) * 1e3)
+            rounds["stitched"][width].append(timed(lambda: stitched(width), r) * 1e3)
+    for name in ("per_tile", "stitched"):
+        result[name]["centerline_stages_ms_without_width_3_rounds"] = rounds[name][False]
+        if not args.without_only:
+            result[name]["centerline_stages_ms_with_width_3_rounds"] = rounds[name][True]
+    if not args.without_only:
+        cleaned = ops.clean_masks(dev, 1, eps, eps)
+        d2 = ops.distance_transform(cleaned, radius)
+        result["per_tile"].update({
+            "foreground_cleaned": float(cleaned.float().mean()), "capped_share_of_foreground": float((d2 == radius * radius).float().sum() / cleaned.sum()),
+            "ms_split": {"thin": timed(lambda: ops.thin_masks(cleaned), r) * 1e3,
+                         "distance_transform": timed(lambda: ops.distance_transform(cleaned, radius), r) * 1e3,
+                         "distance_transform_radius_128": timed(lambda: ops.distance_transform(cleaned, 128), r) * 1e3,
+                         "distance_transform_all_ones_radius_128": timed(
+                             lambda: ops.distance_transform(torch.ones_like(cleaned), 128), r) * 1e3}})
+        cleaned_tiles = ops.clean_masks_stitched(dev_tiles, nbr, 1, eps, eps)
+        result["stitched"]["ms_split"] = {"thin": timed(lambda: ops.thin_masks(cleaned_tiles, nbr), r) * 1e3,
+                                          "distance_transform": timed(lambda: ops.distance_transform(cleaned_tiles, radius, nbr), r) * 1e3,
+                                          "distance_transform_ignoring_seams": timed(lambda: ops.distance_transform(cleaned_tiles, radius), r) * 1e3}
+        try:
+            from scipy import ndimage
+
+            host = cleaned.cpu().numpy() != 0
+            t0 = time.perf_counter()
+            for m in host:
+                ndimage.distance_transform_edt(np.pad(m, radius, constant_values=True))
+            result["per_tile"]["scipy_distance_transform_edt_ms_one_process"] = (time.perf_counter() - t0) * 1e3
+        except ImportError as exc:
+            result["per_tile"]["scipy_distance_transform_edt_ms_one_process"] = "skipped: {}".format(exc)
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "features_width", "bench_width.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def device_stage(images, eps):
     import torch
 
@@ -420,6 +517,10 @@ def main():
     ap.add_argument("--stitch-leg", action="store_true", help="only the stitched path against the per-tile path on an n x n block")
     ap.add_argument("--centerline-leg", action="store_true", help="only thinning and links, on a road network and on its n x n block")
     ap.add_argument("--dedupe-leg", action="store_true", help="only rs features --dedupe: the stages with and without the reference")
+    ap.add_argument("--width-leg", action="store_true", help="only rs features --width: the distance transform beside the thinning")
+    ap.add_argument("--without-only", action="store_true", help="--width-leg: only the stages without the transform")
+    ap.add_argument("--max-width", type=int, default=64, help="--width-leg: as --max_width of rs features (radius N // 2 + 2)")
+    ap.add_argument("--width-block", type=int, default=4, help="--width-leg: tiles per side of the stitched call")
     ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched legs' block")
     ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
@@ -429,6 +530,8 @@ def main():
         return centerline_leg(args)
     if args.dedupe_leg:
         return dedupe_leg(args)
+    if args.width_leg:
+        return width_leg(args)
 
     import torch
 
