@@ -744,6 +744,61 @@ int rs_features_edt(const uint8_t* masks, const int32_t* nbr, uint8_t* g, int32_
  * width_capped = true where any pixel of the chain has d2 == R*R (absent otherwise).  An axis-parallel road of odd width w gives
  * exactly w, one of even width w - 1 (the skeleton runs on one of the two middle rows). */
 
+/* ---- instances: touching objects split by the influence zones of their cores (`rs features --split R`) ----
+ * Given a cleaned mask m (non-zero = set), its canonical labels Lm (rs_features_label, or rs_features_stitch_labels for the one raster
+ * the tiles form) and a radius R:
+ *   seeds  a pixel is a seed pixel iff d2 == R*R in rs_features_edt(m, R): a disc of radius R around it meets no unset pixel.  Pixels
+ *          outside the raster and absent tiles are unknown, as the transform defines them: an object cut by the raster's edge is not
+ *          eroded from that edge.  The seed mask is labelled the way m is (per tile, or stitched): Ls, 4-connected, a core named
+ *          1 + the index of its smallest pixel.
+ *   start  L0 = Ls where Ls != 0; on a component of m that holds no seed pixel L0 = Lm (a thin component keeps its label and is never
+ *          lost); on the other set pixels L0 = -1 (unassigned); on unset pixels 0.
+ *   step   every pixel with L == -1 looks at its 4-neighbours AS THEY STOOD BEFORE THE STEP (Jacobi) in the fixed order N (y - 1),
+ *          W (x - 1), E (x + 1), S (y + 1) and takes the label of the first one with L > 0; with none it stays -1.  Nothing else
+ *          changes.  A pixel outside the raster reads 0.
+ * Steps repeat until no -1 is left.  That always happens: a -1 pixel is 4-connected through m to a seed pixel of its own component,
+ * and the frontier comes one pixel nearer with every step.  A pixel takes the label of the core that reaches it first (geodesic
+ * influence zones), and a tie is broken by where the neighbours lie, never by the labels' values: stitched labels are numbered
+ * differently from the labels of the same pixels on one large raster, and the partition must be the same in both.  The result is a pure
+ * function of the mask.  A core's root keeps L[root] == root + 1 and so does a thin component's, and a root belongs to one of them
+ * only: rs_features_components*, rs_features_edges* and rs_features_overlaps take the result as it is (rs_features_edges emits an
+ * edge wherever the neighbour's label differs, so two instances that touch each get their side of the shared border).
+ *
+ * rs_features_split_cores: d2 int32 [pixels] (rs_features_edt with radius R, 1 .. 128) -> cores uint8 [pixels] = (d2 == R*R).
+ *
+ * rs_features_split_seeds: labels = Lm, seed_labels = Ls, both int32 [pixels]; `group` = pixels per independent raster as in
+ * rs_features_overlaps (H*W per tile, T*H*W stitched; pixels % group == 0; pixels < 2^29) -> out int32 [pixels] = L0 (out may be
+ * labels or seed_labels themselves).  has: `pixels` bytes of scratch, zeroed by the call.  Two launches: the first sets
+ * has[raster * group + Lm[p] - 1] = 1 for every seed pixel p (the Lm root of its component; the only racing store, and every racer
+ * stores the same byte), the second writes L0, every output by one thread.
+ *
+ * rs_features_grow: labels int32 [B][H][W] holding L0 or any later state -> `steps` (1 .. 2^20) steps further, in place.
+ * workspace: rs_features_grow_workspace_bytes(B, H, W) bytes.  nbr NULL: each of the B tiles is a raster of its own.  nbr int32
+ * [B][8] (the table of rs_features_halo): the tiles are one sparse raster -- the 4-neighbour across a seam is the facing pixel of the
+ * neighbouring tile and an absent tile reads 0, as in rs_features_edges_stitched.  counters (int32 [2], device, zeroed by the call):
+ * [0] = pixels assigned by this call, [1] = pixels still -1 after it.  The host enqueues chunks of steps and stops at
+ * counters[1] == 0; the result does not depend on the chunks.  counters[0] == 0 with counters[1] != 0 means the -1 pixels left can
+ * never be reached (no raster that rs_features_split_seeds wrote has such pixels): an error for the host to raise, not to spin on.
+ *
+ * A step reaches one pixel, so K steps on a block of pixels are exact when it is loaded with an apron of K pixels.  A launch takes
+ * K steps (the last launch of a call what is left of `steps`): a workgroup loads its 32 x 64 block of a tile with an apron of K
+ * pixels into LDS (through nbr, corners included, in the stitched form), leaves at once if the block holds no -1, takes the steps
+ * there (a barrier between reading the neighbours and writing the new labels: Jacobi) and writes the block back.  What a step makes
+ * of an apron pixel within s pixels of the loaded region's edge after s steps may be wrong; it cannot reach the block within K steps.
+ * Launches ping-pong between `labels` and the workspace: an apron is read from the launch's input, which no workgroup of that launch
+ * writes (a workgroup that has nothing left to do copies its block across once, and remembers it in a byte of its own in the
+ * workspace).  After an odd number of launches the call copies the workspace back.  K = rs_features_grow_config's `fused` (12:
+ * profiles/features_split, against the same kernel at K = 1; the knob grow_fused, 1 .. 16, overrides it for measurements), clamped to
+ * min(H, W) so that one step in nbr reaches the whole apron.  No workgroup waits for another, every loop is bounded, integers only:
+ * bit-identical for every K and every `steps`.  rs_features_grow_config: the block's rows and columns and the K in force. */
+int rs_features_split_cores(const int32_t* d2, uint8_t* cores, long pixels, int R, rs_stream_t stream);
+int rs_features_split_seeds(const int32_t* labels, const int32_t* seed_labels, uint8_t* has, int32_t* out, long pixels, long group,
+                            rs_stream_t stream);
+long rs_features_grow_workspace_bytes(int B, int H, int W);
+int rs_features_grow_config(int* block_h, int* block_w, int* fused);
+int rs_features_grow(int32_t* labels, void* workspace, const int32_t* nbr, int32_t* counters, int B, int H, int W, int steps,
+                     rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,12 @@ SIGNATURES = {
     "rs_features_skeleton_links": (c_int, [P, P, P, P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),
     # road widths: capped squared Euclidean distance transform (rs features --width)
     "rs_features_edt": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    # instances: seeds and regrowth (rs features --split)
+    "rs_features_split_cores": (c_int, [P, P, c_long, c_int, P]),
+    "rs_features_split_seeds": (c_int, [P, P, P, P, c_long, c_long, P]),
+    "rs_features_grow_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "rs_features_grow_config": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
+    "rs_features_grow": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

@@ -955,6 +955,156 @@ __global__ __launch_bounds__(256) void edt_col_kernel(const uint8_t* __restrict_
   }
 }
 
+// ---- instances: seeds and regrowth (`rs features --split`; definitions: include/robosat_hip.h) -------------------------------
+__global__ __launch_bounds__(256) void split_cores_kernel(const int* __restrict__ d2, uint8_t* __restrict__ cores, long pixels, int cap) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p < pixels) cores[p] = d2[p] == cap ? 1 : 0;
+}
+
+// has[root of the Lm component] = 1 for every seed pixel (every racer stores the same byte).
+__global__ __launch_bounds__(256) void split_mark_kernel(const int* __restrict__ Lm, const int* __restrict__ Ls, uint8_t* has, long pixels,
+                                                         long group) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= pixels || Ls[p] == 0) return;
+  const int lm = Lm[p];
+  if (lm >= 1 && lm <= group) has[p / group * group + lm - 1] = 1;
+}
+
+// (Lm, Ls and out may be one another: a thread reads its own pixel before it writes it, and nobody else's)
+__global__ __launch_bounds__(256) void split_start_kernel(const int* Lm, const int* Ls, const uint8_t* __restrict__ has, int* out,
+                                                          long pixels, long group) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= pixels) return;
+  const int lm = Lm[p], ls = Ls[p];
+  int v = 0;
+  if (ls != 0) v = ls;
+  else if (lm >= 1 && lm <= group) v = has[p / group * group + lm - 1] ? -1 : lm;
+  out[p] = v;
+}
+
+// A block of kGrowH x kGrowW pixels of one tile with an apron of K pixels, in LDS as [kGrowH + 2K][kGrowW + 2K]; thread t owns
+// the region's pixels j * 256 + t.  `pend`: bit j = that pixel is -1 and not on the region's outermost ring (so its four neighbours
+// are in LDS: no bounds in the step loop); `core`: bit j = the pixel is the block's own and inside the tile.
+constexpr int kGrowH = 32, kGrowW = 64;
+constexpr int kGrowMaxK = 16;
+constexpr int kGrowRule = 12;  // steps per launch (profiles/features_split: 0.16 ms against 0.52 ms at K = 1 for 16 x 512 x 512)
+constexpr int kGrowPer = ((kGrowH + 2 * kGrowMaxK) * (kGrowW + 2 * kGrowMaxK) + 255) / 256;  // 24
+
+struct GrowArgs {
+  const int* src;
+  int* dst;
+  const int* nbr;  // STITCH: [B][8]
+  uint8_t* done;   // [2][blocks]: plane `to` = this block's pixels of dst are final
+  int* counters;
+  int B, H, W, K, steps, to, last;
+};
+
+template <bool STITCH>
+__global__ __launch_bounds__(256) void grow_kernel(const GrowArgs a) {
+  extern __shared__ __attribute__((aligned(16))) int region[];
+  const int K = a.K, RH = kGrowH + 2 * K, RW = kGrowW + 2 * K, RN = RH * RW;
+  const int tile = blockIdx.z, y0 = blockIdx.y * kGrowH - K, x0 = blockIdx.x * kGrowW - K;
+  const long HW = (long)a.H * a.W;
+  const long block = ((long)tile * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, blocks = (long)gridDim.x * gridDim.y * gridDim.z;
+  unsigned int pend = 0u, core = 0u;
+  long at[kGrowPer];  // (of the core pixels only: where they go in dst)
+#pragma unroll
+  for (int j = 0; j < kGrowPer; ++j) {
+    const int i = j * 256 + threadIdx.x;
+    at[j] = -1;
+    if (i >= RN) continue;
+    const int ry = i / RW, rx = i - ry * RW;
+    int y = y0 + ry, x = x0 + rx;
+    const int dy = y < 0 ? -1 : y >= a.H ? 1 : 0, dx = x < 0 ? -1 : x >= a.W ? 1 : 0;
+    int v = 0;
+    if (!(dx | dy)) {
+      const long g = (long)tile * HW + (long)y * a.W + x;
+      v = a.src[g];
+      if (ry >= K && ry < K + kGrowH && rx >= K && rx < K + kGrowW) {
+        core |= 1u << j;
+        at[j] = g;
+      }
+    } else if (STITCH) {  // (K <= min(H, W): one step in the table reaches the apron)
+      y -= dy * a.H;
+      x -= dx * a.W;
+      const int n = y >= 0 && y < a.H && x >= 0 && x < a.W ? nbr_slot(a.nbr, tile, dx, dy, a.B) : -1;
+      if (n >= 0) v = a.src[(long)n * HW + (long)y * a.W + x];
+    }
+    region[i] = v;
+    if (v == -1 && ry > 0 && ry < RH - 1 && rx > 0 && rx < RW - 1) pend |= 1u << j;
+  }
+  // bit 0: a pixel of this block is still -1; bit 1: dst already holds this block (the byte is this block's own and is read by
+  // thread 0 alone, before the barrier; the store below comes behind it, so no thread of this launch can see that store)
+  uint8_t* done = a.done + (long)a.to * blocks + block;
+  int state = (pend & core) ? 1 : 0;
+  if (threadIdx.x == 0 && *done) state |= 2;
+  rs_lds_writes_done();
+  state = __syncthreads_or(state);
+  if (!(state & 1)) {  // nothing left in this block: dst gets it once, then the block only looks
+    if (state & 2) return;  // (uniform)
+#pragma unroll
+    for (int j = 0; j < kGrowPer; ++j)
+      if (core & (1u << j)) a.dst[at[j]] = region[j * 256 + threadIdx.x];
+    if (threadIdx.x == 0) *done = 1;
+    return;
+  }
+  const unsigned int before = pend & core;
+  for (int s = 0; s < a.steps; ++s) {
+    int fresh[kGrowPer];
+    unsigned int got = 0u;
+#pragma unroll
+    for (int j = 0; j < kGrowPer; ++j) {
+      fresh[j] = 0;
+      if (pend & (1u << j)) {
+        const int i = j * 256 + threadIdx.x;
+        const int n = region[i - RW], w = region[i - 1], e = region[i + 1], so = region[i + RW];
+        const int v = n > 0 ? n : w > 0 ? w : e > 0 ? e : so > 0 ? so : 0;
+        if (v > 0) {
+          fresh[j] = v;
+          got |= 1u << j;
+        }
+      }
+    }
+    __syncthreads();  // every neighbour has been read as it stood before the step
+#pragma unroll
+    for (int j = 0; j < kGrowPer; ++j)
+      if (got & (1u << j)) region[j * 256 + threadIdx.x] = fresh[j];
+    pend &= ~got;
+    rs_lds_writes_done();
+    if (!__syncthreads_or((int)pend)) break;  // (uniform)
+  }
+#pragma unroll
+  for (int j = 0; j < kGrowPer; ++j)
+    if (core & (1u << j)) a.dst[at[j]] = region[j * 256 + threadIdx.x];
+  int assigned = __popc(before & ~pend), left = __popc(pend & core);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    assigned += __shfl_xor(assigned, o, 64);
+    left += __shfl_xor(left, o, 64);
+  }
+  // one atomic per block and counter
+  __shared__ int tally[2][4];
+  if ((threadIdx.x & 63) == 0) {
+    tally[0][threadIdx.x >> 6] = assigned;
+    tally[1][threadIdx.x >> 6] = left;
+  }
+  rs_lds_writes_done();
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    assigned = tally[0][0] + tally[0][1] + tally[0][2] + tally[0][3];
+    left = tally[1][0] + tally[1][1] + tally[1][2] + tally[1][3];
+    if (assigned) atomicAdd(&a.counters[0], assigned);
+    if (left && a.last) atomicAdd(&a.counters[1], left);
+  }
+}
+
+int grow_fused() {
+  const int k = rs_knobs().grow_fused;
+  return k >= 1 && k <= kGrowMaxK ? k : kGrowRule;
+}
+
+long grow_blocks(int B, int H, int W) { return (long)B * rs_cdiv(H, kGrowH) * rs_cdiv(W, kGrowW); }
+
 // (B rides in gridDim.y; 4 edges per pixel at the very most stay below 2^31 in the int32 edge counter)
 bool shape_ok(int B, int H, int W) { return B > 0 && B <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)B * H * W < (1l << 29); }
 
@@ -1207,6 +1357,75 @@ extern "C" int rs_features_edt(const uint8_t* masks, const int32_t* nbr, uint8_t
   } else {
     edt_row_kernel<false><<<row_grid, 256, 0, s>>>(masks, nullptr, g, B, H, W, R);
     edt_col_kernel<false><<<col_grid, 256, lds, s>>>(g, nullptr, d2, B, H, W, R);
+  }
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_split_cores(const int32_t* d2, uint8_t* cores, long pixels, int R, rs_stream_t stream) {
+  if (!d2 || !cores || pixels <= 0 || pixels >= (1l << 29) || R < 1 || R > kEdtMaxR) return RS_EINVAL;
+  split_cores_kernel<<<rs_cdiv(pixels, 256), 256, 0, (hipStream_t)stream>>>(d2, cores, pixels, R * R);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_split_seeds(const int32_t* labels, const int32_t* seed_labels, uint8_t* has, int32_t* out, long pixels,
+                                       long group, rs_stream_t stream) {
+  if (!labels || !seed_labels || !has || !out || pixels <= 0 || pixels >= (1l << 29) || group <= 0 || pixels % group != 0) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(has, 0, pixels, s);
+  if (e != hipSuccess) return (int)e;
+  split_mark_kernel<<<rs_cdiv(pixels, 256), 256, 0, s>>>(labels, seed_labels, has, pixels, group);
+  split_start_kernel<<<rs_cdiv(pixels, 256), 256, 0, s>>>(labels, seed_labels, has, out, pixels, group);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" long rs_features_grow_workspace_bytes(int B, int H, int W) {
+  if (!shape_ok(B, H, W)) return RS_EINVAL;
+  return (long)B * H * W * 4 + 2 * grow_blocks(B, H, W);
+}
+
+extern "C" int rs_features_grow_config(int* block_h, int* block_w, int* fused) {
+  if (!block_h || !block_w || !fused) return RS_EINVAL;
+  *block_h = kGrowH;
+  *block_w = kGrowW;
+  *fused = grow_fused();
+  return 0;
+}
+
+extern "C" int rs_features_grow(int32_t* labels, void* workspace, const int32_t* nbr, int32_t* counters, int B, int H, int W, int steps,
+                                rs_stream_t stream) {
+  if (!labels || !workspace || ((uintptr_t)workspace & 3) || !counters || !shape_ok(B, H, W) || steps < 1 || steps > (1 << 20))
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)B * H * W, blocks = grow_blocks(B, H, W);
+  int* other = static_cast<int*>(workspace);
+  GrowArgs a;
+  a.nbr = nbr;
+  a.done = reinterpret_cast<uint8_t*>(other + P);
+  a.counters = counters;
+  a.B = B, a.H = H, a.W = W;
+  a.K = grow_fused();
+  if (a.K > (H < W ? H : W)) a.K = H < W ? H : W;
+  hipError_t e = hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), s);
+  if (e == hipSuccess) e = hipMemsetAsync(a.done, 0, 2 * blocks, s);
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid(rs_cdiv(W, kGrowW), rs_cdiv(H, kGrowH), B);
+  const int lds = (kGrowH + 2 * a.K) * (kGrowW + 2 * a.K) * 4;  // at most 24 KB
+  int to = 0;
+  for (int left = steps; left > 0; left -= a.K) {
+    to ^= 1;  // 1: labels -> workspace
+    a.src = to ? labels : other;
+    a.dst = to ? other : labels;
+    a.to = to;
+    a.steps = left < a.K ? left : a.K;
+    a.last = left <= a.K;
+    if (nbr)
+      grow_kernel<true><<<grid, 256, lds, s>>>(a);
+    else
+      grow_kernel<false><<<grid, 256, lds, s>>>(a);
+  }
+  if (to) {
+    e = hipMemcpyAsync(labels, other, P * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return (int)e;
   }
   return RS_LAUNCH_RESULT();
 }

@@ -1782,3 +1782,79 @@ def sample_pixels(raster_i32, coords_i32):
         raise ValueError("robosat_amd: sample_pixels takes an int32 [B, H, W] raster and int32 [N, 3] rows (slot, y, x)")
     c = coords_i32.long()
     return raster_i32[c[:, 0], c[:, 1], c[:, 2]]
+
+
+# ---- rs features --split: touching objects into instances (definitions in include/robosat_hip.h) ---------------------------------
+SPLIT_MAX_RADIUS = 64
+GROW_STEPS = 16  # growth steps enqueued between two reads of the device's counters (profiles/features_split)
+
+
+def grow_config():
+    """(rows, columns, fused steps) of ``rs_features_grow``: the block of pixels a workgroup owns and the steps a launch takes."""
+
+    h, w, k = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    _call("rs_features_grow_config", ctypes.byref(h), ctypes.byref(w), ctypes.byref(k))
+    return h.value, w.value, k.value
+
+
+def split_seeds(labels, seed_labels, stitched=False):
+    """Labels of a mask and of its cores, both int32 [B, H, W] -> int32 [B, H, W], the start raster of the growth: a core's label
+    on its pixels, -1 on the rest of a component that holds a core, the component's own label where it holds none, 0 on background.
+    ``stitched``: the labels are of the one raster the B tiles form."""
+
+    if labels.shape != seed_labels.shape or labels.dim() != 3:
+        raise ValueError("robosat_amd: the label rasters are both [B, H, W], got {} and {}".format(tuple(labels.shape), tuple(seed_labels.shape)))
+    b, h, w = labels.shape
+    pixels = b * h * w
+    lm, ls = _dev(labels, "labels", torch.int32), _dev(seed_labels, "seed_labels", torch.int32)
+    has = torch.empty(pixels, device=labels.device, dtype=torch.uint8)
+    out = torch.empty_like(labels)
+    _call("rs_features_split_seeds", lm, ls, _dev(has, "has", torch.uint8), _dev(out, "out", torch.int32), pixels,
+          pixels if stitched else h * w, _stream())
+    return out
+
+
+def grow_labels(labels, nbr=None, steps=None, want_steps=False):
+    """int32 [B, H, W] as ``split_seeds`` left it -> the same tensor, grown in place until no pixel is -1: every -1 pixel takes the
+    label of the first of its N, W, E, S neighbours that had one before the step.  With ``nbr`` int32 [B, 8] the tiles are one sparse
+    raster.  ``steps`` steps (default ``GROW_STEPS``) are enqueued per read of the counters; the result does not depend on it.
+    ``want_steps``: also the number of steps that were enqueued.  -1 pixels that no label can reach raise."""
+
+    b, h, w = labels.shape
+    steps = GROW_STEPS if steps is None else int(steps)
+    if steps < 1:
+        raise ValueError("robosat_amd: the growth enqueues at least one step per chunk, got {}".format(steps))
+    if nbr is not None:
+        assert nbr.shape == (b, 8), "nbr is [T, 8]"
+    lab = _dev(labels, "labels", torch.int32)  # (a CPU tensor raises before anything is sized)
+    ws = torch.empty(_lib.lib().rs_features_grow_workspace_bytes(b, h, w) // 4 + 1, device=labels.device, dtype=torch.int32)
+    counters = torch.empty(2, device=labels.device, dtype=torch.int32)
+    done = 0
+    while True:
+        _call("rs_features_grow", lab, _dev(ws, "workspace", torch.int32), _dev(nbr, "nbr", torch.int32),
+              _dev(counters, "counters", torch.int32), b, h, w, steps, _stream())
+        done += steps
+        assigned, left = counters.tolist()
+        if left == 0:
+            return (labels, done) if want_steps else labels
+        if assigned == 0:
+            raise RuntimeError("rs_features_grow: {} unassigned pixels that no label reaches (after {} steps)".format(left, done))
+
+
+def split_labels(cleaned, labels, radius, nbr=None, steps=None):
+    """``rs features --split``: the cleaned mask uint8 [B, H, W] and its labels int32 [B, H, W] (``label_components``, or with ``nbr``
+    ``stitch_labels``) -> int32 [B, H, W] labels of instances: the cores a disc of ``radius`` pixels fits into, labelled like the mask
+    and grown back over it; a component without a core keeps its label.  ``radius`` in 1..64, with ``nbr`` at most min(H, W).
+    The host reads back the growth's counters once per chunk and, through the existing helpers that label the cores
+    (``label_components``, ``stitch_labels``), their one-word error flags; no raster comes back."""
+
+    radius = int(radius)
+    if not 1 <= radius <= SPLIT_MAX_RADIUS:
+        raise ValueError("robosat_amd: the split radius is in 1..{}, got {}".format(SPLIT_MAX_RADIUS, radius))
+    d2 = distance_transform(cleaned, radius, nbr)
+    cores = torch.empty_like(cleaned)
+    _call("rs_features_split_cores", _dev(d2, "d2", torch.int32), _dev(cores, "cores", torch.uint8), d2.numel(), radius, _stream())
+    seed_labels = label_components(cores)
+    if nbr is not None:
+        seed_labels = stitch_labels(seed_labels, nbr, inplace=True)
+    return grow_labels(split_seeds(labels, seed_labels, stitched=nbr is not None), nbr, steps)

@@ -12,6 +12,10 @@ road is wider than ``--max_width``, ``width_capped``.
 ``--dedupe DIR`` drops the polygons the reference labels in DIR already map (the reference's ``rs dedupe``, on rasters): both
 sides are labelled on the device, one kernel tabulates the pixels every pair of components shares, and a component whose
 intersection over union with the reference objects it touches reaches ``--dedupe_threshold`` is left out.
+``--split R`` separates objects that touch, or that a few pixels of false positive join, into instances: the cores a disc of
+radius R fits into are labelled and grown back over the mask on the device (geodesic influence zones), and ``--min_area``,
+``--dedupe`` and every property then apply to the instances.  Neighbouring instances are simplified one by one, so after
+``--simplify`` their shared border may overlap or gap by up to the epsilon.
 The stage definitions, and where they depart from OpenCV's, are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
@@ -67,6 +71,12 @@ def add_parser(subparser):
     parser.add_argument("--dedupe_threshold", type=float, default=None, metavar="T",
                         help="with --dedupe (required): a polygon is dropped where the pixels it shares with the reference objects it "
                         "touches are at least T times the pixels of their union, 0 <= T <= 1")
+    parser.add_argument("--split", type=int, default=0, metavar="R",
+                        help="polygon: separate touching objects into instances, 0 = off, else 1..64: the parts of the cleaned mask "
+                        "a disc of radius R pixels fits into are labelled and grown back over the mask, so a bridge narrower than 2 R "
+                        "between two objects is cut; an object no such disc fits into stays as it is. Neighbouring instances are "
+                        "simplified one by one, so after --simplify their shared border may overlap or gap by up to the epsilon. "
+                        "With --stitch R pixels must fit the tile's smaller side")
     parser.set_defaults(func=main)
 
 
@@ -168,11 +178,15 @@ def stitched(items, index, args, device, writer, dedupe=None):
             nbr, origin = torch.from_numpy(nbr).to(device), torch.from_numpy(origin).to(device)
             images = _load([paths[t] for t in tiles], device)
             iou = widths = None
-            if dedupe is not None:  # (the stages of ops.stitched_features, with the reference between the table and the edges)
-                labels = ops.stitch_labels(ops.label_components(ops.clean_masks_stitched(images, nbr, index, args.denoise, args.grow)), nbr,
-                                           inplace=True)
-                table, iou = dedupe.filter(labels, ops.component_table_stitched(labels, origin, args.min_area),
-                                           dedupe.load(tiles, shape, device), nbr, origin)
+            if dedupe is not None or args.split:
+                # (the stages of ops.stitched_features, with the instances behind the labels and the reference behind the table)
+                cleaned = ops.clean_masks_stitched(images, nbr, index, args.denoise, args.grow)
+                labels = ops.stitch_labels(ops.label_components(cleaned), nbr, inplace=True)
+                if args.split:
+                    labels = ops.split_labels(cleaned, labels, args.split, nbr)
+                table = ops.component_table_stitched(labels, origin, args.min_area)
+                if dedupe is not None:
+                    table, iou = dedupe.filter(labels, table, dedupe.load(tiles, shape, device), nbr, origin)
                 rows = ops.boundary_edges_stitched(labels, nbr, origin, table)
             else:
                 if args.width:
@@ -211,6 +225,16 @@ def main(args):
             sys.exit("Error: --dedupe {} is not a directory".format(args.dedupe))
         if args.geometry == "centerline":
             sys.exit("Error: --dedupe compares areas, which says nothing about lines: not with --geometry centerline")
+    if args.split:
+        if not 1 <= args.split <= 64:
+            sys.exit("Error: --split must be in 1..64 (0 = off)")
+        if args.geometry == "centerline":
+            sys.exit("Error: --split separates areas, which says nothing about lines: not with --geometry centerline")
+        if args.stitch:  # (the tile sizes are in the PNG headers: no device needed to say this)
+            for h, w in sorted({shape for _, _, shape in _tile_sizes(args.masks)}):
+                if args.split > min(h, w):
+                    sys.exit("Error: --split {} needs a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
+                             .format(args.split, args.split, h, w, min(h, w)))
     if args.width:
         if args.geometry != "centerline":
             sys.exit("Error: --width measures along centerlines: only with --geometry centerline")
@@ -246,6 +270,8 @@ def main(args):
             images = _load([path for _, path in group], device)
             cleaned = ops.clean_masks(images, index, args.denoise, args.grow)
             labels = ops.label_components(cleaned)
+            if args.split:
+                labels = ops.split_labels(cleaned, labels, args.split)
             table = ops.component_table(labels, args.min_area)
             if args.geometry == "centerline":
                 links = ops.skeleton_links(ops.thin_masks(cleaned), labels, table)

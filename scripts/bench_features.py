@@ -30,6 +30,12 @@
            the stages N times, for rocprofv3; `--width-leg --without-only`: only the stages without the transform, which also runs
            on a tree from before it, for the comparison with the parent commit)
 
+  --split-leg   `rs features --split`: the seed step and the regrowth on 16 tiles of 512 x 512 of tests/split_ref.touching_blobs
+           (discs of about 14 pixels that touch), R = 8: the growth at every candidate number of fused steps K (the knob grow_fused;
+           K = 1 is the baseline, the same kernel) and chunk size, the stages of `ops.split_labels`, the polygon stages per batch
+           without and with the split, and a stitched 4 x 4 call, written to profiles/features_split/bench_split.json
+           (`--split-leg --stage-loop N --fused K`: the growth alone N times at that K, for rocprofv3)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -469,6 +475,128 @@ def width_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+def split_leg(args):
+    """The regrowth at every candidate K, and the polygon stages without and with `--split`."""
+
+    import torch
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import split_ref
+
+    from robosat_amd import ops
+    from robosat_amd.features import stitch_tables
+    from robosat_amd.tiles import Tile
+
+    n, size, r, radius = args.width_block, args.size, args.repeat, args.split_radius
+    batch = np.stack([split_ref.touching_blobs(size, size, seed, radius=14, salt=0) for seed in range(args.batch)]).astype(np.uint8)
+    block = split_ref.touching_blobs(n * size, n * size, 100, radius=14, salt=0).astype(np.uint8)
+    tiles = np.stack([block[y * size:(y + 1) * size, x * size:(x + 1) * size] for x in range(n) for y in range(n)])
+    nbr, origin, _ = stitch_tables([Tile(x, y, 18) for x in range(n) for y in range(n)], (size, size))
+    dev, dev_tiles = torch.from_numpy(batch).to("cuda:0"), torch.from_numpy(tiles).to("cuda:0")
+    nbr, origin = torch.from_numpy(nbr).to("cuda:0"), torch.from_numpy(origin).to("cuda:0")
+
+    def start_of(cleaned, labels, table):
+        d2 = ops.distance_transform(cleaned, radius, table)
+        cores = (d2 == radius * radius).to(torch.uint8)  # (the bench's own threshold: ops.split_labels has a kernel for it)
+        seeds = ops.label_components(cores)
+        if table is not None:
+            seeds = ops.stitch_labels(seeds, table, inplace=True)
+        return cores, ops.split_seeds(labels, seeds, stitched=table is not None)
+
+    labels = ops.label_components(dev)
+    cores, start = start_of(dev, labels, None)
+    work = {}
+
+    def grow(steps=None, source=start, table=None):
+        buf = work.setdefault(tuple(source.shape), torch.empty_like(source))
+        buf.copy_(source)
+        return ops.grow_labels(buf, table, steps, want_steps=True)
+
+    if args.stage_loop:
+        with ops.knob("grow_fused", args.fused):
+            for _ in range(args.stage_loop):
+                grow()
+        return
+
+    final, _ = grow(1)
+    final = final.clone()
+    block_h, block_w, rule = ops.grow_config()
+    result = {"batch": args.batch, "size": size, "radius": radius, "repeat": r, "block": [block_h, block_w], "fused_rule": rule,
+              "default_steps_per_chunk": ops.GROW_STEPS, "per_tile": {}, "stitched": {"tiles": len(tiles)}}
+    result["per_tile"].update({
+        "foreground": float(dev.float().mean()), "unassigned_share_of_foreground": float((start == -1).float().sum() / dev.sum()),
+        "components": int(len(ops.component_table(labels, 0))), "instances": int(len(ops.component_table(final, 0))),
+        "steps_to_converge": grow(1)[1], "copy_of_the_start_raster_ms": timed(lambda: work[tuple(start.shape)].copy_(start), r) * 1e3})
+    # alternating rounds, so that a drift of the machine shows in every K
+    by_fused = {k: [] for k in (1, 2, 4, 6, 8, 12, 16)}
+    for _ in range(3):
+        for k in by_fused:
+            with ops.knob("grow_fused", k):
+                got, _ = grow()
+                assert torch.equal(got, final), "fused = {} changes the result".format(k)
+                by_fused[k].append(timed(grow, r) * 1e3)
+    result["per_tile"]["grow_ms_by_fused_steps_3_rounds"] = {str(k): v for k, v in by_fused.items()}
+    result["per_tile"]["grow_ms_by_steps_per_chunk"] = {str(c): timed(lambda: grow(c), r) * 1e3 for c in (8, 16, 24, 32, 48, 64, 128)}
+    grid = {"{}x{}".format(k, c): [] for k in (8, 12, 16) for c in (16, 32, 48)}  # fused steps x steps per chunk, alternating
+    for _ in range(3):
+        for k in (8, 12, 16):
+            with ops.knob("grow_fused", k):
+                for c in (16, 32, 48):
+                    grid["{}x{}".format(k, c)].append(timed(lambda: grow(c), r) * 1e3)
+    result["per_tile"]["grow_ms_by_fused_x_chunk_3_rounds"] = grid
+    result["per_tile"]["grow_ms_by_steps_per_chunk_fused_1"] = {}
+    with ops.knob("grow_fused", 1):
+        for c in (8, 16, 32, 64):
+            result["per_tile"]["grow_ms_by_steps_per_chunk_fused_1"][str(c)] = timed(lambda: grow(c), r) * 1e3
+    seeds = ops.label_components(cores)
+    result["per_tile"]["ms_split"] = {
+        "label": timed(lambda: ops.label_components(dev), r) * 1e3,
+        "distance_transform": timed(lambda: ops.distance_transform(dev, radius), r) * 1e3,
+        "label_cores": timed(lambda: ops.label_components(cores), r) * 1e3,
+        "split_seeds": timed(lambda: ops.split_seeds(labels, seeds), r) * 1e3,
+        "grow": timed(grow, r) * 1e3,
+        "split_labels": timed(lambda: ops.split_labels(dev, labels, radius), r) * 1e3}
+
+    def polygons(split):
+        lab = ops.label_components(dev)
+        if split:
+            lab = ops.split_labels(dev, lab, radius)
+        table = ops.component_table(lab, 0)
+        return ops.boundary_edges(lab, table).cpu()
+
+    def polygons_stitched(split):
+        lab = ops.stitch_labels(ops.label_components(dev_tiles), nbr, inplace=True)
+        if split:
+            lab = ops.split_labels(dev_tiles, lab, radius, nbr)
+        table = ops.component_table_stitched(lab, origin, 0)
+        return ops.boundary_edges_stitched(lab, nbr, origin, table).cpu()
+
+    rounds = {"per_tile": {False: [], True: []}, "stitched": {False: [], True: []}}
+    for _ in range(3):
+        for split in (False, True):
+            rounds["per_tile"][split].append(timed(lambda: polygons(split), r) * 1e3)
+            rounds["stitched"][split].append(timed(lambda: polygons_stitched(split), r) * 1e3)
+    for name in ("per_tile", "stitched"):
+        result[name]["label_table_edges_ms_without_split_3_rounds"] = rounds[name][False]
+        result[name]["label_table_edges_ms_with_split_3_rounds"] = rounds[name][True]
+
+    stitched_labels = ops.stitch_labels(ops.label_components(dev_tiles), nbr, inplace=True)
+    _, stitched_start = start_of(dev_tiles, stitched_labels, nbr)
+    stitched_final = grow(1, stitched_start, nbr)[0].clone()
+    result["stitched"].update({"instances": int(len(ops.component_table_stitched(stitched_final, origin, 0))),
+                               "steps_to_converge": grow(1, stitched_start, nbr)[1], "grow_ms_by_fused_steps": {}})
+    for k in (1, 8, 16):
+        with ops.knob("grow_fused", k):
+            assert torch.equal(grow(None, stitched_start, nbr)[0], stitched_final)
+            result["stitched"]["grow_ms_by_fused_steps"][str(k)] = timed(lambda: grow(None, stitched_start, nbr), r) * 1e3
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "features_split", "bench_split.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def device_stage(images, eps):
     import torch
 
@@ -521,6 +649,9 @@ def main():
     ap.add_argument("--without-only", action="store_true", help="--width-leg: only the stages without the transform")
     ap.add_argument("--max-width", type=int, default=64, help="--width-leg: as --max_width of rs features (radius N // 2 + 2)")
     ap.add_argument("--width-block", type=int, default=4, help="--width-leg: tiles per side of the stitched call")
+    ap.add_argument("--split-leg", action="store_true", help="only rs features --split: the regrowth at every number of fused steps")
+    ap.add_argument("--split-radius", type=int, default=8, help="--split-leg: as --split of rs features")
+    ap.add_argument("--fused", type=int, default=0, help="--split-leg --stage-loop: the knob grow_fused (0 = the rule)")
     ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched legs' block")
     ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
@@ -532,6 +663,8 @@ def main():
         return dedupe_leg(args)
     if args.width_leg:
         return width_leg(args)
+    if args.split_leg:
+        return split_leg(args)
 
     import torch
 
