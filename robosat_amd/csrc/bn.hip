@@ -657,6 +657,7 @@ extern "C" int rs_bn_bwd(const float* dz, const float* zmask, const float* y, co
 
 extern "C" long rs_bn_workspace_bytes(long M, int C) {
   if (M <= 0 || C <= 0 || (C & 3)) return RS_EINVAL;
-  const Geometry g4 = geometry(M, C, 4), g8 = geometry(M, C, 8);  // (either vector width may run)
-  return (long)(g4.R > g8.R ? g4.R : g8.R) * 2 * C * (long)sizeof(double);
+  const Geometry g4 = geometry(M, C, 4);  // (either vector width may run; C = 4 has no 8-channel geometry: Q = 0 divides by zero)
+  const int R8 = C >= 8 ? geometry(M, C, 8).R : 0;
+  return (long)(g4.R > R8 ? g4.R : R8) * 2 * C * (long)sizeof(double);
 }
