@@ -14,14 +14,13 @@
 //           block per CU; <1, 1>: 32 x 32, two waves (the 32-channel layers).
 //   chunk   eight consecutive tiles of ONE tile row: their patches overlap, so the chunk's source pixels are fetched once -- four
 //           rows x 18 pixels instead of 8 x 16 -- next to two rows x 16 pixels of dy; LDS-DMA, gather table (-1 = zeros: padding,
-//           odd edges, the tail of a row), ring of three stages, as in conv_wgrad_wino_f32.hip.
+//           odd edges, the tail of a row), ring of three stages: wgrad_gather_ring.h, shared with conv_wgrad_wino_f32.hip
+//           (geometry, a wave's DMA role, piece schedule, ring loop with its counted wait, accumulator store).
 //   output  partial tiles [split][16][Cout][Cin]; rs_reduce_splits (fixed order), then wino33_wgrad_finish_kernel applies G^T . G.
 #include "conv_wgrad_f32.h"
-#include "lds_dma.h"
+#include "wgrad_gather_ring.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct Wino33WgradArgs {
   const float* dy;   // [N][H][W][Cout]
@@ -40,21 +39,13 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
   constexpr int PK = 8, NS = PK / 2, RING = 3;
   constexpr int NW = 2 * WCO * WCI;
   constexpr int BM = 32 * WCO, BN = 32 * WCI;
-  constexpr int ROWA = BM * 4, ROWB = BN * 4;
-  constexpr int PPA = ROWA / 16, PPB = ROWB / 16;
-  constexpr int RIA = 1024 / ROWA, RIB = 1024 / ROWB;
   constexpr int NRA = 2 * 2 * PK, NRB = 4 * (2 * PK + 2);  // dy: two rows x 16 pixels; source: four rows x 18 pixels
-  constexpr int IA = NRA / RIA, IB = NRB / RIB;
-  static_assert(IA * RIA == NRA && IB * RIB == NRB, "whole instructions");
-  constexpr int NI = (IA + IB + NW - 1) / NW;
-  constexpr int ABYTES = NRA * ROWA, BBYTES = NRB * ROWB;
-  constexpr int BUF = ABYTES + BBYTES;
-  constexpr int NT = NRA + NRB;
-  static_assert(RING * BUF + RING * NT * 4 <= (NW == 8 ? 160 : 53) * 1024, "one / three blocks per CU");
-  static_assert(NT <= 64 * NW, "one table entry per thread");
+  using Ring = WgradGatherRing<BM, BN, NRA, NRB, NW, RING>;
+  constexpr int ROWA = Ring::ROWA, ROWB = Ring::ROWB, ABYTES = Ring::ABYTES, NT = Ring::NT;
+  static_assert(Ring::LDS_BYTES <= (NW == 8 ? 160 : 53) * 1024, "one / three blocks per CU");
 
-  __shared__ __attribute__((aligned(16))) unsigned char smem[RING * BUF + RING * NT * 4];
-  int* tabs = reinterpret_cast<int*>(smem + RING * BUF);  // [RING][NT]: dy rows (u * 16 + x), then source rows (r * 18 + x)
+  __shared__ __attribute__((aligned(16))) unsigned char smem[Ring::LDS_BYTES];
+  int* tabs = Ring::tables(smem);  // [RING][NT]: dy rows (u * 16 + x), then source rows (r * 18 + x)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -100,32 +91,8 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
     rs_lds_writes_done();  // (read by other waves behind a later barrier, which hipcc emits bare: common.h)
   };
 
-  const int ra_a = lane / PPA, pp_a = lane % PPA;
-  const int ra_b = lane / PPB, pp_b = lane % PPB;
-  const int cola = (co0 + pp_a * 4) * 4, colb = (ci0 + pp_b * 4) * 4;
-  const int cout4 = p.Cout * 4, cin4 = p.Cin * 4;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
-  int voff[NI];
-  unsigned int fL = lds0;
-  auto prepare_dma = [&](int buf, int which) __attribute__((always_inline)) {
-    fL = lds0 + buf * BUF;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int ii = wave + NW * j;  // wave-uniform
-      if (ii < IA) {
-        const int pix = tabs[which * NT + RIA * ii + ra_a];
-        voff[j] = pix >= 0 ? pix * cout4 + cola : -1;
-      } else if (ii < IA + IB) {
-        const int pix = tabs[which * NT + NRA + RIB * (ii - IA) + ra_b];
-        voff[j] = pix >= 0 ? pix * cin4 + colb : -1;
-      }
-    }
-  };
-  auto issue_piece = [&](int j) __attribute__((always_inline)) {
-    const int ii = wave + NW * j;
-    if (ii < IA) rs_dma16(rsrc_dy, fL + ii * 1024, voff[j]);
-    else if (ii < IA + IB) rs_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
-  };
+  // A rows: dy pixels of p.Cout channels from co0; B rows: source pixels of p.Cin channels from ci0
+  typename Ring::Dma dma(rsrc_dy, rsrc_x, smem, wave, lane, p.Cout * 4, p.Cin * 4, co0, ci0);
 
   f32x16 acc[8];
 #pragma unroll
@@ -137,17 +104,21 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
   // dy (u, v) is row u * 16 + 2 t + v, source (r, c) row r * 18 + 2 t + c; this wave reads source rows half .. half + 2 only
   const int arow = (lane >> 5) * 2 * ROWA + (wm * 32 + (lane & 31)) * 4;
   const int brow = ABYTES + ((lane >> 5) * 2 + half * 18) * ROWB + (wn * 32 + (lane & 31)) * 4;
-  auto read_frag = [&](const unsigned char* L, int s, float (&dyv)[4], float (&d)[12]) __attribute__((always_inline)) {
+  struct Frag {
+    float dyv[4], d[12];
+  };
+  auto read_frag = [&](const unsigned char* L, int s, Frag& f) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
-      for (int v = 0; v < 2; ++v) dyv[2 * u + v] = *reinterpret_cast<const float*>(L + arow + (16 * u + 4 * s + v) * ROWA);
+      for (int v = 0; v < 2; ++v) f.dyv[2 * u + v] = *reinterpret_cast<const float*>(L + arow + (16 * u + 4 * s + v) * ROWA);
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-      for (int c = 0; c < 4; ++c) d[4 * r + c] = *reinterpret_cast<const float*>(L + brow + (18 * r + 4 * s + c) * ROWB);
+      for (int c = 0; c < 4; ++c) f.d[4 * r + c] = *reinterpret_cast<const float*>(L + brow + (18 * r + 4 * s + c) * ROWB);
   };
-  auto kstep = [&](const float (&dyv)[4], const float (&d)[12], auto issue, int s) __attribute__((always_inline)) {
+  auto kstep = [&](const Frag& f, auto issue, int s) __attribute__((always_inline)) {
+    const auto& [dyv, d] = f;
     // rows i = 2 half, 2 half + 1 of Z = A dY A^T and V = B^T d B.  With d' = the three patch rows this wave read (half .. half + 2):
     //   half 0: Tz0 = dY0, Tz1 = dY0 + dY1;        Tv0 = d'0 - d'2 (rows 0, 2), Tv1 = d'1 + d'2 (rows 1, 2)
     //   half 1: Tz0 = dY0 - dY1, Tz1 = -dY1;       Tv0 = d'1 - d'0 (rows 2, 1), Tv1 = d'0 - d'2 (rows 1, 3)
@@ -179,65 +150,10 @@ __global__ __launch_bounds__(128 * WCO * WCI, WCO * WCI == 4 ? 1 : 3) void conv_
       acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(Z[x], V[x], acc[x], 0, 0, 0);
     }
   };
-  constexpr int NMMA = NS * 8;
-  constexpr int PSTEP = NMMA / (2 * NI) >= 1 ? NMMA / (2 * NI) : 1;
-  auto chunk_mma = [&](const unsigned char* L, bool fetch) __attribute__((always_inline)) {
-    float dyv[2][4], d[2][12];
-    read_frag(L, 0, dyv[0], d[0]);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (s + 1 < NS) read_frag(L, s + 1, dyv[(s + 1) & 1], d[(s + 1) & 1]);
-      kstep(dyv[s & 1], d[s & 1], [&](int q) __attribute__((always_inline)) {
-        if (fetch && q % PSTEP == 0 && q / PSTEP < NI) issue_piece(q / PSTEP);
-      }, s);
-    }
-    if (fetch) {
-#pragma unroll
-      for (int q = (NMMA + PSTEP - 1) / PSTEP; q < NI; ++q) issue_piece(q);
-    }
-  };
+  Ring::template ring<NS, 8, Frag>(dma, smem, chunk0, chunk1, fill_table, read_frag, kstep);
 
-  if (chunk0 < chunk1) {  // (the pipeline of conv_wgrad_wino_f32.hip: chunk c in stage / table (c - chunk0) % RING)
-#pragma unroll
-    for (int r = 0; r < RING; ++r) fill_table(chunk0 + r, r);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RING - 1; ++r) {
-      if (chunk0 + r < chunk1) {
-        prepare_dma(r, r);
-#pragma unroll
-        for (int q = 0; q < NI; ++q) issue_piece(q);
-      }
-    }
-    rs_dma_wait();
-    __syncthreads();
-    int st = 0;
-    for (int c = chunk0; c < chunk1; ++c) {
-      const int stf = st == 0 ? RING - 1 : st - 1;
-      const bool fetch = c + RING - 1 < chunk1;
-      if (fetch) prepare_dma(stf, stf);
-      chunk_mma(smem + st * BUF, fetch);
-      if (fetch) {
-        fill_table(c + RING, st);
-        rs_dma_wait_n<(RING - 2) * NI>();
-      } else {
-        rs_dma_wait();
-      }
-      __syncthreads();
-      st = st == RING - 1 ? 0 : st + 1;
-    }
-  }
-
-  // D[i][j]: i = cout (tile-local) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), j = cin (tile-local) = lane & 31; xi = 8 half + x
-  float* out = p.part + ((long)split * 16 + 8 * half) * p.Cout * p.Cin;
-  const int ci = ci0 + wn * 32 + (lane & 31);
-#pragma unroll
-  for (int x = 0; x < 8; ++x)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      out[((long)x * p.Cout + co) * p.Cin + ci] = acc[x][r];
-    }
+  float* out = p.part + ((long)split * 16 + 8 * half) * p.Cout * p.Cin;  // xi = 8 half + x
+  rs_wgrad_store_acc(out, acc, p.Cout, p.Cin, co0 + wm * 32, ci0 + wn * 32, lane);
 }
 
 // sum [16][Cout][Cin] -> dW [Cout][3][3][Cin]: dg = G^T dU G, G^T = [1 .5 .5 0; 0 .5 -.5 0; 0 .5 .5 1]

@@ -16,17 +16,18 @@
 // sub-tile: nine accumulators of v_mfma_f32_32x32x2_f32 (144 registers), K = tiles, two per MFMA.
 //   HBM -> LDS   LDS-DMA as in conv_wgrad_f32_dma.hip: whole [pixel] rows of the block's channels, each lane its own offset from
 //                a gather table (tile -> its four dz pixels of parity p and its nine source pixels; -1 = zeros: out of the image,
-//                odd edge, tail).  PK = 8 tiles per chunk: 32 dz rows + 72 source rows, two stages, two blocks per CU.
+//                odd edge, tail).  PK = 8 tiles per chunk: 32 dz rows + 72 source rows, a ring of stages, two blocks per CU.
+//                The geometry, a wave's DMA role, the piece schedule, the ring loop with its counted wait and the accumulator
+//                store are wgrad_gather_ring.h, shared with conv_wgrad_wino33_f32.hip; this file fills the table, reads the
+//                fragments and transforms them.
 //   fragments    lane (i = lane & 31, k = lane >> 5) reads channel i of tile 2 s + k: four dwords of dz, nine of the source patch,
 //                transforms them in registers and feeds the nine MFMAs of the k-step.
 //   output       partial tiles [split][parity][xi][Cout][Cin]; wino_wgrad_finish_kernel sums the splits in a fixed order, applies
 //                G^T . G and adds the (parity, tap) pairs that make up each 3x3 filter tap (combine_phase_wgrad_f32_kernel's rule).
 #include "conv_wgrad_f32.h"
-#include "lds_dma.h"
+#include "wgrad_gather_ring.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kWwPK = 8;  // tiles per chunk of the four-wave blocks (the plan counts chunks of this size; the eight-wave block takes two at a time)
 
@@ -53,21 +54,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
   constexpr int NS = PK / 2;
   constexpr int NW = WGM * WGN;
   constexpr int BM = 32 * WGM, BN = 32 * WGN;
-  constexpr int ROWA = BM * 4, ROWB = BN * 4;          // bytes per LDS row (one pixel)
-  constexpr int PPA = ROWA / 16, PPB = ROWB / 16;      // 16-byte pieces per row
-  constexpr int RIA = 1024 / ROWA, RIB = 1024 / ROWB;  // rows per DMA instruction
-  constexpr int NRA = PK * 4, NRB = PK * 9;            // rows per chunk
-  constexpr int IA = NRA / RIA, IB = NRB / RIB;        // DMA instructions per chunk
-  static_assert(IA * RIA == NRA && IB * RIB == NRB, "whole instructions");
-  constexpr int NI = (IA + IB + NW - 1) / NW;          // per wave
-  constexpr int ABYTES = NRA * ROWA, BBYTES = NRB * ROWB;
-  constexpr int BUF = ABYTES + BBYTES;
-  constexpr int NT = NRA + NRB;  // table entries per chunk
-  static_assert(RING * BUF + RING * NT * 4 <= (NW == 8 ? 160 : 80) * 1024, "one / two blocks per CU");
-  static_assert(NT <= 64 * NW, "one table entry per thread");
+  constexpr int NRA = PK * 4, NRB = PK * 9;  // rows per chunk
+  using Ring = WgradGatherRing<BM, BN, NRA, NRB, NW, RING>;
+  constexpr int ROWA = Ring::ROWA, ROWB = Ring::ROWB, ABYTES = Ring::ABYTES, NT = Ring::NT;
+  static_assert(Ring::LDS_BYTES <= (NW == 8 ? 160 : 80) * 1024, "one / two blocks per CU");
 
-  __shared__ __attribute__((aligned(16))) unsigned char smem[RING * BUF + RING * NT * 4];
-  int* tabs = reinterpret_cast<int*>(smem + RING * BUF);  // [RING][NT]: dz rows (tile * 4 + 2 u + v), then source rows (tile * 9 + 3 r + c)
+  __shared__ __attribute__((aligned(16))) unsigned char smem[Ring::LDS_BYTES];
+  int* tabs = Ring::tables(smem);  // [RING][NT]: dz rows (tile * 4 + 2 u + v), then source rows (tile * 9 + 3 r + c)
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -127,36 +120,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
     rs_lds_writes_done();  // (read by other waves behind a later barrier, which hipcc emits bare: common.h)
   };
 
-  // ---- DMA roles: instruction ii = wave + NW j; ii < IA copies dz rows RIA ii.., else source rows RIB (ii - IA)..
-  const int ra_a = lane / PPA, pp_a = lane % PPA;
-  const int ra_b = lane / PPB, pp_b = lane % PPB;
-  const int cola = (co0 + pp_a * 4) * 4, colb = (cs + pp_b * 4) * 4;
-  const int cout4 = p.Cout * 4, cs4 = Cs * 4;
-  const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
-  int voff[NI];
-  unsigned int fL = lds0;
-  auto prepare_dma = [&](int buf, int which) __attribute__((always_inline)) {
-    fL = lds0 + buf * BUF;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int ii = wave + NW * j;  // wave-uniform
-      if (ii < IA) {
-        const int pix = tabs[which * NT + RIA * ii + ra_a];
-        voff[j] = pix >= 0 ? pix * cout4 + cola : -1;
-      } else if (ii < IA + IB) {
-        const int pix = tabs[which * NT + NRA + RIB * (ii - IA) + ra_b];
-        voff[j] = pix >= 0 ? pix * cs4 + colb : -1;
-      }
-    }
-  };
-  auto issue_piece = [&](int j) __attribute__((always_inline)) {
-    const int ii = wave + NW * j;
-#if defined(RS_WW_KO) && (RS_WW_KO & 1)
-    return;  // (knock-out build: no DMA in the steady state -- wrong results by construction)
-#endif
-    if (ii < IA) rs_dma16(rsrc_dz, fL + ii * 1024, voff[j]);
-    else if (ii < IA + IB) rs_dma16(rsrc_x, fL + ABYTES + (ii - IA) * 1024, voff[j]);
-  };
+  // A rows: dz pixels of p.Cout channels from co0; B rows: pixels of this block's concat source, Cs channels from cs
+  typename Ring::Dma dma(rsrc_dz, rsrc_x, smem, wave, lane, p.Cout * 4, Cs * 4, co0, cs);
 
   f32x16 acc[9];
 #pragma unroll
@@ -167,13 +132,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
   // fragment addressing: k-step s, lane (i = lane & 31, k = lane >> 5): tile 2 s + k, channel (sub-tile base + i)
   const int arow = (lane >> 5) * 4 * ROWA + (wm * 32 + (lane & 31)) * 4;
   const int brow = ABYTES + (lane >> 5) * 9 * ROWB + (wn * 32 + (lane & 31)) * 4;
-  auto read_frag = [&](const unsigned char* L, int s, float (&dzv)[4], float (&d)[9]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) dzv[q] = *reinterpret_cast<const float*>(L + arow + (8 * s + q) * ROWA);
-#pragma unroll
-    for (int q = 0; q < 9; ++q) d[q] = *reinterpret_cast<const float*>(L + brow + (18 * s + q) * ROWB);
+  struct Frag {
+    float dzv[4], d[9];
   };
-  auto kstep = [&](const float (&dzv)[4], const float (&d)[9], auto issue, int s) __attribute__((always_inline)) {
+  auto read_frag = [&](const unsigned char* L, int s, Frag& f) __attribute__((always_inline)) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) f.dzv[q] = *reinterpret_cast<const float*>(L + arow + (8 * s + q) * ROWA);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) f.d[q] = *reinterpret_cast<const float*>(L + brow + (18 * s + q) * ROWB);
+  };
+  auto kstep = [&](const Frag& f, auto issue, int s) __attribute__((always_inline)) {
+    const auto& [dzv, d] = f;
     // Z = A dY A^T (A = [1 0; 1 1; 0 1]); V = B^T d B (B^T = [1 -1 0; 0 1 0; 0 -1 1])
     float Z[9], V[9], T[9];
 #if defined(RS_WW_KO) && (RS_WW_KO & 2)
@@ -212,68 +181,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, WGM * WGN == 8 ? 1 : 2) void conv_w
       acc[x] = __builtin_amdgcn_mfma_f32_32x32x2f32(Z[x], V[x], acc[x], 0, 0, 0);
     }
   };
-  constexpr int NMMA = NS * 9;
-  constexpr int PSTEP = NMMA / (2 * NI) >= 1 ? NMMA / (2 * NI) : 1;  // front-loaded: the chunk's tail covers the latency
-  auto chunk_mma = [&](const unsigned char* L, bool fetch) __attribute__((always_inline)) {
-    float dzv[2][4], d[2][9];
-    read_frag(L, 0, dzv[0], d[0]);
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      if (s + 1 < NS) read_frag(L, s + 1, dzv[(s + 1) & 1], d[(s + 1) & 1]);
-      kstep(dzv[s & 1], d[s & 1], [&](int q) __attribute__((always_inline)) {
-        if (fetch && q % PSTEP == 0 && q / PSTEP < NI) issue_piece(q / PSTEP);
-      }, s);
-    }
-    if (fetch) {
-#pragma unroll
-      for (int q = (NMMA + PSTEP - 1) / PSTEP; q < NI; ++q) issue_piece(q);
-    }
-  };
+  Ring::template ring<NS, 9, Frag>(dma, smem, chunk0, chunk1, fill_table, read_frag, kstep);
 
-  if (chunk0 < chunk1) {
-    // chunk c lives in stage / table (c - chunk0) % RING.  Iteration c runs chunk c's MFMAs with the pieces of chunk c + RING - 1 issued
-    // between them (into the stage chunk c - 1 left at the last barrier), writes the table of chunk c + RING (over chunk c's, read
-    // RING - 1 barriers ago) and waits for chunk c + 1's pieces: all but this wave's (RING - 2) NI youngest.
-#pragma unroll
-    for (int r = 0; r < RING; ++r) fill_table(chunk0 + r, r);
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < RING - 1; ++r) {
-      if (chunk0 + r < chunk1) {
-        prepare_dma(r, r);
-#pragma unroll
-        for (int q = 0; q < NI; ++q) issue_piece(q);
-      }
-    }
-    rs_dma_wait();
-    __syncthreads();
-    int st = 0;  // (c - chunk0) % RING
-    for (int c = chunk0; c < chunk1; ++c) {
-      const int stf = st == 0 ? RING - 1 : st - 1;  // stage / table of chunk c + RING - 1
-      const bool fetch = c + RING - 1 < chunk1;     // (block-uniform)
-      if (fetch) prepare_dma(stf, stf);
-      chunk_mma(smem + st * BUF, fetch);
-      if (fetch) {
-        fill_table(c + RING, st);
-        rs_dma_wait_n<(RING - 2) * NI>();
-      } else {
-        rs_dma_wait();
-      }
-      __syncthreads();
-      st = st == RING - 1 ? 0 : st + 1;
-    }
-  }
-
-  // D[i][j]: i = cout (tile-local) = (r & 3) + 8 (r >> 2) + 4 (lane >> 5), j = cin (tile-local) = lane & 31
   float* out = p.part + ((long)(split * 4 + par) * 9) * p.Cout * Cin;
-  const int ci = ci0 + wn * 32 + (lane & 31);
-#pragma unroll
-  for (int x = 0; x < 9; ++x)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int co = co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      out[((long)x * p.Cout + co) * Cin + ci] = acc[x][r];
-    }
+  rs_wgrad_store_acc(out, acc, p.Cout, Cin, co0 + wm * 32, ci0 + wn * 32, lane);
 }
 
 // part [splits][4][9][Cout][Cin] -> dW [Cout][3][3][Cin]: splits summed in order, dg = G^T dU G per parity (G = [1 0; 1 1; 0 1]),

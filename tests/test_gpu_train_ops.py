@@ -143,12 +143,14 @@ def test_decoder_wgrad_fp32_phase_form_vs_autograd_and_direct_form(n, c1, c2, co
     assert float((dw - direct).abs().max()) <= 1e-4 * float(direct.abs().max())
 
 
-@pytest.mark.parametrize("n,c1,c2,cout,h,w", [(2, 64, 0, 64, 8, 8), (1, 128, 64, 32, 9, 13), (3, 64, 64, 64, 16, 12), (2, 192, 128, 128, 7, 5), (1, 64, 0, 96, 33, 20)])
+@pytest.mark.parametrize("n,c1,c2,cout,h,w", [(2, 64, 0, 64, 8, 8), (1, 128, 64, 32, 9, 13), (3, 64, 64, 64, 16, 12), (2, 192, 128, 128, 7, 5), (1, 64, 0, 96, 33, 20),
+                                              (1, 64, 0, 64, 2, 2), (1, 64, 64, 32, 6, 6), (1, 64, 0, 64, 6, 10)])
 def test_decoder_wgrad_fp32_winograd_domain_vs_autograd_and_phase_form(n, c1, c2, cout, h, w):
     """DecoderBlock's fp32 weight gradient in the Winograd domain of the forward's F(2x2, 2x2) form (conv_wgrad_wino_f32.hip, round 6:
     dU = sum over tiles of (A dY A^T) (.) (B^T d B), dg = G^T dU G; 9/16 of the phase form's multiply-adds) against autograd on the
     reference formulation (unet.py:63-73) and against the phase form on the same launch: odd sizes (half tiles at the edge), two
-    sources, both block shapes (64 and 32 couts), splits that straddle images."""
+    sources, both block shapes (64 and 32 couts), splits that straddle images; the last three: a split of one and of two chunks of
+    eight tiles (1, 9 and 15 tiles), fewer than the ring of wgrad_gather_ring.h has stages: its prologue's guards and all-drain path."""
     import ctypes
 
     from robosat_amd import _lib, ops
@@ -181,12 +183,14 @@ def test_decoder_wgrad_fp32_winograd_domain_vs_autograd_and_phase_form(n, c1, c2
     assert torch.equal(dw, ops.conv2d_wgrad(*args, **kw))  # deterministic: no atomics, splits summed in order
 
 
-@pytest.mark.parametrize("n,cin,cout,h,w", [(2, 64, 64, 8, 8), (1, 32, 32, 9, 13), (3, 64, 128, 16, 12), (2, 128, 64, 7, 5), (1, 64, 96, 33, 20), (2, 64, 64, 34, 50)])
+@pytest.mark.parametrize("n,cin,cout,h,w", [(2, 64, 64, 8, 8), (1, 32, 32, 9, 13), (3, 64, 128, 16, 12), (2, 128, 64, 7, 5), (1, 64, 96, 33, 20), (2, 64, 64, 34, 50),
+                                            (1, 32, 32, 2, 2), (1, 64, 64, 4, 4), (1, 32, 32, 6, 3)])
 def test_wgrad_fp32_3x3_winograd_domain_vs_autograd_and_nine_taps(n, cin, cout, h, w):
     """The fp32 weight gradient of a stride-1 3x3 / pad-1 convolution (torchvision Bottleneck.conv2 under tools/train.py:186) in the
     Winograd domain of F(2x2, 3x3) (conv_wgrad_wino33_f32.hip, round 6: dU = sum over tiles of (A dY A^T) (.) (B^T d B), dg = G^T dU G;
     16/36 of the multiply-adds) against autograd and against the nine-tap kernel on the same launch: odd sizes (half tiles, rows that
-    end inside a chunk of eight tiles), more than one chunk per row, both block shapes, splits that straddle images."""
+    end inside a chunk of eight tiles), more than one chunk per row, both block shapes, splits that straddle images; the last three:
+    one, two and three chunks in all, no more than the ring of wgrad_gather_ring.h has stages: its prologue's guards and all-drain path."""
     import ctypes
 
     from robosat_amd import _lib, ops
