@@ -679,6 +679,27 @@ long rs_features_overlaps_workspace_bytes(long capacity);
 int rs_features_overlaps(const int32_t* labels_a, const int32_t* labels_b, void* workspace, int32_t* rows, long capacity,
                          int32_t* counters, long pixels, long group, rs_stream_t stream);
 
+/* ---- per-component sums of probability bytes (`rs features --score`) ----
+ * labels: int32 [pixels] as rs_features_label, rs_features_stitch_labels or the instances stage leave them; `group` = pixels per
+ * independent raster as in rs_features_overlaps (pixels % group == 0), raster = p / group.  q: uint8 [K][pixels], model k's
+ * quantised probability of the one class under extraction at every pixel (the host picks the class's channel), 1 <= K <= 8.
+ * table / rows: the components wanted, rows of 7 [tile, label, ...] (stitched == 0) or of 6 [label, ...] (stitched != 0, raster 0),
+ * no component twice.  For the component c of row i -- the pixels p of raster tile_i with labels[p] == label_i, i.e. the pixels
+ * rs_features_edges draws the polygon around -- and every model k
+ *   sums[i][k] = sum over p in c of q[k][p]          (uint64 [rows][K], zeroed by the call, 8-byte aligned)
+ * exactly: integers, so the same bits whatever order the device worked in, and for the same raster per tile or stitched.  A sum is
+ * at most 2^29 * 255 < 2^37.  The host makes the score of it: sum_k w_k sums[i][k] / (255 * area_i * sum_k w_k), the mean over the
+ * component of the probability `rs masks` votes with.  Pixels of components the table does not list add nothing.
+ * rowmap: int32 [pixels] scratch: the call fills it with -1 and writes rowmap[raster * group + label - 1] = i for every row (a
+ * component's label is 1 + the index of one of its pixels in its raster: so is an instance's, whose core's root keeps
+ * L[root] == root + 1); a row whose tile lies outside 0 .. pixels / group - 1 or whose label lies outside 1 .. group is skipped and
+ * its sums stay 0.  Two launches; per wave a segmented sum over its 64 consecutive pixels (a run ends where the label changes or a
+ * raster begins: two tiles may both hold label 1 either side of that border), the block's four waves merged in LDS, then one 64-bit
+ * atomic add per run and model.  No workgroup waits for another; every loop is bounded.  rows == 0 returns at once (table and sums
+ * may be NULL).  pixels < 2^29, rows <= pixels; RS_EINVAL otherwise. */
+int rs_features_scores(const int32_t* labels, const uint8_t* q, const int32_t* table, long rows, int stitched, int32_t* rowmap,
+                       uint64_t* sums, long pixels, long group, int K, rs_stream_t stream);
+
 /* ---- centerlines: skeleton and links (`rs features --geometry centerline`) ----
  * Thinning is the Guo-Hall two-subiteration parallel algorithm (CACM 32(3), 1989).  With p2..p9 = the N, NE, E, SE, S, SW, W, NW
  * neighbours of a set pixel p, a pixel outside the raster reading 0:

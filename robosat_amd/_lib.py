@@ -167,6 +167,8 @@ SIGNATURES = {
     # overlap table of two label rasters (rs features --dedupe)
     "rs_features_overlaps_workspace_bytes": (c_long, [c_long]),
     "rs_features_overlaps": (c_int, [P, P, P, P, c_long, P, c_long, c_long, P]),
+    # per-component sums of probability bytes (rs features --score)
+    "rs_features_scores": (c_int, [P, P, P, c_long, c_int, P, P, c_long, c_long, c_int, P]),
     # centerlines: Guo-Hall thinning, skeleton links
     "rs_features_thin": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
     "rs_features_skeleton_links": (c_int, [P, P, P, P, P, c_long, P, P, c_long, P, c_int, c_int, c_int, P]),

@@ -12,6 +12,8 @@
 //   rs_features_edges       directed unit boundary edges of the kept components, compacted by one atomic per wave.
 //   rs_features_overlaps    two label rasters -> (raster, label_a, label_b, shared pixels) through a hash table in global memory,
 //                           equal pairs merged per thread, per wave and per block first (`rs features --dedupe`).
+//   rs_features_scores      label raster + K planes of probability bytes -> the exact sum of every model's bytes per listed component:
+//                           a segmented scan per wave, the block's waves merged in LDS, one 64-bit atomic per run (`rs features --score`).
 // Stitched form (all tiles of a zoom level as one sparse raster; tables nbr [T][8] and origin [T][2] from the host):
 //   rs_features_halo            tile + apron of A pixels from its 8 neighbours (A = reach of open + close), and the crop back.
 //   rs_features_stitch_labels   per-tile canonical labels -> global index space, unions across right / down seams, flatten.
@@ -1098,6 +1100,87 @@ __global__ __launch_bounds__(256) void grow_kernel(const GrowArgs a) {
   }
 }
 
+// ---- per-component sums of probability bytes (`rs features --score`; definitions: include/robosat_hip.h) ----------------------
+// rowmap [pixels]: -1, or the table row of the component whose label names that pixel (label = 1 + the pixel's index in its raster).
+constexpr int kScoreMaxK = 8;
+constexpr int kScorePairs = kScoreMaxK / 2;  // two models share a register: a block's sum is at most 256 * 255 < 2^16
+
+__global__ __launch_bounds__(256) void score_rows_kernel(const int* __restrict__ table, long rows, int width, int* rowmap, long pixels,
+                                                         long group) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows) return;
+  const long raster = width == 7 ? table[i * 7] : 0;
+  const int lab = table[i * width + (width == 7 ? 1 : 0)];
+  if (raster >= 0 && raster < pixels / group && lab >= 1 && lab <= group) rowmap[raster * group + lab - 1] = (int)i;
+}
+
+// One atomic per model and run of a label, a run being consecutive pixels of one label in one raster inside the block's 256 (it may
+// go on across the end of a raster row: sums do not care).  Inside a wave the bytes of a run are summed by a segmented suffix scan
+// (__shfl_down, bounded by the run's end from one ballot); the run that ends a wave takes in the first runs of the waves behind it
+// through LDS, so a tile that is one blob costs one atomic per model and 256 pixels (per pixel they would all hit one row's K words).
+__global__ __launch_bounds__(256) void score_sum_kernel(const int* __restrict__ L, const uint8_t* __restrict__ q,
+                                                        const int* __restrict__ rowmap, unsigned long long* sums, long pixels, long group,
+                                                        int K) {
+  __shared__ int join0[4], lab63[4], full[4];  // the label lane 0 may carry on from the wave before (0: none), lane 63's, "one run"
+  __shared__ unsigned int tot0[4][kScorePairs];
+  const long base = (long)blockIdx.x * 256;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long g = base + threadIdx.x;
+  const bool in = g < pixels;  // (no early return: every lane reaches the shuffles, the ballot and the barrier)
+  const int lab = in ? L[g] : 0;
+  long raster = base / group;  // (uniform; only a block that holds a raster's border divides per lane)
+  long off = base - raster * group + threadIdx.x;
+  if (off >= group) {
+    raster += off / group;
+    off %= group;
+  }
+  unsigned int v[kScorePairs];
+#pragma unroll
+  for (int j = 0; j < kScorePairs; ++j) {
+    v[j] = 0;
+    if (lab != 0 && 2 * j < K) v[j] = q[(long)(2 * j) * pixels + g];
+    if (lab != 0 && 2 * j + 1 < K) v[j] |= (unsigned int)q[(long)(2 * j + 1) * pixels + g] << 16;
+  }
+  const int before = __shfl_up(lab, 1, 64);
+  const bool start = lane == 0 || before != lab || off == 0;
+  const unsigned long long starts = __ballot(start);
+  const unsigned long long above = lane == 63 ? 0ull : starts & ~((2ull << lane) - 1ull);
+  const int end = above ? __ffsll((long long)above) - 1 : 64;  // the run is lanes [its start, end)
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+    for (int j = 0; j < kScorePairs; ++j)
+      if (2 * j < K) {  // (uniform)
+        const unsigned int t = (unsigned int)__shfl_down((int)v[j], o, 64);
+        if (lane + o < end) v[j] += t;  // v = the sum over [lane, min(lane + 2 o, end))
+      }
+  if (lane == 0) {
+    join0[wave] = off == 0 ? 0 : lab;
+    full[wave] = end == 64;
+#pragma unroll
+    for (int j = 0; j < kScorePairs; ++j) tot0[wave][j] = v[j];
+  }
+  if (lane == 63) lab63[wave] = lab;
+  rs_lds_writes_done();
+  __syncthreads();
+  if (!start || lab < 1 || lab > group) return;
+  if (lane == 0 && wave > 0 && join0[wave] != 0 && join0[wave] == lab63[wave - 1]) return;  // the run began in an earlier wave
+  if (end == 64)
+    for (int w = wave + 1; w < 4; ++w) {
+      if (join0[w] == 0 || join0[w] != lab63[w - 1]) break;
+#pragma unroll
+      for (int j = 0; j < kScorePairs; ++j) v[j] += tot0[w][j];
+      if (!full[w]) break;
+    }
+  const int row = rowmap[raster * group + lab - 1];
+  if (row < 0) return;  // (a component the table does not list)
+#pragma unroll
+  for (int j = 0; j < kScorePairs; ++j) {
+    if (2 * j < K && (v[j] & 0xffffu)) atomicAdd(&sums[(long)row * K + 2 * j], (unsigned long long)(v[j] & 0xffffu));
+    if (2 * j + 1 < K && (v[j] >> 16)) atomicAdd(&sums[(long)row * K + 2 * j + 1], (unsigned long long)(v[j] >> 16));
+  }
+}
+
 int grow_fused() {
   const int k = rs_knobs().grow_fused;
   return k >= 1 && k <= kGrowMaxK ? k : kGrowRule;
@@ -1339,6 +1422,21 @@ extern "C" int rs_features_overlaps(const int32_t* labels_a, const int32_t* labe
                                                                        (unsigned long long)(slots - 1),
                                                                        (int)(slots < kOvMaxProbe ? slots : kOvMaxProbe), pixels, group, vec);
   overlaps_rows_kernel<<<rs_cdiv(slots, 256 * kOvRowsRun), 256, 0, s>>>(keys, counts, rows, capacity, counters, slots, group);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_features_scores(const int32_t* labels, const uint8_t* q, const int32_t* table, long rows, int stitched,
+                                  int32_t* rowmap, uint64_t* sums, long pixels, long group, int K, rs_stream_t stream) {
+  if (!labels || !q || !rowmap || rows < 0 || rows > pixels || (rows > 0 && (!table || !sums || ((uintptr_t)sums & 7))) || pixels <= 0 ||
+      pixels >= (1l << 29) || group <= 0 || pixels % group != 0 || K < 1 || K > kScoreMaxK)
+    return RS_EINVAL;
+  if (rows == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(rowmap, 0xff, pixels * sizeof(int32_t), s);
+  if (e == hipSuccess) e = hipMemsetAsync(sums, 0, rows * K * sizeof(uint64_t), s);
+  if (e != hipSuccess) return (int)e;
+  score_rows_kernel<<<rs_cdiv(rows, 256), 256, 0, s>>>(table, rows, stitched ? 6 : 7, rowmap, pixels, group);
+  score_sum_kernel<<<rs_cdiv(pixels, 256), 256, 0, s>>>(labels, q, rowmap, reinterpret_cast<unsigned long long*>(sums), pixels, group, K);
   return RS_LAUNCH_RESULT();
 }
 

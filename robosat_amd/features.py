@@ -218,12 +218,12 @@ def polygon_is_valid(rings):
     return True
 
 
-def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, iou=None):
+def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, iou=None, score=None):
     """Edge rows + component table rows (tile, label, area, ...) of one batch -> GeoJSON features.  ``tiles[i]`` is the
     ``Tile`` of batch index i, ``shape`` = (H, W).  Rings are simplified, checked, reversed to RFC 7946 winding (outer ring
     counter-clockwise, holes clockwise in lon / lat), closed and georeferenced from pixel corners.  Plain GeoJSON Feature
     dicts, ordered by (batch index, label).  ``iou`` (``--dedupe``): {(batch index, label): float}, added as the property
-    ``iou``."""
+    ``iou``; ``score`` (``--score``): the same keys, added as the property ``score``."""
 
     h, w = shape
     area = {(int(r[0]), int(r[1])): int(r[2]) for r in np.asarray(table).reshape(-1, 7)}
@@ -250,6 +250,8 @@ def featurize(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, iou=No
         })
         if iou is not None:
             features[-1]["properties"]["iou"] = float(iou[(index, label)])
+        if score is not None:
+            features[-1]["properties"]["score"] = float(score[(index, label)])
     return features
 
 
@@ -366,12 +368,12 @@ def tile_vertex_location(tile, px, py, shape):
     return east if px == w else lon, south if py == h else lat
 
 
-def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, georeference=True, iou=None):
+def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stderr, georeference=True, iou=None, score=None):
     """``featurize`` for one stitched call: edge rows (label, X, Y, dir) + table rows (label, area, X0, Y0, X1, Y1) in
     mosaic pixels, ``tiles`` the call's tiles in slot order.  A feature's ``tile`` is the tile holding its canonical pixel (the
     one its label names: label - 1 = slot * H * W + y * W + x), ``area_px`` the area of the whole component; features come in
     label order, which is (slot, label).  ``georeference=False`` leaves the vertices as mosaic pixel corners [X, Y].  ``iou``
-    (``--dedupe``): {label: float}, added as the property ``iou``."""
+    (``--dedupe``): {label: float}, added as the property ``iou``; ``score`` (``--score``): the same keys, the property ``score``."""
 
     h, w = shape
     x_min, y_min = min(t.x for t in tiles), min(t.y for t in tiles)
@@ -402,6 +404,8 @@ def featurize_stitched(edges, table, tiles, shape, simplify=0.01, warn=sys.stder
         })
         if iou is not None:
             features[-1]["properties"]["iou"] = float(iou[label])
+        if score is not None:
+            features[-1]["properties"]["score"] = float(score[label])
     return features
 
 
@@ -448,6 +452,33 @@ def dedupe_keep(table, ref_table, pairs, threshold):
         keep[i] = shared < float(threshold) * union
         iou[i] = shared / union
     return keep, iou
+
+
+# ---- rs features --score: a polygon's confidence from the sums of its pixels' probability bytes ---------------------------------
+def scores_from_sums(sums, areas, weights=None):
+    """``sums`` int [N, K] (``ops.component_scores``: per component and model, the sum of the quantised probability bytes over its
+    pixels), ``areas`` int [N] (the component table's) and K weights (unset: all 1) -> float64 [N]:
+    ``sum_k w_k * sums[c][k] / (255 * area_c * sum_k w_k)`` in Python floats -- the mean over the component's pixels of the
+    probability ``rs masks`` votes with, ``np.average(linspace(0, 1, 256)[q], axis=0, weights=w)``."""
+
+    sums = np.asarray(sums)
+    if sums.ndim != 2 or sums.shape[1] < 1:
+        raise ValueError("sums are [N, K] with K >= 1, got {}".format(sums.shape))
+    areas = np.asarray(areas).reshape(-1)
+    if len(areas) != len(sums):
+        raise ValueError("{} areas for {} rows of sums".format(len(areas), len(sums)))
+    weights = [1.0] * sums.shape[1] if weights is None else [float(w) for w in weights]
+    if len(weights) != sums.shape[1]:
+        raise ValueError("{} weights for {} models".format(len(weights), sums.shape[1]))
+    total = sum(weights)
+    if not (all(0 <= w < float("inf") for w in weights) and total > 0):
+        raise ValueError("weights are finite, not negative and not all 0, got {}".format(weights))
+    if len(areas) and int(areas.min()) < 1:
+        raise ValueError("a component has at least one pixel, got an area of {}".format(int(areas.min())))
+    out = np.zeros(len(sums), dtype=np.float64)
+    for i, (row, area) in enumerate(zip(sums.tolist(), areas.tolist())):  # (plain Python numbers: the formula as it is written)
+        out[i] = sum(w * n for w, n in zip(weights, row)) / (255 * area * total)
+    return out
 
 
 # ---- rs features --geometry centerline: skeleton links -> lines ----------------------------------------------------------------

@@ -1667,6 +1667,40 @@ def overlap_table(labels_a, labels_b, stitched=False, capacity=None):
     return rows.contiguous()
 
 
+# ---- rs features --score: per-component sums of probability bytes (definitions in include/robosat_hip.h) ------------------------
+SCORE_MAX_MODELS = 8
+
+
+def component_scores(labels, table, quantized, stitched=False):
+    """int32 [B, H, W] labels (``label_components``, ``stitch_labels`` or ``split_labels``), the rows of ``component_table``
+    (``component_table_stitched`` with ``stitched``) or any subset of them, and uint8 [K, B, H, W] quantised probabilities of the
+    class (one plane per model, 1 <= K <= 8) -> int64 [N, K]: row i holds, for every model, the exact sum of its bytes over the pixels
+    of the table's i-th component."""
+
+    if labels.dim() != 3:
+        raise ValueError("robosat_amd: the label raster is [B, H, W], got {}".format(tuple(labels.shape)))
+    if quantized.dim() != 4 or tuple(quantized.shape[1:]) != tuple(labels.shape):
+        raise ValueError("robosat_amd: the probabilities are [K, B, H, W] over the labels' {}, got {}".format(tuple(labels.shape),
+                                                                                                            tuple(quantized.shape)))
+    k = quantized.shape[0]
+    if not 1 <= k <= SCORE_MAX_MODELS:
+        raise ValueError("robosat_amd: 1 to {} models are summed in one call, got {}".format(SCORE_MAX_MODELS, k))
+    if table.dim() != 2 or table.shape[1] != (6 if stitched else 7):
+        raise ValueError("robosat_amd: the table is [N, {}], got {}".format(6 if stitched else 7, tuple(table.shape)))
+    if labels.device != quantized.device or labels.device != table.device:
+        raise ValueError("robosat_amd: labels, table and probabilities are on {}, {} and {}".format(labels.device, table.device,
+                                                                                                   quantized.device))
+    b, h, w = labels.shape
+    pixels = b * h * w
+    table = table.contiguous()
+    rowmap = torch.empty(pixels, device=labels.device, dtype=torch.int32)
+    sums = torch.empty((len(table), k), device=labels.device, dtype=torch.int64)
+    _call("rs_features_scores", _dev(labels, "labels", torch.int32), _dev(quantized, "quantized", torch.uint8),
+          _dev(table, "table", torch.int32) if len(table) else None, len(table), int(bool(stitched)), _dev(rowmap, "rowmap", torch.int32),
+          _dev(sums, "sums", torch.int64) if len(table) else None, pixels, pixels if stitched else h * w, k, _stream())
+    return sums
+
+
 # ---- rs features --geometry centerline: skeleton and links (definitions in include/robosat_hip.h) --------------------------------
 THIN_PAIRS = 16  # pairs of sub-iterations enqueued between two reads of the device's counter (profiles/features_centerline)
 

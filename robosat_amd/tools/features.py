@@ -16,9 +16,14 @@ intersection over union with the reference objects it touches reaches ``--dedupe
 radius R fits into are labelled and grown back over the mask on the device (geodesic influence zones), and ``--min_area``,
 ``--dedupe`` and every property then apply to the instances.  Neighbouring instances are simplified one by one, so after
 ``--simplify`` their shared border may overlap or gap by up to the epsilon.
+``--score DIR`` (one per model, as ``rs masks`` takes them) gives every polygon its confidence: the probability tiles ``rs predict``
+wrote go to the device beside the labels, one kernel sums every model's bytes of the class over each component, and the host divides
+once: ``score`` is the mean over the polygon's pixels, as written, of the probability ``rs masks`` votes with (``--score_weights`` as
+its ``--weights``).  ``--min_score S`` drops the polygons below S.
 The stage definitions, and where they depart from OpenCV's, are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
+import math
 import os
 import sys
 
@@ -30,8 +35,9 @@ from tqdm import tqdm
 from robosat_amd import ops
 from robosat_amd.config import load_config
 from robosat_amd.features import (FeatureWriter, Widths, centerlines, centerlines_stitched, dedupe_keep, featurize, featurize_stitched,
-                                  group_clusters, pack_clusters, stitch_tables)
+                                  group_clusters, pack_clusters, scores_from_sums, stitch_tables)
 from robosat_amd.tiles import tiles_from_slippy_map
+from robosat_amd.tools.masks import load_quantized
 
 
 def add_parser(subparser):
@@ -77,6 +83,16 @@ def add_parser(subparser):
                         "between two objects is cut; an object no such disc fits into stays as it is. Neighbouring instances are "
                         "simplified one by one, so after --simplify their shared border may overlap or gap by up to the epsilon. "
                         "With --stitch R pixels must fit the tile's smaller side")
+    parser.add_argument("--score", type=str, action="append", default=None, metavar="DIR",
+                        help="polygon: slippy map directory with the class probabilities rs predict wrote for these masks; give it once "
+                        "per model that rs masks voted with (at most 8). Every polygon gains the property score: the mean over its "
+                        "pixels, as written (after --denoise, --grow, --stitch and --split), of the probability of --type, averaged over "
+                        "the models")
+    parser.add_argument("--score_weights", type=float, nargs="+", default=None, metavar="W",
+                        help="with --score: one weight per directory for the average over the models, as rs masks --weights")
+    parser.add_argument("--min_score", type=float, default=None, metavar="S",
+                        help="with --score: polygons with a score below S are dropped (after --min_area and --split, before --dedupe), "
+                        "0 <= S <= 1")
     parser.set_defaults(func=main)
 
 
@@ -128,6 +144,56 @@ class Dedupe:
         return table[torch.from_numpy(keep).to(table.device)].contiguous(), dict(zip(keys, iou[keep].tolist()))
 
 
+class Score:
+    """``--score``: the probability tiles of a batch or call, the scores of its components, and the count of what was scored and
+    dropped.  ``channel``: the class's channel in the probability tiles (class index - 1)."""
+
+    def __init__(self, directories, weights, channel, min_score=None):
+        self.directories = list(directories)
+        self.paths = [{tile: path for tile, path in tiles_from_slippy_map(directory)} for directory in self.directories]
+        self.weights, self.channel, self.min_score = weights, channel, min_score
+        self.scored = self.dropped = 0
+
+    def load(self, tiles, shape, device):
+        """uint8 [K, T, H, W]: every model's bytes of the class, the tiles in slot order."""
+
+        planes, channels = [], None
+        for directory, paths in zip(self.directories, self.paths):
+            for tile in tiles:
+                path = paths.get(tile)
+                name = "{}/{}/{}".format(tile.z, tile.x, tile.y)
+                if path is None:
+                    sys.exit("Error: --score {} has no probabilities for the mask tile {}".format(directory, name))
+                q = load_quantized(path)
+                if q.shape[:2] != tuple(shape):
+                    sys.exit("Error: {} is {}x{}; the mask tile {} is {}x{}".format(path, q.shape[0], q.shape[1], name, shape[0], shape[1]))
+                if channels is None:
+                    channels = (q.shape[2], path)
+                if q.shape[2] != channels[0]:
+                    sys.exit("Error: {} (tile {}) holds the probabilities of {} classes, {} those of {}: the --score directories are "
+                             "of models with the same classes".format(path, name, q.shape[2] + 1, channels[1], channels[0] + 1))
+                if self.channel >= q.shape[2]:
+                    sys.exit("Error: {} (tile {}) holds the probabilities of {} classes; --type is class {} of the dataset".format(
+                        path, name, q.shape[2] + 1, self.channel + 1))
+                planes.append(np.ascontiguousarray(q[:, :, self.channel], dtype=np.uint8))
+        stack = np.stack(planes).reshape(len(self.directories), len(tiles), shape[0], shape[1])
+        return torch.from_numpy(stack).to(device)
+
+    def filter(self, labels, table, quantized, stitched=False):
+        """Labels and component table + the probabilities (``load``) -> (the table's kept rows, {feature key: score} for
+        ``featurize``)."""
+
+        rows = table.cpu().numpy()
+        sums = ops.component_scores(labels, table, quantized, stitched=stitched).cpu().numpy()
+        scores = scores_from_sums(sums, rows[:, 1 if stitched else 2], self.weights)
+        keep = np.ones(len(rows), dtype=bool) if self.min_score is None else scores >= self.min_score
+        self.scored += len(keep)
+        self.dropped += int((~keep).sum())
+        kept = rows[keep]
+        keys = [int(r[0]) for r in kept] if stitched else [(int(r[0]), int(r[1])) for r in kept]
+        return table[torch.from_numpy(keep).to(table.device)].contiguous(), dict(zip(keys, scores[keep].tolist()))
+
+
 def width_radius(max_width):
     """Radius of the distance transform that measures a road of ``max_width`` pixels uncapped."""
 
@@ -152,7 +218,7 @@ def _tile_sizes(masks):
         yield tile, path, (height, width)
 
 
-def stitched(items, index, args, device, writer, dedupe=None):
+def stitched(items, index, args, device, writer, dedupe=None, score=None):
     """``--stitch``: per zoom level, the 8-connected clusters of tiles packed whole into device calls."""
 
     by_zoom = {}
@@ -177,14 +243,16 @@ def stitched(items, index, args, device, writer, dedupe=None):
             nbr, origin, _ = stitch_tables(tiles, shape)
             nbr, origin = torch.from_numpy(nbr).to(device), torch.from_numpy(origin).to(device)
             images = _load([paths[t] for t in tiles], device)
-            iou = widths = None
-            if dedupe is not None or args.split:
-                # (the stages of ops.stitched_features, with the instances behind the labels and the reference behind the table)
+            iou = scores = widths = None
+            if dedupe is not None or args.split or score is not None:
+                # (the stages of ops.stitched_features, with the instances behind the labels, the scores and the reference behind the table)
                 cleaned = ops.clean_masks_stitched(images, nbr, index, args.denoise, args.grow)
                 labels = ops.stitch_labels(ops.label_components(cleaned), nbr, inplace=True)
                 if args.split:
                     labels = ops.split_labels(cleaned, labels, args.split, nbr)
                 table = ops.component_table_stitched(labels, origin, args.min_area)
+                if score is not None:
+                    table, scores = score.filter(labels, table, score.load(tiles, shape, device), stitched=True)
                 if dedupe is not None:
                     table, iou = dedupe.filter(labels, table, dedupe.load(tiles, shape, device), nbr, origin)
                 rows = ops.boundary_edges_stitched(labels, nbr, origin, table)
@@ -202,7 +270,8 @@ def stitched(items, index, args, device, writer, dedupe=None):
                     writer.add(centerlines_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.prune, args.tolerance,
                                                     widths=widths))
                 else:
-                    writer.add(featurize_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify, iou=iou))
+                    writer.add(featurize_stitched(rows.cpu().numpy(), table.cpu().numpy(), tiles, shape, args.simplify, iou=iou,
+                                                  score=scores))
             except ValueError as exc:
                 sys.exit("Error: {}".format(exc))
 
@@ -235,6 +304,31 @@ def main(args):
                 if args.split > min(h, w):
                     sys.exit("Error: --split {} needs a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
                              .format(args.split, args.split, h, w, min(h, w)))
+    if args.score is None:
+        if args.score_weights is not None:
+            sys.exit("Error: --score_weights {} weighs the models of --score: not without it".format(" ".join(map(str, args.score_weights))))
+        if args.min_score is not None:
+            sys.exit("Error: --min_score {} is a bound on the --score property: not without --score".format(args.min_score))
+    else:
+        for directory in args.score:
+            if not os.path.isdir(directory):
+                sys.exit("Error: --score {} is not a directory".format(directory))
+        if len(args.score) > ops.SCORE_MAX_MODELS:
+            sys.exit("Error: --score takes at most {} directories, got {}".format(ops.SCORE_MAX_MODELS, len(args.score)))
+        if args.score_weights is not None:
+            if len(args.score_weights) != len(args.score):
+                sys.exit("Error: --score_weights has {} weights for the {} directories of --score".format(len(args.score_weights),
+                                                                                                          len(args.score)))
+            for weight in args.score_weights:
+                if not (math.isfinite(weight) and weight >= 0):
+                    sys.exit("Error: --score_weights are finite and not negative, got {}".format(weight))
+            if sum(args.score_weights) <= 0:
+                sys.exit("Error: --score_weights {} are all 0".format(" ".join(map(str, args.score_weights))))
+        if args.min_score is not None and not 0 <= args.min_score <= 1:  # (false for nan too)
+            sys.exit("Error: --min_score is a probability, 0 <= S <= 1, got {}".format(args.min_score))
+        if args.geometry == "centerline":
+            sys.exit("Error: --score sums over areas; lines are not scored yet: not with --geometry centerline (got --score {})".format(
+                " ".join(args.score)))
     if args.width:
         if args.geometry != "centerline":
             sys.exit("Error: --width measures along centerlines: only with --geometry centerline")
@@ -251,6 +345,7 @@ def main(args):
     device = torch.device("cuda", 0)
     index = classes.index(args.type)
     dedupe = Dedupe(args.dedupe, args.dedupe_threshold, index) if args.dedupe is not None else None
+    score = Score(args.score, args.score_weights, index - 1, args.min_score) if args.score is not None else None
 
     by_shape = {}  # (H, W) -> [(tile, path)]: the header gives the size, a mask is decoded when its batch runs
     for tile, path, (height, width) in _tile_sizes(args.masks):
@@ -260,7 +355,8 @@ def main(args):
 
     writer = FeatureWriter()
     if args.stitch:
-        stitched([(tile, path, shape) for shape, items in by_shape.items() for tile, path in items], index, args, device, writer, dedupe)
+        stitched([(tile, path, shape) for shape, items in by_shape.items() for tile, path in items], index, args, device, writer, dedupe,
+                 score)
         by_shape = {}
     for shape, items in by_shape.items():  # tiles of one batch share a shape
         # (the library takes B*H*W < 2^29 per call, link_rings fewer than 1024 tiles)
@@ -282,11 +378,17 @@ def main(args):
                 writer.add(centerlines(links.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.prune,
                                        args.tolerance, widths=widths))
                 continue
-            iou = None
+            iou = scores = None
+            if score is not None:
+                table, scores = score.filter(labels, table, score.load([tile for tile, _ in group], shape, device))
             if dedupe is not None:
                 table, iou = dedupe.filter(labels, table, dedupe.load([tile for tile, _ in group], shape, device))
             edges = ops.boundary_edges(labels, table)
-            writer.add(featurize(edges.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.simplify, iou=iou))
+            writer.add(featurize(edges.cpu().numpy(), table.cpu().numpy(), [tile for tile, _ in group], shape, args.simplify, iou=iou,
+                                 score=scores))
     writer.save(args.out)
+    if score is not None:
+        print("Score: {} components scored, {} dropped below --min_score{}".format(
+            score.scored, score.dropped, "" if args.min_score is None else " {}".format(args.min_score)), file=sys.stderr)
     if dedupe is not None:
         print("Dedupe: {} components examined, {} dropped as already mapped".format(dedupe.examined, dedupe.dropped), file=sys.stderr)

@@ -36,6 +36,12 @@
            without and with the split, and a stitched 4 x 4 call, written to profiles/features_split/bench_split.json
            (`--split-leg --stage-loop N --fused K`: the growth alone N times at that K, for rocprofv3)
 
+  --score-leg   `rs features --score`: the polygon stages per batch without and with the scoring stage (K = 1 and K = 3 models) on the
+           blob batch, and `ops.component_scores` alone on the shapes that bound it (one component per tile, one per pixel) beside
+           `ops.component_table` on the same tiles, written to profiles/features_score/bench_score.json
+           (`--score-leg --stage-loop N`: the two calls on the blob batch and on the bounds N times, for rocprofv3;
+           `--score-leg --stage-loop N --phases TRACE.csv`: no device, that run's kernel trace -> median us per launch and phase)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -385,6 +391,107 @@ def dedupe_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+SCORE_PHASES = ["blobs_k1", "blobs_k3", "all_ones_k1", "all_ones_k3", "checkerboard_k1", "checkerboard_k3"]  # (the stage loop's order)
+
+
+def score_phases(path, loop):
+    """The kernel trace of `--score-leg --stage-loop N` (rocprofv3's *_kernel_trace.csv) -> median us per launch of the table's and the
+    scores' kernels in each of the loop's phases.  An iteration ends with its `score_sum_kernel`; of the kernels a table launched twice
+    (a second pass with the exact capacity) the last launch counts."""
+
+    import csv
+    import statistics
+
+    names = ("score_sum_kernel", "score_rows_kernel", "comp_stats_kernel", "comp_roots_kernel", "comp_filter_kernel")
+    with open(path) as fp:
+        rows = sorted(csv.DictReader(fp), key=lambda r: int(r["Start_Timestamp"]))
+    iterations, current = [], {}
+    for row in rows:
+        name = next((n for n in names if n in row["Kernel_Name"]), None)
+        if name is None:
+            continue
+        current[name] = (int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1e3
+        if name == "score_sum_kernel":
+            iterations.append(current)
+            current = {}
+    if len(iterations) != loop * len(SCORE_PHASES):
+        raise SystemExit("{} iterations in {}, {} x {} expected".format(len(iterations), path, len(SCORE_PHASES), loop))
+    result = {"loop": loop, "us_per_launch_median": {}}
+    for i, phase in enumerate(SCORE_PHASES):
+        chunk = iterations[i * loop:(i + 1) * loop]
+        result["us_per_launch_median"][phase] = {n: round(statistics.median(c[n] for c in chunk), 2) for n in names}
+    print(json.dumps(result, indent=1, sort_keys=True))
+
+
+def score_leg(args):
+    """The polygon path with the scoring stage between the table and the edges, beside the path without it."""
+
+    if args.phases:
+        return score_phases(args.phases, args.stage_loop)
+
+    import torch
+
+    from robosat_amd import ops
+    from robosat_amd.features import scores_from_sums
+
+    size, eps, r = args.size, args.eps, args.repeat
+    dev = torch.from_numpy(blob_masks(args.batch, size, 0)).to("cuda:0")
+    rng = np.random.RandomState(5)
+    q3 = torch.from_numpy(rng.randint(0, 256, size=(3, args.batch, size, size)).astype(np.uint8)).to("cuda:0")
+    quantized = {1: q3[:1].contiguous(), 3: q3}
+
+    def plain():
+        labels = ops.label_components(ops.clean_masks(dev, 1, eps, eps))
+        table = ops.component_table(labels, 0)
+        return table, ops.boundary_edges(labels, table).cpu()
+
+    def scored(k):
+        labels = ops.label_components(ops.clean_masks(dev, 1, eps, eps))
+        table = ops.component_table(labels, 0)
+        scores = scores_from_sums(ops.component_scores(labels, table, quantized[k]).cpu().numpy(), table[:, 2].cpu().numpy())
+        return table, ops.boundary_edges(labels, table).cpu(), scores
+
+    full = torch.ones((args.batch, size, size), dtype=torch.uint8, device="cuda:0")
+    yy, xx = np.mgrid[:size, :size]
+    board = torch.from_numpy(np.repeat(((yy + xx) % 2 == 0)[None], args.batch, 0).astype(np.uint8)).to("cuda:0")
+    labels = ops.label_components(ops.clean_masks(dev, 1, eps, eps))
+    table = ops.component_table(labels, 0)
+    if args.stage_loop:
+        for masks_u8 in (None, full, board):  # (in this order in the trace: blobs, all ones, checkerboard; K = 1 then K = 3)
+            hard = labels if masks_u8 is None else ops.label_components(masks_u8)
+            rows = table if masks_u8 is None else ops.component_table(hard, 0)
+            for k in (1, 3):
+                for _ in range(args.stage_loop):
+                    ops.component_table(hard, 0)
+                    ops.component_scores(hard, rows, quantized[k])
+        return
+
+    result = {"batch": args.batch, "size": size, "eps": eps, "components": int(len(table)),
+              "foreground": float((labels != 0).float().mean()),
+              "ms_per_batch": {"without": timed(plain, r) * 1e3, "with_k1": timed(lambda: scored(1), r) * 1e3,
+                               "with_k3": timed(lambda: scored(3), r) * 1e3},
+              "ms_split": {"component_table": timed(lambda: ops.component_table(labels, 0), r) * 1e3}, "bounds": {}}
+    result["ms_per_batch"]["without_again"] = timed(plain, r) * 1e3  # (the spread of the same path in the same process)
+    for k in (1, 3):
+        result["ms_split"]["component_scores_k{}".format(k)] = timed(lambda: ops.component_scores(labels, table, quantized[k]), r) * 1e3
+        result["ms_split"]["component_scores_k{}_with_copy_to_host".format(k)] = timed(
+            lambda: ops.component_scores(labels, table, quantized[k]).cpu(), r) * 1e3
+    for name, masks_u8 in (("all_ones", full), ("checkerboard", board)):
+        hard = ops.label_components(masks_u8)
+        rows = ops.component_table(hard, 0)
+        entry = {"rows": int(len(rows)), "component_table_ms": timed(lambda: ops.component_table(hard, 0), r) * 1e3}
+        for k in (1, 3):
+            entry["component_scores_k{}_ms".format(k)] = timed(lambda: ops.component_scores(hard, rows, quantized[k]), r) * 1e3
+        result["bounds"][name] = entry
+
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "features_score", "bench_score.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def width_leg(args):
     """The distance transform beside the thinning, and the centerline stages per batch without and with it."""
 
@@ -645,6 +752,8 @@ def main():
     ap.add_argument("--stitch-leg", action="store_true", help="only the stitched path against the per-tile path on an n x n block")
     ap.add_argument("--centerline-leg", action="store_true", help="only thinning and links, on a road network and on its n x n block")
     ap.add_argument("--dedupe-leg", action="store_true", help="only rs features --dedupe: the stages with and without the reference")
+    ap.add_argument("--score-leg", action="store_true", help="only rs features --score: the stages with and without the per-component sums")
+    ap.add_argument("--phases", type=str, default=None, help="--score-leg --stage-loop N: the kernel trace of that run, split by phase (no device)")
     ap.add_argument("--width-leg", action="store_true", help="only rs features --width: the distance transform beside the thinning")
     ap.add_argument("--without-only", action="store_true", help="--width-leg: only the stages without the transform")
     ap.add_argument("--max-width", type=int, default=64, help="--width-leg: as --max_width of rs features (radius N // 2 + 2)")
@@ -661,6 +770,8 @@ def main():
         return centerline_leg(args)
     if args.dedupe_leg:
         return dedupe_leg(args)
+    if args.score_leg:
+        return score_leg(args)
     if args.width_leg:
         return width_leg(args)
     if args.split_leg:
