@@ -85,9 +85,17 @@ __device__ __forceinline__ int w33_swz(int row) { return (row ^ (row >> 1)) & 3;
 // BatchNorm's statistics over the block's outputs (sum y, sum y^2 per cout and m block), summed in a fixed order: lane (its 2x2
 // pixels) -> the wave's 16 tiles (DPP row rotations: no LDS) -> the block's tile groups (through LDS, picked up behind the first
 // barrier of the block's next item like the head's exchange) -> one row of `stats` per m block.
-template <int TG, int CG, int MODE = 0>
+// HC (HEAD only): the compile-time bound of the class loops, 2 / 4 / 8 -- the smallest >= p.hC, chosen at launch: registers, exchange
+// rows and weights in LDS are HC wide, the classes p.hC <= c < HC have zero weights and are never stored.
+//
+// Per-item bookkeeping: an item's (mblk, nblk) and its sub-blocks' (image, patch origin) are wave-uniform and are decoded ONCE per
+// item, without a division for the item index (it advances by gridDim.x: quotient and remainder by ncb are carried); the table
+// builder, the fetch side (one item ahead: `nxt`) and the epilogue (`cur`) read that state.  What depends on the thread alone -- its
+// halo rows' (sub-block, hy, hx), its filter rows' offsets -- is computed once per block.
+template <int TG, int CG, int MODE = 0, int HC = kHeadMaxC>
 __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Args p) {
   constexpr int HEAD = (MODE >= 1 && MODE <= 3) ? MODE : 0;
+  static_assert(HC == 2 || HC == 4 || HC == 8, "class bound of the fused head");
   constexpr bool BWD = MODE == 5;
   constexpr bool STATS = MODE == 4 || BWD;  // (BWD: only when p.stats is given -- block-uniform)
   constexpr int NW = TG * CG;
@@ -96,6 +104,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   constexpr int BMT = 16 * TG, BN = 16 * CG;
   constexpr int SB = BMT / (kPB * kPB);
   static_assert(SB * kPB * kPB == BMT, "whole sub-blocks per block");
+  static_assert(SB == 1 || SB == 2, "the item state below: one or two sub-blocks");
   constexpr int AROWS = SB * kSBROWS;
   constexpr int IA = (AROWS + 15) / 16, IB = 16 * BN / 16;
   constexpr int AROWS_PAD = IA * 16;
@@ -103,10 +112,11 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   constexpr int STAGE = (AROWS_PAD + 16 * BN) * 64;
   constexpr int KC = 16;
 
-  // HEAD: + the class weights [8][32] and biases [8], + the exchange of the two cout groups' partial logits [tile][pixel][8]
-  //       (two exchange buffers: an item's second half runs behind the first barrier of the block's NEXT item)
-  // (exchange rows of 36 floats: 16 lanes' 16-byte accesses at a 144-byte pitch fall into 16 different bank groups)
-  constexpr int HEADW = kHeadMaxC * 32 + kHeadMaxC, XROW = 4 * kHeadMaxC + 4, XCH = BMT * XROW;
+  // HEAD: + the class weights [HC][32] and biases [HC] (padded to whole 16 bytes), + the exchange of the two cout groups' partial
+  //       logits [tile][pixel][HC] (two exchange buffers: an item's second half runs behind the first barrier of the block's NEXT item)
+  // (exchange rows of 4 HC + 4 floats: the 16 tiles' rows of one access start in different bank groups -- pitch 144 bytes at HC = 8,
+  //  80 at HC = 4, 48 at HC = 2, where a half wave's 8-byte reads cover all 64 banks once)
+  constexpr int HEADW = HC * 32 + (HC + 3) / 4 * 4, XROW = 4 * HC + 4, XCH = BMT * XROW;
   constexpr int XST = 2 * TG * BN;  // STATS: per exchange buffer [2 sums][TG tile groups][BN couts]
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 2 * AROWS_PAD * 4 + (HEAD ? (HEADW + 2 * XCH) * 4 : 0) + (STATS ? 2 * XST * 4 : 0)];
   int* tabs = reinterpret_cast<int*>(smem + 2 * STAGE);
@@ -125,69 +135,128 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   const long img = (long)p.H * p.W * p.Cin;
 
-  auto decode = [&](int it, int& mblk, int& nblk) __attribute__((always_inline)) {
-    mblk = it / p.ncb;
-    nblk = it - mblk * p.ncb;
+  // ---- an item, decoded once: wave-uniform, kept in scalar registers ---------------------------------------------------------
+  // (sub-block sb of the item: image n[sb], halo origin (y0, x0) = (16 bby - 1, 16 bbx - 1), table base nb = (n - nfirst) * H;
+  //  the sub-blocks of an item follow each other in (n, bby, bbx) order and may lie in different images)
+  struct Item {
+    int mblk, nblk, nfirst;
+    int n[SB], y0[SB], x0[SB], nb[SB];
+    bool live[SB];
   };
-  auto build_table = [&](int seq) __attribute__((always_inline)) {
-    int mblk, nblk;
-    decode(first + seq * (int)gridDim.x, mblk, nblk);
-    const int sub0 = mblk * SB, nfirst = sub0 / per_img;
-    int* tab = tabs + (seq & 1) * AROWS_PAD;
-    for (int rho = tid; rho < AROWS_PAD; rho += 64 * NW) {
-      int v = -1;
-      if (rho < AROWS) {
-        const int sb = rho / kSBROWS, rem = rho - sb * kSBROWS;
-        const int hy = rem / kPITCH, xs = rem - hy * kPITCH;
-        const int hx = hy >= kHW ? -1 : (xs < kHALF ? 2 * xs : 2 * (xs - kHALF) + 1);
-        const int sub = sub0 + sb;
-        if (hx >= 0 && sub < p.nsub) {
-          const int n = sub / per_img, r2 = sub - n * per_img;
-          const int bby = r2 / p.BBX, bbx = r2 - bby * p.BBX;
-          const int y = 2 * bby * kPB - 1 + hy, x = 2 * bbx * kPB - 1 + hx;
-          if ((unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W) v = ((n - nfirst) * p.H + y) * p.W + x;
+  const int uni_first = __builtin_amdgcn_readfirstlane(first), uni_grid = __builtin_amdgcn_readfirstlane((int)gridDim.x);
+  int d_mblk = uni_first / p.ncb, d_nblk = uni_first - d_mblk * p.ncb;  // the next item to decode; + (dq, dr) per item
+  const int dq = uni_grid / p.ncb, dr = uni_grid - dq * p.ncb;
+  auto decode_next = [&](Item& s) __attribute__((always_inline)) {
+    s.mblk = d_mblk;
+    s.nblk = d_nblk;
+    const int sub0 = d_mblk * SB;
+    int n = __builtin_amdgcn_readfirstlane(sub0 / per_img);
+    const int r2 = sub0 - n * per_img;
+    int bby = __builtin_amdgcn_readfirstlane(r2 / p.BBX);
+    int bbx = r2 - bby * p.BBX;
+    s.nfirst = n;
+#pragma unroll
+    for (int sb = 0; sb < SB; ++sb) {
+      s.live[sb] = sub0 + sb < p.nsub;
+      s.n[sb] = n;
+      s.y0[sb] = 2 * bby * kPB - 1;
+      s.x0[sb] = 2 * bbx * kPB - 1;
+      s.nb[sb] = (n - s.nfirst) * p.H;
+      if (++bbx == p.BBX) {
+        bbx = 0;
+        if (++bby == p.BBY) {
+          bby = 0;
+          ++n;
         }
       }
-      tab[rho] = v;
+    }
+    d_mblk += dq;
+    d_nblk += dr;
+    if (d_nblk >= p.ncb) {
+      d_nblk -= p.ncb;
+      ++d_mblk;
+    }
+  };
+  Item cur, nxt;  // the item in the accumulators / the last one decoded (what the fetch side is at, one item ahead at most)
+  decode_next(cur);
+  nxt = cur;
+
+  // this thread's rows of the gather table: sub-block and halo position (hy, hx) of row rho = tid + 512 e.  Rows of the padding (no
+  // halo pixel) get hy far outside every image: the bounds test below turns them into -1 like the pixels past the border.
+  constexpr int NT = (AROWS_PAD + 64 * NW - 1) / (64 * NW);
+  int t_hy[NT], t_hx[NT];
+  bool t_sb[NT];
+#pragma unroll
+  for (int e = 0; e < NT; ++e) {
+    const int rho = tid + 64 * NW * e;
+    const int sb = rho / kSBROWS, rem = rho - sb * kSBROWS;
+    const int hy = rem / kPITCH, xs = rem - hy * kPITCH;
+    const bool halo = rho < AROWS && hy < kHW;
+    t_sb[e] = sb > 0 && sb < SB;
+    t_hy[e] = halo ? hy : -(1 << 24);
+    t_hx[e] = xs < kHALF ? 2 * xs : 2 * (xs - kHALF) + 1;
+  }
+  auto build_table = [&](const Item& s, int seq) __attribute__((always_inline)) {
+    int* tab = tabs + (seq & 1) * AROWS_PAD;
+#pragma unroll
+    for (int e = 0; e < NT; ++e) {
+      const int rho = tid + 64 * NW * e;
+      if (rho < AROWS_PAD) {
+        const bool one = SB > 1 && t_sb[e];
+        const int y = (one ? s.y0[SB - 1] : s.y0[0]) + t_hy[e], x = (one ? s.x0[SB - 1] : s.x0[0]) + t_hx[e];
+        const bool in = (one ? s.live[SB - 1] : s.live[0]) && (unsigned)y < (unsigned)p.H && (unsigned)x < (unsigned)p.W;
+        tab[rho] = in ? ((one ? s.nb[SB - 1] : s.nb[0]) + y) * p.W + x : -1;
+      }
     }
     rs_lds_writes_done();  // (read by every wave behind a later barrier, which hipcc emits bare: common.h)
   };
 
   // ---- fetch side (see conv_wino_f32.hip): one chunk ahead, across work items --------------------------------------------
+  // Source rows: byte offsets from the gather table, per item.  Filter rows: the item's cout block goes into the DMA's scalar offset
+  // (f_nb), what is left -- row xi * BN + cout of block 0 -- is the same for every item and computed here once.
   const int ra = lane >> 2, pp = lane & 3;
   int doff[NI];
-  int f_seq = 0, f_kc = 0, f_g = 0;
+#pragma unroll
+  for (int j = 0; j < NI; ++j) {
+    const int ii = wave + NW * j;
+    static_assert((BN & (BN - 1)) == 0, "BN: a power of two");
+    const unsigned int w = 16u * (unsigned int)(ii - IA) + ra;  // filter row: xi * BN + cout
+    const int xi = (int)(w / BN), co = (int)(w % BN);
+    doff[j] = ii < IA ? kDmaOOB : ((xi * p.Cout + co) * p.Cin) * 4 + ((pp ^ w33_swz((int)w)) & 3) * 16;
+  }
+  int f_seq = 0, f_kc = 0, f_g = 0, f_nb = 0;
   __amdgpu_buffer_rsrc_t rsrc = rs_dma_rsrc<kDmaClamp>(p.src, 0);
   const __amdgpu_buffer_rsrc_t rsrcu = rs_dma_rsrc<kDmaClamp>(p.u, (long)16 * p.Cout * p.Cin * 4);
-  auto fetch_item = [&]() __attribute__((always_inline)) {
-    int mblk, nblk;
-    decode(first + f_seq * (int)gridDim.x, mblk, nblk);
-    const int nfirst = __builtin_amdgcn_readfirstlane((mblk * SB) / per_img);
-    rsrc = rs_dma_rsrc<kDmaClamp>(p.src + nfirst * img, (long)(p.N - nfirst) * img * 4);
+  auto fetch_item = [&](const Item& s) __attribute__((always_inline)) {
+    rsrc = rs_dma_rsrc<kDmaClamp>(p.src + s.nfirst * img, (long)(p.N - s.nfirst) * img * 4);
+    f_nb = s.nblk * BN * p.Cin * 4;
     const int* tab = tabs + (f_seq & 1) * AROWS_PAD;
+    // every table read of the wave first (rows past the wave's share clamped: read, not used), one wait, then the offsets
+    int pix[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int ii = wave + NW * j;
-      if (ii < IA) {
+      if (NW * j < IA) pix[j] = tab[16 * (ii < IA ? ii : IA - 1) + ra];
+    }
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+      const int ii = wave + NW * j;
+      if (NW * j < IA && ii < IA) {
         const int rho = 16 * ii + ra;
-        const int pix = tab[rho];
-        doff[j] = pix < 0 ? kDmaOOB : pix * (p.Cin * 4) + ((pp ^ w33_swz(rho)) & 3) * 16;
-      } else {
-        const int w = 16 * (ii - IA) + ra;  // filter row: xi * BN + cout
-        const int xi = w / BN, co = w - xi * BN;
-        doff[j] = ((xi * p.Cout + nblk * BN + co) * p.Cin) * 4 + ((pp ^ w33_swz(w)) & 3) * 16;
+        doff[j] = pix[j] < 0 ? kDmaOOB : pix[j] * (p.Cin * 4) + ((pp ^ w33_swz(rho)) & 3) * 16;
       }
     }
   };
   // (`past`: beyond the block's last chunk the previous pieces are issued again into the free stage; see conv_wino_f32.hip)
   auto fetch_chunk = [&](auto interleave, bool past) __attribute__((always_inline)) {
-    if (!past && f_kc == 0) fetch_item();
+    if (!past && f_kc == 0) fetch_item(nxt);
     const unsigned int fL = lds0 + (f_g & 1) * STAGE;
-    const int fs = f_kc * KC * 4;
+    // (readfirstlane: the DMA's scalar offset must be provably uniform -- lds_dma.h)
+    const int fs = __builtin_amdgcn_readfirstlane(f_kc * KC * 4), fsu = __builtin_amdgcn_readfirstlane(fs + f_nb);
     interleave([&](int j) __attribute__((always_inline)) {
       const int ii = wave + NW * j;  // wave-uniform
       if (ii < IA) rs_dma16(rsrc, fL + ii * 1024, doff[j], fs);
-      else if (ii < IA + IB) rs_dma16(rsrcu, fL + ii * 1024, doff[j], fs);
+      else if (ii < IA + IB) rs_dma16(rsrcu, fL + ii * 1024, doff[j], fsu);
     });
     ++f_g;
     if (!past && ++f_kc == nk) {
@@ -199,7 +268,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   // ---- fragment addressing: lane = tile (lane & 15) of the wave's 16, 16-byte piece (lane >> 4) ---------------------------
   const int l15 = lane & 15, pc = lane >> 4;
   const int t = 16 * tg + w33_lane_tile(l15);
-  const int tsb = t / (kPB * kPB), tq = t - tsb * (kPB * kPB);
+  const int tsb = 16 * tg / (kPB * kPB), tq = t - tsb * (kPB * kPB);  // (the wave's 16 tiles lie in one sub-block: wave-uniform)
   const int tty = tq / kPB, ttx = tq - tty * kPB;
   int addrA[4][4];
   {
@@ -216,11 +285,11 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
 
   if constexpr (HEAD) {
     for (int f = threadIdx.x; f < HEADW; f += 64 * NW) {
-      const int c = f < kHeadMaxC * 32 ? f / 32 : f - kHeadMaxC * 32;
-      hws[f] = c >= p.hC ? 0.f : (f < kHeadMaxC * 32 ? p.hw[f] : (p.hb ? p.hb[c] : 0.f));
+      const int c = f < HC * 32 ? f / 32 : f - HC * 32;
+      hws[f] = c >= p.hC ? 0.f : (f < HC * 32 ? p.hw[f] : (p.hb ? p.hb[c] : 0.f));
     }
   }
-  build_table(0);
+  build_table(cur, 0);
   __syncthreads();
   fetch_chunk([&](auto issue) __attribute__((always_inline)) {
 #pragma unroll
@@ -229,19 +298,32 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
   const int total = nitems * nk;
 
   // HEAD: the cg = 0 lanes' pixel of the previous item, waiting for the other cout group's half (finish_head)
-  float hmine[kHeadMaxC];
-  long hpix = -1;
+  //       (image hn -- -1: no pixel -- row hpy, column hpx)
+  float hmine[HC];
+  int hn = -1, hpy = 0, hpx = 0;
   int hbuf = 0;
   auto finish_head = [&]() __attribute__((always_inline)) {
     if constexpr (HEAD) {
       if (cg == 0) {
-        const float* xrow = xch + hbuf * XCH + (16 * tg + l15) * XROW + pc * kHeadMaxC;
-        const f32x4 o0 = *reinterpret_cast<const f32x4*>(xrow), o1 = *reinterpret_cast<const f32x4*>(xrow + 4);
-        float lg[kHeadMaxC];
+        const float* xrow = xch + hbuf * XCH + (16 * tg + l15) * XROW + pc * HC;
+        float o[HC];
+        if constexpr (HC == 2) {
+          const f32x2 v = *reinterpret_cast<const f32x2*>(xrow);
+          o[0] = v[0];
+          o[1] = v[1];
+        } else {
 #pragma unroll
-        for (int c = 0; c < kHeadMaxC; ++c) lg[c] = (hmine[c] + (c < 4 ? o0[c] : o1[c - 4])) + hws[kHeadMaxC * 32 + c];
-        if (hpix >= 0)
-          rs_final_epilogue_rt(lg, p.hC, hpix, (long)p.H * p.W, HEAD == 1 ? (p.hmode & 1) : HEAD, p.hanchors, p.hq, p.hout, p.W, p.hov);
+          for (int q = 0; q < HC / 4; ++q) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xrow + 4 * q);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[4 * q + e] = v[e];
+          }
+        }
+        float lg[HC];
+#pragma unroll
+        for (int c = 0; c < HC; ++c) lg[c] = (hmine[c] + o[c]) + hws[HC * 32 + c];
+        if (hn >= 0)
+          rs_final_epilogue_rt<HC>(lg, p.hC, hn, hpy, hpx, p.H, p.W, HEAD == 1 ? (p.hmode & 1) : HEAD, p.hanchors, p.hq, p.hout, p.hov);
       }
     }
   };
@@ -328,18 +410,20 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
         }
       };
       fetch_chunk([&](auto issue) __attribute__((always_inline)) { mfmas(issue); }, !more);
-      if (kc == 0 && seq + 1 < nitems) build_table(seq + 1);
+      if (kc == 0 && seq + 1 < nitems) {  // (the fetch side turns to item seq + 1 in this item's last chunk: nk >= 2)
+        decode_next(nxt);
+        build_table(nxt, seq + 1);
+      }
     }
 
     // ---- Y = A^T M A (y0 = m0 + m1 + m2, y1 = m1 - m2 - m3 each way), scale / shift, ReLU, store --------------------------
-    int mblk, nblk;
-    decode(first + seq * (int)gridDim.x, mblk, nblk);
-    const int sub = mblk * SB + tsb;
-    const bool live = sub < p.nsub;
-    const int n = sub / per_img, r2 = sub - n * per_img;
-    const int bby = r2 / p.BBX, bbx = r2 - bby * p.BBX;
-    const int a0 = 2 * (bby * kPB + tty), b0 = 2 * (bbx * kPB + ttx);
+    const int mblk = cur.mblk, nblk = cur.nblk;
+    const bool one = SB > 1 && tsb > 0;  // (wave-uniform)
+    const bool live = one ? cur.live[SB - 1] : cur.live[0];
+    const int n = one ? cur.n[SB - 1] : cur.n[0];
+    const int a0 = (one ? cur.y0[SB - 1] : cur.y0[0]) + 1 + 2 * tty, b0 = (one ? cur.x0[SB - 1] : cur.x0[0]) + 1 + 2 * ttx;
     const int co = nblk * BN + 16 * cg + 4 * pc;
+    cur = nxt;
     f32x4 Y[2][2];
     if (live || HEAD) {
       f32x4 sc = {1.f, 1.f, 1.f, 1.f}, sh = {0.f, 0.f, 0.f, 0.f};
@@ -451,10 +535,12 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
       // ---- self.final on the block's 32 channels: this lane's 4 couts -> the wave's 16 (lanes l15 + 16 pc) -> both cout
       //      groups (waves tg and tg + TG, through LDS) + bias; then one pixel per lane of the cg = 0 waves (pixel pc of tile
       //      l15).  The order of the sums is fixed by the layout, not by the batch.
-      float part[4][kHeadMaxC];
+      // (HC was chosen as the smallest bound >= p.hC: the classes c <= HC / 2 exist without a test, HC = 2 also computes a second
+      //  class for a one-class head -- zero weights, never stored)
+      float part[4][HC];
 #pragma unroll
-      for (int c = 0; c < kHeadMaxC; ++c) {
-        if (c < p.hC) {
+      for (int c = 0; c < HC; ++c) {
+        if (c <= HC / 2 || c < p.hC) {
           const f32x4 wv = *reinterpret_cast<const f32x4*>(hws + c * 32 + 16 * cg + 4 * pc);
 #pragma unroll
           for (int px = 0; px < 4; ++px) {
@@ -485,15 +571,21 @@ __global__ __launch_bounds__(512, 1) void conv_wino33_f32_kernel(const Wino33Arg
         float* xrow = xch + hbuf * XCH + (16 * tg + l15) * XROW;
 #pragma unroll
         for (int px = 0; px < 4; ++px) {
-          *reinterpret_cast<f32x4*>(xrow + px * kHeadMaxC) = f32x4{part[px][0], part[px][1], part[px][2], part[px][3]};
-          *reinterpret_cast<f32x4*>(xrow + px * kHeadMaxC + 4) = f32x4{part[px][4], part[px][5], part[px][6], part[px][7]};
+          if constexpr (HC == 2) {
+            *reinterpret_cast<f32x2*>(xrow + px * HC) = f32x2{part[px][0], part[px][1]};
+          } else {
+#pragma unroll
+            for (int q = 0; q < HC / 4; ++q)
+              *reinterpret_cast<f32x4*>(xrow + px * HC + 4 * q) = f32x4{part[px][4 * q], part[px][4 * q + 1], part[px][4 * q + 2], part[px][4 * q + 3]};
+          }
         }
         rs_lds_writes_done();  // (the cg = 0 waves read it right behind the next barrier, which hipcc emits bare: common.h)
       }
 #pragma unroll
-      for (int c = 0; c < kHeadMaxC; ++c) hmine[c] = pc == 0 ? part[0][c] : (pc == 1 ? part[1][c] : (pc == 2 ? part[2][c] : part[3][c]));
-      const int a = a0 + (pc >> 1), b = b0 + (pc & 1);
-      hpix = (live && a < p.H && b < p.W) ? (long)(n * p.H + a) * p.W + b : -1;
+      for (int c = 0; c < HC; ++c) hmine[c] = pc == 0 ? part[0][c] : (pc == 1 ? part[1][c] : (pc == 2 ? part[2][c] : part[3][c]));
+      hpy = a0 + (pc >> 1);
+      hpx = b0 + (pc & 1);
+      hn = (live && hpy < p.H && hpx < p.W) ? n : -1;
     }
   }
   if constexpr (HEAD) {
@@ -655,9 +747,17 @@ extern "C" int rs_conv2d_fwd_wino33_head(const rs_conv_desc* d, const float* src
   if (items >= (1L << 31)) return RS_EINVAL;
   const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
-  if (mode <= 1) conv_wino33_f32_kernel<4, 2, 1><<<grid, 512, 0, s>>>(a);
-  else if (mode == 2) conv_wino33_f32_kernel<4, 2, 2><<<grid, 512, 0, s>>>(a);
-  else conv_wino33_f32_kernel<4, 2, 3><<<grid, 512, 0, s>>>(a);
+  // (the class loops' bound: the smallest of 2 / 4 / 8 that holds C)
+#define RS_W33_HEAD(MODE)                                                          \
+  do {                                                                             \
+    if (C <= 2) conv_wino33_f32_kernel<4, 2, MODE, 2><<<grid, 512, 0, s>>>(a);      \
+    else if (C <= 4) conv_wino33_f32_kernel<4, 2, MODE, 4><<<grid, 512, 0, s>>>(a); \
+    else conv_wino33_f32_kernel<4, 2, MODE, 8><<<grid, 512, 0, s>>>(a);             \
+  } while (0)
+  if (mode <= 1) RS_W33_HEAD(1);
+  else if (mode == 2) RS_W33_HEAD(2);
+  else RS_W33_HEAD(3);
+#undef RS_W33_HEAD
   return RS_LAUNCH_RESULT();
 }
 

@@ -8,35 +8,37 @@
 
 constexpr int kHeadMaxC = 8;
 
-__device__ __forceinline__ void rs_final_epilogue_rt(float (&acc)[kHeadMaxC], int C, long pix, long HW, int softmax,
+// `acc` holds HC >= C logits (HC: the caller's compile-time bound, 2 / 4 / 8 -- the loops below are HC long, not kHeadMaxC);
+// the pixel arrives as image n, row yy, column xx of an Himg x Wimg image: nothing is divided here.
+template <int HC>
+__device__ __forceinline__ void rs_final_epilogue_rt(float (&acc)[HC], int C, int n, int yy, int xx, int Himg, int Wimg, int softmax,
                                                      const double* __restrict__ anchors, uint8_t* __restrict__ qout,
-                                                     float* __restrict__ out, int Wimg, int ov) {
+                                                     float* __restrict__ out, int ov) {
+  static_assert(HC >= 1 && HC <= kHeadMaxC, "at most kHeadMaxC classes");
   if (softmax == 1 || softmax == 2) {
     float mx = acc[0];
 #pragma unroll
-    for (int c = 1; c < kHeadMaxC; ++c)
+    for (int c = 1; c < HC; ++c)
       if (c < C) mx = fmaxf(mx, acc[c]);
     float sum = 0.f;
 #pragma unroll
-    for (int c = 0; c < kHeadMaxC; ++c)
+    for (int c = 0; c < HC; ++c)
       if (c < C) {
         acc[c] = expf(acc[c] - mx);
         sum += acc[c];
       }
 #pragma unroll
-    for (int c = 0; c < kHeadMaxC; ++c)
+    for (int c = 0; c < HC; ++c)
       if (c < C) acc[c] = acc[c] / sum;
   }
-  const long n = pix / HW, hw = pix - n * HW;
+  const long HW = (long)Himg * Wimg, hw = (long)yy * Wimg + xx;
   if (softmax == 2) {  // un-buffer crop + np.digitize of every non-background class: C - 1 bytes per pixel
     if (C < 2) return;
-    const int Himg = (int)(HW / Wimg);
-    const int yy = (int)(hw / Wimg), xx = (int)(hw - (long)yy * Wimg);
     const int S_h = Himg - 2 * ov, S_w = Wimg - 2 * ov;
     if (yy < ov || yy >= Himg - ov || xx < ov || xx >= Wimg - ov) return;
-    uint8_t* qo = qout + ((n * S_h + (yy - ov)) * (long)S_w + (xx - ov)) * (C - 1);
+    uint8_t* qo = qout + (((long)n * S_h + (yy - ov)) * (long)S_w + (xx - ov)) * (C - 1);
 #pragma unroll
-    for (int c = 1; c < kHeadMaxC; ++c)
+    for (int c = 1; c < HC; ++c)
       if (c < C) {
         const double pf = (double)acc[c];
         int q = (int)(pf * 255.0);  // anchors[i] ~ i/255: first guess, then settle on the exact table (anchors ascending)
@@ -51,16 +53,16 @@ __device__ __forceinline__ void rs_final_epilogue_rt(float (&acc)[kHeadMaxC], in
     int best = 0;
     float bv = acc[0];
 #pragma unroll
-    for (int c = 1; c < kHeadMaxC; ++c)
+    for (int c = 1; c < HC; ++c)
       if (c < C && acc[c] > bv) {
         bv = acc[c];
         best = c;
       }
-    qout[pix] = (uint8_t)best;
+    qout[(long)n * HW + hw] = (uint8_t)best;
     return;
   }
-  float* o = out + n * C * HW + hw;
+  float* o = out + (long)n * C * HW + hw;
 #pragma unroll
-  for (int c = 0; c < kHeadMaxC; ++c)
+  for (int c = 0; c < HC; ++c)
     if (c < C) o[c * HW] = acc[c];
 }

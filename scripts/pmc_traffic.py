@@ -47,8 +47,9 @@ def bench_name(k):
     if m:
         return "conv_wino_f32<{},p{},{}x{}>".format("dgrad4x4" if m.group(5) == "1" else "phase", m.group(1), 16 * int(m.group(2)),
                                                     16 * int(m.group(4)) * int(m.group(3)))
-    m = re.search(r"conv_wino33_f32_kernel<(\d+), (\d+)(?:, (true|false|\d+))?>", k)
-    if m:  # (third parameter: 0 / absent = the layer alone, 1..3 = + self.final with one of its three output kinds, 4 = + BatchNorm partial sums, 5 = the data gradient)
+    m = re.search(r"conv_wino33_f32_kernel<(\d+), (\d+)(?:, (true|false|\d+))?(?:, \d+)?>", k)
+    if m:  # (third parameter: 0 / absent = the layer alone, 1..3 = + self.final with one of its three output kinds, 4 = + BatchNorm partial sums, 5 = the data gradient;
+        #    fourth: the fused head's class bound 2 / 4 / 8 -- one report name for all three)
         kind = "+stats" if m.group(3) == "4" else "+bwd" if m.group(3) == "5" else "" if m.group(3) in (None, "false", "0") else "+final"
         return "conv_wino_f32<3x3{},p8,{}x{}>".format(kind, 16 * int(m.group(1)), 16 * int(m.group(2)))
     m = re.search(r"conv_thin_bf16<(\d)>", k)
