@@ -820,6 +820,41 @@ int rs_features_grow_config(int* block_h, int* block_w, int* fused);
 int rs_features_grow(int32_t* labels, void* workspace, const int32_t* nbr, int32_t* counters, int B, int H, int W, int steps,
                      rs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * `rs evaluate` (robosat_amd/tools/evaluate.py): the counting passes over two rasters (csrc/evaluate.hip).
+ * Pixels come in groups of `group` consecutive ones as in rs_features_scores (H*W: one group per tile; the whole call: one group for
+ * stitched tiles); pixels % group == 0, 0 < pixels < 2^31, RS_EINVAL otherwise.  G = pixels / group.  All counting is in integers:
+ * the same bits in every run, whatever order the device worked in.
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* rs_eval_confusion: predicted, actual: uint8 [pixels] class indices (any address: no alignment is asked for), 2 <= C <= 8.
+ *   counts[g][a][p] = the number of pixels of group g with actual == a and predicted == p, for a, p < C   (int64 [G][C][C])
+ *   bad[g]          = the number of pixels of group g where either value is >= C; they are counted in no cell   (int64 [G])
+ * both set by the call, not added to, 8-byte aligned.  The orientation is M[actual][predicted], as rs_confusion_matrix and
+ * robosat_amd/metrics.py have it.
+ *
+ * rs_eval_boundary: d2_a, d2_b: int32 [pixels], rs_features_edt(m, R) of the two masks with R = D + 1, 1 <= D <= 127 (so that R stays
+ * within the transform's 128).  The band of a mask is X_D = { pixel : 1 <= d2 <= D*D }: its set pixels within D pixels, centre to
+ * centre, of an unset pixel of the same raster (R = D + 1 keeps the cap (D+1)^2 above D*D: a capped pixel is never in the band).
+ *   counts[g] = (|A_D|, |B_D|, |A_D and B_D|) over the pixels of group g   (int64 [G][3], set by the call, 8-byte aligned)
+ * from which the host makes the Boundary IoU of Cheng et al. (CVPR 2021), shared / (|A_D| + |B_D| - shared).  One departure from the
+ * paper's code, which pads the mask with zeros before it erodes: rs_features_edt lets no distance come from outside the raster or
+ * from an absent tile, so a raster edge is NOT a boundary here -- an object cut by the edge has no band along the cut (nothing is
+ * known beyond it), and a mask that fills its raster has an empty band.  With stitched transforms (nbr given to rs_features_edt) a
+ * seam between two present tiles is interior.
+ *
+ * One launch each behind the fill of the outputs (one fill for rs_eval_confusion where bad == counts + G*C*C, two otherwise).  A workgroup of 256 threads covers rs_eval_config's block_pixels (4096)
+ * consecutive pixels of the call, a thread 16 consecutive ones (16-byte loads where its first address is 16-byte aligned and its run
+ * ends within `pixels`, single checked loads otherwise), and walks the groups those pixels lie in: a block may straddle two groups,
+ * or hold many small ones.  Per group the counts are merged on chip -- confusion: runs of equal cells within a thread, then one
+ * histogram per wave in LDS, then the four waves' sum; boundary: bit counts within a thread, a sum over the wave's lanes, then over
+ * the waves -- and one 64-bit atomic add goes out per block, group and non-empty cell: at most C*C + 1, or 3.  No workgroup waits for
+ * another; every loop is bounded. */
+int rs_eval_config(int* block_pixels);
+int rs_eval_confusion(const uint8_t* predicted, const uint8_t* actual, int64_t* counts, int64_t* bad, long pixels, long group, int C,
+                      rs_stream_t stream);
+int rs_eval_boundary(const int32_t* d2_a, const int32_t* d2_b, int64_t* counts, long pixels, long group, int D, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -180,6 +180,10 @@ SIGNATURES = {
     "rs_features_grow_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "rs_features_grow_config": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int)]),
     "rs_features_grow": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    # rs evaluate: per-group counts over two rasters (csrc/evaluate.hip)
+    "rs_eval_config": (c_int, [POINTER(c_int)]),
+    "rs_eval_confusion": (c_int, [P, P, P, P, c_long, c_long, c_int, P]),
+    "rs_eval_boundary": (c_int, [P, P, P, c_long, c_long, c_int, P]),
 }
 
 _lib = None

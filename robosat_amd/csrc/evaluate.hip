@@ -1,0 +1,202 @@
+// `rs evaluate` (robosat_amd/tools/evaluate.py): the counting passes over two rasters, per group of pixels (definitions in
+// include/robosat_hip.h).  Integer work, HBM-bound: every pixel of both rasters is read once.
+//
+//   rs_eval_confusion  two class-index rasters -> per group the C x C matrix counts[actual][predicted] and the number of pixels with a
+//                      value that is no class
+//   rs_eval_boundary   two capped distance transforms (rs_features_edt) -> per group the sizes of the two boundary bands and of their
+//                      intersection
+//
+// Both kernels share one shape.  A block of 256 threads covers kEvalBlock = 4096 consecutive pixels of the whole call, a thread 16
+// consecutive ones, held in registers: a 16-byte load per raster (four for the int32 rasters) where the thread's first address is
+// 16-byte aligned and its run ends within `pixels`, single loads with a bound check otherwise (the call's last thread; a raster that
+// is a view at an odd offset).  Runs are laid over the call, not over the groups, so where a group begins (byte 63 for the second
+// tile of a 7 x 9 batch) has no say in the alignment.  The block then walks the groups its pixels lie in -- one for a tile of at least
+// 4096 pixels away from its ends, two where the block straddles a border, more only for tiles smaller than a block -- and per group
+// counts the pixels of that group only, merges on chip and sends one 64-bit atomic add per non-empty cell.  No workgroup waits for
+// another and every loop is bounded (the group loop by the block's 4096 pixels).
+#include "common.h"
+
+namespace {
+
+constexpr int kEvalRun = 16;                            // consecutive pixels of a thread
+constexpr int kEvalThreads = 256;                       // four waves
+constexpr int kEvalBlock = kEvalRun * kEvalThreads;     // pixels of a block
+constexpr int kEvalBad = 64;                            // the bin of pixels with a value >= C, behind the 8 x 8 cells
+constexpr int kEvalBins = kEvalBad + 1;
+
+// The thread's part [jlo, jhi) of its run that lies in group g: pixel j counts iff g*group <= base + j < min((g+1)*group, pixels).
+__device__ __forceinline__ void eval_range(long base, long g, long group, long pixels, int& jlo, int& jhi) {
+  long lo = g * group - base, hi = (g + 1) * group - base;
+  const long top = pixels - base;
+  if (hi > top) hi = top;
+  jlo = lo < 0 ? 0 : lo > kEvalRun ? kEvalRun : (int)lo;
+  jhi = hi < 0 ? 0 : hi > kEvalRun ? kEvalRun : (int)hi;
+}
+
+__device__ __forceinline__ void eval_load_bytes(const uint8_t* __restrict__ p, long base, long pixels, unsigned int (&w)[4]) {
+  if (base + kEvalRun <= pixels && (reinterpret_cast<uintptr_t>(p + base) & 15) == 0) {
+    const u32x4 q = *reinterpret_cast<const u32x4*>(p + base);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = q[e];
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) w[e] = 0;
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j)
+      if (base + j < pixels) w[j >> 2] |= (unsigned int)p[base + j] << ((j & 3) * 8);
+  }
+}
+
+// Bit j set where 1 <= d2[base + j] <= dd.
+__device__ __forceinline__ unsigned int eval_load_band(const int* __restrict__ d2, long base, long pixels, unsigned int dd) {
+  unsigned int bits = 0;
+  if (base + kEvalRun <= pixels && (reinterpret_cast<uintptr_t>(d2 + base) & 15) == 0) {
+    u32x4 q[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] = *(reinterpret_cast<const u32x4*>(d2 + base) + e);
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j) bits |= (unsigned int)(q[j >> 2][j & 3] - 1u < dd) << j;  // (0 wraps to 2^32 - 1: not in the band)
+  } else {
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j)
+      if (base + j < pixels) bits |= (unsigned int)((unsigned int)d2[base + j] - 1u < dd) << j;
+  }
+  return bits;
+}
+
+// ---- confusion matrix per group --------------------------------------------------------------------------------------
+// A pixel's cell is actual * C + predicted (< 64), or kEvalBad where either byte is >= C.  Per group: a thread turns its pixels into
+// runs of equal cells and adds one run at a time to its wave's private histogram in LDS (a tile that is all one cell costs one LDS
+// atomic per thread, not 16; the four private copies keep the waves off each other's counters), the four copies are summed per bin,
+// and the bins that are not empty go out: at most C*C + 1 global atomics per block and group.
+__global__ __launch_bounds__(kEvalThreads) void eval_confusion_kernel(const uint8_t* __restrict__ predicted, const uint8_t* __restrict__ actual,
+                                                                      unsigned long long* __restrict__ counts,
+                                                                      unsigned long long* __restrict__ bad, long pixels, long group, int C) {
+  __shared__ unsigned int hist[4][kEvalBins];
+  const long block0 = (long)blockIdx.x * kEvalBlock;
+  const long base = block0 + (long)threadIdx.x * kEvalRun;
+  unsigned int cells[4] = {0, 0, 0, 0};  // 16 cells, a byte each
+  if (base < pixels) {
+    unsigned int pw[4], aw[4];
+    eval_load_bytes(predicted, base, pixels, pw);
+    eval_load_bytes(actual, base, pixels, aw);
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j) {
+      const unsigned int p = (pw[j >> 2] >> ((j & 3) * 8)) & 255u, a = (aw[j >> 2] >> ((j & 3) * 8)) & 255u;
+      const unsigned int cell = (p >= (unsigned int)C || a >= (unsigned int)C) ? (unsigned int)kEvalBad : a * C + p;
+      cells[j >> 2] |= cell << ((j & 3) * 8);
+    }
+  }
+  const long block1 = block0 + kEvalBlock < pixels ? block0 + kEvalBlock : pixels;  // (block0 < pixels: the grid is cdiv(pixels, kEvalBlock))
+  const long g0 = block0 / group, g1 = (block1 - 1) / group;
+  unsigned int* h = hist[threadIdx.x >> 6];
+  const int cc = C * C;
+  for (long g = g0; g <= g1; ++g) {
+    for (int i = threadIdx.x; i < 4 * kEvalBins; i += kEvalThreads) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    int jlo, jhi;
+    eval_range(base, g, group, pixels, jlo, jhi);
+    unsigned int cur = 0, run = 0;
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j) {
+      if (j >= jlo && j < jhi) {
+        const unsigned int cell = (cells[j >> 2] >> ((j & 3) * 8)) & 255u;
+        if (run && cell != cur) {
+          atomicAdd(&h[cur], run);
+          run = 0;
+        }
+        cur = cell;
+        ++run;
+      }
+    }
+    if (run) atomicAdd(&h[cur], run);
+    __syncthreads();
+    if (threadIdx.x < kEvalBins) {
+      const int t = threadIdx.x;
+      const unsigned int tot = hist[0][t] + hist[1][t] + hist[2][t] + hist[3][t];
+      if (tot) {
+        if (t == kEvalBad)
+          atomicAdd(&bad[g], (unsigned long long)tot);
+        else if (t < cc)  // (a cell is below C*C by construction)
+          atomicAdd(&counts[g * cc + t], (unsigned long long)tot);
+      }
+    }
+    __syncthreads();  // (the next group zeroes the histograms)
+  }
+}
+
+// ---- boundary bands per group ----------------------------------------------------------------------------------------
+// Three counters per group, so no histogram: a thread keeps its 16 pixels as two 16-bit masks, counts the bits of its part of the
+// group, the wave sums over its lanes, the block over its waves, and up to three global atomics go out per block and group.
+__global__ __launch_bounds__(kEvalThreads) void eval_boundary_kernel(const int* __restrict__ d2_a, const int* __restrict__ d2_b,
+                                                                     unsigned long long* __restrict__ counts, long pixels, long group,
+                                                                     unsigned int dd) {
+  __shared__ unsigned int part[4][3];
+  const long block0 = (long)blockIdx.x * kEvalBlock;
+  const long base = block0 + (long)threadIdx.x * kEvalRun;
+  unsigned int ma = 0, mb = 0;
+  if (base < pixels) {
+    ma = eval_load_band(d2_a, base, pixels, dd);
+    mb = eval_load_band(d2_b, base, pixels, dd);
+  }
+  const long block1 = block0 + kEvalBlock < pixels ? block0 + kEvalBlock : pixels;
+  const long g0 = block0 / group, g1 = (block1 - 1) / group;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (long g = g0; g <= g1; ++g) {
+    int jlo, jhi;
+    eval_range(base, g, group, pixels, jlo, jhi);
+    const unsigned int in = jhi > jlo ? ((1u << jhi) - 1u) & ~((1u << jlo) - 1u) : 0u;  // (jhi <= 16: no shift by 32)
+    unsigned int n[3] = {(unsigned int)__popc(ma & in), (unsigned int)__popc(mb & in), (unsigned int)__popc(ma & mb & in)};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) n[k] += __shfl_xor(n[k], o, 64);
+      if (lane == 0) part[wave][k] = n[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+      const int t = threadIdx.x;
+      const unsigned int tot = part[0][t] + part[1][t] + part[2][t] + part[3][t];
+      if (tot) atomicAdd(&counts[g * 3 + t], (unsigned long long)tot);
+    }
+    __syncthreads();  // (the next group overwrites the partial sums)
+  }
+}
+
+bool eval_shape_ok(long pixels, long group) { return pixels > 0 && pixels < (1l << 31) && group > 0 && pixels % group == 0; }
+
+}  // namespace
+
+extern "C" int rs_eval_config(int* block_pixels) {
+  if (!block_pixels) return RS_EINVAL;
+  *block_pixels = kEvalBlock;
+  return 0;
+}
+
+extern "C" int rs_eval_confusion(const uint8_t* predicted, const uint8_t* actual, int64_t* counts, int64_t* bad, long pixels, long group,
+                                 int C, rs_stream_t stream) {
+  if (!predicted || !actual || !counts || !bad || (((uintptr_t)counts | (uintptr_t)bad) & 7) || !eval_shape_ok(pixels, group) || C < 2 ||
+      C > 8)
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long groups = pixels / group;
+  // (one fill where `bad` follows `counts` directly, as ops.mask_confusion lays them out: a fill costs about what the kernel does)
+  const bool joined = bad == counts + groups * C * C;
+  hipError_t e = hipMemsetAsync(counts, 0, groups * (C * C + (joined ? 1 : 0)) * sizeof(int64_t), s);
+  if (e == hipSuccess && !joined) e = hipMemsetAsync(bad, 0, groups * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  eval_confusion_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(predicted, actual, reinterpret_cast<unsigned long long*>(counts),
+                                                                             reinterpret_cast<unsigned long long*>(bad), pixels, group, C);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_eval_boundary(const int32_t* d2_a, const int32_t* d2_b, int64_t* counts, long pixels, long group, int D,
+                                rs_stream_t stream) {
+  if (!d2_a || !d2_b || !counts || ((uintptr_t)counts & 7) || !eval_shape_ok(pixels, group) || D < 1 || D > 127) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(counts, 0, pixels / group * 3 * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  eval_boundary_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(d2_a, d2_b, reinterpret_cast<unsigned long long*>(counts), pixels,
+                                                                            group, (unsigned int)(D * D));
+  return RS_LAUNCH_RESULT();
+}

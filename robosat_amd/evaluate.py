@@ -1,0 +1,185 @@
+"""Host side of ``rs evaluate``: scores from confusion matrices, object matching from component and overlap tables, the report and
+the per-tile list.  The device counts (``ops.mask_confusion``, ``ops.boundary_counts``, the ``rs features`` stages); everything here
+works on those integers, as Python numbers, and divides once at the end.  Definitions: DESIGN.md, "rs evaluate"."""
+
+import csv
+import math
+from fractions import Fraction
+
+import numpy as np
+
+from robosat_amd.metrics import Metrics
+
+
+def _number(value):
+    """A score as the report carries it: a float, or None where the ratio is undefined (NaN never reaches the JSON)."""
+
+    value = float(value)
+    return None if math.isnan(value) else value
+
+
+def _ratio(num, den):
+    return num / den if den else None
+
+
+def confusion_scores(matrix, classes):
+    """C x C integers ``M[actual][predicted]`` and the class names -> {"iou": {name: IoU}, "miou", "fg_iou", "mcc", "accuracy"}:
+    ``robosat_amd.metrics.Metrics``'s expressions on that matrix (for two classes the reference's own), accuracy = trace / sum;
+    None where a ratio is undefined (a class neither present nor predicted; an empty matrix)."""
+
+    matrix = np.asarray(matrix, dtype=np.int64)
+    metrics = Metrics.from_confusion(classes, matrix)
+    total = int(matrix.sum())
+    return {
+        "iou": {name: _number(v) for name, v in zip(classes, metrics.get_class_ious())},
+        "miou": _number(metrics.get_miou()),
+        "fg_iou": _number(metrics.get_fg_iou()),
+        "mcc": _number(metrics.get_mcc()),
+        "accuracy": _ratio(int(np.trace(matrix)), total),
+    }
+
+
+def match_objects(table_p, table_g, pairs, threshold, stitched):
+    """Predicted and actual objects -> (matched, predicted, actual, ious).  ``table_p`` / ``table_g``: the rows of
+    ``ops.component_table`` (rows of 7: tile, label, area, ...) or with ``stitched`` of ``ops.component_table_stitched`` (rows of 6:
+    label, area, ...), after ``--min_area``; ``pairs``: the rows of ``ops.overlap_table`` (raster, predicted label, actual label,
+    shared pixels).  An object's key is (raster, label), raster 0 throughout with ``stitched``: without it a pair lies within one tile
+    by construction.  A pair's IoU is inter / (area_p + area_g - inter); a pair with a component that is not among its table's rows (below
+    ``--min_area``) is ignored.  Pairs are taken greedily by decreasing IoU, ties by the smaller predicted key, then the smaller actual
+    key, and a pair matches where neither side is matched yet and IoU >= ``threshold``.  IoUs are compared as fractions of integers
+    (``threshold`` by the exact value of its float), never as rounded quotients.  Above 0.5 the matching is the unique one; at exactly
+    0.5 an object can reach two others and the order decides.  ``ious``: the matches' IoUs as floats, in the order they were taken."""
+
+    width = 6 if stitched else 7
+    table_p = np.asarray(table_p, dtype=np.int64).reshape(-1, width)
+    table_g = np.asarray(table_g, dtype=np.int64).reshape(-1, width)
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 4)
+    if stitched:
+        pairs = pairs.copy()
+        pairs[:, 0] = 0
+
+    def areas(table, raster, label):
+        """The areas of the pairs' components in ``table`` and whether they are listed there (keys: tiles <= 65535, labels < 2^31)."""
+
+        key = (np.zeros(len(table), dtype=np.int64) if stitched else table[:, 0]) << 31 | table[:, 0 if stitched else 1]
+        order = np.argsort(key, kind="stable")
+        want = raster << 31 | label
+        at = np.minimum(np.searchsorted(key[order], want), max(len(key) - 1, 0))
+        if len(key) == 0:
+            return np.zeros(len(want), dtype=np.int64), np.zeros(len(want), dtype=bool)
+        return table[:, 1 if stitched else 2][order][at], key[order][at] == want
+
+    area_p, listed_p = areas(table_p, pairs[:, 0], pairs[:, 1])
+    area_g, listed_g = areas(table_g, pairs[:, 0], pairs[:, 2])
+    bound = Fraction(threshold)
+    union = area_p + area_g - pairs[:, 3]
+    # a float screen first (a quotient of integers below 2^31 is off by far less than the margin), then the exact comparison
+    listed = listed_p & listed_g & (pairs[:, 3] / np.maximum(union, 1) >= float(threshold) - 1e-9)
+    candidates = []
+    for (raster, a, b, inter), u in zip(pairs[listed].tolist(), union[listed].tolist()):
+        if inter * bound.denominator >= bound.numerator * u:
+            candidates.append((-Fraction(inter, u), (raster, a), (raster, b)))
+    candidates.sort()
+    taken_p, taken_g, ious = set(), set(), []
+    for iou, kp, kg in candidates:
+        if kp in taken_p or kg in taken_g:
+            continue
+        taken_p.add(kp)
+        taken_g.add(kg)
+        ious.append(float(-iou))
+    return len(ious), len(table_p), len(table_g), ious
+
+
+class ObjectScores:
+    """Matches summed over batches or calls -> the report's ``objects``."""
+
+    def __init__(self, threshold, min_area, stitched):
+        self.threshold, self.min_area, self.stitched = threshold, min_area, stitched
+        self.matched = self.predicted = self.actual = 0
+        self.ious = []
+
+    def add(self, table_p, table_g, pairs):
+        matched, predicted, actual, ious = match_objects(table_p, table_g, pairs, self.threshold, self.stitched)
+        self.matched += matched
+        self.predicted += predicted
+        self.actual += actual
+        self.ious.extend(ious)
+
+    def report(self):
+        return {
+            "threshold": self.threshold,
+            "min_area": self.min_area,
+            "stitched": bool(self.stitched),
+            "predicted": self.predicted,
+            "actual": self.actual,
+            "matched": self.matched,
+            "precision": _ratio(self.matched, self.predicted),
+            "recall": _ratio(self.matched, self.actual),
+            "f1": _ratio(2 * self.matched, self.predicted + self.actual),
+            "mean_matched_iou": _ratio(math.fsum(self.ious), len(self.ious)),
+        }
+
+
+def boundary_report(d, counts):
+    """``d`` and the summed (predicted, actual, shared) band pixels -> the report's ``boundary``."""
+
+    predicted, actual, shared = (int(v) for v in counts)
+    return {"d": int(d), "predicted": predicted, "actual": actual, "shared": shared, "iou": _ratio(shared, predicted + actual - shared)}
+
+
+def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None):
+    """The report of one run.  ``matrix``: C x C Python integers summed over every evaluated tile; ``kind``: ``--type`` or None;
+    ``objects`` / ``boundary``: ``ObjectScores.report()`` / ``boundary_report()`` or None."""
+
+    matrix = [[int(v) for v in row] for row in matrix]
+    report = {
+        "classes": list(classes),
+        "tiles": int(tiles),
+        "tiles_without_label": int(tiles_without_label),
+        "pixels": sum(sum(row) for row in matrix),
+        "confusion": matrix,
+    }
+    report.update(confusion_scores(matrix, classes))
+    if kind is not None:
+        report["type"] = kind
+        report["objects"] = objects
+    if boundary is not None:
+        report["boundary"] = boundary
+    return report
+
+
+def tile_rows(tiles, matrices, classes, kind=None):
+    """One row per evaluated tile: ``tiles`` and their C x C matrices -> dicts with z, x, y, pixels, iou_<class> per class, miou,
+    predicted_share, actual_share (the share of non-background pixels on each side), sorted worst first: by the IoU of ``kind``
+    (``--type``), or by miou without it, undefined values last, then by (z, x, y)."""
+
+    rows = []
+    for tile, matrix in zip(tiles, matrices):
+        matrix = np.asarray(matrix, dtype=np.int64)
+        scores = confusion_scores(matrix, classes)
+        total = int(matrix.sum())
+        row = {"z": int(tile.z), "x": int(tile.x), "y": int(tile.y), "pixels": total}
+        for name in classes:
+            row["iou_" + name] = scores["iou"][name]
+        row["miou"] = scores["miou"]
+        row["predicted_share"] = _ratio(total - int(matrix[:, 0].sum()), total)
+        row["actual_share"] = _ratio(total - int(matrix[0, :].sum()), total)
+        rows.append(row)
+    column = "miou" if kind is None else "iou_" + kind
+    rows.sort(key=lambda r: (r[column] is None, r[column] if r[column] is not None else 0.0, r["z"], r["x"], r["y"]))
+    return rows
+
+
+def tile_columns(classes):
+    return ["z", "x", "y", "pixels"] + ["iou_" + name for name in classes] + ["miou", "predicted_share", "actual_share"]
+
+
+def write_tile_rows(path, rows, classes):
+    """``tile_rows`` as CSV; an undefined value is an empty field, a float is written with ``repr`` (it reads back as it was)."""
+
+    with open(path, "w", newline="") as fp:
+        writer = csv.writer(fp)
+        columns = tile_columns(classes)
+        writer.writerow(columns)
+        for row in rows:
+            writer.writerow(["" if row[c] is None else repr(row[c]) for c in columns])

@@ -35,6 +35,16 @@ class Metrics:
         self._counts = None  # int64 [C*C] on the device: M[actual][predicted]
         self._host = np.zeros(self.num_classes * self.num_classes, dtype=np.int64)
 
+    @classmethod
+    def from_confusion(cls, labels, matrix):
+        """The scores of a matrix counted elsewhere (``rs evaluate``): C x C integers ``M[actual][predicted]``; nothing on a device."""
+
+        self = cls(labels)
+        matrix = np.asarray(matrix, dtype=np.int64)
+        assert matrix.shape == (self.num_classes, self.num_classes), "C x C counts"
+        self._host = matrix.reshape(-1).copy()
+        return self
+
     def _buf(self, device):
         if self._counts is None:
             self._counts = torch.zeros(self.num_classes * self.num_classes, device=device, dtype=torch.int64)

@@ -1892,3 +1892,61 @@ def split_labels(cleaned, labels, radius, nbr=None, steps=None):
     if nbr is not None:
         seed_labels = stitch_labels(seed_labels, nbr, inplace=True)
     return grow_labels(split_seeds(labels, seed_labels, stitched=nbr is not None), nbr, steps)
+
+
+# ---- rs evaluate: per-group counts over two rasters (csrc/evaluate.hip; definitions in include/robosat_hip.h) --------------------
+EVAL_MAX_CLASSES = 8
+EVAL_MAX_DISTANCE = EDT_MAX_RADIUS - 1  # the band's D: the transform behind it has the radius D + 1
+
+
+def eval_config():
+    """Pixels one workgroup of ``mask_confusion`` / ``boundary_counts`` covers (consecutive ones of the whole call)."""
+
+    n = ctypes.c_int()
+    _call("rs_eval_config", ctypes.byref(n))
+    return n.value
+
+
+def _eval_pair(a, b, names, dtype):
+    """The shared argument checks of the two counting calls -> (pointer, pointer, pixels, H*W)."""
+
+    if a.dim() != 3 or a.shape != b.shape:
+        raise ValueError("robosat_amd: {} and {} are both [B, H, W], got {} and {}".format(names[0], names[1], tuple(a.shape), tuple(b.shape)))
+    if a.device != b.device:
+        raise ValueError("robosat_amd: {} and {} are on {} and {}".format(names[0], names[1], a.device, b.device))
+    if a.numel() == 0 or a.numel() >= 1 << 31:
+        raise ValueError("robosat_amd: a call counts 1 to 2^31 - 1 pixels, got {}".format(a.numel()))
+    return _dev(a, names[0], dtype), _dev(b, names[1], dtype), a.numel(), a.shape[1] * a.shape[2]
+
+
+def mask_confusion(predicted_u8, actual_u8, classes, stitched=False):
+    """Two uint8 [B, H, W] class-index rasters -> (int64 [G, C, C], int64 [G]): per tile (G = B), or with ``stitched`` for the one
+    raster the B tiles form (G = 1), ``counts[g][a][p]`` = the pixels with actual == a and predicted == p, and the number of pixels
+    where either value is no class of 0 .. ``classes`` - 1 (they are in no cell).  2 <= ``classes`` <= 8."""
+
+    classes = int(classes)
+    if not 2 <= classes <= EVAL_MAX_CLASSES:
+        raise ValueError("robosat_amd: 2 to {} classes are counted, got {}".format(EVAL_MAX_CLASSES, classes))
+    p, a, pixels, hw = _eval_pair(predicted_u8, actual_u8, ("predicted", "actual"), torch.uint8)
+    groups = 1 if stitched else predicted_u8.shape[0]
+    # (one buffer, `bad` behind `counts`: the library then zeroes both with one fill)
+    both = torch.empty(groups * (classes * classes + 1), device=predicted_u8.device, dtype=torch.int64)
+    counts, bad = both[:groups * classes * classes].view(groups, classes, classes), both[groups * classes * classes:]
+    _call("rs_eval_confusion", p, a, _dev(counts, "counts", torch.int64), _dev(bad, "bad", torch.int64), pixels,
+          pixels if stitched else hw, classes, _stream())
+    return counts, bad
+
+
+def boundary_counts(d2_a, d2_b, d, stitched=False):
+    """Two int32 [B, H, W] rasters of ``distance_transform(mask, d + 1)`` (with ``nbr`` for ``stitched``) -> int64 [G, 3]: per tile,
+    or with ``stitched`` for the one raster the B tiles form, the pixels in the first mask's band, in the second's and in both.  A
+    mask's band is its pixels with 1 <= d2 <= d*d: those within ``d`` pixels of an unset pixel of the raster; the raster's edge is
+    no boundary.  1 <= ``d`` <= 127."""
+
+    d = int(d)
+    if not 1 <= d <= EVAL_MAX_DISTANCE:
+        raise ValueError("robosat_amd: the boundary band's distance is in 1..{}, got {}".format(EVAL_MAX_DISTANCE, d))
+    a, b, pixels, hw = _eval_pair(d2_a, d2_b, ("d2_a", "d2_b"), torch.int32)
+    counts = torch.empty((1 if stitched else d2_a.shape[0], 3), device=d2_a.device, dtype=torch.int64)
+    _call("rs_eval_boundary", a, b, _dev(counts, "counts", torch.int64), pixels, pixels if stitched else hw, d, _stream())
+    return counts

@@ -1,0 +1,213 @@
+"""``rs evaluate``: how good a directory of class-index masks (what ``rs masks`` writes) is against a directory of labels.  Three
+views, all counted on the MI355X (``csrc/evaluate.hip`` and the ``rs features`` raster stages) and divided once on the host
+(``robosat_amd/evaluate.py``):
+
+  * pixels: the confusion matrix ``M[actual][predicted]`` per tile (``ops.mask_confusion``), summed over the tiles; per-class IoU,
+    mIoU, the IoU of class 1, MCC (``robosat_amd.metrics.Metrics``'s expressions) and accuracy.  ``--tiles`` lists the tiles worst
+    first: the list hard negatives are mined from (the reference's ``rs compare --minimum/--maximum``).
+  * outlines (``--type --boundary D``): the Boundary IoU of Cheng et al. 2021 at D pixels, from capped distance transforms of both
+    sides.  The raster's edge is no boundary here (the paper's code pads with zeros): nothing is known beyond it.
+  * objects (``--type``): both sides labelled as they are, the pixels every pair of objects shares tabulated, pairs matched greedily
+    by IoU at ``--match``; predicted, actual, matched, precision, recall, F1.  Per tile an object cut by a tile border counts once per
+    tile; ``--stitch`` evaluates the one sparse raster the tiles of a zoom level form, where it is one object on both sides.
+
+The definitions are in ``include/robosat_hip.h`` and DESIGN.md."""
+
+import argparse
+import json
+import os
+import sys
+
+import torch
+from PIL import Image
+from tqdm import tqdm
+
+from robosat_amd import ops
+from robosat_amd.config import load_config
+from robosat_amd.evaluate import ObjectScores, boundary_report, build_report, tile_rows, write_tile_rows
+from robosat_amd.features import group_clusters, pack_clusters, stitch_tables
+from robosat_amd.tiles import tiles_from_slippy_map
+from robosat_amd.tools.features import _load, _tile_sizes
+
+
+def add_parser(subparser):
+    parser = subparser.add_parser(
+        "evaluate",
+        help="scores segmentation masks against labels: pixels, boundaries and objects",
+        formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+    )
+    parser.add_argument("masks", type=str, help="slippy map directory with segmentation masks (class-index PNGs); its tiles are the set")
+    parser.add_argument("labels", type=str, help="slippy map directory with the labels; a mask tile without a label is skipped and counted")
+    parser.add_argument("--dataset", type=str, required=True, help="path to dataset configuration file")
+    parser.add_argument("out", type=str, help="path to the JSON report")
+    parser.add_argument("--type", type=str, default=None, help="class of the dataset to score boundaries and objects for, and to sort --tiles by")
+    parser.add_argument("--boundary", type=int, default=0, metavar="D",
+                        help="with --type: boundary IoU at D pixels, 0 = off, else 1..127: of each side the pixels of the class within D "
+                        "pixels of a pixel that is not, shared / (predicted + actual - shared). The edge of the raster is not a "
+                        "boundary (nothing is known beyond it; the paper's code pads with zeros), nor with --stitch a seam between two "
+                        "tiles. With --stitch D + 1 pixels must fit the tile's smaller side")
+    parser.add_argument("--match", type=float, default=None, metavar="T",
+                        help="with --type: a predicted and an actual object match where their IoU is at least T, 0 < T <= 1 (0.5 where "
+                        "not given); pairs are taken greedily, best IoU first")
+    parser.add_argument("--min_area", type=int, default=None, metavar="N",
+                        help="with --type: objects with fewer pixels are left out on both sides (0 where not given)")
+    parser.add_argument("--stitch", action="store_true",
+                        help="with --type: objects and boundaries of the one raster the tiles of a zoom level form. Without it objects are "
+                        "per tile: an object cut by a tile border counts once per tile, on both sides")
+    parser.add_argument("--tiles", type=str, default=None, metavar="CSV",
+                        help="path to a CSV with one row per evaluated tile: z, x, y, pixels, the IoU of every class, miou and the share "
+                        "of non-background pixels on each side, sorted worst first by the IoU of --type (by miou without it)")
+    parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
+    parser.set_defaults(func=main)
+
+
+MATCH_DEFAULT = 0.5
+
+
+def validate(args, classes):
+    """Every check that needs no device; ends the run with a message.  Returns (match threshold, min_area)."""
+
+    if not 2 <= len(classes) <= ops.EVAL_MAX_CLASSES:
+        sys.exit("Error: 2 to {} classes are counted, the dataset has {}".format(ops.EVAL_MAX_CLASSES, len(classes)))
+    if args.type is None:
+        for given, flag in ((args.boundary != 0, "--boundary"), (args.match is not None, "--match"), (args.min_area is not None, "--min_area"),
+                            (args.stitch, "--stitch")):
+            if given:
+                sys.exit("Error: {} scores the boundaries or objects of one class: not without --type".format(flag))
+    elif args.type not in classes[1:]:
+        sys.exit("Error: --type must be a non-background class of the dataset ({}), got '{}'".format(", ".join(classes[1:]), args.type))
+    if not 0 <= args.boundary <= ops.EVAL_MAX_DISTANCE:
+        sys.exit("Error: --boundary must be in 1..{} (0 = off), got {}".format(ops.EVAL_MAX_DISTANCE, args.boundary))
+    match = MATCH_DEFAULT if args.match is None else args.match
+    if not 0 < match <= 1:  # (false for nan too)
+        sys.exit("Error: --match is an intersection over union, 0 < T <= 1, got {}".format(match))
+    min_area = 0 if args.min_area is None else args.min_area
+    if min_area < 0:
+        sys.exit("Error: --min_area is a number of pixels, not negative, got {}".format(min_area))
+    if args.batch_size < 1:
+        sys.exit("Error: --batch_size is at least 1, got {}".format(args.batch_size))
+    for name in ("masks", "labels"):
+        if not os.path.isdir(getattr(args, name)):
+            sys.exit("Error: {} is not a directory".format(getattr(args, name)))
+    if args.stitch and args.boundary:  # (the tile sizes are in the PNG headers: no device needed to say this)
+        for h, w in sorted({shape for _, _, shape in _tile_sizes(args.masks)}):
+            if args.boundary + 1 > min(h, w):
+                sys.exit("Error: --boundary {} needs a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
+                         .format(args.boundary, args.boundary + 1, h, w, min(h, w) - 1))
+    return match, min_area
+
+
+def _name(tile):
+    return "{}/{}/{}".format(tile.z, tile.x, tile.y)
+
+
+class Evaluation:
+    """The sums of a run, and the device stages of one batch (tiles on their own) or call (tiles as one sparse raster)."""
+
+    def __init__(self, classes, index, boundary, objects):
+        self.classes, self.index, self.boundary, self.objects = classes, index, boundary, objects
+        n = len(classes)
+        self.matrix = [[0] * n for _ in range(n)]  # Python integers: no bound on the pixels of a run
+        self.band = [0, 0, 0]
+        self.tiles, self.matrices = [], []
+
+    def add(self, tiles, paths, label_paths, shape, device, nbr=None, origin=None):
+        predicted = _load([paths[t] for t in tiles], device)
+        label_files = []
+        for tile in tiles:
+            with Image.open(label_paths[tile]) as image:
+                if (image.size[1], image.size[0]) != tuple(shape):
+                    sys.exit("Error: the label {} of tile {} is {}x{}; its mask is {}x{}".format(label_paths[tile], _name(tile), image.size[1],
+                                                                                              image.size[0], shape[0], shape[1]))
+            label_files.append(label_paths[tile])
+        actual = _load(label_files, device)
+        counts, bad = ops.mask_confusion(predicted, actual, len(self.classes))
+        for tile, wrong in zip(tiles, bad.tolist()):
+            if wrong:
+                sys.exit("Error: tile {} has {} pixels whose value, in the mask or the label, is none of the dataset's {} classes".format(
+                    _name(tile), wrong, len(self.classes)))
+        for tile, matrix in zip(tiles, counts.tolist()):
+            self.tiles.append(tile)
+            self.matrices.append(matrix)
+            for a, row in enumerate(matrix):
+                for p, v in enumerate(row):
+                    self.matrix[a][p] += v
+        if self.index is None:
+            return
+        stitched = nbr is not None
+        # (discs of 0: the class's pixels as they are, on both sides)
+        mask_p, mask_g = ops.clean_masks(predicted, self.index, 0, 0), ops.clean_masks(actual, self.index, 0, 0)
+        if self.boundary:
+            d2_p = ops.distance_transform(mask_p, self.boundary + 1, nbr)
+            d2_g = ops.distance_transform(mask_g, self.boundary + 1, nbr)
+            for row in ops.boundary_counts(d2_p, d2_g, self.boundary, stitched=stitched).tolist():
+                for k in range(3):
+                    self.band[k] += row[k]
+        labels_p, labels_g = ops.label_components(mask_p), ops.label_components(mask_g)
+        if stitched:
+            labels_p, labels_g = ops.stitch_labels(labels_p, nbr, inplace=True), ops.stitch_labels(labels_g, nbr, inplace=True)
+            table_p = ops.component_table_stitched(labels_p, origin, self.objects.min_area)
+            table_g = ops.component_table_stitched(labels_g, origin, self.objects.min_area)
+        else:
+            table_p, table_g = ops.component_table(labels_p, self.objects.min_area), ops.component_table(labels_g, self.objects.min_area)
+        pairs = ops.overlap_table(labels_p, labels_g, stitched=stitched)
+        self.objects.add(table_p.cpu().numpy(), table_g.cpu().numpy(), pairs.cpu().numpy())
+
+
+def main(args):
+    classes = load_config(args.dataset)["common"]["classes"]
+    match, min_area = validate(args, classes)
+    if not torch.cuda.is_available():
+        sys.exit("Error: this build computes on the MI355X only")
+    device = torch.device("cuda", 0)
+    index = None if args.type is None else classes.index(args.type)
+    objects = None if index is None else ObjectScores(match, min_area, args.stitch)
+    run = Evaluation(classes, index, args.boundary, objects)
+
+    label_paths = {tile: path for tile, path in tiles_from_slippy_map(args.labels)}
+    without_label = 0
+    by_shape = {}  # (H, W) -> [tile]: the header gives the size, a tile is decoded when its batch runs
+    paths = {}
+    for tile, path, (height, width) in _tile_sizes(args.masks):
+        if tile not in label_paths:
+            without_label += 1
+            continue
+        if not (1 <= height <= 4096 and 1 <= width <= 4096):
+            sys.exit("Error: {} is {}x{}; tiles are at most 4096x4096".format(path, height, width))
+        paths[tile] = path
+        by_shape.setdefault((height, width), []).append(tile)
+
+    if args.stitch:
+        by_zoom = {}
+        for shape, tiles in by_shape.items():
+            for tile in tiles:
+                by_zoom.setdefault(tile.z, []).append((tile, shape))
+        for z, group in sorted(by_zoom.items()):
+            shapes = sorted({shape for _, shape in group})
+            if len(shapes) > 1:
+                sys.exit("Error: --stitch needs tiles of one size per zoom level; zoom {} has {}".format(
+                    z, ", ".join("{}x{}".format(h, w) for h, w in shapes)))
+            h, w = shape = shapes[0]
+            try:
+                calls = pack_clusters(group_clusters([tile for tile, _ in group]), h * w, side=max(h, w))
+            except ValueError as exc:
+                sys.exit("Error: {}".format(exc))
+            for tiles in tqdm(calls, desc="Evaluate z{} {}x{}".format(z, h, w), unit="call", ascii=True):
+                nbr, origin, _ = stitch_tables(tiles, shape)
+                run.add(tiles, paths, label_paths, shape, device, torch.from_numpy(nbr).to(device), torch.from_numpy(origin).to(device))
+        by_shape = {}
+    for shape, tiles in by_shape.items():  # tiles of one batch share a shape
+        batch = max(1, min(args.batch_size, 65535, ((1 << 29) - 1) // (shape[0] * shape[1])))
+        for start in tqdm(range(0, len(tiles), batch), desc="Evaluate {}x{}".format(*shape), unit="batch", ascii=True):
+            run.add(tiles[start:start + batch], paths, label_paths, shape, device)
+
+    report = build_report(classes, run.matrix, len(run.tiles), without_label, kind=args.type,
+                          objects=None if objects is None else objects.report(),
+                          boundary=boundary_report(args.boundary, run.band) if args.boundary else None)
+    with open(args.out, "w") as fp:
+        json.dump(report, fp, indent=2, allow_nan=False)
+        fp.write("\n")
+    if args.tiles is not None:
+        write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type), classes)
+    if without_label:
+        print("Evaluate: {} mask tiles without a label were skipped".format(without_label), file=sys.stderr)

@@ -42,6 +42,13 @@
            (`--score-leg --stage-loop N`: the two calls on the blob batch and on the bounds N times, for rocprofv3;
            `--score-leg --stage-loop N --phases TRACE.csv`: no device, that run's kernel trace -> median us per launch and phase)
 
+  --evaluate-leg   `rs evaluate`: per batch the counting pass alone (`ops.mask_confusion` and the copy of its counts to the host), with
+           `--boundary 3` and with the object stages, on the blob batch against a copy of it moved by (3, 5) pixels, beside clean ->
+           label -> table -> edges of `rs features` on the same tiles; and the counting call at its bounds (blobs, all one cell,
+           random cells of 8 classes) beside `ops.label_histogram_u8` over the same two rasters, written to
+           profiles/evaluate/bench_evaluate.json (`--evaluate-leg --stage-loop N`: the calls at the three bounds N times, for
+           rocprofv3; `--evaluate-leg --stage-loop N --phases TRACE.csv`: no device, that run's kernel trace -> median us per launch)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -704,6 +711,128 @@ def split_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+EVALUATE_PHASES = ["blobs", "one_cell", "random"]  # (the stage loop's order)
+
+
+def evaluate_phases(path, loop):
+    """The kernel trace of `--evaluate-leg --stage-loop N` (rocprofv3's *_kernel_trace.csv) -> median us per launch of the counting
+    kernels and of the label histogram (its two launches, one per raster, summed) in each of the loop's phases (in the trace in the
+    loop's order; the boundary kernel runs on the blob batch alone)."""
+
+    import csv
+    import statistics
+
+    names = ("eval_confusion_kernel", "eval_boundary_kernel", "label_histogram_kernel")
+    with open(path) as fp:
+        rows = sorted(csv.DictReader(fp), key=lambda r: int(r["Start_Timestamp"]))
+    result = {"loop": loop, "us_per_launch_median": {}}
+    for name in names:
+        times = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if name in r["Kernel_Name"]]
+        phases = EVALUATE_PHASES if name != "eval_boundary_kernel" else EVALUATE_PHASES[:1]
+        per = 2 if name == "label_histogram_kernel" else 1  # (one launch per raster: an iteration's two are summed)
+        if len(times) != per * loop * len(phases):
+            raise SystemExit("{} launches of {} in {}, {} x {} x {} expected".format(len(times), name, path, len(phases), loop, per))
+        times = [sum(times[i:i + per]) for i in range(0, len(times), per)]
+        for i, phase in enumerate(phases):
+            key = name if per == 1 else name + "_both_rasters"
+            result["us_per_launch_median"].setdefault(phase, {})[key] = round(statistics.median(times[i * loop:(i + 1) * loop]), 2)
+    print(json.dumps(result, indent=1, sort_keys=True))
+
+
+def evaluate_leg(args):
+    """`rs evaluate`: the counting pass alone, with the boundary band and with the object stages, beside the polygon stages of
+    `rs features` on the same tiles; and the counting kernel at its bounds beside the label histogram over the same bytes."""
+
+    if args.phases:
+        return evaluate_phases(args.phases, args.stage_loop)
+
+    import torch
+
+    from robosat_amd import ops
+    from robosat_amd.evaluate import match_objects
+
+    size, eps, r, d = args.size, args.eps, args.repeat, args.boundary
+    blobs = blob_masks(args.batch, size, 0)
+    predicted = torch.from_numpy(blobs).to("cuda:0")
+    actual = torch.from_numpy(np.roll(blobs, (3, 5), axis=(1, 2))).to("cuda:0")  # the labels: the same blobs a few pixels away
+    rng = np.random.RandomState(9)
+    bounds = {
+        "blobs": (predicted, actual),
+        "one_cell": (torch.ones_like(predicted), torch.ones_like(predicted)),
+        "random": tuple(torch.from_numpy(rng.randint(0, 8, size=blobs.shape).astype(np.uint8)).to("cuda:0") for _ in range(2)),
+    }
+    classes = {"blobs": 2, "one_cell": 2, "random": 8}
+    hist = torch.zeros(256, dtype=torch.int64, device="cuda:0")
+
+    def confusion():
+        counts, bad = ops.mask_confusion(predicted, actual, 2)
+        return counts.cpu(), bad.cpu()
+
+    def masks():
+        return ops.clean_masks(predicted, 1, 0, 0), ops.clean_masks(actual, 1, 0, 0)
+
+    def boundary():
+        mask_p, mask_g = masks()
+        return confusion(), ops.boundary_counts(ops.distance_transform(mask_p, d + 1), ops.distance_transform(mask_g, d + 1), d).cpu()
+
+    def objects():
+        mask_p, mask_g = masks()
+        labels_p, labels_g = ops.label_components(mask_p), ops.label_components(mask_g)
+        table_p, table_g = ops.component_table(labels_p, 0), ops.component_table(labels_g, 0)
+        pairs = ops.overlap_table(labels_p, labels_g)
+        return confusion(), match_objects(table_p.cpu().numpy(), table_g.cpu().numpy(), pairs.cpu().numpy(), 0.5, False)
+
+    def features():
+        labels = ops.label_components(ops.clean_masks(predicted, 1, eps, eps))
+        table = ops.component_table(labels, 0)
+        return table, ops.boundary_edges(labels, table).cpu()
+
+    if args.stage_loop:
+        for name in EVALUATE_PHASES:  # (in this order in the trace)
+            p, a = bounds[name]
+            for _ in range(args.stage_loop):
+                ops.mask_confusion(p, a, classes[name])
+                ops.label_histogram_u8(p.view(-1), hist)
+                ops.label_histogram_u8(a.view(-1), hist)
+        mask_p, mask_g = masks()
+        d2_p, d2_g = ops.distance_transform(mask_p, d + 1), ops.distance_transform(mask_g, d + 1)
+        for _ in range(args.stage_loop):
+            ops.boundary_counts(d2_p, d2_g, d)
+        torch.cuda.synchronize()
+        return
+
+    labels = ops.label_components(ops.clean_masks(predicted, 1, eps, eps))
+    matched = objects()[1]
+    mask_p, mask_g = masks()
+    labels_p, labels_g = ops.label_components(mask_p), ops.label_components(mask_g)
+    tables = [t.cpu().numpy() for t in (ops.component_table(labels_p, 0), ops.component_table(labels_g, 0), ops.overlap_table(labels_p, labels_g))]
+    result = {"batch": args.batch, "size": size, "eps": eps, "boundary": d, "block_pixels": ops.eval_config(),
+              "objects": {"matched": matched[0], "predicted": matched[1], "actual": matched[2], "pairs": int(len(tables[2]))},
+              "ms_per_batch": {"confusion": timed(confusion, r) * 1e3, "with_boundary": timed(boundary, r) * 1e3,
+                               "with_objects": timed(objects, r) * 1e3, "features_clean_label_table_edges": timed(features, r) * 1e3},
+              "ms_split": {"component_table": timed(lambda: ops.component_table(labels, 0), r) * 1e3,
+                           "mask_confusion_no_copy": timed(lambda: ops.mask_confusion(predicted, actual, 2), r) * 1e3,
+                           "match_objects_on_the_host": timed(lambda: match_objects(tables[0], tables[1], tables[2], 0.5, False), r) * 1e3,
+                           "overlap_table": timed(lambda: ops.overlap_table(labels_p, labels_g), r) * 1e3,
+                           "component_table_unopened": timed(lambda: ops.component_table(labels_p, 0), r) * 1e3},
+              "bounds_us_per_call": {}}
+    result["ms_per_batch"]["confusion_again"] = timed(confusion, r) * 1e3  # (the spread of the same path in the same process)
+    for name in EVALUATE_PHASES:  # (calls enqueued back to back: launch + memsets of the outputs, no copy to the host)
+        p, a = bounds[name]
+        result["bounds_us_per_call"][name] = {
+            "mask_confusion": timed(lambda: ops.mask_confusion(p, a, classes[name]), 10 * r) * 1e6,
+            "label_histogram_u8_both_rasters": timed(lambda: (ops.label_histogram_u8(p.view(-1), hist), ops.label_histogram_u8(a.view(-1), hist)),
+                                                     10 * r) * 1e6,
+        }
+
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "evaluate", "bench_evaluate.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def device_stage(images, eps):
     import torch
 
@@ -753,7 +882,7 @@ def main():
     ap.add_argument("--centerline-leg", action="store_true", help="only thinning and links, on a road network and on its n x n block")
     ap.add_argument("--dedupe-leg", action="store_true", help="only rs features --dedupe: the stages with and without the reference")
     ap.add_argument("--score-leg", action="store_true", help="only rs features --score: the stages with and without the per-component sums")
-    ap.add_argument("--phases", type=str, default=None, help="--score-leg --stage-loop N: the kernel trace of that run, split by phase (no device)")
+    ap.add_argument("--phases", type=str, default=None, help="--score-leg / --evaluate-leg --stage-loop N: the kernel trace of that run, split by phase (no device)")
     ap.add_argument("--width-leg", action="store_true", help="only rs features --width: the distance transform beside the thinning")
     ap.add_argument("--without-only", action="store_true", help="--width-leg: only the stages without the transform")
     ap.add_argument("--max-width", type=int, default=64, help="--width-leg: as --max_width of rs features (radius N // 2 + 2)")
@@ -761,6 +890,8 @@ def main():
     ap.add_argument("--split-leg", action="store_true", help="only rs features --split: the regrowth at every number of fused steps")
     ap.add_argument("--split-radius", type=int, default=8, help="--split-leg: as --split of rs features")
     ap.add_argument("--fused", type=int, default=0, help="--split-leg --stage-loop: the knob grow_fused (0 = the rule)")
+    ap.add_argument("--evaluate-leg", action="store_true", help="only rs evaluate: the counting pass, the boundary band and the object stages")
+    ap.add_argument("--boundary", type=int, default=3, help="--evaluate-leg: as --boundary of rs evaluate")
     ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched legs' block")
     ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
@@ -776,6 +907,8 @@ def main():
         return width_leg(args)
     if args.split_leg:
         return split_leg(args)
+    if args.evaluate_leg:
+        return evaluate_leg(args)
 
     import torch
 
