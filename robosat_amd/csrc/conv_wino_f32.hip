@@ -93,6 +93,13 @@ __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {  // a - b on two flo
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1] neg_hi:[0,1]" : "=v"(d) : "v"(a), "v"(b));
   return d;
 }
+// the lane index computed where it is used (volatile: not hoisted out of the item loop).  Carried from the kernel's entry across the
+// MFMA loops, the thread index behind the gather table's addresses cost the 128 x 64 block a scratch slot and a reload per item.
+__device__ __forceinline__ int wino_lane_now() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
 __device__ __forceinline__ int wino_swz(int row) { return (row ^ (row >> 1)) & 3; }  // 16-byte piece c of a row is stored at c ^ swz(row)
 
 // TG tile groups (16 tiles each) x CG cout groups (32 couts each) = 8 waves per block
@@ -114,13 +121,16 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   constexpr int AROWS = SB * G::SBROWS;
   constexpr int IA = (AROWS + 15) / 16, IB = 9 * BN / 16;
   constexpr int AROWS_PAD = IA * 16;
-  constexpr int NI = (IA + IB + NW - 1) / NW;  // DMA instructions per wave and chunk
+  constexpr int JA = (IA + NW - 1) / NW, JB = (IB + NW - 1) / NW;  // halo / filter pieces per wave and chunk (the last of either: some waves)
+  constexpr int NI = JA + JB;                                     // DMA instructions per wave and chunk
   constexpr int STAGE = (AROWS_PAD + 9 * BN) * 64;
   constexpr int KC = 16;  // channels per chunk (64-byte rows)
 
-  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 2 * AROWS_PAD * 4];
+  constexpr int NTR = (AROWS_PAD + 64 * NW - 1) / (64 * NW);  // gather-table rows per thread
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + 2 * AROWS_PAD * 4 + NTR * 64 * NW * 4];
   int* tabs = reinterpret_cast<int*>(smem + 2 * STAGE);  // [2][AROWS_PAD]: halo row -> source pixel relative to the item's first image, -1 = zeros
 
+  int* trows = tabs + 2 * AROWS_PAD;                     // [NTR][512]: what a thread knows about its table rows, see build_table
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tg = wave % TG, cg = wave / TG;
@@ -131,81 +141,160 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   const int first = rs_xcd_remap(blockIdx.x, gridDim.x);
   // this block walks items first, first + grid, ...; DG: each output item as four consecutive units (the parity planes of dz)
   const int nitems = (ntiles - first + (int)gridDim.x - 1) / (int)gridDim.x * (DG ? 4 : 1);
-  auto item_of = [&](int seq) __attribute__((always_inline)) {  // the (m block, cout block, parity) index of the block's unit `seq`
-    return DG ? (((first + (seq >> 2) * (int)gridDim.x) << 2) | (seq & 3)) : first + seq * (int)gridDim.x;
-  };
   const unsigned int lds0 = __builtin_amdgcn_readfirstlane(rs_lds_addr(smem));
   const long img1 = (long)p.Hs * p.Ws * p.C1 * (DG ? 4 : 1), img2 = (long)p.Hs * p.Ws * p.C2;  // (DG: dz images are 2 Hs x 2 Ws)
 
-  // item -> (parity, m block, cout block)
-  auto decode = [&](int it, int& py, int& px, int& mblk, int& nblk) __attribute__((always_inline)) {
-    py = (it >> 1) & 1;
-    px = it & 1;
-    const int rest = it >> 2;
-    mblk = rest / p.ncb;
-    nblk = rest - mblk * p.ncb;
+  // ---- an item, decoded once: wave-uniform, kept in scalar registers -------------------------------------------------------------
+  // The block's items advance by gridDim.x: parity, and quotient and remainder of the rest by ncb, are carried from item to item, so
+  // the item index is never divided.  Sub-block sb of the item: image n[sb], parity-less halo origin (y0, x0) = (2 PB bby - 1,
+  // 2 PB bbx - 1); the sub-blocks of an item follow each other in (n, bby, bbx) order and may lie in different images.  The table
+  // builder and the fetch side run one item ahead (`nxt`), the epilogue reads the item in the accumulators (`cur`).  The p4 blocks
+  // (4 / 8 sub-blocks of 16 tiles: the small layers, none of them in the benchmark) keep only the first sub-block's index and divide
+  // per sub-block where they need one -- that many scalars would live in memory.
+  constexpr int SBS = SB <= 2 ? SB : 1;
+  struct Item {
+    int py, px, nblk, nfirst, sub0;
+    int n[SBS], y0[SBS], x0[SBS];
+    bool live[SBS];
   };
-  auto build_table = [&](int seq) __attribute__((always_inline)) {  // all threads; visible after the next barrier
-    int py, px, mblk, nblk;
-    decode(item_of(seq), py, px, mblk, nblk);
-    const int sub0 = mblk * SB, nfirst = sub0 / per_img;
-    int* tab = tabs + (seq & 1) * AROWS_PAD;
-    for (int rho = tid; rho < AROWS_PAD; rho += 64 * NW) {
-      int v = -1;
-      if (rho < AROWS) {
-        const int sb = rho / G::SBROWS, rem = rho - sb * G::SBROWS;
-        const int hy = rem / G::PITCH, xs = rem - hy * G::PITCH;
-        const int hx = hy >= G::HW ? -1 : (xs < G::HALF ? 2 * xs : 2 * (xs - G::HALF) + 1);
-        const int sub = sub0 + sb;
-        if (hx >= 0 && sub < p.nsub) {
-          const int n = sub / per_img, r2 = sub - n * per_img;
-          const int bby = r2 / p.BBX, bbx = r2 - bby * p.BBX;
-          const int y = 2 * bby * PB - 1 + py + hy, x = 2 * bbx * PB - 1 + px + hx;
-          if ((unsigned)y < (unsigned)p.Hs && (unsigned)x < (unsigned)p.Ws)
-            v = DG ? ((n - nfirst) * 2 * p.Hs + 2 * y + 1 - py) * (2 * p.Ws) + 2 * x + 1 - px  // plane (1 - py, 1 - px) of dz, pixel (y, x)
-                   : ((n - nfirst) * p.Hs + y) * p.Ws + x;
+  const int uni_first = __builtin_amdgcn_readfirstlane(first), uni_grid = __builtin_amdgcn_readfirstlane((int)gridDim.x);
+  // forward: item = 4 rest + parity, + gridDim.x per item; DG: rest = the output item, + gridDim.x once its four planes are through
+  const int d_step = DG ? uni_grid : uni_grid >> 2, d_parstep = DG ? 1 : uni_grid & 3;
+  int d_par = DG ? 0 : uni_first & 3;
+  int d_mblk = (DG ? uni_first : uni_first >> 2) / p.ncb, d_nblk = (DG ? uni_first : uni_first >> 2) - d_mblk * p.ncb;
+  const int dq = d_step / p.ncb, dr = d_step - dq * p.ncb;
+  auto decode_next = [&](Item& s) __attribute__((always_inline)) {
+    s.py = d_par >> 1;
+    s.px = d_par & 1;
+    if (!DG || d_par == 0) {  // (DG: the four units of an output item share everything but the plane)
+      s.nblk = d_nblk;
+      const int sub0 = s.sub0 = d_mblk * SB;
+      int n = __builtin_amdgcn_readfirstlane(sub0 / per_img);
+      const int r2 = sub0 - n * per_img;
+      int bby = __builtin_amdgcn_readfirstlane(r2 / p.BBX);
+      int bbx = r2 - bby * p.BBX;
+      s.nfirst = n;
+#pragma unroll
+      for (int sb = 0; sb < SBS; ++sb) {
+        s.live[sb] = sub0 + sb < p.nsub;
+        s.n[sb] = n;
+        s.y0[sb] = 2 * bby * PB - 1;
+        s.x0[sb] = 2 * bbx * PB - 1;
+        if (++bbx == p.BBX) {
+          bbx = 0;
+          if (++bby == p.BBY) {
+            bby = 0;
+            ++n;
+          }
         }
       }
-      tab[rho] = v;
+    }
+    d_par += d_parstep;
+    const int carry = d_par >> 2;
+    d_par &= 3;
+    if (!DG || carry) {
+      d_mblk += dq;
+      d_nblk += dr + (DG ? 0 : carry);
+      if (d_nblk >= p.ncb) {
+        d_nblk -= p.ncb;
+        ++d_mblk;
+      }
+    }
+  };
+  Item cur, nxt;
+  decode_next(cur);
+  nxt = cur;
+  // sub-block sb of item s: image, halo origin, liveness
+  auto sub_block = [&](const Item& s, int sb, int& n, int& y0, int& x0, bool& live) __attribute__((always_inline)) {
+    if constexpr (SB <= 2) {
+      const bool one = SB > 1 && sb > 0;
+      n = one ? s.n[SBS - 1] : s.n[0];
+      y0 = one ? s.y0[SBS - 1] : s.y0[0];
+      x0 = one ? s.x0[SBS - 1] : s.x0[0];
+      live = one ? s.live[SBS - 1] : s.live[0];
+    } else {
+      const int sub = s.sub0 + sb;
+      n = sub / per_img;
+      const int r2 = sub - n * per_img, bby = r2 / p.BBX, bbx = r2 - bby * p.BBX;
+      y0 = 2 * bby * PB - 1;
+      x0 = 2 * bbx * PB - 1;
+      live = sub < p.nsub;
+    }
+  };
+
+  // this thread's rows of the gather table: sub-block and halo position (hy, hx) of row rho = tid + 512 e -- item-independent.  Rows
+  // of the padding (no halo pixel) get an hy far outside every image: the bounds test below turns them into -1 like the pixels past
+  // the border.  One word per row, hy << 16 | hx << 8 | sb, parked in LDS (each thread reads back its own): the 128 x 64 block has
+  // no register left for it between two items.
+#pragma unroll
+  for (int e = 0; e < NTR; ++e) {
+    const int rho = tid + 64 * NW * e;
+    const int sb = rho / G::SBROWS, rem = rho - sb * G::SBROWS;
+    const int hy = rem / G::PITCH, xs = rem - hy * G::PITCH;
+    const int hx = xs < G::HALF ? 2 * xs : 2 * (xs - G::HALF) + 1;
+    trows[rho] = ((rho < AROWS && hy < G::HW) ? hy << 16 : -(1 << 28)) | (hx << 8) | sb;
+  }
+  auto build_table = [&](const Item& s, int seq) __attribute__((always_inline)) {  // all threads; visible after the next barrier
+    int* tab = tabs + (seq & 1) * AROWS_PAD;
+    const int tnow = 64 * wave + wino_lane_now();
+#pragma unroll
+    for (int e = 0; e < NTR; ++e) {
+      const int rho = tnow + 64 * NW * e;
+      if (rho < AROWS_PAD) {
+        int n, y0, x0;
+        bool live;
+        const int row = trows[rho];
+        sub_block(s, row & 255, n, y0, x0, live);
+        const int y = y0 + s.py + (row >> 16), x = x0 + s.px + ((row >> 8) & 255);
+        const bool in = live && (unsigned)y < (unsigned)p.Hs && (unsigned)x < (unsigned)p.Ws;
+        const int v = DG ? ((n - s.nfirst) * 2 * p.Hs + 2 * y + 1 - s.py) * (2 * p.Ws) + 2 * x + 1 - s.px  // plane (1 - py, 1 - px) of dz, pixel (y, x)
+                         : ((n - s.nfirst) * p.Hs + y) * p.Ws + x;
+        tab[rho] = in ? v : -1;
+      }
     }
     rs_lds_writes_done();  // (read by every wave behind a later barrier, which hipcc emits bare: common.h)
   };
 
   // ---- fetch side: runs ONE chunk ahead of the MFMAs, across item boundaries (the next item's first chunk streams in while
-  //      this item's outputs are stored).  Instruction ii = wave + NW j copies 16 rows of 64 bytes (4 lanes per row); ii < IA
-  //      halo rows, else filter rows.  Per lane and instruction ONE register: the byte offset for the current item and source.
+  //      this item's outputs are stored).  A piece copies 16 rows of 64 bytes (4 lanes per row).  Piece j of a wave is of the same
+  //      kind in every wave: j < JA halo rows 16 (wave + NW j) .., then filter rows 16 (wave + NW (j - JA)) ..; only the last piece of
+  //      either kind asks whether the wave still has one.  Per lane and halo piece ONE register: the row's byte offset for the
+  //      current item and source (from the gather table).  The filter pieces share one register, the offset of row 16 wave + (lane >> 2)
+  //      = xi * BN + cout for every item: piece j - JA lies 128 rows = 128 / BN positions xi further (same cout, same swizzle), which
+  //      goes into the DMA's scalar offset with the item's cout block and the chunk; the parity's filter set is the descriptor's base.
   const int ra = lane >> 2, pp = lane & 3;
-  int doff[NI];
+  static_assert(128 % BN == 0, "a wave's filter pieces: the same cout, whole positions apart");
+  int doff[JA], doffu;
+  {
+    const int w = 16 * wave + ra, xi = w / BN, co = w - xi * BN;
+    doffu = ((xi * p.Cout + co) * Cin) * 4 + ((pp ^ wino_swz(w)) & 3) * 16;
+  }
+  const int ustep = (128 / BN) * p.Cout * Cin * 4;
   int f_seq = 0, f_kc = 0, f_g = 0;  // item / chunk / global chunk being fetched
-  __amdgpu_buffer_rsrc_t rsrc1 = rs_dma_rsrc<kDmaClamp>(p.src1, 0), rsrc2 = rsrc1, rsrcu = rsrc1;
-  auto fetch_item = [&]() __attribute__((always_inline)) {  // f_seq changed: descriptors and filter offsets of the new item
-    int py, px, mblk, nblk;
-    decode(item_of(f_seq), py, px, mblk, nblk);
-    const int nfirst = __builtin_amdgcn_readfirstlane((mblk * SB) / per_img);
-    rsrc1 = rs_dma_rsrc<kDmaClamp>(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * 4);
-    rsrc2 = rs_dma_rsrc<kDmaClamp>(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * 4);
-    rsrcu = rs_dma_rsrc<kDmaClamp>(p.u + (long)(2 * py + px) * 9 * p.Cout * Cin, (long)9 * p.Cout * Cin * 4);
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-      const int ii = wave + NW * j;
-      if (ii >= IA) {
-        const int w = 16 * (ii - IA) + ra;  // filter row: xi * BN + cout
-        const int xi = w / BN, co = w - xi * BN;
-        doff[j] = ((xi * p.Cout + nblk * BN + co) * Cin) * 4 + ((pp ^ wino_swz(w)) & 3) * 16;
-      }
-    }
+  int f_nb = 0, f_nfirst = 0;        // of item f_seq: byte offset of its cout block's filter rows, first image
+  __amdgpu_buffer_rsrc_t rsrcs = rs_dma_rsrc<kDmaClamp>(p.src1, 0), rsrcu = rsrcs;
+  auto fetch_item = [&](const Item& s) __attribute__((always_inline)) {  // f_seq changed: what the new item's pieces need
+    f_nfirst = s.nfirst;
+    f_nb = s.nblk * BN * Cin * 4;
+    rsrcu = rs_dma_rsrc<kDmaClamp>(p.u + (long)(2 * s.py + s.px) * 9 * p.Cout * Cin, (long)9 * p.Cout * Cin * 4);
   };
   auto set_source = [&](bool src_first) __attribute__((always_inline)) {
     const int cb = (src_first ? p.C1 : p.C2) * 4;
+    rsrcs = rs_dma_rsrc<kDmaClamp>(src_first ? p.src1 + f_nfirst * img1 : p.src2 + f_nfirst * img2,
+                                   (long)(p.N - f_nfirst) * (src_first ? img1 : img2) * 4);
     const int* tab = tabs + (f_seq & 1) * AROWS_PAD;
+    // every table read of the wave first (a row past the wave's share clamped: read, its piece never issued), then the offsets
+    int pix[JA];
 #pragma unroll
-    for (int j = 0; j < NI; ++j) {
+    for (int j = 0; j < JA; ++j) {
       const int ii = wave + NW * j;
-      if (ii < IA) {
-        const int rho = 16 * ii + ra;
-        const int pix = tab[rho];
-        doff[j] = pix < 0 ? kDmaOOB : pix * cb + ((pp ^ wino_swz(rho)) & 3) * 16;
-      }
+      pix[j] = tab[16 * (ii < IA ? ii : IA - 1) + ra];
+    }
+#pragma unroll
+    for (int j = 0; j < JA; ++j) {
+      const int ii = wave + NW * j;
+      const int rho = 16 * (ii < IA ? ii : IA - 1) + ra;
+      doff[j] = pix[j] < 0 ? kDmaOOB : pix[j] * cb + ((pp ^ wino_swz(rho)) & 3) * 16;
     }
   };
   // issue chunk (f_seq, f_kc) into stage f_g & 1, then advance.  Past the block's last chunk (`past`: once, during its very
@@ -215,18 +304,19 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
     const int c0 = f_kc * KC;
     const bool src_first = c0 < p.C1;
     if (!past) {
-      if (f_kc == 0) fetch_item();
+      if (f_kc == 0) fetch_item(nxt);
       if (c0 == 0 || c0 == p.C1) set_source(src_first);
     }
     const unsigned int fL = lds0 + (f_g & 1) * STAGE;
-    const int fsa = (src_first ? c0 : c0 - p.C1) * 4, fsu = c0 * 4;
+    // (readfirstlane: the DMA's scalar offset must be provably uniform -- lds_dma.h)
+    const int fsa = __builtin_amdgcn_readfirstlane((src_first ? c0 : c0 - p.C1) * 4), fsu = __builtin_amdgcn_readfirstlane(c0 * 4 + f_nb);
     interleave([&](int j) __attribute__((always_inline)) {
-      const int ii = wave + NW * j;  // wave-uniform
-      if (ii < IA) {
-        if (src_first) rs_dma16(rsrc1, fL + ii * 1024, doff[j], fsa);
-        else rs_dma16(rsrc2, fL + ii * 1024, doff[j], fsa);
-      } else if (ii < IA + IB) {
-        rs_dma16(rsrcu, fL + ii * 1024, doff[j], fsu);
+      if (j < JA) {
+        const int ii = wave + NW * j;  // wave-uniform
+        if (j < JA - 1 || JA * NW == IA || ii < IA) rs_dma16(rsrcs, fL + ii * 1024, doff[j], fsa);
+      } else {
+        const int fi = wave + NW * (j - JA);
+        if (j < NI - 1 || JB * NW == IB || fi < IB) rs_dma16(rsrcu, fL + (IA + fi) * 1024, doffu, fsu + (j - JA) * ustep);
       }
     });
     ++f_g;
@@ -239,7 +329,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   // ---- fragment addressing (item-independent): lane = tile (lane & 15) of the wave's 16, 16-byte piece (lane >> 4) --------
   const int l15 = lane & 15, pc = lane >> 4;
   const int t = 16 * tg + wino_lane_tile<PB>(l15);
-  const int tsb = t / (PB * PB), tq = t - tsb * (PB * PB);
+  const int tsb = 16 * tg / (PB * PB), tq = t - tsb * (PB * PB);  // (the wave's 16 tiles lie in one sub-block: wave-uniform)
   const int tty = tq / PB, ttx = tq - tty * PB;
   int addrA[3][3];
   {
@@ -255,7 +345,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   // filter rows xi * BN + 32 cg + 16 m + l15: BN and 16 are multiples of 8, so the swizzle only sees l15
   const int addrB = AROWS_PAD * 64 + (16 * NM * cg + l15) * 64 + ((pc ^ wino_swz(l15)) & 3) * 16;  // + (xi * BN + 16 m) * 64
 
-  build_table(0);
+  build_table(cur, 0);
   __syncthreads();
   fetch_chunk([&](auto issue) __attribute__((always_inline)) {
 #pragma unroll
@@ -273,7 +363,16 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   //      MFMA streams.  Stage g & 1 is free for chunk g + 2 once every wave has passed chunk g's barrier (its last reads of the
   //      stage are waited for in front of it), and chunk g + 2 is issued in chunk g + 1's head.  Every accumulator receives the
   //      same MFMAs in the same order from the same transforms as in the unpipelined loop: only issue times moved.
-  constexpr int TAIL = NM >= 4 ? 1 : 2;  // positions behind the barrier: 16 MFMAs to cover every wave's nine patch reads
+  // positions behind the barrier (0: the unpipelined loop -- barrier, patch reads and transform between two chunks' MFMAs).  The
+  // 128 x 64 block needs one: 16 MFMAs cover every wave's nine patch reads.  The NM = 2 forms, 8 MFMAs per position, each keep what
+  // measured fastest (profiles/wino_items/ab_steps.txt): none for 128 x 32 (dec4) and the data gradient, one for 64 x 64 (dec0); the p4
+  // blocks were not measured and keep their two.  (RS_WINO_TAIL2: a measurement build's value for all NM = 2 forms.)
+#ifdef RS_WINO_TAIL2
+  constexpr int TAIL = NM >= 4 ? 1 : RS_WINO_TAIL2;
+#else
+  constexpr int TAIL = NM >= 4 ? 1 : PB == 4 ? 2 : (DG || TG == 8) ? 0 : 1;
+#endif
+  static_assert(TAIL >= 0 && TAIL <= 2, "positions behind the barrier");
   constexpr int NMMA = 36 * NM, NHEAD = (9 - TAIL) * 4 * NM, NT = TAIL * 4 * NM;
   constexpr int PSTEP = 2 * NMMA / 3 / NI >= 1 ? 2 * NMMA / 3 / NI : 1;
   static_assert((NI - 1) * PSTEP < NHEAD, "the DMA pieces go out in the chunk's head");
@@ -371,7 +470,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
       // the next item's gather table (its buffer held item seq - 1's, whose last reader, the fetch of that item's C2 switch, was
       // two barriers ago at the latest); published by the barrier below and first read by the fetch of item seq + 1's chunk 0,
       // in item seq's last chunk -- a later one, since nk >= 2 (wino_plan)
-      if (kc == 0 && seq + 1 < nitems) build_table(seq + 1);
+      if (kc == 0 && seq + 1 < nitems) {
+        decode_next(nxt);
+        build_table(nxt, seq + 1);
+      }
       rs_lds_writes_done();  // (and every LDS read of stage g & 1 by this wave has returned: other waves refill it behind the barrier)
       rs_dma_wait();
       __syncthreads();  // chunk g + 1 is in stage (g + 1) & 1; no wave reads stage g & 1 any more
@@ -386,18 +488,19 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
     }
 
     // ---- Y = A^T M A, ReLU, store: lane = tile l15, couts 32 cg + 16 m + 4 pc + (0..3) -------------------------------------
-    if (DG && (seq & 3) != 3) continue;
-    int py, px, mblk, nblk;
-    decode(item_of(seq), py, px, mblk, nblk);
-    const int sub = mblk * SB + tsb;
+    // (reads `cur`, the item decoded when its table was built: no decode, and at one or two sub-blocks per block no division)
+    int e_n, e_y0, e_x0;
+    bool e_live;
+    sub_block(cur, tsb, e_n, e_y0, e_x0, e_live);
+    // (the lane's tile and cout piece afresh, a few VALU per item: see wino_lane_now)
+    const int e_lane = wino_lane_now(), e_pc = e_lane >> 4;
+    const int e_tq = 16 * tg + wino_lane_tile<PB>(e_lane & 15) - tsb * (PB * PB), e_ty = e_tq / PB, e_tx = e_tq - e_ty * PB;
+    const int a0 = e_y0 + 1 + 2 * e_ty, b0 = e_x0 + 1 + 2 * e_tx;
     if constexpr (DG) {
-      if (sub < p.nsub) {
-        const int n = sub / per_img, r2 = sub - n * per_img;
-        const int bby = r2 / p.BBX, bbx = r2 - bby * p.BBX;
-        const int a0 = 2 * (bby * PB + tty), b0 = 2 * (bbx * PB + ttx);
+      if ((seq & 3) == 3 && e_live) {
         // destination of this wave's couts (block-uniform: a cout block never straddles csplit)
-        const int co = nblk * BN + 16 * NM * cg + 4 * pc;
-        const bool second = p.out2 != nullptr && nblk * BN >= p.csplit;
+        const int co = cur.nblk * BN + 16 * NM * cg + 4 * e_pc;
+        const bool second = p.out2 != nullptr && cur.nblk * BN >= p.csplit;
         float* ob = second ? p.out2 : p.out;
         const float* mb = second ? p.mask2 : p.mask1;
         const int ostride = p.out2 ? (second ? p.Cout - p.csplit : p.csplit) : p.Cout;
@@ -408,7 +511,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
           for (int v = 0; v < 2; ++v) {
             const int a = a0 + u, b = b0 + v;
             if (a >= p.Hs || b >= p.Ws) continue;
-            const long o = ((long)(n * p.Hs + a) * p.Ws + b) * ostride + ocol;
+            const long o = ((long)(e_n * p.Hs + a) * p.Ws + b) * ostride + ocol;
 #pragma unroll
             for (int m = 0; m < NM; ++m) {
               f32x4 y = (acc[u * 3 + v][m] + acc[u * 3 + v + 1][m]) + (acc[(u + 1) * 3 + v][m] + acc[(u + 1) * 3 + v + 1][m]);
@@ -421,20 +524,15 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
             }
           }
       }
-      continue;
-    }
-    if (sub < p.nsub) {
-      const int n = sub / per_img, r2 = sub - n * per_img;
-      const int bby = r2 / p.BBX, bbx = r2 - bby * p.BBX;
-      const int a0 = 2 * (bby * PB + tty), b0 = 2 * (bbx * PB + ttx);
-      float* obase = p.out + nblk * BN + 16 * NM * cg + 4 * pc;
+    } else if (e_live) {
+      float* obase = p.out + cur.nblk * BN + 16 * NM * cg + 4 * e_pc;
 #pragma unroll
       for (int u = 0; u < 2; ++u)
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
           const int a = a0 + u, b = b0 + v;
           if (a >= p.Hs || b >= p.Ws) continue;
-          float* o = obase + ((long)(n * Ho + 2 * a + py) * Wo + 2 * b + px) * p.Cout;
+          float* o = obase + ((long)(e_n * Ho + 2 * a + cur.py) * Wo + 2 * b + cur.px) * p.Cout;
 #pragma unroll
           for (int m = 0; m < NM; ++m) {
             f32x4 y = (acc[u * 3 + v][m] + acc[u * 3 + v + 1][m]) + (acc[(u + 1) * 3 + v][m] + acc[(u + 1) * 3 + v + 1][m]);
@@ -446,6 +544,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
           }
         }
     }
+    cur = nxt;
   }
   rs_dma_wait();  // (the re-issued pieces of the last chunk: landed before this block's LDS is handed to the next one)
 }
