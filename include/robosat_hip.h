@@ -586,6 +586,31 @@ int rs_softvote_masks(const uint8_t* q, const double* weights, const double* anc
 int rs_augment_tiles(const uint8_t* images, const uint8_t* masks, const int32_t* index, const int32_t* op, const float* mean,
                      const float* std, float* out_images, int64_t* out_masks, int N, int S, int C, rs_stream_t stream);
 
+/* Zoom and colour jitter on top of the eight views (csrc/augment.hip; an extension, the `[augment]` table of `rs train`).
+ *
+ * rs_tile_band_sums: sums[t][c] = the sum of band c of tile t of images [T][S][S][C] (uint8 HWC, C <= 4, any base address),
+ * int64 [T][C], overwritten.  Integer arithmetic only: every run gives the same bits.
+ *
+ * rs_augment_tiles_jitter: rs_augment_tiles with, per batch item n, a square window geom[n] = (w, x0, y0) of the source tile
+ * that is enlarged to the S x S frame, and the colour factors color[n] = (brightness, contrast, saturation, gamma).  geom and
+ * color are HOST arrays like mean / std ([N][3] and [N][4]); index, op and band_sums (the sums above, of the same `images`)
+ * are device arrays.  op[n] is undone first, as in rs_augment_tiles, giving (y, x) in the frame; per axis, frame index j reads
+ *   mask (nearest):   source index x0 + ((2j+1)*w) / (2S), integer division;
+ *   image (bilinear, half-pixel centres): t = max((2j+1)*w - S, 0), i0 = t / (2S), f = float(t % (2S)) / float(2S),
+ *                     i1 = min(i0 + 1, w - 1), taps x0 + i0 and x0 + i1; per band on the bytes as floats
+ *                     top = a + fx*(b - a), bot likewise, v = top + fy*(bot - top)   (w = S: i0 = j, f = 0, the byte itself).
+ * Then v = v / 255 and, in fp32, each stage whose factor is not exactly 1.0f, each followed by a clamp to [0, 1]:
+ *   brightness v*b;  contrast m_c + k*(v - m_c), m_c = sums[tile][c] / (S*S*255) (float64 quotient rounded to fp32);
+ *   saturation g + s*(v - g) on bands 0..2 with g = 0.299f*R + 0.587f*G + 0.114f*B, only when `rgb` is set;  gamma powf(v, gamma).
+ * Then (v - mean[c]) / std[c].  All factors 1.0f and w = S: the bits of rs_augment_tiles.
+ * RS_EINVAL: C > 4, S > 16384, w outside [1, S], a window that leaves the tile (x0, y0 outside [0, S - w]), `rgb` with C < 3,
+ * a contrast factor other than 1.0f without band_sums.  masks / out_masks may be NULL together. */
+int rs_tile_band_sums(const uint8_t* images, int64_t* sums, int T, int S, int C, rs_stream_t stream);
+int rs_augment_tiles_jitter(const uint8_t* images, const uint8_t* masks, const int32_t* index, const int32_t* op,
+                            const int32_t* geom, const float* color, const int64_t* band_sums, const float* mean,
+                            const float* std, float* out_images, int64_t* out_masks, int N, int S, int C, int rgb,
+                            rs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * `rs features` (robosat/tools/features.py, robosat/features/core.py): the raster stages on the device
  * (csrc/features.hip).  Batched over B tiles of equal H x W, 1 <= H, W <= 4096, B <= 65535,

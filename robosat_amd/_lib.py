@@ -153,6 +153,10 @@ SIGNATURES = {
     "rs_label_histogram_u8": (c_int, [P, c_long, P, P]),
     "rs_softvote_masks": (c_int, [P, P, P, P, c_int, c_long, c_int, P]),
     "rs_augment_tiles": (c_int, [P, P, P, P, POINTER(c_float), POINTER(c_float), P, P, c_int, c_int, c_int, P]),
+    # zoom and colour jitter of the training feed (csrc/augment.hip)
+    "rs_tile_band_sums": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "rs_augment_tiles_jitter": (c_int, [P, P, P, P, POINTER(c_int32), POINTER(c_float), P, POINTER(c_float), POINTER(c_float), P, P,
+                                        c_int, c_int, c_int, c_int, P]),
     # rs features: raster stages (csrc/features.hip)
     "rs_features_clean_form": (c_int, [c_int, c_int]),
     "rs_features_clean_workspace_bytes": (c_long, [c_int, c_int, c_int]),

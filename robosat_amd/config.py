@@ -1,6 +1,7 @@
 """TOML configuration files (model / dataset), same keys as the reference (``robosat/config.py``, ``config/*.toml``).
 
 Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, loss
+         [augment] zoom, brightness, contrast, saturation, gamma   (extension, optional: robosat_amd/augment.py)
 Dataset: [common] dataset, classes, colors                   [weights] values
 ``cuda = true`` means "use the MI355X" (the HIP device shows up as torch's ``cuda``); ``cuda = false`` is rejected by
 the tools because this implementation has no CPU compute path.

@@ -148,9 +148,12 @@ class UnaugmentedTiles(torch.utils.data.Dataset):
     exactly the pixels its random flips / rotations and ``ToTensor`` + ``Normalize`` start from.  With ``draw=True`` the four
     random numbers of the random part are drawn right here, where the reference's chain draws them (same worker, same order),
     and travel as an op code; the transposes, ``ToTensor`` and ``Normalize`` then run on the device (``rs_augment_tiles``).
-    A tile crosses the DataLoader's queues and PCIe as 1 MiB of bytes instead of 5 MiB of floats + int64 labels."""
+    A tile crosses the DataLoader's queues and PCIe as 1 MiB of bytes instead of 5 MiB of floats + int64 labels.
 
-    def __init__(self, image_dirs, label_dir, size, draw, modes=None):
+    With ``jitter`` (``robosat_amd.augment.Jitter``, the model config's ``[augment]`` table; needs ``draw``) seven more numbers
+    are drawn behind the four and the items are ``(image, mask, op code, window int32 [3], factors float32 [4], tiles)``."""
+
+    def __init__(self, image_dirs, label_dir, size, draw, modes=None, jitter=None):
         super().__init__()
         from .transforms import CenterCrop, ConvertImageMode, Resize
 
@@ -160,7 +163,8 @@ class UnaugmentedTiles(torch.utils.data.Dataset):
         assert len(modes) == len(image_dirs), "one mode per image directory"
         self.to_image = [[ConvertImageMode(m), Resize(target, Image.BILINEAR), CenterCrop(target)] for m in modes]
         self.to_mask = [ConvertImageMode("P"), Resize(target, Image.NEAREST), CenterCrop(target)]
-        self.draw = draw
+        assert jitter is None or draw, "the jitter is drawn where the flips and rotations are"
+        self.draw, self.jitter, self.size = draw, jitter, size
 
     def __len__(self):
         return len(self.source)
@@ -182,6 +186,12 @@ class UnaugmentedTiles(torch.utils.data.Dataset):
         image = torch.from_numpy(np.ascontiguousarray(np.concatenate(planes, axis=2)))
         mask = torch.from_numpy(np.array(mask, dtype=np.uint8))
         code = draw_flip_rotations() if self.draw else 0
+        if self.jitter is not None:
+            from .augment import draw_jitter
+
+            geom, color = draw_jitter(self.jitter, self.size)
+            return (image, mask, code, torch.tensor(geom, dtype=torch.int32), torch.tensor(color, dtype=torch.float32),
+                    [tile for _, tile in tiles_and_images])
         return image, mask, code, [tile for _, tile in tiles_and_images]
 
 
@@ -190,7 +200,7 @@ class DecodedTileCache:
     8f, N4): the items of ``UnaugmentedTiles`` (decoded by ``workers`` DataLoader processes).  A 512x512 RGB tile + its
     mask is 1 MiB: 100 000 tiles fit the MI355X's 288 GB with room to spare, and an epoch then costs no PNG/JPEG decode at all."""
 
-    def __init__(self, image_dirs, label_dir, size, device, workers=0, modes=None):
+    def __init__(self, image_dirs, label_dir, size, device, workers=0, modes=None, band_sums=False):
         source = UnaugmentedTiles(image_dirs, label_dir, size, draw=False, modes=modes)
         images, masks = [], []
         for image, mask, _, _ in torch.utils.data.DataLoader(source, batch_size=64, num_workers=workers):
@@ -201,6 +211,12 @@ class DecodedTileCache:
         self.images = torch.cat(images)  # [T, S, S, C] uint8
         self.masks = torch.cat(masks)    # [T, S, S] uint8
         self.device = device
+        # [T, C] int64, once: the band means of the jitter's contrast stage (only a loader with `[augment]` asks for them)
+        self.band_sums = None
+        if band_sums:
+            from . import ops
+
+            self.band_sums = ops.tile_band_sums(self.images)
 
     def __len__(self):
         return len(self.tiles)
@@ -219,10 +235,14 @@ class HostDecodeLoader:
     it stops being deterministic: ``workers`` processes decode, convert, resize, crop and DRAW (``UnaugmentedTiles``); flip /
     rot90 / ``ToTensor`` / ``Normalize`` run in one kernel on the device.  Yields what the reference's loader yields --
     ``(images [N,C,S,S] fp32 normalised, masks [N,S,S] int64, tiles)`` -- already on the device; same augmentation
-    distribution, same seeded draws per worker as the host chain, bit-equal tensors (tests/test_gpu_tools.py)."""
+    distribution, same seeded draws per worker as the host chain, bit-equal tensors (tests/test_gpu_tools.py).
 
-    def __init__(self, image_dirs, label_dir, size, batch_sampler, workers, device, mean, std, modes=None):
-        self.dataset = UnaugmentedTiles(image_dirs, label_dir, size, draw=True, modes=modes)
+    With ``jitter`` (the ``[augment]`` table) the workers draw the window and the colour factors too, and the one kernel is
+    ``rs_augment_tiles_jitter``, with the band sums of each uploaded batch."""
+
+    def __init__(self, image_dirs, label_dir, size, batch_sampler, workers, device, mean, std, modes=None, jitter=None):
+        self.dataset = UnaugmentedTiles(image_dirs, label_dir, size, draw=True, modes=modes, jitter=jitter)
+        self.jitter = jitter
         self.loader = torch.utils.data.DataLoader(self.dataset, num_workers=workers, pin_memory=True, batch_sampler=batch_sampler)
         self.device, self.mean, self.std = device, list(mean), list(std)
         self.batch_sampler = batch_sampler  # (``set_epoch`` of the sharded sampler is reached through it, as on a DataLoader)
@@ -233,14 +253,20 @@ class HostDecodeLoader:
     def __iter__(self):
         from . import ops
 
-        for images, masks, codes, tiles in self.loader:
+        for item in self.loader:
+            images, masks, codes, tiles = item[0], item[1], item[2], item[-1]
             images = images.to(self.device, non_blocking=True)
             masks = masks.to(self.device, non_blocking=True)
             n, channels = images.shape[0], images.shape[3]
             mean, std = _per_band(self.mean, channels), _per_band(self.std, channels)
             index = torch.arange(n, dtype=torch.int32, device=self.device)
             op = codes.to(torch.int32).to(self.device, non_blocking=True)
-            out, om = ops.augment_tiles(images, masks, index, op, mean, std)
+            if self.jitter is None:
+                out, om = ops.augment_tiles(images, masks, index, op, mean, std)
+            else:
+                geom, color = item[3], item[4]
+                out, om = ops.augment_tiles_jitter(images, masks, index, op, geom, color, ops.tile_band_sums(images), mean, std,
+                                                   self.jitter.rgb)
             yield out, om, tiles
 
 
@@ -250,10 +276,16 @@ class DeviceAugmentLoader:
     transform chain -- horizontal flip with p = 0.5, then three independent 90-degree rotations with p = 0.5 each -- is drawn
     on the host from Python's ``random`` in the reference's order (four numbers per sample), so a seeded run augments every
     sample exactly as the host chain would; flip, rotations, ``ToTensor`` and ``Normalize`` then run in ONE kernel
-    (``rs_augment_tiles``) straight from the cache."""
+    (``rs_augment_tiles``) straight from the cache.
 
-    def __init__(self, cache, batch_sampler, mean, std):
+    With ``jitter`` (the ``[augment]`` table; the cache must hold its band sums) every item draws its four numbers and then the
+    seven of ``robosat_amd.augment.draw_jitter``, as a DataLoader worker of ``HostDecodeLoader`` does, and the one kernel is
+    ``rs_augment_tiles_jitter``."""
+
+    def __init__(self, cache, batch_sampler, mean, std, jitter=None):
         self.cache, self.batch_sampler, self.mean, self.std = cache, batch_sampler, list(mean), list(std)
+        assert jitter is None or cache.band_sums is not None, "a jittering loader needs DecodedTileCache(..., band_sums=True)"
+        self.jitter = jitter
 
     def __len__(self):
         return len(self.batch_sampler)
@@ -267,8 +299,22 @@ class DeviceAugmentLoader:
         channels = c.images.shape[3]
         mean, std = _per_band(self.mean, channels), _per_band(self.std, channels)
         for batch in self.batch_sampler:
-            codes = [self.draw_op() for _ in batch]
+            if self.jitter is None:
+                codes = [self.draw_op() for _ in batch]
+            else:
+                from .augment import draw_jitter
+
+                codes, geom, color = [], [], []
+                for _ in batch:  # per item: the four draws, then the seven
+                    codes.append(self.draw_op())
+                    g, f = draw_jitter(self.jitter, c.size)
+                    geom.append(g)
+                    color.append(f)
             index = torch.tensor(batch, dtype=torch.int32).to(c.device, non_blocking=True)
             op = torch.tensor(codes, dtype=torch.int32).to(c.device, non_blocking=True)
-            images, masks = ops.augment_tiles(c.images, c.masks, index, op, mean, std)
+            if self.jitter is None:
+                images, masks = ops.augment_tiles(c.images, c.masks, index, op, mean, std)
+            else:
+                images, masks = ops.augment_tiles_jitter(c.images, c.masks, index, op, geom, color, c.band_sums, mean, std,
+                                                         self.jitter.rgb)
             yield images, masks, [[c.tiles[i]] for i in batch]

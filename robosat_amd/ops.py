@@ -1384,6 +1384,44 @@ def augment_tiles(images, masks, index, op, mean, std):
     return out, om
 
 
+def tile_band_sums(images):
+    """images uint8 [T,S,S,C] (C <= 4; any slice that is contiguous) -> int64 [T,C]: the sum of every band of every tile, in
+    integers (the band means of the contrast stage of ``augment_tiles_jitter``)."""
+
+    t, s, s2, c = images.shape
+    assert s == s2, "square tiles"
+    sums = torch.empty((t, c), device=images.device, dtype=torch.int64)
+    _call("rs_tile_band_sums", _dev(images, "images", torch.uint8), _dev(sums, "sums", torch.int64), t, s, c, _stream())
+    return sums
+
+
+def augment_tiles_jitter(images, masks, index, op, geom, color, band_sums, mean, std, rgb):
+    """``augment_tiles`` with a zoom-in window and colour factors per item (include/robosat_hip.h): ``geom`` int32 [N,3] =
+    (w, x0, y0) and ``color`` float32 [N,4] = (brightness, contrast, saturation, gamma) are HOST values (tensors or nested
+    lists), ``band_sums`` is ``tile_band_sums(images)`` (None is allowed when no item has a contrast factor), ``rgb`` says
+    that bands 0..2 are R, G, B (saturation runs only then).  Identity parameters give ``augment_tiles`` bit for bit."""
+
+    t, s, s2, c = images.shape
+    assert s == s2, "square tiles (a 90-degree rotation must keep the shape)"
+    n = index.numel()
+    geom = torch.as_tensor(geom, dtype=torch.int32).contiguous()
+    color = torch.as_tensor(color, dtype=torch.float32).contiguous()
+    if geom.is_cuda or color.is_cuda:
+        raise RuntimeError("robosat_amd: `geom` and `color` are host values (the launch checks them and carries them as arguments)")
+    if tuple(geom.shape) != (n, 3) or tuple(color.shape) != (n, 4):
+        raise ValueError("robosat_amd: `geom` must be [N,3] and `color` [N,4] for the N = {} items of `index`".format(n))
+    if band_sums is not None and tuple(band_sums.shape) != (t, c):
+        raise ValueError("robosat_amd: `band_sums` must be [T,C] = [{},{}], the sums of these `images`".format(t, c))
+    out = torch.empty((n, c, s, s), device=images.device, dtype=torch.float32)
+    om = torch.empty((n, s, s), device=images.device, dtype=torch.int64) if masks is not None else None
+    fm, fs = (ctypes.c_float * c)(*mean), (ctypes.c_float * c)(*std)
+    _call("rs_augment_tiles_jitter", _dev(images, "images", torch.uint8), _dev(masks, "masks", torch.uint8),
+          _dev(index, "index", torch.int32), _dev(op, "op", torch.int32), ctypes.cast(geom.data_ptr(), ctypes.POINTER(ctypes.c_int32)),
+          ctypes.cast(color.data_ptr(), ctypes.POINTER(ctypes.c_float)), _dev(band_sums, "band_sums", torch.int64), fm, fs,
+          _dev(out, "out"), _dev(om, "out_masks", torch.int64), n, s, c, int(bool(rgb)), _stream())
+    return out, om
+
+
 # ---- rs features: raster stages (csrc/features.hip; definitions in include/robosat_hip.h) --------------------------------
 CLEAN_AUTO, CLEAN_LDS, CLEAN_HBM = 0, 1, 2
 

@@ -22,6 +22,8 @@ Differences by design:
   * extension keys, all optional: dataset ``[common] image_dirs / image_modes / mean / std`` (band layout: robosat_amd/bands.py;
     default = the reference's one RGB directory), model ``[model] in_channels``, ``compute_dtype``, ``pretrained``,
     ``device_augment``, ``grad_dtype`` (bf16 gradient exchange), ``graph`` (the step as one hipGraph replay).
+  * ``[augment]`` (extension table, optional: robosat_amd/augment.py): a random zoom-in crop and brightness / contrast /
+    saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.
 """
 
 import argparse
@@ -38,6 +40,7 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from robosat_amd import launch, parallel
+from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
 from robosat_amd.config import check_num_classes, load_config
 from robosat_amd.datasets import SlippyMapTilesConcatenation
@@ -117,6 +120,22 @@ def lovasz_softmax_options(model, world):
     return per_image, classes
 
 
+def augment_options(model, dataset):
+    """The ``Jitter`` of the model config's optional ``[augment]`` table (``robosat_amd.augment``), or None without one; exits
+    with ``Error: [augment] <key> ...`` on a bad table, and when the reference's host pipeline is asked for as well: the
+    jitter has a device path only."""
+
+    if "augment" not in model:
+        return None
+    if os.environ.get("ROBOSAT_TRAIN_HOST_PIPELINE", "0") == "1":
+        sys.exit("Error: [augment] runs on the device only and ROBOSAT_TRAIN_HOST_PIPELINE=1 keeps the whole transform chain on "
+                 "the host; unset one of them")
+    try:
+        return jitter_from_config(model, bands_from_config(dataset, model))
+    except ValueError as err:
+        sys.exit("Error: {}".format(err))
+
+
 def main(args):
     model = load_config(args.model)
     dataset = load_config(args.dataset)
@@ -131,6 +150,7 @@ def main(args):
         sys.exit("Error: CUDA requested but not available")
 
     batch_size = model["common"]["batch_size"]
+    jitter = augment_options(model, dataset)  # (a bad `[augment]` table ends here, before any rank starts)
     if not launch.under_launcher():
         # the reference uses every visible GPU (DataParallel, tools/train.py:69): one process per GPU here
         gpus = int(os.environ.get("ROBOSAT_GPUS", torch.cuda.device_count()))
@@ -262,6 +282,8 @@ def main(args):
     say("Loss function:\t {}".format(loss_name))
     if weight is not None:
         say("Weights :\t {}".format(dataset["weights"]["values"]))
+    if jitter is not None:
+        say("Augmentation:\t {}".format(describe_jitter(jitter)))
     say("---")
 
     fmt = "{} loss: {:.4f}, mIoU: {:.3f}, {} IoU: {:.3f}, MCC: {:.3f}"
@@ -462,13 +484,15 @@ class ShardedBatchSampler:
 
 def get_split_loaders(model, dataset, workers, device, rank=0, world=1):
     """The loaders of ``get_dataset_loaders`` with the transform chain split between the DataLoader workers (decode, mode
-    conversion, resize, crop, the random draws) and the device (flip, rotations, ToTensor, Normalize)."""
+    conversion, resize, crop, the random draws) and the device (flip, rotations, ToTensor, Normalize).  The model config's
+    ``[augment]`` table (``robosat_amd.augment``) adds its zoom and colour jitter to the training loader alone."""
     from robosat_amd.datasets import HostDecodeLoader
 
     size = model["common"]["image_size"]
     batch_size = model["common"]["batch_size"] // world
     path = dataset["common"]["dataset"]
     bands = bands_from_config(dataset, model)
+    jitter = jitter_from_config(model, bands)
     seed = int(os.environ.get("ROBOSAT_SEED", "0"))
     loaders = []
     for split, shuffle in (("training", True), ("validation", False)):
@@ -476,26 +500,30 @@ def get_split_loaders(model, dataset, workers, device, rank=0, world=1):
         count = len(SlippyMapTilesConcatenation(images, labels))
         assert count > 0, "at least one tile in {} dataset".format(split)
         sampler = ShardedBatchSampler(count, batch_size, rank, world, shuffle, seed if shuffle else 0)
-        loaders.append(HostDecodeLoader(images, labels, size, sampler, workers, device, bands.mean, bands.std, modes=bands.modes))
+        loaders.append(HostDecodeLoader(images, labels, size, sampler, workers, device, bands.mean, bands.std, modes=bands.modes,
+                                        jitter=jitter if split == "training" else None))
     return loaders
 
 
 def get_device_loaders(model, dataset, device, rank=0, world=1, workers=0):
-    """The loaders of ``get_dataset_loaders`` with the tiles decoded once into HBM and augmented on the device."""
+    """The loaders of ``get_dataset_loaders`` with the tiles decoded once into HBM and augmented on the device; with the
+    model config's ``[augment]`` table the training cache also holds its band sums and the training loader jitters."""
     from robosat_amd.datasets import DecodedTileCache, DeviceAugmentLoader
 
     size = model["common"]["image_size"]
     batch_size = model["common"]["batch_size"] // world
     path = dataset["common"]["dataset"]
     bands = bands_from_config(dataset, model)
+    jitter = jitter_from_config(model, bands)
     seed = int(os.environ.get("ROBOSAT_SEED", "0"))
     loaders = []
     for split, shuffle in (("training", True), ("validation", False)):
+        split_jitter = jitter if split == "training" else None
         cache = DecodedTileCache([os.path.join(path, split, d) for d in bands.dirs], os.path.join(path, split, "labels"), size,
-                                 device, workers, modes=bands.modes)
+                                 device, workers, modes=bands.modes, band_sums=split_jitter is not None)
         assert len(cache) > 0, "at least one tile in {} dataset".format(split)
         sampler = ShardedBatchSampler(len(cache), batch_size, rank, world, shuffle, seed if shuffle else 0)
-        loaders.append(DeviceAugmentLoader(cache, sampler, bands.mean, bands.std))
+        loaders.append(DeviceAugmentLoader(cache, sampler, bands.mean, bands.std, jitter=split_jitter))
     return loaders
 
 
