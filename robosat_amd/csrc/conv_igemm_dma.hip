@@ -371,6 +371,15 @@ bool np_f32_mode(const rs_conv_desc* d, bool phase4, bool plain, bool has_res) {
   return np != 0 && tuning().tile < 0 && !phase4 && plain && rs_conv1x1_np_f32_ok(d) && (np > 0 || (has_res && d->C1 >= 128 && d->C1 <= 512));
 }
 
+// The fixed epilogue kind of an fp32 direct-form EPI_EVAL launch (EK_RT: none -- the run-time path): scale AND shift, both 16-byte
+// aligned (the kernel fetches a thread's four values as one piece), no ReLU mask, one destination; a residual only with ReLU behind it.
+int eval_kind(const float* scale, const float* shift, bool res, bool mask_or_out2, int relu, int epi, bool phase4) {
+  if ((RS_EVAL_TILE_STEPS & 2) == 0 || epi != EPI_EVAL || phase4 || !scale || !shift || mask_or_out2) return EK_RT;
+  if ((((unsigned long)scale | (unsigned long)shift) & 15) != 0) return EK_RT;
+  if (res) return relu ? EK_RES_RELU : EK_RT;
+  return relu ? EK_RELU : EK_AFFINE;
+}
+
 template <typename T>
 int conv_fwd(const rs_conv_desc* d, const void* src1, const void* src2, const void* weight, const float* scale,
              const float* shift, const void* residual, const void* relu_mask, void* out, rs_stream_t stream,
@@ -518,6 +527,18 @@ int conv_fwd(const rs_conv_desc* d, const void* src1, const void* src2, const vo
   a.ntiles = rs_cdiv(d->Cout, kTileBN[tile]);  // the last N tile may be ragged (pick_tile)
   const int grid = rs_cdiv(M, kTileBM[tile]) * a.ntiles * (phase4 ? 4 : 1);
   hipStream_t s = (hipStream_t)stream;
+  if constexpr (sizeof(T) == 4) {
+    // the epilogue's launch-uniform options at compile time, and the table-free prologue of the plain 1x1 launches (conv_epix in
+    // conv_igemm_dma_kernel.h): same tile, same rows, same K order, same arithmetic -- bit-identical to the run-time path, which
+    // keeps every other launch (and every tile the fixed kinds are not instantiated on)
+    const int ek = eval_kind(scale, shift, a.res != nullptr, a.mask != nullptr || out2 != nullptr, d->relu, epi, phase4);
+    if (ek != EK_RT) {
+      const bool fast1 = (RS_EVAL_TILE_STEPS & 4) != 0 && d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->ups == 0 && d->C2 == 0 &&
+                         d->Ho == d->Hs && d->Wo == d->Ws;
+      auto* const kind_launch = ek == EK_AFFINE ? rs_conv_launch_f32_eval_affine : (ek == EK_RELU ? rs_conv_launch_f32_eval_relu : rs_conv_launch_f32_eval_res_relu);
+      if (kind_launch(fast1 ? 1 : 0, tile, kc == kc128 ? 128 : 64, grid, s, a) == 0) return RS_LAUNCH_RESULT();
+    }
+  }
   launch(kc == kc128 ? 128 : 64, phase4, epi, tile, grid, s, a);
   return RS_LAUNCH_RESULT();
 }

@@ -25,6 +25,20 @@ enum Tile { T128x128 = 0, T128x64, T128x32, T64x64, TSTEM_RESERVED, T256x128, T2
 // parity of the DecoderBlock phase form (2x2 taps on the source grid);  HALO_DG4: the 4x4 / stride-2 data gradient of the
 // phase form = four 2x2 convolutions, one per parity plane of dz, accumulated into the same output patch (16 taps).
 enum { HALO_NONE = 0, HALO_33 = 1, HALO_PHASE = 2, HALO_DG4 = 3 };
+// Launch-uniform options of the fp32 direct-form EPI_EVAL launches, at COMPILE time: they ride in the kernel's EPI template value above
+// its low four bits (conv_epix), so that every other instantiation keeps its symbol.
+//   kind (bits 4-7): what the epilogue applies -- EK_RT: whatever the argument block says, tested per row (ReLU mask, two destinations,
+//     no scale: the data gradients); EK_AFFINE: scale + shift; EK_RELU: + ReLU; EK_RES_RELU: + residual, then ReLU (what predict runs).
+//     The three fixed kinds have scale AND shift, 16-byte aligned, and nothing else.
+//   FAST1 (bit 8): 1x1 / stride 1 / pad 0, one source, no upsample: source pixel = output pixel = problem row m, so the block builds no
+//     gather table and reads none back -- its first K-chunk is requested at kernel entry.
+enum { EK_RT = 0, EK_AFFINE = 1, EK_RELU = 2, EK_RES_RELU = 3 };
+constexpr int conv_epix(int epi, int ek, bool fast1) { return epi | (ek << 4) | (fast1 ? 0x100 : 0); }
+// A/B builds (`make EXTRA=-DRS_EVAL_TILE_STEPS=n`, profiles/igemm_eval_tile): bit 0 = a pass's residual pieces and scale / shift in flight
+// early (kernel), bit 1 = the dispatcher picks the fixed kinds, bit 2 = ... and FAST1
+#ifndef RS_EVAL_TILE_STEPS
+#define RS_EVAL_TILE_STEPS 7
+#endif
 
 template <typename T>
 struct ConvArgsT {
@@ -73,6 +87,13 @@ struct ConvArgsT {
 #define RS_CONV_LAUNCHER(name, T) \
   __attribute__((visibility("hidden"))) void name(int tile, int rowb, int grid, hipStream_t s, const ConvArgsT<T>& a)
 RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_eval, float);
+// ... with a fixed epilogue kind (one translation unit per kind; tiles 128x128, 128x64, 128x32 and 64x64 -- what pick_tile answers in
+// fp32 -- at both row sizes, table and FAST1 prologue); 0, or RS_EINVAL for a tile they do not carry
+#define RS_CONV_KIND_LAUNCHER(name) \
+  __attribute__((visibility("hidden"))) int name(int fast1, int tile, int rowb, int grid, hipStream_t s, const ConvArgsT<float>& a)
+RS_CONV_KIND_LAUNCHER(rs_conv_launch_f32_eval_affine);
+RS_CONV_KIND_LAUNCHER(rs_conv_launch_f32_eval_relu);
+RS_CONV_KIND_LAUNCHER(rs_conv_launch_f32_eval_res_relu);
 RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_stats, float);
 RS_CONV_LAUNCHER(rs_conv_launch_f32_plain_bwd, float);
 RS_CONV_LAUNCHER(rs_conv_launch_f32_phase_eval, float);
@@ -194,11 +215,18 @@ constexpr int conv_waves_per_simd(int nw, int bm, int bn, int rowb, int es, int 
 //   EPI_STATS : raw output + per-tile BatchNorm partial sums (sum y, sum y^2): the train-mode forward
 //   EPI_BWD   : residual, ReLU mask, + partial sums (sum g, sum g * xhat) against bn_y: data gradient into a BatchNorm
 //   EPI_SPLITK: a slice of the K loop; the raw fp32 accumulators go to the workspace (ConvArgsT::ws), no epilogue operand
+// EPIX = EPI, or for the fp32 direct-form EPI_EVAL launches conv_epix(EPI_EVAL, kind, FAST1): the epilogue's launch-uniform options and
+// the table-free 1x1 prologue as compile-time values (see EK_* above).  Arithmetic, K order and accumulators do not depend on them.
 // KO (measurement builds only, conv_halo_ko.hip; results are WRONG for KO != 0): knock-outs of the halo main loop that say
 // where its time goes -- 1: no waits / barriers, 2: no DMA, 3: no fragment reads (one set reused), 4: no MFMAs.
-template <typename T, int BM, int BN, int WGM, int WGN, int ROWB, bool PHASE, int EPI, int HALO = HALO_NONE, int KO = 0>
-__global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, BN, ROWB, (int)sizeof(T), EPI, HALO)) void conv_igemm_dma(
+template <typename T, int BM, int BN, int WGM, int WGN, int ROWB, bool PHASE, int EPIX, int HALO = HALO_NONE, int KO = 0>
+__global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, BN, ROWB, (int)sizeof(T), EPIX & 15, HALO)) void conv_igemm_dma(
     const ConvArgsT<T> p) {
+  constexpr int EPI = EPIX & 15;         // EPI_*
+  constexpr int EK = (EPIX >> 4) & 15;   // EK_*: the epilogue's options at compile time (see conv_epix)
+  constexpr bool FAST1 = (EPIX & 0x100) != 0;
+  constexpr bool EARLY = EK != EK_RT && (RS_EVAL_TILE_STEPS & 1) != 0;  // epilogue operands requested early
+  static_assert(EPIX == EPI || (sizeof(T) == 4 && EPI == EPI_EVAL && HALO == HALO_NONE && !PHASE), "fixed kinds / FAST1: the fp32 direct-form EVAL launches");
   static_assert(WGM * WGN == 4 || WGM * WGN == 8, "4 or 8 waves per block");
   static_assert(ROWB == 128 || ROWB == 64, "a K-chunk is a 128- or 64-byte row");
   constexpr int NBUF = 2;  // pipeline buffers (3 and 4 with counted vmcnt waits were measured: no gain)
@@ -285,7 +313,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
     hy0 = ty * PHT;
     hx0 = (rem - ty * p.tpx) * PWD;
   }
-  const int nfirst = HL ? hn : __builtin_amdgcn_readfirstlane(m0 / HdWd);
+  const int nfirst = HL ? hn : (FAST1 ? 0 : __builtin_amdgcn_readfirstlane(m0 / HdWd));
   const int ush = p.ups ? 1 : 0;
   const int upar = p.ups == 2 ? 1 : 0;
   const int pad_y = PHASE ? 1 - py : p.pad, pad_x = PHASE ? 1 - px : p.pad;
@@ -300,7 +328,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
       orow[e] = v;
     }
   }
-  for (int e = tid; e < (HL ? 0 : (p.kh + p.kw + 1) * BM); e += NT) {
+  for (int e = tid; e < ((HL || FAST1) ? 0 : (p.kh + p.kw + 1) * BM); e += NT) {
     const int t = e / BM, row = e - t * BM;
     const int m = m0 + row;
     int v = -1;
@@ -326,8 +354,11 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
 
   const long img1 = (long)p.Hs * p.Ws * p.C1;
   const long img2 = (long)p.Hs * p.Ws * p.C2;
-  const __amdgpu_buffer_rsrc_t rsrc1 = rs_dma_rsrc<kDmaClamp>(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * ES);
-  const __amdgpu_buffer_rsrc_t rsrc2 = rs_dma_rsrc<kDmaClamp>(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * ES);
+  // (FAST1: the descriptor starts at the tile's first row m0 -- no image index, no division -- and ends behind row M - 1)
+  const __amdgpu_buffer_rsrc_t rsrc1 = FAST1 ? rs_dma_rsrc<kDmaClamp>(p.src1 + (long)m0 * p.C1, (long)(p.M - m0) * p.C1 * ES)
+                                             : rs_dma_rsrc<kDmaClamp>(p.src1 + nfirst * img1, (long)(p.N - nfirst) * img1 * ES);
+  const __amdgpu_buffer_rsrc_t rsrc2 =
+      FAST1 ? rsrc1 : rs_dma_rsrc<kDmaClamp>(p.C2 ? p.src2 + nfirst * img2 : p.src1, (long)(p.N - nfirst) * img2 * ES);
   const __amdgpu_buffer_rsrc_t rsrcw =
       rs_dma_rsrc<kDmaClamp>(p.wgt + (long)(2 * py + px) * p.Cout * p.Kw, (long)p.Cout * p.Kw * ES);  // phase weights follow each other
 
@@ -342,7 +373,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   int wrow[NI];                 // byte offset of this lane's piece in weight row (n0 + RI*jj + ra), chunk 0
 #pragma unroll
   for (int j = 0; j < NI; ++j) wrow[j] = ((n0 + RI * (wave + NW * j - IA) + ra) * p.Kw + gp * EPP) * ES;
-  __syncthreads();
+  if constexpr (!FAST1) __syncthreads();  // (FAST1: no table to publish -- nothing stands between kernel entry and the first DMA)
 
   // Per-lane byte offsets of the pixel pieces for the (tap, source) being fetched, chunk 0 of it; kDmaOOB for a padding
   // row.  Rebuilt from the gather tables only when the tap or the concat source changes -- the chunks in between differ
@@ -362,6 +393,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   // (K order = the weights' memory order: taps outer, channel chunks inner.  Channel chunks outer / taps inner was tried
   // for the phase form -- same fabric traffic per launch (FETCH_SIZE), same time -- and dropped: its summation order
   // depends on the chunk size, which depends on the batch, and predictions must not.)
+  if constexpr (FAST1) {  // one tap, one source: the identity map, set once; rows past M fetch zeros
+#pragma unroll
+    for (int j = 0; j < NIA; ++j) {
+      const int row = RI * (wave + NW * j) + ra;
+      pbase[j] = m0 + row < p.M ? row * (p.C1 * ES) + gp * 16 : kDmaOOB;
+    }
+  }
   int lr = 0, ls = 0, lc = 0, lk = 0;
   int nkl = p.nk;  // chunks this block walks
   if constexpr (SPLIT) {
@@ -381,6 +419,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   __amdgpu_buffer_rsrc_t frs = rsrc1;
   int fsa = 0, fsb = 0;
   auto begin_chunk = [&](int buf) __attribute__((always_inline)) {
+    if constexpr (FAST1) {  // chunk lk = channels [lk * KC, + KC) of the only source and of the filter row
+      fL = lds0 + buf * BUF;
+      fsa = fsb = lk * ROWB;
+      ++lk;
+      return;
+    }
     const int c0 = lc * KC;
     const bool first = c0 < p.C1;
     if (lc == 0 || c0 == p.C1) load_tap(pbase, lr, ls, first);  // (uniform) new tap, or the second concat source begins
@@ -438,6 +482,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
 #pragma unroll
     for (int q = 0; q < NI; ++q) issue_piece(q);
   }
+  }
+  // fixed kinds: this thread's four scale / shift values as one 16-byte load each, in flight under the whole K loop (the run-time path
+  // asks for them one dword at a time behind the last MFMA).  A column past Cout (ragged last N tile) reads column 0 and is never stored.
+  f32x4 scv = {1.f, 1.f, 1.f, 1.f}, shv = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (EARLY) {
+    const int ecol = n0 + (tid % (BN / EPP)) * EPP;
+    scv = *reinterpret_cast<const f32x4*>(p.scale + (ecol < p.Cout ? ecol : 0));
+    shv = *reinterpret_cast<const f32x4*>(p.shift + (ecol < p.Cout ? ecol : 0));
   }
   // The pieces of chunk kc+1 are issued BETWEEN the MFMAs of chunk kc (one piece every PSTEP MFMAs from the start of the
   // chunk): an LDS-DMA instruction costs the issuing wave 60-180 cycles, which a burst at the top of the chunk would add
@@ -715,15 +767,20 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   if constexpr (EPI == EPI_EVAL) {
 #pragma unroll
     for (int e = 0; e < EPP; ++e) {
-      sc[e] = (p.scale && cvalid) ? p.scale[col + e] : 1.f;
-      sh[e] = (p.shift && cvalid) ? p.shift[col + e] : 0.f;
+      if constexpr (EARLY) {
+        sc[e] = scv[e % 4];
+        sh[e] = shv[e % 4];
+      } else {
+        sc[e] = (p.scale && cvalid) ? p.scale[col + e] : 1.f;
+        sh[e] = (p.shift && cvalid) ? p.shift[col + e] : 0.f;
+      }
     }
   }
   T* outp = p.out;  // destination of this block's couts (block-uniform: a tile never straddles csplit)
   if constexpr (SPLIT) outp = p.ws;  // rows = (slice, parity, problem row m): see load_group
   const T* maskp = p.mask;
   int ostride = p.Cout, ocol = col;
-  if (EPI == EPI_EVAL && p.out2) {
+  if (EPI == EPI_EVAL && EK == EK_RT && p.out2) {
     if (n0 >= p.csplit) {
       outp = p.out2;
       maskp = p.mask2;
@@ -750,9 +807,16 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
   // row's loads behind the previous row's store (they may alias for all it knows): one HBM round trip per row.  The first
   // group's requests go out BEFORE the accumulators are staged, so their latency overlaps the LDS round trip + barrier.
   constexpr int NIT = WN / (2 * EPP);  // rows per thread per pass = WGM*32 / RPI
-  constexpr int G = (ES == 4 && EPI == EPI_BWD) ? 1 : 2;  // (up to 3 tensors x G x 4 registers of loads in flight per thread)
+  // (EK_RES_RELU: the residual is the only operand -- the whole pass's pieces go out at once, NIT x 4 registers, one exposed round trip
+  // per pass where groups of two leave NIT / 2 - 1 behind the first; a launch with residual AND mask keeps G = 2 on the run-time path)
+  // Where the accumulators take 64 registers -- the 128x128 tile -- half a pass at a time: all eight pieces, with their addresses, went
+  // past the 128 registers of four waves per SIMD (14-20 spilled on 64-byte rows, 140-144 allocated on 128-byte rows).
+  constexpr int GRES = TM * TN * 16 + NIT * EPP > 80 ? NIT / 2 : NIT;
+  constexpr int G = (ES == 4 && EPI == EPI_BWD) ? 1 : ((EARLY && EK == EK_RES_RELU) ? GRES : 2);  // (up to 3 tensors x G x 4 registers of loads in flight per thread)
   static_assert(NIT * RPI == WGM * 32 && NIT % G == 0, "row groups tile the pass");
-  const bool has_res = EPI != EPI_STATS && !SPLIT && p.res != nullptr, has_mask = EPI != EPI_STATS && !SPLIT && maskp != nullptr;
+  const bool has_res = EK != EK_RT ? EK == EK_RES_RELU : (EPI != EPI_STATS && !SPLIT && p.res != nullptr);
+  const bool has_mask = EK == EK_RT && EPI != EPI_STATS && !SPLIT && maskp != nullptr;
+  const bool do_relu = EK != EK_RT ? EK != EK_AFFINE : (EPI == EPI_EVAL && p.relu != 0);
   const bool has_bits = EPI == EPI_BWD && p.mask_bits != nullptr;
   constexpr bool has_bny = EPI == EPI_BWD;
   auto load_group = [&](int tm, int g0, long (&o)[G], bool (&ok)[G], u32x4 (&rr_)[G], u32x4 (&rm_)[G], u32x4 (&ry_)[G])
@@ -761,7 +825,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
     for (int i = 0; i < G; ++i) {
       const int lrow = rr + (g0 + i) * RPI;
       const int row = (lrow >> 5) * WM + 32 * tm + (lrow & 31);  // tile row of pass-local row lrow
-      const int opix = orow[row];
+      const int opix = FAST1 ? (m0 + row < p.M ? m0 + row : -1) : orow[row];
       ok[i] = opix >= 0 && cvalid;
       if constexpr (SPLIT) o[i] = ok[i] ? (((long)ksl * (PHASE ? 4 : 1) + (2 * py + px)) * p.M + m0 + row) * p.Cout + col : 0;
       else o[i] = ok[i] ? (long)opix * ostride + ocol : 0;
@@ -814,7 +878,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, conv_waves_per_simd(WGM * WGN, BM, 
 #pragma unroll
         for (int e = 0; e < EPP; ++e) v[e] += r[e];
       }
-      if (EPI == EPI_EVAL && p.relu) {
+      if (do_relu) {
 #pragma unroll
         for (int e = 0; e < EPP; ++e) v[e] = fmaxf(v[e], 0.f);
       }
@@ -923,6 +987,19 @@ void launch_rows(int tile, int grid, hipStream_t s, const ConvArgsT<T>& a) {
   }
 }
 
+// fixed epilogue kinds of the fp32 direct form (conv_epix): the four tiles pick_tile answers in fp32
+template <int ROWB, int EK, bool FAST1>
+int launch_eval_kind(int tile, int grid, hipStream_t s, const ConvArgsT<float>& a) {
+  constexpr int X = conv_epix(EPI_EVAL, EK, FAST1);
+  switch (tile) {
+    case T128x128: conv_igemm_dma<float, 128, 128, 2, 2, ROWB, false, X><<<grid, 256, 0, s>>>(a); return 0;
+    case T128x64: conv_igemm_dma<float, 128, 64, 2, 2, ROWB, false, X><<<grid, 256, 0, s>>>(a); return 0;
+    case T128x32: conv_igemm_dma<float, 128, 32, 4, 1, ROWB, false, X><<<grid, 256, 0, s>>>(a); return 0;
+    case T64x64: conv_igemm_dma<float, 64, 64, 2, 2, ROWB, false, X><<<grid, 256, 0, s>>>(a); return 0;
+    default: return RS_EINVAL;
+  }
+}
+
 // split K (EPI_SPLITK): the 64x64 tile -- the launches that want it are the ones too small to fill the chip with any other
 template <int ROWB, bool PHASE>
 void launch_splitk(int grid, hipStream_t s, const ConvArgsT<float>& a) {
@@ -946,6 +1023,11 @@ void launch_halo(int bn, int grid, hipStream_t s, const ConvArgsT<bf16_t>& a) {
   void name(int tile, int rowb, int grid, hipStream_t s, const ConvArgsT<T>& a) {               \
     if (rowb == 128) launch_rows<T, 128, PHASE, EPI>(tile, grid, s, a);                         \
     else launch_rows<T, 64, PHASE, EPI>(tile, grid, s, a);                                      \
+  }
+#define RS_CONV_DEFINE_KIND_LAUNCHER(name, EK)                                                                    \
+  int name(int fast1, int tile, int rowb, int grid, hipStream_t s, const ConvArgsT<float>& a) {                   \
+    if (fast1) return rowb == 128 ? launch_eval_kind<128, EK, true>(tile, grid, s, a) : launch_eval_kind<64, EK, true>(tile, grid, s, a);  \
+    return rowb == 128 ? launch_eval_kind<128, EK, false>(tile, grid, s, a) : launch_eval_kind<64, EK, false>(tile, grid, s, a);           \
   }
 #define RS_CONV_DEFINE_SPLITK_LAUNCHER(name, PHASE)                                              \
   void name(int, int rowb, int grid, hipStream_t s, const ConvArgsT<float>& a) {                \
