@@ -284,10 +284,12 @@ void launch(int rowb, bool phase4, int epi, int tile, int grid, hipStream_t s, c
 
 // Which all-taps kernel of conv_thin_bf16.hip runs this bf16 launch (-1: none): the 32-channel decoder tail, plain epilogue
 // (ReLU / ReLU mask only).  A forced igemm tile (rs_conv2d_set_tuning) keeps the generic kernel, for tests and A/B runs.
-int thin_mode(const rs_conv_desc* d, bool phase4, bool plain_epilogue) {
+// `has_mask`: the launch carries a ReLU mask -- the phase kernel has no mask input (the forward DecoderBlock never has one), so
+// such a launch keeps the generic kernel instead of losing its mask.
+int thin_mode(const rs_conv_desc* d, bool phase4, bool plain_epilogue, bool has_mask) {
   const int ft = tuning().tile;
   if (!plain_epilogue || (ft != -1 && ft != TTHIN) || d->C2 != 0) return -1;
-  if (phase4) return (d->C1 == 128 && d->Cout == 32) ? 1 : -1;
+  if (phase4) return (!has_mask && d->C1 == 128 && d->Cout == 32) ? 1 : -1;
   if (d->ups != 0) return -1;
   if (d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && d->C1 == 32 && d->Cout == 32 && d->Ho == d->Hs && d->Wo == d->Ws) return 0;
   if (d->kh == 4 && d->kw == 4 && d->stride == 2 && d->pad == 1 && d->C1 == 32 && d->Cout == 128 && 2 * d->Ho == d->Hs && 2 * d->Wo == d->Ws)
@@ -395,7 +397,7 @@ int conv_fwd(const rs_conv_desc* d, const void* src1, const void* src2, const vo
   if (d->C2 > 0 && !src2) return RS_EINVAL;
   constexpr long ES = (long)sizeof(T);
   if constexpr (sizeof(T) == 2) {
-    const int tm = thin_mode(d, phase4, !scale && !shift && !residual && !stats && !out2);
+    const int tm = thin_mode(d, phase4, !scale && !shift && !residual && !stats && !out2, relu_mask != nullptr);
     if (tm >= 0) {
       const int rc = rs_conv_thin_bf16_launch(tm, src1, weight, relu_mask, out, d->N, d->Hs, d->Ws, d->relu, stream);
       if (rc != RS_EINVAL) return rc;  // (RS_EINVAL: the launch does not fit its 32-bit offsets -> generic kernel)
@@ -572,7 +574,7 @@ extern "C" int rs_conv2d_config(const rs_conv_desc* d, int es, int form, int* ti
   if (!valid(d) || (es != 2 && es != 4) || (phase4 && !phase_ok(d))) return RS_EINVAL;
   const int kc128 = 128 / es;
   const bool can128 = d->C1 % kc128 == 0 && d->C2 % kc128 == 0;
-  if (es == 2 && thin_mode(d, phase4 != 0, true) >= 0) {  // (as for a launch with a plain epilogue)
+  if (es == 2 && thin_mode(d, phase4 != 0, true, !plain) >= 0) {  // (as for a launch with a plain epilogue, or with a ReLU mask)
     if (tile) *tile = TTHIN;
     if (rowb) *rowb = d->C1 * 2;
     return 0;

@@ -415,7 +415,7 @@ def conv2d_phase(src1, weight_phase, src2=None, scale=None, shift=None, residual
               _dev(relu_mask, "relu_mask", act), _dev(out, "out", act), _stream())
     if ev:
         _stop(ev)
-        _record(ev, conv_tile_name(d, act == BF16, phase=True) if ws is None else _splitk_name(ws, ws_rowb, phase=True), conv_flops(d), _shape(d),
+        _record(ev, conv_tile_name(d, act == BF16, phase=True, plain=relu_mask is None) if ws is None else _splitk_name(ws, ws_rowb, phase=True), conv_flops(d), _shape(d),
                 conv_bytes(d, _esize(act), (residual is not None) + (relu_mask is not None)) + (0 if ws is None else 8 * ws.numel()),
                 conv_flops(d) * 4.0 / 9.0)
     return out
@@ -721,7 +721,8 @@ def conv1x1_wave(x, w, scale, shift, residual=None, relu=False):
 def conv_tile_name(d, bf16=False, phase=False, plain=True):
     """Report name of the kernel a convolution launch runs, 1:1 with the launched symbol:
     ``conv_igemm_<f32|bf16><[phase,]BMxBN,r<row bytes>>`` (or the stem kernel).  ``plain=False``: a launch with fused
-    BatchNorm statistics / a ReLU mask (never the plain-epilogue 1x1 kernel of conv1x1_ew_f32.hip)."""
+    BatchNorm statistics / a ReLU mask / two destinations: never the plain-epilogue 1x1 kernel of conv1x1_ew_f32.hip, and in bf16 never
+    the thin phase kernel, which has no mask input -- a 128 -> 32 phase launch is then reported as the generic tile that runs it."""
 
     lib = _lib.lib()
     if d.stem:
