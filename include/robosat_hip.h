@@ -209,6 +209,42 @@ long rs_lovasz_softmax_workspace_bytes(int N, int C, int H, int W, int per_image
 int rs_lovasz_softmax_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out, int N,
                           int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream);
 
+/* The five losses above with an IGNORE LABEL: `ignore` is a label value that is no class, C <= ignore <= 255 (RS_EINVAL otherwise;
+ * the label rasters are bytes).  Each entry point is its base signature plus `int ignore`, with the base call's workspace.  The loss
+ * is the base definition evaluated on the VALID pixels only (targets != ignore): as if the ignored pixels had been cut out of every
+ * image and the rest packed together in their (n, h, w) order.  Labels >= C other than `ignore` are undefined, as in the base calls.
+ *   - rs_nll_loss_*_ig: loss = sum_valid w l / sum_valid w; stats[1] is that denominator.  A denominator of 0 (no valid pixel, or
+ *     only classes of weight 0) gives loss 0 and gradient 0, not NaN.
+ *   - rs_miou_loss_*_ig: the soft-IoU sums of each (class, image) run over the valid pixels; an image with no valid pixel has ratio 1
+ *     in every class (no loss, no gradient) and the mean stays over C*N terms.  The NLL term is as above; the max(miou, nll) branch
+ *     and the stats layout are the base call's.
+ *   - rs_lovasz_fwd_ig: per image the sort runs over the C*K entries of its K valid pixels with gts = K; an image with K = 0
+ *     contributes 0; the divisor stays N.
+ *   - rs_lovasz_softmax_fwd_ig: a segment holds valid pixels only and the present classes are judged on them; per image, an image
+ *     with no valid pixel contributes 0 and the divisor stays N; flattened, no valid pixel at all gives 0.  Equal errors stay in
+ *     ascending pixel index.  probs_out still receives the softmax of every pixel.
+ * In all of them d loss / d logits is exactly +0.0f in every class plane of an ignored pixel, the label of an ignored pixel never
+ * indexes `weight`, and for finite logits neither loss nor gradient depends on the logits at ignored pixels (non-finite logits
+ * under ignored pixels are not shielded in the two Lovasz forms, whose softmax / sort still see them).  With no pixel ignored the
+ * results are the base calls' bit for bit.  The fixed divisors (N, C*N) and the exchanged normaliser stats[1] are what the
+ * data-parallel exchange of robosat_amd/losses.py rests on: it is unchanged.
+ * In the two Lovasz forms an ignored pixel's entries get a key behind every valid key (error -inf / -1) and label bit 0: the stable
+ * sort puts them in the tail of their segment, where they change no prefix count, add 0 to the loss and get gradient 0; each
+ * segment's gts is counted from its label bits.  No host synchronisation: every call can be captured into a graph. */
+int rs_nll_loss_fwd_ig(const float* logits, const long long* targets, const float* weight, float* loss, float* stats, int N,
+                       int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream, int ignore);
+int rs_nll_loss_bwd_ig(const float* logits, const long long* targets, const float* weight, const float* stats,
+                       const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                       rs_stream_t stream, int ignore);
+int rs_miou_loss_fwd_ig(const float* logits, const long long* targets, const float* weight, float* loss, float* stats, int N,
+                        int C, int H, int W, void* workspace, rs_stream_t stream, int ignore);
+int rs_miou_loss_bwd_ig(const float* logits, const long long* targets, const float* weight, const float* stats,
+                        const float* grad_out, float* dlogits, int N, int C, int H, int W, rs_stream_t stream, int ignore);
+int rs_lovasz_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C, int H, int W,
+                     void* workspace, rs_stream_t stream, int ignore);
+int rs_lovasz_softmax_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out, int N,
+                             int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream, int ignore);
+
 /* Metrics.add over a whole batch (metrics.py:27-41): counts[0..3] += (tn, fn, fp, tp) in the reference's naming. */
 int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C, int H,
                         int W, rs_stream_t stream);
@@ -879,6 +915,13 @@ int rs_eval_config(int* block_pixels);
 int rs_eval_confusion(const uint8_t* predicted, const uint8_t* actual, int64_t* counts, int64_t* bad, long pixels, long group, int C,
                       rs_stream_t stream);
 int rs_eval_boundary(const int32_t* d2_a, const int32_t* d2_b, int64_t* counts, long pixels, long group, int D, rs_stream_t stream);
+
+/* rs_eval_confusion with an ignore label, C <= ignore <= 255: a pixel whose ACTUAL byte equals `ignore` over a predicted byte that
+ * is a class lies in no cell and is counted in ignored[g] (int64 [G], set by the call, 8-byte aligned) instead of bad[g].  A
+ * predicted byte >= C is bad whatever lies under it; so is an actual byte >= C other than `ignore`.  One fill where
+ * bad == counts + G*C*C and ignored == bad + G, three otherwise. */
+int rs_eval_confusion_ig(const uint8_t* predicted, const uint8_t* actual, int64_t* counts, int64_t* bad, int64_t* ignored, long pixels,
+                         long group, int C, rs_stream_t stream, int ignore);
 
 #ifdef __cplusplus
 }

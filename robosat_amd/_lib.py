@@ -71,6 +71,13 @@ SIGNATURES = {
     "rs_lovasz_softmax_workspace_bytes": (c_long, [c_int, c_int, c_int, c_int, c_int]),
     "rs_lovasz_softmax_fwd": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rs_confusion_counts": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    # the same losses over the pixels whose label is not `ignore` (the base signature + int ignore)
+    "rs_nll_loss_fwd_ig": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, c_int]),
+    "rs_nll_loss_bwd_ig": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, c_int]),
+    "rs_miou_loss_fwd_ig": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int]),
+    "rs_miou_loss_bwd_ig": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int]),
+    "rs_lovasz_fwd_ig": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int]),
+    "rs_lovasz_softmax_fwd_ig": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int]),
     # bf16 path (activations typed by a dtype code / bf16 entry points)
     "rs_conv2d_fwd_bf16": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "rs_conv2d_tile_bf16": (c_int, [POINTER(ConvDesc)]),
@@ -188,6 +195,7 @@ SIGNATURES = {
     "rs_eval_config": (c_int, [POINTER(c_int)]),
     "rs_eval_confusion": (c_int, [P, P, P, P, c_long, c_long, c_int, P]),
     "rs_eval_boundary": (c_int, [P, P, P, c_long, c_long, c_int, P]),
+    "rs_eval_confusion_ig": (c_int, [P, P, P, P, P, c_long, c_long, c_int, P, c_int]),
 }
 
 _lib = None

@@ -3,6 +3,7 @@
 Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, loss
          [augment] zoom, brightness, contrast, saturation, gamma   (extension, optional: robosat_amd/augment.py)
 Dataset: [common] dataset, classes, colors                   [weights] values
+         [common] ignore   (extension, optional: the label value of pixels that carry no class, ``ignore_label`` below)
 ``cuda = true`` means "use the MI355X" (the HIP device shows up as torch's ``cuda``); ``cuda = false`` is rejected by
 the tools because this implementation has no CPU compute path.
 """
@@ -22,6 +23,22 @@ def check_num_classes(num_classes, tool):
     hi = MAX_CLASSES_PREDICT if tool == "predict" else MAX_CLASSES_TRAIN
     if not MIN_CLASSES <= num_classes <= hi:
         raise ValueError("rs {} handles {}..{} classes; the dataset config lists {}".format(tool, MIN_CLASSES, hi, num_classes))
+
+
+def ignore_label(dataset):
+    """The dataset config's optional ``[common] ignore``: the label byte of pixels that carry none of the classes (nodata, unmapped
+    ground, "don't know").  ``rs train`` leaves them out of the loss, ``rs weights`` out of the counts and ``rs evaluate`` out of the
+    pixel scores.  Returns ``None`` without the key; raises ``ValueError`` unless it is an integer with
+    ``len(classes) <= ignore <= 255`` (a label tile holds bytes, and a class index cannot be ignored)."""
+
+    common = dataset["common"]
+    if "ignore" not in common:
+        return None
+    value, num_classes = common["ignore"], len(common["classes"])
+    if isinstance(value, bool) or not isinstance(value, int) or not num_classes <= value <= 255:
+        raise ValueError("[common] ignore must be an integer in {}..255 (no class index of the {} classes, and a byte), got {}".format(
+            num_classes, num_classes, _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)))
+    return value
 
 
 def load_config(path):

@@ -200,3 +200,96 @@ extern "C" int rs_eval_boundary(const int32_t* d2_a, const int32_t* d2_b, int64_
                                                                             group, (unsigned int)(D * D));
   return RS_LAUNCH_RESULT();
 }
+
+// ---- confusion matrix per group with an ignore label (rs_eval_confusion_ig) ----------------------------------------------------
+// eval_confusion_kernel with one more bin behind `bad`: a pixel whose ACTUAL byte equals `ignore` (>= C) and whose predicted byte
+// is a class lies in no cell and is counted in ignored[g].  A predicted byte >= C is bad whatever lies under it, and so is an
+// actual byte >= C other than `ignore`.  The kernel above is left as it is.
+namespace {
+
+constexpr int kEvalIgnored = kEvalBad + 1;
+constexpr int kEvalBinsIg = kEvalIgnored + 1;
+
+__global__ __launch_bounds__(kEvalThreads) void eval_confusion_ig_kernel(const uint8_t* __restrict__ predicted, const uint8_t* __restrict__ actual,
+                                                                         unsigned long long* __restrict__ counts,
+                                                                         unsigned long long* __restrict__ bad,
+                                                                         unsigned long long* __restrict__ ignored, long pixels, long group,
+                                                                         int C, unsigned int ignore) {
+  __shared__ unsigned int hist[4][kEvalBinsIg];
+  const long block0 = (long)blockIdx.x * kEvalBlock;
+  const long base = block0 + (long)threadIdx.x * kEvalRun;
+  unsigned int cells[4] = {0, 0, 0, 0};  // 16 cells, a byte each
+  if (base < pixels) {
+    unsigned int pw[4], aw[4];
+    eval_load_bytes(predicted, base, pixels, pw);
+    eval_load_bytes(actual, base, pixels, aw);
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j) {
+      const unsigned int p = (pw[j >> 2] >> ((j & 3) * 8)) & 255u, a = (aw[j >> 2] >> ((j & 3) * 8)) & 255u;
+      const unsigned int cell = p >= (unsigned int)C ? (unsigned int)kEvalBad
+                                : a == ignore        ? (unsigned int)kEvalIgnored
+                                : a >= (unsigned int)C ? (unsigned int)kEvalBad
+                                                       : a * C + p;
+      cells[j >> 2] |= cell << ((j & 3) * 8);
+    }
+  }
+  const long block1 = block0 + kEvalBlock < pixels ? block0 + kEvalBlock : pixels;
+  const long g0 = block0 / group, g1 = (block1 - 1) / group;
+  unsigned int* h = hist[threadIdx.x >> 6];
+  const int cc = C * C;
+  for (long g = g0; g <= g1; ++g) {
+    for (int i = threadIdx.x; i < 4 * kEvalBinsIg; i += kEvalThreads) (&hist[0][0])[i] = 0;
+    __syncthreads();
+    int jlo, jhi;
+    eval_range(base, g, group, pixels, jlo, jhi);
+    unsigned int cur = 0, run = 0;
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j) {
+      if (j >= jlo && j < jhi) {
+        const unsigned int cell = (cells[j >> 2] >> ((j & 3) * 8)) & 255u;
+        if (run && cell != cur) {
+          atomicAdd(&h[cur], run);
+          run = 0;
+        }
+        cur = cell;
+        ++run;
+      }
+    }
+    if (run) atomicAdd(&h[cur], run);
+    __syncthreads();
+    if (threadIdx.x < kEvalBinsIg) {
+      const int t = threadIdx.x;
+      const unsigned int tot = hist[0][t] + hist[1][t] + hist[2][t] + hist[3][t];
+      if (tot) {
+        if (t == kEvalIgnored)
+          atomicAdd(&ignored[g], (unsigned long long)tot);
+        else if (t == kEvalBad)
+          atomicAdd(&bad[g], (unsigned long long)tot);
+        else if (t < cc)
+          atomicAdd(&counts[g * cc + t], (unsigned long long)tot);
+      }
+    }
+    __syncthreads();  // (the next group zeroes the histograms)
+  }
+}
+
+}  // namespace
+
+extern "C" int rs_eval_confusion_ig(const uint8_t* predicted, const uint8_t* actual, int64_t* counts, int64_t* bad, int64_t* ignored,
+                                    long pixels, long group, int C, rs_stream_t stream, int ignore) {
+  if (!predicted || !actual || !counts || !bad || !ignored || (((uintptr_t)counts | (uintptr_t)bad | (uintptr_t)ignored) & 7) ||
+      !eval_shape_ok(pixels, group) || C < 2 || C > 8 || ignore < C || ignore > 255)
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long groups = pixels / group;
+  // (one fill where `bad` and `ignored` follow `counts` directly, as ops.mask_confusion lays them out)
+  const bool joined = bad == counts + groups * C * C && ignored == bad + groups;
+  hipError_t e = hipMemsetAsync(counts, 0, groups * (C * C + (joined ? 2 : 0)) * sizeof(int64_t), s);
+  if (e == hipSuccess && !joined) e = hipMemsetAsync(bad, 0, groups * sizeof(int64_t), s);
+  if (e == hipSuccess && !joined) e = hipMemsetAsync(ignored, 0, groups * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  eval_confusion_ig_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(
+      predicted, actual, reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<unsigned long long*>(bad),
+      reinterpret_cast<unsigned long long*>(ignored), pixels, group, C, (unsigned int)ignore);
+  return RS_LAUNCH_RESULT();
+}

@@ -420,3 +420,318 @@ extern "C" int rs_miou_loss_bwd(const float* logits, const long long* targets, c
   hipStream_t s = (hipStream_t)stream;
   RS_DISPATCH_C(C, run_miou_bwd<K>(logits, targets, weight, stats, grad_out, dlogits, N, HW, s));
 }
+
+// ---- the same losses over the pixels whose label is not `ignore` (rs_*_ig in include/robosat_hip.h) -----------------------------
+// The loss of the valid pixels alone, as if the ignored ones had been cut out of every image: an ignored pixel has no weight, no
+// loss and a gradient of +0.0f in every class plane, its label byte never indexes `weight`, and its logits reach no result.  The
+// kernels above are left as they are (the same instructions as before, profiles/ignore_label/asm_identity.txt); these are their
+// copies with the one compare per pixel, so that with no pixel ignored they do the same arithmetic in the same order.
+namespace {
+
+bool ignore_ok(int ignore, int C) { return ignore >= C && ignore <= 255; }
+
+template <int C>
+__global__ __launch_bounds__(256) void nll_fwd_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                         const float* __restrict__ weight, double* __restrict__ partial,
+                                                         long P, long HW, int mode, float gamma, int ignore) {
+  __shared__ double red[2][4];
+  double sl = 0, sw = 0;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
+    const int t = (int)tgt[p];
+    if (t == ignore) continue;
+    const long n = p / HW, hw = p - n * HW;
+    float v[C];
+    load_logits<C>(x, n, hw, HW, v);
+    const float w = weight ? weight[t] : 1.f;
+    const float l = pixel_loss<C>(v, t, mode, gamma, nullptr);
+    sl += (double)(w * l);
+    sw += (double)w;
+  }
+  sl = rs_wave_sum(sl);
+  sw = rs_wave_sum(sw);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][wave] = sl;
+    red[1][wave] = sw;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    partial[blockIdx.x * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+// nll_finalize_kernel; no valid weight at all (sum(w) == 0) gives loss 0, and stats[1] = 0 tells the backward
+__global__ void nll_finalize_ig_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss,
+                                       float* __restrict__ stats) {
+  __shared__ double red[2][256];
+  double sl = 0, sw = 0;
+  for (int b = threadIdx.x; b < nblocks; b += 256) {
+    sl += partial[b * 2];
+    sw += partial[b * 2 + 1];
+  }
+  red[0][threadIdx.x] = sl;
+  red[1][threadIdx.x] = sw;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + o];
+      red[1][threadIdx.x] += red[1][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float l = red[1][0] > 0.0 ? (float)(red[0][0] / red[1][0]) : 0.f;
+    loss[0] = l;
+    stats[0] = l;
+    stats[1] = (float)red[1][0];
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void nll_bwd_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                         const float* __restrict__ weight, const float* __restrict__ stats,
+                                                         const float* __restrict__ gout, float* __restrict__ dx, long P, long HW,
+                                                         int mode, float gamma, int ignore) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const long n = p / HW, hw = p - n * HW;
+  const int t = (int)tgt[p];
+  if (t == ignore || !(stats[1] > 0.f)) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
+    return;
+  }
+  float v[C], g[C];
+  load_logits<C>(x, n, hw, HW, v);
+  const float w = weight ? weight[t] : 1.f;
+  pixel_loss<C>(v, t, mode, gamma, &g);
+  const float k = (gout ? gout[0] : 1.f) * w / stats[1];
+#pragma unroll
+  for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = k * g[c];
+}
+
+template <int C>
+int run_fwd_ig(const float* x, const long long* t, const float* w, float* loss, float* stats, double* part, long P, long HW,
+               int mode, float gamma, int ignore, hipStream_t s) {
+  const long nb = (P + 255) / 256;
+  const int grid = nb < kLossBlocks ? (int)nb : kLossBlocks;
+  nll_fwd_ig_kernel<C><<<grid, 256, 0, s>>>(x, t, w, part, P, HW, mode, gamma, ignore);
+  nll_finalize_ig_kernel<<<1, 256, 0, s>>>(part, grid, loss, stats);
+  return RS_LAUNCH_RESULT();
+}
+
+template <int C>
+int run_bwd_ig(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, long P,
+               long HW, int mode, float gamma, int ignore, hipStream_t s) {
+  nll_bwd_ig_kernel<C><<<rs_cdiv(P, 256), 256, 0, s>>>(x, t, w, stats, gout, dx, P, HW, mode, gamma, ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+// miou_partial_kernel over the valid pixels: A, B, cnt and the two NLL sums all leave an ignored pixel out
+template <int C>
+__global__ __launch_bounds__(256) void miou_partial_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                              const float* __restrict__ weight, double* __restrict__ partial,
+                                                              long HW, int nblk, int ignore) {
+  __shared__ double red[4][3 * C + 2];
+  const long n = blockIdx.y;
+  double acc[3 * C + 2];
+#pragma unroll
+  for (int i = 0; i < 3 * C + 2; ++i) acc[i] = 0;
+  for (long hw = (long)blockIdx.x * 256 + threadIdx.x; hw < HW; hw += (long)nblk * 256) {
+    const int t = (int)tgt[n * HW + hw];
+    if (t == ignore) continue;
+    float v[C];
+    load_logits<C>(x, n, hw, HW, v);
+    float mx = v[0];
+#pragma unroll
+    for (int c = 1; c < C; ++c) mx = fmaxf(mx, v[c]);
+    float e[C], sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      e[c] = expf(v[c] - mx);
+      sum += e[c];
+    }
+    float xt = 0.f;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+      const float sc = e[c] / sum;
+      acc[c] += (c == t) ? (double)sc : 0.0;
+      acc[C + c] += (double)sc;
+      acc[2 * C + c] += (c == t) ? 1.0 : 0.0;
+      xt = (c == t) ? v[c] : xt;
+    }
+    const float w = weight ? weight[t] : 1.f;
+    acc[3 * C] += (double)(w * ((logf(sum) + mx) - xt));
+    acc[3 * C + 1] += (double)w;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < 3 * C + 2; ++i) {
+    const double s = rs_wave_sum(acc[i]);
+    if (lane == 0) red[wave][i] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 * C + 2) {
+    const int i = threadIdx.x;
+    partial[(n * nblk + blockIdx.x) * (3 * C + 2) + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+  }
+}
+
+// miou_finalize_kernel with the stats layout kept.  An image with no valid pixel (sum_c cnt == 0) has ratio 1 and coefficients 0
+// in every class -- no loss, no gradient -- and the mean stays over C * N terms; sum(w) == 0 gives nll = 0.
+__global__ void miou_finalize_ig_kernel(const double* __restrict__ partial, int N, int C, int nblk, float* __restrict__ loss,
+                                        float* __restrict__ stats) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int S = 3 * C + 2;
+  double sl = 0, sw = 0, rsum = 0;
+  for (int n = 0; n < N; ++n) {
+    // (one walk over the image's partials, as in miou_finalize_kernel: this thread is alone and every read is a round trip)
+    double A[kMaxC], B[kMaxC], cnt[kMaxC], valid = 0;
+    for (int c = 0; c < C; ++c) {
+      A[c] = B[c] = cnt[c] = 0;
+      for (int b = 0; b < nblk; ++b) {
+        const double* p = partial + ((long)n * nblk + b) * S;
+        A[c] += p[c];
+        B[c] += p[C + c];
+        cnt[c] += p[2 * C + c];
+      }
+      valid += cnt[c];
+    }
+    for (int c = 0; c < C; ++c) {
+      if (valid == 0) {
+        rsum += 1.0;
+        stats[3 + n * C + c] = 0.f;
+        stats[3 + N * C + n * C + c] = 0.f;
+        continue;
+      }
+      const double U = B[c] + cnt[c] - A[c];
+      rsum += A[c] / U;
+      const double k = 1.0 / ((double)C * (double)N);
+      stats[3 + n * C + c] = (float)(-k / U);
+      stats[3 + N * C + n * C + c] = (float)(k * A[c] / (U * U));
+    }
+    for (int b = 0; b < nblk; ++b) {
+      const double* p = partial + ((long)n * nblk + b) * S;
+      sl += p[3 * C];
+      sw += p[3 * C + 1];
+    }
+  }
+  const float miou = (float)(1.0 - rsum / ((double)C * (double)N));
+  const float nll = sw > 0.0 ? (float)(sl / sw) : 0.f;
+  const bool use_nll = nll > miou;
+  loss[0] = use_nll ? nll : miou;
+  stats[0] = loss[0];
+  stats[1] = (float)sw;
+  stats[2] = use_nll ? 1.f : 0.f;
+  stats[3 + 2 * N * C] = miou;
+  stats[4 + 2 * N * C] = (float)sl;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void miou_bwd_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                          const float* __restrict__ weight, const float* __restrict__ stats,
+                                                          const float* __restrict__ gout, float* __restrict__ dx, int N, long HW,
+                                                          int ignore) {
+  const long hw = (long)blockIdx.x * 256 + threadIdx.x;
+  const long n = blockIdx.y;
+  if (hw >= HW) return;
+  const int t = (int)tgt[n * HW + hw];
+  if (t == ignore) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
+    return;
+  }
+  float v[C], g[C];
+  load_logits<C>(x, n, hw, HW, v);
+  const float go = gout ? gout[0] : 1.f;
+  if (stats[2] > 0.5f) {
+    const float w = weight ? weight[t] : 1.f;
+    pixel_loss<C>(v, t, 0, 0.f, &g);
+    const float k = go * w / stats[1];
+#pragma unroll
+    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = k * g[c];
+    return;
+  }
+  float mx = v[0];
+#pragma unroll
+  for (int c = 1; c < C; ++c) mx = fmaxf(mx, v[c]);
+  float sum = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    v[c] = expf(v[c] - mx);
+    sum += v[c];
+  }
+  float dot = 0.f;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    v[c] = v[c] / sum;
+    g[c] = (c == t) ? stats[3 + n * C + c] : stats[3 + N * C + n * C + c];
+    dot += g[c] * v[c];
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = go * v[c] * (g[c] - dot);
+}
+
+template <int C>
+int run_miou_fwd_ig(const float* x, const long long* t, const float* w, float* loss, float* stats, double* part, int N, long HW,
+                    int ignore, hipStream_t s) {
+  const long nb = (HW + 255) / 256;
+  const int nblk = nb < kMiouBlocks ? (int)nb : kMiouBlocks;
+  miou_partial_ig_kernel<C><<<dim3(nblk, N), 256, 0, s>>>(x, t, w, part, HW, nblk, ignore);
+  miou_finalize_ig_kernel<<<1, 64, 0, s>>>(part, N, C, nblk, loss, stats);
+  return RS_LAUNCH_RESULT();
+}
+
+template <int C>
+int run_miou_bwd_ig(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, int N,
+                    long HW, int ignore, hipStream_t s) {
+  miou_bwd_ig_kernel<C><<<dim3(rs_cdiv(HW, 256), N), 256, 0, s>>>(x, t, w, stats, gout, dx, N, HW, ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+}  // namespace
+
+extern "C" int rs_nll_loss_fwd_ig(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
+                                  int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream,
+                                  int ignore) {
+  if (!logits || !targets || !loss || !stats || !workspace || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
+      mode < 0 || mode > 1 || !ignore_ok(ignore, C))
+    return RS_EINVAL;
+  const long HW = (long)H * W, P = (long)N * HW;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(workspace);
+  RS_DISPATCH_C(C, run_fwd_ig<K>(logits, targets, weight, loss, stats, part, P, HW, mode, gamma, ignore, s));
+}
+
+extern "C" int rs_nll_loss_bwd_ig(const float* logits, const long long* targets, const float* weight, const float* stats,
+                                  const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                                  rs_stream_t stream, int ignore) {
+  if (!logits || !targets || !stats || !dlogits || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || mode < 0 || mode > 1 ||
+      !ignore_ok(ignore, C))
+    return RS_EINVAL;
+  const long HW = (long)H * W, P = (long)N * HW;
+  hipStream_t s = (hipStream_t)stream;
+  RS_DISPATCH_C(C, run_bwd_ig<K>(logits, targets, weight, stats, grad_out, dlogits, P, HW, mode, gamma, ignore, s));
+}
+
+extern "C" int rs_miou_loss_fwd_ig(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
+                                   int N, int C, int H, int W, void* workspace, rs_stream_t stream, int ignore) {
+  if (!logits || !targets || !loss || !stats || !workspace || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
+      !ignore_ok(ignore, C))
+    return RS_EINVAL;
+  const long HW = (long)H * W;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(workspace);
+  RS_DISPATCH_C(C, run_miou_fwd_ig<K>(logits, targets, weight, loss, stats, part, N, HW, ignore, s));
+}
+
+extern "C" int rs_miou_loss_bwd_ig(const float* logits, const long long* targets, const float* weight, const float* stats,
+                                   const float* grad_out, float* dlogits, int N, int C, int H, int W, rs_stream_t stream,
+                                   int ignore) {
+  if (!logits || !targets || !stats || !dlogits || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || !ignore_ok(ignore, C))
+    return RS_EINVAL;
+  const long HW = (long)H * W;
+  hipStream_t s = (hipStream_t)stream;
+  RS_DISPATCH_C(C, run_miou_bwd_ig<K>(logits, targets, weight, stats, grad_out, dlogits, N, HW, ignore, s));
+}

@@ -863,3 +863,331 @@ extern "C" int rs_lovasz_softmax_fwd(const float* logits, const long long* targe
   lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, S * cv.nblk_scan, 1.f, loss);
   return RS_LAUNCH_RESULT();
 }
+
+// ---- both Lovasz losses over the pixels whose label is not `ignore` (rs_lovasz_fwd_ig, rs_lovasz_softmax_fwd_ig) ----------------
+// The loss of the valid pixels alone, as if the ignored ones had been cut out of every image and the rest packed in (n, h, w)
+// order.  The sort, the scans and the workspace are the ones above; the kernels above are left as they are (the same
+// instructions as before: profiles/ignore_label/asm_identity.txt).  An ignored pixel's C entries get a key that sorts strictly
+// behind every valid key -- an error of -inf in the hinge form (valid errors are finite), of -1 in the softmax form (valid errors
+// lie in [0, 1]) -- and label bit 0.  The sort is stable, so they form the TAIL of their segment and the valid entries keep the
+// order, the ranks and the label prefix counts they would have without them: every valid rank keeps its delta.  Each segment's
+// gts is its number of set label bits, which only valid pixels have (in the hinge form: one per valid pixel, so gts = K of the
+// image where the kernel above has H*W).  The apply kernels add 0 to the loss for a tail entry and write +0.0f as its gradient.
+// With no pixel ignored every kernel here does the arithmetic of its twin above in the same order: the same bits.
+namespace {
+
+constexpr float kIgnoredSoftmaxErr = -1.f;
+
+__global__ void lovasz_keys_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt, uint32_t* __restrict__ keys,
+                                      uint32_t* __restrict__ vals, long P, long HW, int ignore) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long n = blockIdx.y;
+  if (i >= P) return;
+  const long c = i / HW, hw = i - c * HW;
+  const long long t = tgt[n * HW + hw];
+  const uint32_t m = (t == c) ? 1u : 0u;
+  const float v = x[n * P + i];
+  const float err = (t == ignore) ? -INFINITY : 1.f - (m ? v : -v);
+  keys[n * P + i] = desc_key(err);
+  vals[n * P + i] = (uint32_t)i | (m << 31);
+}
+
+__global__ __launch_bounds__(256) void lovasz_keys4_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long P, long HW,
+                                                              int ignore) {
+  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  const long n = blockIdx.y;
+  if (i >= P) return;
+  const long c = i / HW, hw = i - c * HW;  // (HW % 4 == 0: the four elements share the class plane)
+  const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * P + i);
+  const lv_i64x2 t0 = *reinterpret_cast<const lv_i64x2*>(tgt + n * HW + hw), t1 = *reinterpret_cast<const lv_i64x2*>(tgt + n * HW + hw + 2);
+  const long long t[4] = {t0[0], t0[1], t1[0], t1[1]};
+  lv_u32x4 k, w;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const uint32_t m = (t[e] == c) ? 1u : 0u;
+    const float err = (t[e] == ignore) ? -INFINITY : 1.f - (m ? v[e] : -v[e]);
+    k[e] = desc_key(err);
+    w[e] = (uint32_t)(i + e) | (m << 31);
+  }
+  *reinterpret_cast<lv_u32x4*>(keys + n * P + i) = k;
+  *reinterpret_cast<lv_u32x4*>(vals + n * P + i) = w;
+}
+
+// the four sorted entries of a thread of the apply kernels (ranks r0 .. r0 + 3 of segment n); returns their label count
+__device__ __forceinline__ uint32_t lovasz_load4(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, long n, long P,
+                                                 long r0, uint32_t (&lab)[4], uint32_t (&key)[4], uint32_t (&idx)[4]) {
+  uint32_t s = 0;
+  if ((P & 3) == 0 && r0 + 3 < P) {
+    const lv_u32x4 v = *reinterpret_cast<const lv_u32x4*>(vals + n * P + r0), k = *reinterpret_cast<const lv_u32x4*>(keys + n * P + r0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lab[e] = v[e] >> 31;
+      idx[e] = v[e] & 0x7fffffffu;
+      key[e] = k[e];
+      s += lab[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      lab[e] = 0;
+      key[e] = 0;
+      idx[e] = 0;
+      if (r0 + e < P) {
+        const uint32_t v = vals[n * P + r0 + e];
+        lab[e] = v >> 31;
+        idx[e] = v & 0x7fffffffu;
+        key[e] = keys[n * P + r0 + e];
+      }
+      s += lab[e];
+    }
+  }
+  return s;
+}
+
+// lovasz_apply_kernel with gts = the image's number of valid pixels (gts_px[n], from lovasz_softmax_scan_blocks_kernel)
+__global__ __launch_bounds__(256) void lovasz_apply_ig_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                              const uint32_t* __restrict__ boff, const uint32_t* __restrict__ gts_px,
+                                                              double* __restrict__ partial, float* __restrict__ grad, long P,
+                                                              int nblk, float inv_n, int xcd_affine) {
+  __shared__ uint32_t sm[4];
+  __shared__ double red[4];
+  long n = blockIdx.y;
+  int bx = blockIdx.x;
+  if (xcd_affine) {
+    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    const int x = (int)(L & 7);
+    const long k = L >> 3;
+    n = x + 8 * (k / nblk);
+    bx = (int)(k % nblk);
+  }
+  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
+  uint32_t lab[4], key[4], idx[4];
+  const uint32_t s = lovasz_load4(keys, vals, n, P, r0, lab, key, idx);
+  uint32_t total;
+  uint32_t cs = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
+  const float gts = (float)gts_px[n];
+  double acc = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long r = r0 + e;
+    if (r < P) {
+      const float cs_prev = (float)cs;
+      cs += lab[e];
+      const float cs_inc = (float)cs;
+      const float jac = 1.f - (gts - cs_inc) / (gts + ((float)(r + 1) - cs_inc));
+      float delta = jac;
+      if (r > 0) {
+        const float jac_p = 1.f - (gts - cs_prev) / (gts + ((float)r - cs_prev));
+        delta = jac - jac_p;
+      }
+      const float err = key_to_float(key[e]);
+      // (the tail has err = -inf: not above 0, like every valid entry inside its margin -- no loss term, gradient +0.0f)
+      const float pos = err > 0.f ? err : 0.f;
+      if (err > 0.f) acc += (double)(pos * delta);
+      if (grad) {
+        const float g = err > 0.f ? delta : 0.f;
+        grad[n * P + idx[e]] = (lab[e] ? -g : g) * inv_n;
+      }
+    }
+  }
+  acc = rs_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[n * nblk + bx] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <int VEC>
+__global__ __launch_bounds__(256) void lovasz_softmax_keys_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
+                                                                     float* __restrict__ probs, long NHW, long HW, int C, int per_image,
+                                                                     int ignore) {
+#pragma clang fp contract(off)
+  const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (q >= NHW) return;
+  const long n = q / HW, hw = q - n * HW;
+  const float* xp = x + n * C * HW + hw;
+  float mx[VEC], sum[VEC], v[VEC], pr[VEC];
+  lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
+  long long t[VEC];
+  if constexpr (VEC == 4) {
+    const lv_i64x2 t0 = *reinterpret_cast<const lv_i64x2*>(tgt + q), t1 = *reinterpret_cast<const lv_i64x2*>(tgt + q + 2);
+    t[0] = t0[0]; t[1] = t0[1]; t[2] = t1[0]; t[3] = t1[1];
+  } else {
+    t[0] = tgt[q];
+  }
+  const uint32_t pos = (uint32_t)(per_image ? hw : q);
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+    uint32_t k[VEC], w[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+      pr[e] = lvs_prob(v[e], mx[e], sum[e]);
+      const uint32_t m = (t[e] == c) ? 1u : 0u;
+      k[e] = desc_key(t[e] == ignore ? kIgnoredSoftmaxErr : m ? 1.f - pr[e] : pr[e]);
+      w[e] = (pos + (uint32_t)e) | (m << 31);
+    }
+    const long o = lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image);
+    if constexpr (VEC == 4) {
+      *reinterpret_cast<lv_u32x4*>(keys + o) = lv_u32x4{k[0], k[1], k[2], k[3]};
+      *reinterpret_cast<lv_u32x4*>(vals + o) = lv_u32x4{w[0], w[1], w[2], w[3]};
+    } else {
+      keys[o] = k[0];
+      vals[o] = w[0];
+    }
+    if (probs) lvs_write<VEC>(probs + (n * C + c) * HW + hw, pr);
+  }
+}
+
+// lovasz_softmax_apply_kernel; a tail entry (negative error) adds nothing and gets dL/dp = +0.0f, whatever its delta
+__global__ __launch_bounds__(256) void lovasz_softmax_apply_ig_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                                      const uint32_t* __restrict__ boff, const uint32_t* __restrict__ gts,
+                                                                      const double* __restrict__ w, double* __restrict__ partial,
+                                                                      float* __restrict__ gp, long P, int nblk, int xcd_affine) {
+  __shared__ uint32_t sm[4];
+  __shared__ double red[4];
+  long n = blockIdx.y;  // the segment
+  int bx = blockIdx.x;
+  if (xcd_affine) {
+    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    const long k = L >> 3;
+    n = (L & 7) + 8 * (k / nblk);
+    bx = (int)(k % nblk);
+  }
+  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
+  uint32_t lab[4], key[4], idx[4];
+  const uint32_t s = lovasz_load4(keys, vals, n, P, r0, lab, key, idx);
+  uint32_t total;
+  long long k = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
+  const long long g = gts[n];
+  const double ws = w[n];
+  double acc = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const long long r = r0 + e;
+    if (r < P) {
+      const long long Ip = g - k, Up = g + r - k;  // I_{r-1}, U_{r-1}
+      k += lab[e];
+      const long long I = g - k, U = g + r + 1 - k;
+      const double delta = r == 0 ? 1.0 / (double)U : (double)(Ip * U - I * Up) / (double)(U * Up);
+      const float err = key_to_float(key[e]);
+      const bool tail = err < 0.f;
+      if (!tail) acc += (double)err * delta;
+      if (gp) gp[n * P + idx[e]] = tail ? 0.f : (float)(ws * (lab[e] ? -delta : delta));
+    }
+  }
+  acc = rs_wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[n * nblk + bx] = ws * ((red[0] + red[1]) + (red[2] + red[3]));
+}
+
+// lovasz_softmax_jacobian_kernel; +0.0f in every class plane of an ignored pixel
+template <int VEC>
+__global__ __launch_bounds__(256) void lovasz_softmax_jacobian_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                                         const float* __restrict__ gp, float* __restrict__ grad, long NHW,
+                                                                         long HW, int C, int per_image, int ignore) {
+  const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  if (q >= NHW) return;
+  const long n = q / HW, hw = q - n * HW;
+  const float* xp = x + n * C * HW + hw;
+  float mx[VEC], sum[VEC], v[VEC], gv[VEC], out[VEC];
+  bool skip[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) skip[e] = tgt[q + e] == ignore;
+  lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
+  double dot[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) dot[e] = 0.0;
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+    lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) dot[e] += (double)lvs_prob(v[e], mx[e], sum[e]) * (double)gv[e];
+  }
+  for (int c = 0; c < C; ++c) {
+    lvs_load<VEC>(xp + c * HW, v);
+    lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e)
+      out[e] = skip[e] ? 0.f : (float)((double)lvs_prob(v[e], mx[e], sum[e]) * ((double)gv[e] - dot[e]));
+    lvs_write<VEC>(grad + (n * C + c) * HW + hw, out);
+  }
+}
+
+}  // namespace
+
+extern "C" int rs_lovasz_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C,
+                                int H, int W, void* workspace, rs_stream_t stream, int ignore) {
+  if (!logits || !targets || !loss || !workspace || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (long)C * H * W >= (1L << 31) ||
+      ignore < C || ignore > 255)
+    return RS_EINVAL;
+  const Carve cv = carve(N, C, H, W);
+  char* ws = reinterpret_cast<char*>(workspace);
+  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
+  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
+  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
+  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
+  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
+  double* partial = reinterpret_cast<double*>(ws + cv.partial);
+  hipStream_t s = (hipStream_t)stream;
+  const long P = cv.P, HW = (long)H * W;
+  const int sc_affine = (N % 8 == 0 && N >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
+
+  if ((HW & 3) == 0) lovasz_keys4_ig_kernel<<<dim3(rs_cdiv(P / 4, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW, ignore);
+  else lovasz_keys_ig_kernel<<<dim3(rs_cdiv(P, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW, ignore);
+  radix_sort_segments(k0, v0, k1, v1, counts, N, cv, sc_affine, s);
+  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(v0, bsum, P, cv.nblk_scan);
+  // the sort is done with its digit counts (at least 256 words per image): their first N words take the images' valid pixel
+  // counts, so the workspace is rs_lovasz_workspace_bytes' as it stands
+  uint32_t* gts_px = counts;
+  lovasz_softmax_scan_blocks_kernel<<<N, 256, 0, s>>>(bsum, gts_px, cv.nblk_scan);
+  const float inv_n = 1.f / (float)N;
+  const int xcd_affine = (N % 8 == 0 && P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
+  lovasz_apply_ig_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(k0, v0, bsum, gts_px, partial, grad_unit, P, cv.nblk_scan, inv_n, xcd_affine);
+  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, (long)N * cv.nblk_scan, inv_n, loss);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_lovasz_softmax_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out,
+                                        int N, int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream,
+                                        int ignore) {
+  if (!logits || !targets || !loss || !workspace || !lovasz_softmax_shape_ok(N, C, H, W, per_image) || ignore < C || ignore > 255)
+    return RS_EINVAL;
+  const SoftmaxCarve sc = carve_softmax(N, C, H, W, per_image);
+  const Carve& cv = sc.cv;
+  char* ws = reinterpret_cast<char*>(workspace);
+  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
+  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
+  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
+  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
+  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
+  double* partial = reinterpret_cast<double*>(ws + cv.partial);
+  uint32_t* gts = reinterpret_cast<uint32_t*>(ws + sc.gts);
+  double* w = reinterpret_cast<double*>(ws + sc.w);
+  hipStream_t s = (hipStream_t)stream;
+  const long S = sc.S, HW = (long)H * W, NHW = (long)N * HW;
+  const int pi = per_image ? 1 : 0;
+  const int sc_affine = (S % 8 == 0 && S >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
+
+  if ((HW & 3) == 0)
+    lovasz_softmax_keys_ig_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi, ignore);
+  else lovasz_softmax_keys_ig_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi, ignore);
+  radix_sort_segments(k0, v0, k1, v1, counts, S, cv, sc_affine, s, sc.chunked_scan ? reinterpret_cast<uint32_t*>(ws + sc.csum) : nullptr);
+  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(v0, bsum, cv.P, cv.nblk_scan);
+  lovasz_softmax_scan_blocks_kernel<<<S, 256, 0, s>>>(bsum, gts, cv.nblk_scan);  // (g of a segment: its valid pixels of the class)
+  const int groups = per_image ? N : 1;
+  lovasz_softmax_weights_kernel<<<rs_cdiv(groups, 256), 256, 0, s>>>(gts, w, groups, C, all_classes ? 1 : 0);
+  float* gp = grad_unit ? reinterpret_cast<float*>(k1) : nullptr;
+  const int xcd_affine = (S % 8 == 0 && cv.P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
+  lovasz_softmax_apply_ig_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(k0, v0, bsum, gts, w, partial, gp, cv.P, cv.nblk_scan, xcd_affine);
+  if (grad_unit) {
+    if ((HW & 3) == 0)
+      lovasz_softmax_jacobian_ig_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, gp, grad_unit, NHW, HW, C, pi, ignore);
+    else lovasz_softmax_jacobian_ig_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, gp, grad_unit, NHW, HW, C, pi, ignore);
+  }
+  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, S * cv.nblk_scan, 1.f, loss);
+  return RS_LAUNCH_RESULT();
+}

@@ -127,9 +127,11 @@ def boundary_report(d, counts):
     return {"d": int(d), "predicted": predicted, "actual": actual, "shared": shared, "iou": _ratio(shared, predicted + actual - shared)}
 
 
-def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None):
+def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None, ignore=None, ignored=0):
     """The report of one run.  ``matrix``: C x C Python integers summed over every evaluated tile; ``kind``: ``--type`` or None;
-    ``objects`` / ``boundary``: ``ObjectScores.report()`` / ``boundary_report()`` or None."""
+    ``objects`` / ``boundary``: ``ObjectScores.report()`` / ``boundary_report()`` or None.  With the dataset's ``ignore`` label the
+    report also carries it and ``ignored``, the pixels whose label has that value: they are in no cell, so ``pixels`` (the matrix's
+    sum) counts the valid ones and ``pixels + ignored`` is every pixel of the evaluated tiles."""
 
     matrix = [[int(v) for v in row] for row in matrix]
     report = {
@@ -140,6 +142,9 @@ def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects
         "confusion": matrix,
     }
     report.update(confusion_scores(matrix, classes))
+    if ignore is not None:
+        report["ignore"] = int(ignore)
+        report["ignored"] = int(ignored)
     if kind is not None:
         report["type"] = kind
         report["objects"] = objects
@@ -148,17 +153,20 @@ def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects
     return report
 
 
-def tile_rows(tiles, matrices, classes, kind=None):
+def tile_rows(tiles, matrices, classes, kind=None, ignored=None):
     """One row per evaluated tile: ``tiles`` and their C x C matrices -> dicts with z, x, y, pixels, iou_<class> per class, miou,
     predicted_share, actual_share (the share of non-background pixels on each side), sorted worst first: by the IoU of ``kind``
-    (``--type``), or by miou without it, undefined values last, then by (z, x, y)."""
+    (``--type``), or by miou without it, undefined values last, then by (z, x, y).  ``ignored`` (with the dataset's ignore label):
+    the tiles' counts of ignored label pixels, an ``ignored`` entry of each row; ``pixels`` and the shares are over the valid ones."""
 
     rows = []
-    for tile, matrix in zip(tiles, matrices):
+    for i, (tile, matrix) in enumerate(zip(tiles, matrices)):
         matrix = np.asarray(matrix, dtype=np.int64)
         scores = confusion_scores(matrix, classes)
         total = int(matrix.sum())
         row = {"z": int(tile.z), "x": int(tile.x), "y": int(tile.y), "pixels": total}
+        if ignored is not None:
+            row["ignored"] = int(ignored[i])
         for name in classes:
             row["iou_" + name] = scores["iou"][name]
         row["miou"] = scores["miou"]
@@ -170,16 +178,18 @@ def tile_rows(tiles, matrices, classes, kind=None):
     return rows
 
 
-def tile_columns(classes):
-    return ["z", "x", "y", "pixels"] + ["iou_" + name for name in classes] + ["miou", "predicted_share", "actual_share"]
+def tile_columns(classes, ignored=False):
+    return (["z", "x", "y", "pixels"] + (["ignored"] if ignored else []) + ["iou_" + name for name in classes]
+            + ["miou", "predicted_share", "actual_share"])
 
 
-def write_tile_rows(path, rows, classes):
-    """``tile_rows`` as CSV; an undefined value is an empty field, a float is written with ``repr`` (it reads back as it was)."""
+def write_tile_rows(path, rows, classes, ignored=False):
+    """``tile_rows`` as CSV; an undefined value is an empty field, a float is written with ``repr`` (it reads back as it was).
+    ``ignored``: the rows carry the ``ignored`` column (``tile_rows`` was given the counts)."""
 
     with open(path, "w", newline="") as fp:
         writer = csv.writer(fp)
-        columns = tile_columns(classes)
+        columns = tile_columns(classes, ignored)
         writer.writerow(columns)
         for row in rows:
             writer.writerow(["" if row[c] is None else repr(row[c]) for c in columns])

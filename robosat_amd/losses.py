@@ -1,7 +1,12 @@
 """Losses of the reference (``robosat/losses.py``) on the MI355X: same class names, constructor arguments and
 ``forward(inputs[N,C,H,W] float32, targets[N,H,W] int64) -> 0-dim tensor`` contract (tools/train.py:97-106,185), with
 the arithmetic in ``librobosat_hip.so`` (``rs_nll_loss_*``, ``rs_lovasz_fwd``), and one loss the reference does not have:
-``LovaszSoftmax2d`` (``rs_lovasz_softmax_fwd``).  No CPU path."""
+``LovaszSoftmax2d`` (``rs_lovasz_softmax_fwd``).  No CPU path.
+
+Every loss takes ``ignore_index=None``, the ``ignore_index`` of ``nn.CrossEntropyLoss`` for all five: a label value (no class, at
+most 255) whose pixels are left out -- the loss is the same definition evaluated on the other pixels only, as if the ignored
+ones had been cut out of every image (``rs_*_ig``, include/robosat_hip.h; DESIGN.md "Ignore label").  ``None`` makes exactly the
+calls made without the argument."""
 
 import torch
 import torch.nn as nn
@@ -15,6 +20,18 @@ def _check(inputs, targets):
     assert inputs.dim() == 4 and targets.dim() == 3 and inputs.shape[0] == targets.shape[0] and inputs.shape[2:] == targets.shape[1:]
     assert targets.dtype == torch.int64
     return inputs.contiguous(), targets.contiguous()
+
+
+def _check_ignore(ignore_index, inputs):
+    """``ignore_index`` against the class count of the logits it meets in ``forward`` (``None`` passes)."""
+
+    if ignore_index is None:
+        return None
+    classes = inputs.shape[1]
+    if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index or not classes <= ignore_index <= 255:
+        raise ValueError("ignore_index must be an integer in {}..255 for logits of {} classes (a class index cannot be ignored), "
+                         "got {!r}".format(classes, classes, ignore_index))
+    return int(ignore_index)
 
 
 def _dp_world(global_batch):
@@ -85,61 +102,61 @@ def _global_batch_miou(loss, stats, global_batch):
 
 class _NLLFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, inputs, targets, weight, mode, gamma, global_batch=False):
+    def forward(ctx, inputs, targets, weight, mode, gamma, global_batch=False, ignore=None):
         x = inputs.detach().float()
-        loss, stats = ops.nll_loss_fwd(x, targets, weight, mode, gamma)
+        loss, stats = ops.nll_loss_fwd(x, targets, weight, mode, gamma, ignore=ignore)
         loss = _global_batch_normaliser(loss, stats, global_batch)
         ctx.save_for_backward(x, targets, stats)
-        ctx.weight, ctx.mode, ctx.gamma = weight, mode, gamma
+        ctx.weight, ctx.mode, ctx.gamma, ctx.ignore = weight, mode, gamma, ignore
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         x, targets, stats = ctx.saved_tensors
         g = grad_out.detach().float().contiguous()
-        return ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma), None, None, None, None, None
+        return ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma, ignore=ctx.ignore), None, None, None, None, None, None
 
 
 class _MIoUFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, inputs, targets, weight, global_batch=False):
+    def forward(ctx, inputs, targets, weight, global_batch=False, ignore=None):
         x = inputs.detach().float()
-        loss, stats = ops.miou_loss_fwd(x, targets, weight)
+        loss, stats = ops.miou_loss_fwd(x, targets, weight, ignore=ignore)
         loss = _global_batch_miou(loss, stats, global_batch)
         ctx.save_for_backward(x, targets, stats)
-        ctx.weight = weight
+        ctx.weight, ctx.ignore = weight, ignore
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         x, targets, stats = ctx.saved_tensors
-        return ops.miou_loss_bwd(x, targets, ctx.weight, stats, grad_out.detach().float().contiguous()), None, None, None
+        return ops.miou_loss_bwd(x, targets, ctx.weight, stats, grad_out.detach().float().contiguous(), ignore=ctx.ignore), None, None, None, None
 
 
 class _LovaszFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, inputs, targets):
-        loss, grad_unit = ops.lovasz_fwd(inputs.detach().float(), targets, want_grad=True)
+    def forward(ctx, inputs, targets, ignore=None):
+        loss, grad_unit = ops.lovasz_fwd(inputs.detach().float(), targets, want_grad=True, ignore=ignore)
         ctx.save_for_backward(grad_unit)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         (grad_unit,) = ctx.saved_tensors
-        return ops.scale_by_scalar(grad_unit, grad_out.detach().float().contiguous()), None
+        return ops.scale_by_scalar(grad_unit, grad_out.detach().float().contiguous()), None, None
 
 
 class _LovaszSoftmaxFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, inputs, targets, per_image, classes):
-        loss, grad_unit, _ = ops.lovasz_softmax_fwd(inputs.detach().float(), targets, per_image, classes, want_grad=True)
+    def forward(ctx, inputs, targets, per_image, classes, ignore=None):
+        loss, grad_unit, _ = ops.lovasz_softmax_fwd(inputs.detach().float(), targets, per_image, classes, want_grad=True, ignore=ignore)
         ctx.save_for_backward(grad_unit)
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         (grad_unit,) = ctx.saved_tensors
-        return ops.scale_by_scalar(grad_unit, grad_out.detach().float().contiguous()), None, None, None
+        return ops.scale_by_scalar(grad_unit, grad_out.detach().float().contiguous()), None, None, None, None
 
 
 class _WeightedLoss(nn.Module):
@@ -148,8 +165,9 @@ class _WeightedLoss(nn.Module):
     # gathered logits.  It adds a small blocking collective to forward(): every rank must call the loss equally often.
     global_batch = False
 
-    def __init__(self, weight=None):
+    def __init__(self, weight=None, ignore_index=None):
         super().__init__()
+        self.ignore_index = ignore_index
         # a buffer (not a parameter) so that ``criterion.to(device)`` moves it, as nn.NLLLoss(weight) does
         self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).clone())
 
@@ -159,19 +177,25 @@ class CrossEntropyLoss2d(_WeightedLoss):
 
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
-        return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        if ignore is None:
+            return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch)
+        return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch, ignore)
 
 
 class FocalLoss2d(_WeightedLoss):
     """Focal loss, gamma = 2 by default (reference losses.py:28-50)."""
 
-    def __init__(self, gamma=2, weight=None):
-        super().__init__(weight)
+    def __init__(self, gamma=2, weight=None, ignore_index=None):
+        super().__init__(weight, ignore_index)
         self.gamma = gamma
 
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
-        return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        if ignore is None:
+            return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch)
+        return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch, ignore)
 
 
 class mIoULoss2d(_WeightedLoss):
@@ -181,15 +205,25 @@ class mIoULoss2d(_WeightedLoss):
 
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
-        return _MIoUFn.apply(inputs, targets, self.weight, self.global_batch)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        if ignore is None:
+            return _MIoUFn.apply(inputs, targets, self.weight, self.global_batch)
+        return _MIoUFn.apply(inputs, targets, self.weight, self.global_batch, ignore)
 
 
 class LovaszLoss2d(nn.Module):
     """The reference's Lovasz hinge variant over the flattened C*H*W vector per image (losses.py:86-119)."""
 
+    def __init__(self, ignore_index=None):
+        super().__init__()
+        self.ignore_index = ignore_index
+
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
-        return _LovaszFn.apply(inputs, targets)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        if ignore is None:
+            return _LovaszFn.apply(inputs, targets)
+        return _LovaszFn.apply(inputs, targets, ignore)
 
 
 class LovaszSoftmax2d(nn.Module):
@@ -198,8 +232,9 @@ class LovaszSoftmax2d(nn.Module):
     the Jaccard loss over the errors ``|1[y = c] - p_c|``, averaged over the classes present (``classes="present"``) or
     over all of them (``"all"``), per image then over the batch (``per_image=True``) or once over the whole batch."""
 
-    def __init__(self, per_image=True, classes="present"):
+    def __init__(self, per_image=True, classes="present", ignore_index=None):
         super().__init__()
+        self.ignore_index = ignore_index
         if classes not in ("present", "all"):
             raise ValueError("classes must be \"present\" or \"all\" (got {!r})".format(classes))
         self.per_image = bool(per_image)
@@ -207,4 +242,7 @@ class LovaszSoftmax2d(nn.Module):
 
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
-        return _LovaszSoftmaxFn.apply(inputs, targets, self.per_image, self.classes)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        if ignore is None:
+            return _LovaszSoftmaxFn.apply(inputs, targets, self.per_image, self.classes)
+        return _LovaszSoftmaxFn.apply(inputs, targets, self.per_image, self.classes, ignore)

@@ -56,7 +56,8 @@ class Metrics:
         self.add_batch(actual.unsqueeze(0), predicted.unsqueeze(0))
 
     def add_batch(self, actual, predicted):
-        """A whole batch: ``actual`` [N,H,W] int64, ``predicted`` [N,C,H,W] float32."""
+        """A whole batch: ``actual`` [N,H,W] int64, ``predicted`` [N,C,H,W] float32.  A pixel whose label lies outside the classes
+        (the dataset's ``[common] ignore`` value, say) is not counted: it is in no cell of the matrix."""
 
         assert predicted.size(1) == self.num_classes
         ops.confusion_matrix(predicted.detach().float().contiguous(), actual.contiguous(), self._buf(predicted.device))

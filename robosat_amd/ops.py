@@ -1257,56 +1257,98 @@ def final_conv1x1_bwd(x, w, dlogits, relu_mask=True, dw=None, db=None):
 NLL_CROSS_ENTROPY, NLL_FOCAL = 0, 1
 
 
-def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0):
+def _ignore_label(ignore, classes):
+    """The ``ignore`` argument of the losses and counts below as the C ABI's int: ``None`` stays ``None`` (the entry points without
+    ``_ig``), an integer must be no class of 0 .. ``classes`` - 1 and fit the label byte."""
+
+    if ignore is None:
+        return None
+    if isinstance(ignore, bool) or int(ignore) != ignore or not classes <= int(ignore) <= 255:
+        raise ValueError("robosat_amd: the ignore label is an integer in {}..255 for {} classes, got {!r}".format(classes, classes, ignore))
+    return int(ignore)
+
+
+def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None):
+    """``ignore`` (here and in the four losses below): the label value whose pixels are left out of the loss
+    (``rs_*_ig`` in include/robosat_hip.h); ``None`` calls the entry point without it."""
+
     n, c, h, w = logits.shape
     lib = _lib.lib()
+    ignore = _ignore_label(ignore, c)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     stats = torch.empty(2, device=logits.device, dtype=torch.float32)
+    if ignore is not None:
+        _call("rs_nll_loss_fwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma),
+              _workspace(lib.rs_nll_loss_workspace_bytes(), logits.device), _stream(), ignore)
+        return loss, stats
     _call("rs_nll_loss_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(loss, "loss"),
           _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma), _workspace(lib.rs_nll_loss_workspace_bytes(), logits.device),
           _stream())
     return loss, stats
 
 
-def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0):
+def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0, ignore=None):
     n, c, h, w = logits.shape
+    ignore = _ignore_label(ignore, c)
     dlogits = torch.empty_like(logits)
+    if ignore is not None:
+        _call("rs_nll_loss_bwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mode, ctypes.c_float(gamma),
+              _stream(), ignore)
+        return dlogits
     _call("rs_nll_loss_bwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(stats, "stats"),
           _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mode, ctypes.c_float(gamma), _stream())
     return dlogits
 
 
-def miou_loss_fwd(logits, targets, weight):
+def miou_loss_fwd(logits, targets, weight, ignore=None):
     n, c, h, w = logits.shape
     lib = _lib.lib()
+    ignore = _ignore_label(ignore, c)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     stats = torch.empty(5 + 2 * n * c, device=logits.device, dtype=torch.float32)
+    if ignore is not None:
+        _call("rs_miou_loss_fwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w, _workspace(lib.rs_miou_loss_workspace_bytes(n, c), logits.device),
+              _stream(), ignore)
+        return loss, stats
     _call("rs_miou_loss_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(loss, "loss"),
           _dev(stats, "stats"), n, c, h, w, _workspace(lib.rs_miou_loss_workspace_bytes(n, c), logits.device), _stream())
     return loss, stats
 
 
-def miou_loss_bwd(logits, targets, weight, stats, grad_out):
+def miou_loss_bwd(logits, targets, weight, stats, grad_out, ignore=None):
     n, c, h, w = logits.shape
+    ignore = _ignore_label(ignore, c)
     dlogits = torch.empty_like(logits)
+    if ignore is not None:
+        _call("rs_miou_loss_bwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, _stream(), ignore)
+        return dlogits
     _call("rs_miou_loss_bwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(stats, "stats"),
           _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, _stream())
     return dlogits
 
 
-def lovasz_fwd(logits, targets, want_grad=True):
+def lovasz_fwd(logits, targets, want_grad=True, ignore=None):
     """Returns (loss, d loss / d logits for grad_out = 1 or None)."""
 
     n, c, h, w = logits.shape
     lib = _lib.lib()
+    ignore = _ignore_label(ignore, c)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     grad = torch.empty_like(logits) if want_grad else None
+    if ignore is not None:
+        _call("rs_lovasz_fwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"), _dev(grad, "grad"),
+              n, c, h, w, _workspace(lib.rs_lovasz_workspace_bytes(n, c, h, w), logits.device), _stream(), ignore)
+        return loss, grad
     _call("rs_lovasz_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"), _dev(grad, "grad"), n, c, h,
           w, _workspace(lib.rs_lovasz_workspace_bytes(n, c, h, w), logits.device), _stream())
     return loss, grad
 
 
-def lovasz_softmax_fwd(logits, targets, per_image=True, classes="present", want_grad=True, want_probs=False):
+def lovasz_softmax_fwd(logits, targets, per_image=True, classes="present", want_grad=True, want_probs=False, ignore=None):
     """Lovasz-Softmax (``rs_lovasz_softmax_fwd``): returns (loss, d loss / d logits for grad_out = 1 or None, fp32
     softmax probabilities NCHW or None)."""
 
@@ -1319,6 +1361,12 @@ def lovasz_softmax_fwd(logits, targets, per_image=True, classes="present", want_
     grad = torch.empty_like(logits) if want_grad else None
     probs = torch.empty_like(logits) if want_probs else None
     nbytes = lib.rs_lovasz_softmax_workspace_bytes(n, c, h, w, pi)
+    ignore = _ignore_label(ignore, c)
+    if ignore is not None:
+        _call("rs_lovasz_softmax_fwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"),
+              _dev(grad, "grad"), _dev(probs, "probs"), n, c, h, w, pi, 1 if classes == "all" else 0, _workspace(nbytes, logits.device),
+              _stream(), ignore)
+        return loss, grad, probs
     _call("rs_lovasz_softmax_fwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(loss, "loss"), _dev(grad, "grad"),
           _dev(probs, "probs"), n, c, h, w, pi, 1 if classes == "all" else 0, _workspace(nbytes, logits.device), _stream())
     return loss, grad, probs
@@ -1958,16 +2006,27 @@ def _eval_pair(a, b, names, dtype):
     return _dev(a, names[0], dtype), _dev(b, names[1], dtype), a.numel(), a.shape[1] * a.shape[2]
 
 
-def mask_confusion(predicted_u8, actual_u8, classes, stitched=False):
+def mask_confusion(predicted_u8, actual_u8, classes, stitched=False, ignore=None):
     """Two uint8 [B, H, W] class-index rasters -> (int64 [G, C, C], int64 [G]): per tile (G = B), or with ``stitched`` for the one
     raster the B tiles form (G = 1), ``counts[g][a][p]`` = the pixels with actual == a and predicted == p, and the number of pixels
-    where either value is no class of 0 .. ``classes`` - 1 (they are in no cell).  2 <= ``classes`` <= 8."""
+    where either value is no class of 0 .. ``classes`` - 1 (they are in no cell).  2 <= ``classes`` <= 8.
+
+    With ``ignore`` (``rs_eval_confusion_ig``) a third tensor follows, int64 [G]: the pixels whose ACTUAL value is ``ignore`` over a
+    predicted value that is a class.  They are in no cell and not among the bad ones."""
 
     classes = int(classes)
     if not 2 <= classes <= EVAL_MAX_CLASSES:
         raise ValueError("robosat_amd: 2 to {} classes are counted, got {}".format(EVAL_MAX_CLASSES, classes))
+    ignore = _ignore_label(ignore, classes)
     p, a, pixels, hw = _eval_pair(predicted_u8, actual_u8, ("predicted", "actual"), torch.uint8)
     groups = 1 if stitched else predicted_u8.shape[0]
+    if ignore is not None:
+        cc = groups * classes * classes
+        three = torch.empty(cc + 2 * groups, device=predicted_u8.device, dtype=torch.int64)
+        counts, bad, ignored = three[:cc].view(groups, classes, classes), three[cc:cc + groups], three[cc + groups:]
+        _call("rs_eval_confusion_ig", p, a, _dev(counts, "counts", torch.int64), _dev(bad, "bad", torch.int64),
+              _dev(ignored, "ignored", torch.int64), pixels, pixels if stitched else hw, classes, _stream(), ignore)
+        return counts, bad, ignored
     # (one buffer, `bad` behind `counts`: the library then zeroes both with one fill)
     both = torch.empty(groups * (classes * classes + 1), device=predicted_u8.device, dtype=torch.int64)
     counts, bad = both[:groups * classes * classes].view(groups, classes, classes), both[groups * classes * classes:]

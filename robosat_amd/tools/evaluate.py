@@ -11,6 +11,11 @@ views, all counted on the MI355X (``csrc/evaluate.hip`` and the ``rs features`` 
     by IoU at ``--match``; predicted, actual, matched, precision, recall, F1.  Per tile an object cut by a tile border counts once per
     tile; ``--stitch`` evaluates the one sparse raster the tiles of a zoom level form, where it is one object on both sides.
 
+With the dataset's ``[common] ignore`` a pixel whose LABEL has that value is in no cell of the pixel view: the report and the
+``--tiles`` rows count it as ``ignored`` and their ``pixels`` are the valid ones.  A mask byte, or another label byte, that is no
+class still ends the run.  With ``--type`` a label tile that holds an ignored pixel ends the run, naming the tile: what a
+boundary or an object cut by an unknown region should count as is not defined yet.
+
 The definitions are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
@@ -23,7 +28,7 @@ from PIL import Image
 from tqdm import tqdm
 
 from robosat_amd import ops
-from robosat_amd.config import load_config
+from robosat_amd.config import ignore_label, load_config
 from robosat_amd.evaluate import ObjectScores, boundary_report, build_report, tile_rows, write_tile_rows
 from robosat_amd.features import group_clusters, pack_clusters, stitch_tables
 from robosat_amd.tiles import tiles_from_slippy_map
@@ -56,7 +61,8 @@ def add_parser(subparser):
                         "per tile: an object cut by a tile border counts once per tile, on both sides")
     parser.add_argument("--tiles", type=str, default=None, metavar="CSV",
                         help="path to a CSV with one row per evaluated tile: z, x, y, pixels, the IoU of every class, miou and the share "
-                        "of non-background pixels on each side, sorted worst first by the IoU of --type (by miou without it)")
+                        "of non-background pixels on each side, sorted worst first by the IoU of --type (by miou without it); with the "
+                        "dataset's [common] ignore also the tile's ignored label pixels, and pixels are the others")
     parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
     parser.set_defaults(func=main)
 
@@ -104,12 +110,12 @@ def _name(tile):
 class Evaluation:
     """The sums of a run, and the device stages of one batch (tiles on their own) or call (tiles as one sparse raster)."""
 
-    def __init__(self, classes, index, boundary, objects):
-        self.classes, self.index, self.boundary, self.objects = classes, index, boundary, objects
+    def __init__(self, classes, index, boundary, objects, ignore=None):
+        self.classes, self.index, self.boundary, self.objects, self.ignore = classes, index, boundary, objects, ignore
         n = len(classes)
         self.matrix = [[0] * n for _ in range(n)]  # Python integers: no bound on the pixels of a run
         self.band = [0, 0, 0]
-        self.tiles, self.matrices = [], []
+        self.tiles, self.matrices, self.ignored = [], [], []
 
     def add(self, tiles, paths, label_paths, shape, device, nbr=None, origin=None):
         predicted = _load([paths[t] for t in tiles], device)
@@ -121,7 +127,16 @@ class Evaluation:
                                                                                               image.size[0], shape[0], shape[1]))
             label_files.append(label_paths[tile])
         actual = _load(label_files, device)
-        counts, bad = ops.mask_confusion(predicted, actual, len(self.classes))
+        if self.ignore is None:
+            counts, bad = ops.mask_confusion(predicted, actual, len(self.classes))
+        else:
+            counts, bad, ignored = ops.mask_confusion(predicted, actual, len(self.classes), ignore=self.ignore)
+            ignored = ignored.tolist()
+            for tile, n in zip(tiles, ignored):
+                if n and self.index is not None:
+                    sys.exit("Error: the label of tile {} has {} pixels of the ignore value {}; --type scores boundaries and objects, "
+                             "which are not defined next to ignored pixels yet: evaluate without --type".format(_name(tile), n, self.ignore))
+            self.ignored.extend(ignored)
         for tile, wrong in zip(tiles, bad.tolist()):
             if wrong:
                 sys.exit("Error: tile {} has {} pixels whose value, in the mask or the label, is none of the dataset's {} classes".format(
@@ -155,14 +170,19 @@ class Evaluation:
 
 
 def main(args):
-    classes = load_config(args.dataset)["common"]["classes"]
+    dataset = load_config(args.dataset)
+    classes = dataset["common"]["classes"]
+    try:
+        ignore = ignore_label(dataset)
+    except ValueError as err:
+        sys.exit("Error: {}".format(err))
     match, min_area = validate(args, classes)
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
     index = None if args.type is None else classes.index(args.type)
     objects = None if index is None else ObjectScores(match, min_area, args.stitch)
-    run = Evaluation(classes, index, args.boundary, objects)
+    run = Evaluation(classes, index, args.boundary, objects, ignore)
 
     label_paths = {tile: path for tile, path in tiles_from_slippy_map(args.labels)}
     without_label = 0
@@ -203,11 +223,16 @@ def main(args):
 
     report = build_report(classes, run.matrix, len(run.tiles), without_label, kind=args.type,
                           objects=None if objects is None else objects.report(),
-                          boundary=boundary_report(args.boundary, run.band) if args.boundary else None)
+                          boundary=boundary_report(args.boundary, run.band) if args.boundary else None,
+                          **({} if ignore is None else {"ignore": ignore, "ignored": sum(run.ignored)}))
     with open(args.out, "w") as fp:
         json.dump(report, fp, indent=2, allow_nan=False)
         fp.write("\n")
     if args.tiles is not None:
-        write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type), classes)
+        if ignore is None:
+            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type), classes)
+        else:
+            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, ignored=run.ignored), classes,
+                            ignored=True)
     if without_label:
         print("Evaluate: {} mask tiles without a label were skipped".format(without_label), file=sys.stderr)

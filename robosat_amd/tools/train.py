@@ -22,6 +22,8 @@ Differences by design:
   * extension keys, all optional: dataset ``[common] image_dirs / image_modes / mean / std`` (band layout: robosat_amd/bands.py;
     default = the reference's one RGB directory), model ``[model] in_channels``, ``compute_dtype``, ``pretrained``,
     ``device_augment``, ``grad_dtype`` (bf16 gradient exchange), ``graph`` (the step as one hipGraph replay).
+  * dataset ``[common] ignore`` (extension key, optional: robosat_amd/config.py): the label value of pixels that carry no class.
+    They are left out of the loss (the criterion's ``ignore_index``) and, as every label outside the classes, of the metrics.
   * ``[augment]`` (extension table, optional: robosat_amd/augment.py): a random zoom-in crop and brightness / contrast /
     saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.
 """
@@ -42,7 +44,7 @@ from tqdm import tqdm
 from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
-from robosat_amd.config import check_num_classes, load_config
+from robosat_amd.config import check_num_classes, ignore_label, load_config
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
 from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, mIoULoss2d
@@ -139,6 +141,10 @@ def augment_options(model, dataset):
 def main(args):
     model = load_config(args.model)
     dataset = load_config(args.dataset)
+    try:
+        ignore = ignore_label(dataset)  # (dataset `[common] ignore`, optional: label pixels that are left out of the loss)
+    except ValueError as err:
+        sys.exit("Error: {}".format(err))  # (before any work starts)
 
     if not model["common"]["cuda"]:
         # (a deliberate deviation from the reference, which falls back to the CPU here -- tools/train.py:60-63 -- and from BASELINE.json
@@ -227,17 +233,19 @@ def main(args):
     parallel.broadcast_module(net)
 
     loss_name = model["opt"]["loss"]
+    # (without `[common] ignore` the criteria are built and called exactly as before)
+    ignored = {} if ignore is None else {"ignore_index": ignore}
     if loss_name == "CrossEntropy":
-        criterion = CrossEntropyLoss2d(weight=weight).to(device)
+        criterion = CrossEntropyLoss2d(weight=weight, **ignored).to(device)
     elif loss_name == "mIoU":
-        criterion = mIoULoss2d(weight=weight).to(device)
+        criterion = mIoULoss2d(weight=weight, **ignored).to(device)
     elif loss_name == "Focal":
-        criterion = FocalLoss2d(weight=weight).to(device)
+        criterion = FocalLoss2d(weight=weight, **ignored).to(device)
     elif loss_name == "Lovasz":
-        criterion = LovaszLoss2d().to(device)
+        criterion = LovaszLoss2d(**ignored).to(device)
     elif loss_name == "LovaszSoftmax":
         per_image, classes = lovasz_softmax_options(model, world)
-        criterion = LovaszSoftmax2d(per_image=per_image, classes=classes).to(device)
+        criterion = LovaszSoftmax2d(per_image=per_image, classes=classes, **ignored).to(device)
     else:
         sys.exit("Error: Unknown [opt][loss] value !")
     if world > 1 and hasattr(criterion, "global_batch"):
@@ -282,6 +290,8 @@ def main(args):
     say("Loss function:\t {}".format(loss_name))
     if weight is not None:
         say("Weights :\t {}".format(dataset["weights"]["values"]))
+    if ignore is not None:
+        say("Ignore label:\t {}".format(ignore))
     if jitter is not None:
         say("Augmentation:\t {}".format(describe_jitter(jitter)))
     say("---")

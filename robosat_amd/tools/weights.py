@@ -13,7 +13,7 @@ from torch.utils.data import DataLoader
 from tqdm import tqdm
 
 from robosat_amd import ops
-from robosat_amd.config import load_config
+from robosat_amd.config import ignore_label, load_config
 from robosat_amd.datasets import SlippyMapTiles
 from robosat_amd.transforms import Compose, ConvertImageMode
 
@@ -37,8 +37,22 @@ def _collate(items):
     return torch.cat([labels for labels, _ in items])
 
 
-def class_counts(label_dir, num_classes, device, batch_size=64, workers=0):
-    """(pixels, int64 counts per class) of every label tile under ``label_dir``, counted on the device."""
+def valid_counts(n, counts256, num_classes, ignore, where):
+    """(pixels, int64 counts per class) from the 256-bin histogram of ``n`` label bytes: pixels of the ``ignore`` value (or None)
+    are left out of the counts and of the pixel total; any other byte outside the classes raises."""
+
+    counts256 = np.array(counts256, dtype=np.int64)
+    if ignore is not None:
+        n -= int(counts256[ignore])
+        counts256[ignore] = 0
+    if counts256[num_classes:].any():  # np.bincount would have grown past `num_classes` and the reference's `+=` would raise
+        raise ValueError("labels outside [0, {}) in {}".format(num_classes, where))
+    return n, counts256[:num_classes]
+
+
+def class_counts(label_dir, num_classes, device, batch_size=64, workers=0, ignore=None):
+    """(pixels, int64 counts per class) of every label tile under ``label_dir``, counted on the device; with ``ignore`` (the
+    dataset's ``[common] ignore``) over the pixels of another value only."""
 
     dataset = SlippyMapTiles(label_dir, transform=Compose([ConvertImageMode(mode="P"), _MaskToBytes()]))
     counts = torch.zeros(256, device=device, dtype=torch.int64)
@@ -47,10 +61,7 @@ def class_counts(label_dir, num_classes, device, batch_size=64, workers=0):
     for labels in tqdm(loader, desc="Loading", unit="batch", ascii=True):
         n += labels.numel()
         ops.label_histogram_u8(labels.to(device, non_blocking=True).contiguous(), counts)
-    counts = counts.cpu().numpy()
-    if counts[num_classes:].any():  # np.bincount would have grown past `num_classes` and the reference's `+=` would raise
-        raise ValueError("labels outside [0, {}) in {}".format(num_classes, label_dir))
-    return n, counts[:num_classes].astype(np.int64)
+    return valid_counts(n, counts.cpu().numpy(), num_classes, ignore, label_dir)
 
 
 def weights_from_counts(n, counts):
@@ -64,11 +75,15 @@ def weights_from_counts(n, counts):
 
 def main(args):
     dataset = load_config(args.dataset)
+    try:
+        ignore = ignore_label(dataset)
+    except ValueError as err:
+        sys.exit("Error: {}".format(err))
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
     path = dataset["common"]["dataset"]
     num_classes = len(dataset["common"]["classes"])
-    n, counts = class_counts(os.path.join(path, "training", "labels"), num_classes, device)
+    n, counts = class_counts(os.path.join(path, "training", "labels"), num_classes, device, ignore=ignore)
     assert n > 0, "dataset with masks must not be empty"
     print(weights_from_counts(n, counts))
