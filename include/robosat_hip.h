@@ -614,6 +614,14 @@ int rs_label_histogram_u8(const uint8_t* labels, long n, int64_t* counts256, rs_
 int rs_softvote_masks(const uint8_t* q, const double* weights, const double* anchors, uint8_t* out, int K, long P, int C,
                       rs_stream_t stream);
 
+/* `rs masks --threshold T`, binary models only: q [K][P], the same un-quantisation and weighted average as rs_softvote_masks
+ * (float64, models accumulated in order), then out[p] = voted foreground >= T in place of the argmax:
+ * np.average(anchors[q], axis=0, weights) >= T.  threshold: T, one double in HOST memory, read before the call returns (every
+ * value the ABI passes by value is an int, a long or a float, and T must arrive as the float64 it is); 0 < T <= 1, RS_EINVAL
+ * otherwise.  With one model and T = anchors[k] the mask is `byte >= k`, the operating point k of `rs evaluate --probs`. */
+int rs_softvote_masks_threshold(const uint8_t* q, const double* weights, const double* anchors, uint8_t* out, int K, long P,
+                                const double* threshold, rs_stream_t stream);
+
 /* Training-set augmentation from a cache of decoded tiles in HBM (robosat/tools/train.py:248-260,
  * robosat/transforms.py:127-221): for batch item n take tile index[n] of images [T][S][S][C] (uint8 HWC) / masks [T][S][S],
  * apply op[n] = f + 2*k (PIL FLIP_LEFT_RIGHT when f, then k x ROTATE_90), ToTensor + Normalize ((v/255 - mean)/std, fp32),
@@ -922,6 +930,25 @@ int rs_eval_boundary(const int32_t* d2_a, const int32_t* d2_b, int64_t* counts, 
  * bad == counts + G*C*C and ignored == bad + G, three otherwise. */
 int rs_eval_confusion_ig(const uint8_t* predicted, const uint8_t* actual, int64_t* counts, int64_t* bad, int64_t* ignored, long pixels,
                          long group, int C, rs_stream_t stream, int ignore);
+
+/* rs_eval_prob_hist (`rs evaluate --probs`): prob: uint8 [pixels], the probability bytes of ONE class as `rs predict` stores them;
+ * actual: uint8 [pixels] labels (any address for both); 2 <= C <= 8, 1 <= cls <= C - 1, ignore = -1 for none, else C <= ignore <= 255.
+ * A byte q stands for q / 255 = np.linspace(0, 1, 256)[q], the value `rs masks` and `rs features --score` un-quantise it to.
+ * Byte 0 is read as probability 0, as those tools read it: that includes the reference's wrap of p == 1.0 to byte 0
+ * (robosat/tools/predict.py quantises with np.digitize, which puts exactly 1.0 behind the last anchor, and the uint8 cast wraps it).
+ * This view describes the files as the other tools read them, not what the network meant.
+ *   hist[g][pos][q] = the number of pixels of group g with prob == q and (actual == cls) == pos, among the pixels whose label is a
+ *                     class (actual < C)                                                                   (int64 [G][2][256])
+ *   skipped[g][0]   = the pixels of group g whose label is >= C and not `ignore` (the bad ones)
+ *   skipped[g][1]   = the pixels of group g whose label equals `ignore`; neither kind is in a hist cell        (int64 [G][2])
+ * both set by the call, not added to, 8-byte aligned; one fill where skipped == hist + G*512, two otherwise.  The shape is
+ * rs_eval_confusion's (4096 pixels per workgroup, 16 per thread, the block walks its groups).  Per group: a wave whose pixels all
+ * lie in one cell sums its count over the lanes and sends one LDS add; otherwise runs of equal cells within a thread go to the
+ * wave's own histogram (32-bit counters: a block holds 4096 pixels) one LDS atomic per run; the four copies are summed per cell
+ * and put back to zero by the thread that sums them, and one 64-bit atomic add goes out per block, group and non-empty cell: at
+ * most 514.  No workgroup waits for another; every loop is bounded. */
+int rs_eval_prob_hist(const uint8_t* prob, const uint8_t* actual, int64_t* hist, int64_t* skipped, long pixels, long group, int C,
+                      int cls, int ignore, rs_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,7 @@ SIGNATURES = {
     "rs_confusion_matrix": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "rs_label_histogram_u8": (c_int, [P, c_long, P, P]),
     "rs_softvote_masks": (c_int, [P, P, P, P, c_int, c_long, c_int, P]),
+    "rs_softvote_masks_threshold": (c_int, [P, P, P, P, c_int, c_long, P, P]),
     "rs_augment_tiles": (c_int, [P, P, P, P, POINTER(c_float), POINTER(c_float), P, P, c_int, c_int, c_int, P]),
     # zoom and colour jitter of the training feed (csrc/augment.hip)
     "rs_tile_band_sums": (c_int, [P, P, c_int, c_int, c_int, P]),
@@ -196,6 +197,7 @@ SIGNATURES = {
     "rs_eval_confusion": (c_int, [P, P, P, P, c_long, c_long, c_int, P]),
     "rs_eval_boundary": (c_int, [P, P, P, c_long, c_long, c_int, P]),
     "rs_eval_confusion_ig": (c_int, [P, P, P, P, P, c_long, c_long, c_int, P, c_int]),
+    "rs_eval_prob_hist": (c_int, [P, P, P, P, c_long, c_long, c_int, c_int, c_int, P]),
 }
 
 _lib = None

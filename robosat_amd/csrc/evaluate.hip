@@ -5,8 +5,10 @@
 //                      value that is no class
 //   rs_eval_boundary   two capped distance transforms (rs_features_edt) -> per group the sizes of the two boundary bands and of their
 //                      intersection
+//   rs_eval_prob_hist  the probability bytes of one class and the label raster -> per group the 2 x 256 histogram of (label is the
+//                      class, byte) and the numbers of pixels with a bad and with an ignored label (at the end of the file)
 //
-// Both kernels share one shape.  A block of 256 threads covers kEvalBlock = 4096 consecutive pixels of the whole call, a thread 16
+// The kernels share one shape.  A block of 256 threads covers kEvalBlock = 4096 consecutive pixels of the whole call, a thread 16
 // consecutive ones, held in registers: a 16-byte load per raster (four for the int32 rasters) where the thread's first address is
 // 16-byte aligned and its run ends within `pixels`, single loads with a bound check otherwise (the call's last thread; a raster that
 // is a view at an odd offset).  Runs are laid over the call, not over the groups, so where a group begins (byte 63 for the second
@@ -291,5 +293,128 @@ extern "C" int rs_eval_confusion_ig(const uint8_t* predicted, const uint8_t* act
   eval_confusion_ig_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(
       predicted, actual, reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<unsigned long long*>(bad),
       reinterpret_cast<unsigned long long*>(ignored), pixels, group, C, (unsigned int)ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+// ---- probability histogram per group (rs_eval_prob_hist) ---------------------------------------------------------------------
+// `rs evaluate --probs`: the joint histogram of (label is the class, probability byte), 2 x 256 bins per group, and two counters
+// for the pixels that are in none of them.  A pixel's cell is pos * 256 + q, or kProbBad / kProbIgnored behind the 512 bins.  The
+// shape is eval_confusion_kernel's (16 pixels per thread in registers, the block walks its groups), with three differences that
+// the 514 cells ask for:
+//   * the four wave-private histograms are zeroed ONCE; the thread that merges a bin puts it back to zero (only where it was
+//     not), so a group costs two reads of the histograms and no fill, and two barriers;
+//   * a wave whose pixels of the group all lie in one cell (saturated tiles: nearly every pixel is (negative, byte 1)) adds its
+//     count over the lanes and sends ONE LDS add, where 64 lanes adding to one address would be served one after another;
+//   * otherwise runs of equal cells within a thread are merged as in the confusion kernel, one LDS atomic per run: 16 per
+//     thread at worst (uniformly random bytes), into 512 counters of the wave's own copy.
+// Per block and group at most 514 global 64-bit atomics go out, for non-empty cells only.  Counters in LDS are 32 bits: a block
+// holds 4096 pixels.  No workgroup waits for another; every loop is bounded.
+namespace {
+
+constexpr int kProbBins = 512;                 // [pos][q]
+constexpr int kProbBad = kProbBins;            // label >= C and not `ignore`
+constexpr int kProbIgnored = kProbBins + 1;    // label == ignore
+constexpr int kProbCells = kProbIgnored + 1;
+
+__global__ __launch_bounds__(kEvalThreads) void eval_prob_hist_kernel(const uint8_t* __restrict__ prob, const uint8_t* __restrict__ actual,
+                                                                      unsigned long long* __restrict__ hist_out,
+                                                                      unsigned long long* __restrict__ skipped, long pixels, long group,
+                                                                      unsigned int C, unsigned int cls, unsigned int ignore) {
+  __shared__ unsigned int hist[4][kProbCells];
+  const long block0 = (long)blockIdx.x * kEvalBlock;
+  const long base = block0 + (long)threadIdx.x * kEvalRun;
+  unsigned int qw[4] = {0, 0, 0, 0};  // 16 probability bytes
+  unsigned int codes = 0;             // 16 x 2 bits: 0 negative, 1 positive, 2 bad, 3 ignored (cells kProbBad - 2 + code)
+  if (base < pixels) {
+    unsigned int aw[4];
+    eval_load_bytes(prob, base, pixels, qw);
+    eval_load_bytes(actual, base, pixels, aw);
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j) {
+      const unsigned int a = (aw[j >> 2] >> ((j & 3) * 8)) & 255u;
+      const unsigned int code = a < C ? (unsigned int)(a == cls) : a == ignore ? 3u : 2u;  // (ignore is 256 where there is none)
+      codes |= code << (2 * j);
+    }
+  }
+  for (int i = threadIdx.x; i < 4 * kProbCells; i += kEvalThreads) (&hist[0][0])[i] = 0;
+  __syncthreads();
+  const long block1 = block0 + kEvalBlock < pixels ? block0 + kEvalBlock : pixels;
+  const long g0 = block0 / group, g1 = (block1 - 1) / group;
+  unsigned int* h = hist[threadIdx.x >> 6];
+  const int lane = threadIdx.x & 63;
+  for (long g = g0; g <= g1; ++g) {
+    int jlo, jhi;
+    eval_range(base, g, group, pixels, jlo, jhi);
+    // the thread's first cell of the group, and whether all its pixels of the group lie in it
+    unsigned int first = 0;
+    bool same = true;
+#pragma unroll
+    for (int j = kEvalRun - 1; j >= 0; --j) {
+      if (j >= jlo && j < jhi) {
+        const unsigned int code = (codes >> (2 * j)) & 3u, q = (qw[j >> 2] >> ((j & 3) * 8)) & 255u;
+        const unsigned int cell = code < 2u ? (code << 8) | q : (unsigned int)kProbBad - 2u + code;
+        same = same && (j == jhi - 1 || cell == first);
+        first = cell;
+      }
+    }
+    unsigned int n = jhi > jlo ? (unsigned int)(jhi - jlo) : 0u;
+    const unsigned long long live = __ballot(n != 0u);
+    if (live) {  // (wave-uniform)
+      const unsigned int lead = __shfl(first, __ffsll((long long)live) - 1, 64);
+      if (__all(n == 0u || (same && first == lead))) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+        if (lane == 0) atomicAdd(&h[lead], n);
+      } else {
+        unsigned int cur = 0, run = 0;
+#pragma unroll
+        for (int j = 0; j < kEvalRun; ++j) {
+          if (j >= jlo && j < jhi) {
+            const unsigned int code = (codes >> (2 * j)) & 3u, q = (qw[j >> 2] >> ((j & 3) * 8)) & 255u;
+            const unsigned int cell = code < 2u ? (code << 8) | q : (unsigned int)kProbBad - 2u + code;
+            if (run && cell != cur) {
+              atomicAdd(&h[cur], run);
+              run = 0;
+            }
+            cur = cell;
+            ++run;
+          }
+        }
+        if (run) atomicAdd(&h[cur], run);
+      }
+    }
+    __syncthreads();
+    // merge: a thread owns cells t and t + 256 (threads 0 and 1 also the two counters behind them) in all four copies
+    for (int t = threadIdx.x; t < kProbCells; t += kEvalThreads) {
+      const unsigned int tot = hist[0][t] + hist[1][t] + hist[2][t] + hist[3][t];
+      if (tot) {
+        hist[0][t] = hist[1][t] = hist[2][t] = hist[3][t] = 0;
+        if (t < kProbBins)
+          atomicAdd(&hist_out[g * kProbBins + t], (unsigned long long)tot);
+        else
+          atomicAdd(&skipped[g * 2 + (t - kProbBins)], (unsigned long long)tot);
+      }
+    }
+    __syncthreads();  // (the next group counts into the cells put back to zero)
+  }
+}
+
+}  // namespace
+
+extern "C" int rs_eval_prob_hist(const uint8_t* prob, const uint8_t* actual, int64_t* hist, int64_t* skipped, long pixels, long group, int C,
+                                 int cls, int ignore, rs_stream_t stream) {
+  if (!prob || !actual || !hist || !skipped || (((uintptr_t)hist | (uintptr_t)skipped) & 7) || !eval_shape_ok(pixels, group) || C < 2 ||
+      C > 8 || cls < 1 || cls >= C || (ignore != -1 && (ignore < C || ignore > 255)))
+    return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long groups = pixels / group;
+  // (one fill where `skipped` follows `hist` directly, as ops.prob_histogram lays them out)
+  const bool joined = skipped == hist + groups * kProbBins;
+  hipError_t e = hipMemsetAsync(hist, 0, groups * (kProbBins + (joined ? 2 : 0)) * sizeof(int64_t), s);
+  if (e == hipSuccess && !joined) e = hipMemsetAsync(skipped, 0, groups * 2 * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  eval_prob_hist_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(
+      prob, actual, reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(skipped), pixels, group,
+      (unsigned int)C, (unsigned int)cls, ignore < 0 ? 256u : (unsigned int)ignore);
   return RS_LAUNCH_RESULT();
 }

@@ -4,6 +4,7 @@
 //                         counters are the C = 2 matrix: tn = [0][0], "fn" = [0][1], "fp" = [1][0], tp = [1][1])
 //   rs_label_histogram_u8 robosat/tools/weights.py:41-47: np.bincount over every label tile of the training set
 //   rs_softvote_masks     robosat/tools/masks.py:42-84: un-quantise K probability PNGs, weighted average, argmax
+//   rs_softvote_masks_threshold  the same vote for binary models, `voted foreground >= T` in place of the argmax (rs masks --threshold)
 //   rs_augment_tiles      robosat/tools/train.py:248-260 + robosat/transforms.py:127-221: random horizontal flip + up to
 //                         three 90-degree rotations + ToTensor + Normalize, from a cache of decoded uint8 tiles in HBM
 #include "common.h"
@@ -107,6 +108,28 @@ __global__ __launch_bounds__(256) void softvote_kernel(const uint8_t* __restrict
   out[p] = (uint8_t)best;
 }
 
+// softvote_kernel for binary models with a threshold in place of the argmax: q [K][P], the voted foreground probability formed
+// as above (float64, models in order, the same division), out[p] = voted >= T -- numpy's
+// np.average(anchors[q], axis=0, weights=w) >= T on the same values.
+__global__ __launch_bounds__(256) void softvote_threshold_kernel(const uint8_t* __restrict__ q, const double* __restrict__ weights,
+                                                                 const double* __restrict__ anchors, uint8_t* __restrict__ out, int K,
+                                                                 long P, double T) {
+  __shared__ double anc[256];
+  anc[threadIdx.x] = anchors[threadIdx.x];
+  __syncthreads();
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= P) return;
+  double acc = 0.0, scl = 0.0;
+  for (int k = 0; k < K; ++k) {
+    const double wk = weights ? weights[k] : 1.0;
+    scl += wk;
+    const double f = anc[q[(long)k * P + p]];
+    acc += weights ? f * wk : f;
+  }
+  const double v = weights ? acc / scl : acc / (double)K;
+  out[p] = (uint8_t)(v >= T);
+}
+
 // ---- augmentation from a decoded-tile cache ----------------------------------------------------------------------------
 // op = f + 2*k: PIL FLIP_LEFT_RIGHT when f, then k times ROTATE_90 (counter-clockwise; out[i][j] = in[j][S-1-i]).
 // One thread per output pixel: all C channels of the image (ToTensor + Normalize: (v/255 - mean)/std in fp32, IEEE
@@ -166,6 +189,13 @@ extern "C" int rs_softvote_masks(const uint8_t* q, const double* weights, const 
                                  int C, rs_stream_t stream) {
   if (!q || !anchors || !out || K <= 0 || P <= 0 || C < 2 || C > 8) return RS_EINVAL;
   softvote_kernel<<<rs_cdiv(P, 256), 256, 0, (hipStream_t)stream>>>(q, weights, anchors, out, K, P, C - 1);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_softvote_masks_threshold(const uint8_t* q, const double* weights, const double* anchors, uint8_t* out, int K, long P,
+                                           const double* threshold, rs_stream_t stream) {
+  if (!q || !anchors || !out || !threshold || K <= 0 || P <= 0 || !(*threshold > 0.0 && *threshold <= 1.0)) return RS_EINVAL;  // (false for NaN too)
+  softvote_threshold_kernel<<<rs_cdiv(P, 256), 256, 0, (hipStream_t)stream>>>(q, weights, anchors, out, K, P, *threshold);
   return RS_LAUNCH_RESULT();
 }
 

@@ -127,11 +127,13 @@ def boundary_report(d, counts):
     return {"d": int(d), "predicted": predicted, "actual": actual, "shared": shared, "iou": _ratio(shared, predicted + actual - shared)}
 
 
-def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None, ignore=None, ignored=0):
+def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None, ignore=None, ignored=0,
+                 probability=None):
     """The report of one run.  ``matrix``: C x C Python integers summed over every evaluated tile; ``kind``: ``--type`` or None;
     ``objects`` / ``boundary``: ``ObjectScores.report()`` / ``boundary_report()`` or None.  With the dataset's ``ignore`` label the
     report also carries it and ``ignored``, the pixels whose label has that value: they are in no cell, so ``pixels`` (the matrix's
-    sum) counts the valid ones and ``pixels + ignored`` is every pixel of the evaluated tiles."""
+    sum) counts the valid ones and ``pixels + ignored`` is every pixel of the evaluated tiles.  ``probability`` (with ``--probs``):
+    ``probability_report()``, the last key."""
 
     matrix = [[int(v) for v in row] for row in matrix]
     report = {
@@ -150,14 +152,18 @@ def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects
         report["objects"] = objects
     if boundary is not None:
         report["boundary"] = boundary
+    if probability is not None:
+        report["probability"] = probability
     return report
 
 
-def tile_rows(tiles, matrices, classes, kind=None, ignored=None):
+def tile_rows(tiles, matrices, classes, kind=None, ignored=None, brier=None):
     """One row per evaluated tile: ``tiles`` and their C x C matrices -> dicts with z, x, y, pixels, iou_<class> per class, miou,
     predicted_share, actual_share (the share of non-background pixels on each side), sorted worst first: by the IoU of ``kind``
     (``--type``), or by miou without it, undefined values last, then by (z, x, y).  ``ignored`` (with the dataset's ignore label):
-    the tiles' counts of ignored label pixels, an ``ignored`` entry of each row; ``pixels`` and the shares are over the valid ones."""
+    the tiles' counts of ignored label pixels, an ``ignored`` entry of each row; ``pixels`` and the shares are over the valid ones.
+    ``brier`` (with ``--probs``): the tiles' own Brier scores (``brier_score``), a ``brier`` entry of each row; it has no say in the
+    order."""
 
     rows = []
     for i, (tile, matrix) in enumerate(zip(tiles, matrices)):
@@ -172,24 +178,171 @@ def tile_rows(tiles, matrices, classes, kind=None, ignored=None):
         row["miou"] = scores["miou"]
         row["predicted_share"] = _ratio(total - int(matrix[:, 0].sum()), total)
         row["actual_share"] = _ratio(total - int(matrix[0, :].sum()), total)
+        if brier is not None:
+            row["brier"] = brier[i]
         rows.append(row)
     column = "miou" if kind is None else "iou_" + kind
     rows.sort(key=lambda r: (r[column] is None, r[column] if r[column] is not None else 0.0, r["z"], r["x"], r["y"]))
     return rows
 
 
-def tile_columns(classes, ignored=False):
+def tile_columns(classes, ignored=False, brier=False):
     return (["z", "x", "y", "pixels"] + (["ignored"] if ignored else []) + ["iou_" + name for name in classes]
-            + ["miou", "predicted_share", "actual_share"])
+            + ["miou", "predicted_share", "actual_share"] + (["brier"] if brier else []))
 
 
-def write_tile_rows(path, rows, classes, ignored=False):
+def write_tile_rows(path, rows, classes, ignored=False, brier=False):
     """``tile_rows`` as CSV; an undefined value is an empty field, a float is written with ``repr`` (it reads back as it was).
-    ``ignored``: the rows carry the ``ignored`` column (``tile_rows`` was given the counts)."""
+    ``ignored`` / ``brier``: the rows carry that column (``tile_rows`` was given the values)."""
 
     with open(path, "w", newline="") as fp:
         writer = csv.writer(fp)
-        columns = tile_columns(classes, ignored)
+        columns = tile_columns(classes, ignored, brier)
         writer.writerow(columns)
         for row in rows:
             writer.writerow(["" if row[c] is None else repr(row[c]) for c in columns])
+
+
+# ---- rs evaluate --probs: scores of the probability bytes of one class (DESIGN.md, "rs evaluate --probs") ----------------------
+CALIBRATION_BINS = 10
+ANCHORS = np.linspace(0, 1, 256)  # a byte's probability: what ``rs masks`` and ``rs features --score`` un-quantise it to
+
+POINT_COLUMNS = ["threshold_byte", "threshold", "tp", "fp", "fn", "tn", "precision", "recall", "f1", "iou"]
+
+
+def _fraction(num, den):
+    return Fraction(num, den) if den else None
+
+
+def _float(value):
+    return None if value is None else float(value)
+
+
+def _histograms(pos, neg):
+    pos, neg = [int(v) for v in pos], [int(v) for v in neg]
+    if len(pos) != 256 or len(neg) != 256 or min(pos + neg) < 0:
+        raise ValueError("robosat_amd: 256 counts of positives and 256 of negatives, none below zero")
+    return pos, neg
+
+
+def _points(pos, neg):
+    """The 256 operating points "predict the class where byte >= k" as (k, tp, fp, fn, tn)."""
+
+    p, n = sum(pos), sum(neg)
+    points, tp, fp = [None] * 256, 0, 0
+    for k in range(255, -1, -1):
+        tp += pos[k]
+        fp += neg[k]
+        points[k] = (k, tp, fp, p - tp, n - fp)
+    return points
+
+
+def _point_scores(point):
+    """(precision, recall, F1, IoU) of an operating point as fractions, None where undefined."""
+
+    _, tp, fp, fn, _ = point
+    return _fraction(tp, tp + fp), _fraction(tp, tp + fn), _fraction(2 * tp, 2 * tp + fp + fn), _fraction(tp, tp + fp + fn)
+
+
+def _point_row(point):
+    k, tp, fp, fn, tn = point
+    precision, recall, f1, iou = _point_scores(point)
+    return {"threshold_byte": k, "threshold": float(ANCHORS[k]), "tp": tp, "fp": fp, "fn": fn, "tn": tn,
+            "precision": _float(precision), "recall": _float(recall), "f1": _float(f1), "iou": _float(iou)}
+
+
+def _best(points, which):
+    """The point with the highest exact score (2: F1, 3: IoU), the smallest k among equals; None where no point has one."""
+
+    best, best_score = None, None
+    for point in points:
+        score = _point_scores(point)[which]
+        if score is not None and (best_score is None or score > best_score):
+            best, best_score = point, score
+    return best
+
+
+def curve_rows(pos, neg):
+    """The 256 operating points, k = 0 .. 255: dicts of ``POINT_COLUMNS``."""
+
+    return [_point_row(point) for point in _points(*_histograms(pos, neg))]
+
+
+def write_curve_rows(path, rows):
+    """``curve_rows`` as CSV; an undefined value is an empty field, a float is written with ``repr``, like ``write_tile_rows``."""
+
+    with open(path, "w", newline="") as fp:
+        writer = csv.writer(fp)
+        writer.writerow(POINT_COLUMNS)
+        for row in rows:
+            writer.writerow(["" if row[c] is None else repr(row[c]) for c in POINT_COLUMNS])
+
+
+def brier_score(pos, neg):
+    """sum_q (pos[q] (255 - q)^2 + neg[q] q^2) / (255^2 (P + N)) as a float, None for no pixels."""
+
+    pos, neg = _histograms(pos, neg)
+    total = sum(pos) + sum(neg)
+    return _float(_fraction(sum(pos[q] * (255 - q) ** 2 + neg[q] * q * q for q in range(256)), 255 * 255 * total))
+
+
+def probability_scores(pos, neg):
+    """``pos[q]`` / ``neg[q]``: the pixels with probability byte q whose label is / is not the class, 256 integers each, summed
+    over the tiles -> the report's ``probability`` scores: ap, auc, brier, ece, calibration, best_f1, best_iou, at_half.  Every
+    score is an exact fraction of integers turned into a float once; an undefined one is None."""
+
+    pos, neg = _histograms(pos, neg)
+    p, n = sum(pos), sum(neg)
+    total = p + n
+    points = _points(pos, neg)
+
+    ap = None
+    if p:
+        ap, above = Fraction(0), 0  # above: TP_{k+1}
+        for k, tp, fp, _, _ in reversed(points):
+            if tp != above:  # (a step of recall; tp > 0 here, so the precision is defined)
+                ap += Fraction(tp - above, p) * Fraction(tp, tp + fp)
+            above = tp
+    auc = None
+    if p and n:
+        below, wins = 0, 0  # below: N_{<q}; wins: twice the pairs won, ties counting half
+        for q in range(256):
+            wins += pos[q] * (2 * below + neg[q])
+            below += neg[q]
+        auc = Fraction(wins, 2 * p * n)
+
+    bins = []
+    ece = Fraction(0) if total else None
+    for b in range(CALIBRATION_BINS):
+        members = [q for q in range(256) if min(CALIBRATION_BINS * q // 255, CALIBRATION_BINS - 1) == b]
+        pixels = sum(pos[q] + neg[q] for q in members)
+        confidence = _fraction(sum(q * (pos[q] + neg[q]) for q in members), 255 * pixels)
+        accuracy = _fraction(sum(pos[q] for q in members), pixels)
+        if pixels:
+            ece += Fraction(pixels, total) * abs(accuracy - confidence)
+        bins.append({"lo": float(ANCHORS[members[0]]), "hi": float(ANCHORS[members[-1]]), "pixels": pixels,
+                     "confidence": _float(confidence), "accuracy": _float(accuracy)})
+
+    best_f1, best_iou = _best(points, 2), _best(points, 3)
+    return {
+        "ap": _float(ap),
+        "auc": _float(auc),
+        "brier": brier_score(pos, neg),
+        "ece": _float(ece),
+        "calibration": bins,
+        "best_f1": None if best_f1 is None else _point_row(best_f1),
+        "best_iou": None if best_iou is None else _point_row(best_iou),
+        "at_half": _point_row(points[128]),
+    }
+
+
+def probability_report(kind, pos, neg, ignored=None):
+    """The report's ``probability``: the class, ``pixels`` (those with a label that is a class), ``positives``, with the dataset's
+    ignore label ``ignored``, and ``probability_scores``."""
+
+    pos, neg = _histograms(pos, neg)
+    report = {"class": kind, "pixels": sum(pos) + sum(neg), "positives": sum(pos)}
+    if ignored is not None:
+        report["ignored"] = int(ignored)
+    report.update(probability_scores(pos, neg))
+    return report

@@ -1404,15 +1404,26 @@ def label_histogram_u8(labels, counts256):
     return counts256
 
 
-def softvote_masks(quantized, weights=None):
+def softvote_masks(quantized, weights=None, threshold=None):
     """quantized uint8 [K, P] (binary models) or [K, P, C-1] -> uint8 [P] class indices: the weighted soft vote of
-    tools/masks.py:42-84 over K models' probability bytes."""
+    tools/masks.py:42-84 over K models' probability bytes.  With ``threshold`` (binary models only, 0 < T <= 1) the mask is
+    ``voted foreground >= T`` in place of the argmax (``rs_softvote_masks_threshold``)."""
 
     if quantized.dim() == 2:
         quantized = quantized.unsqueeze(-1)
     k, p, cq = quantized.shape
     out = torch.empty(p, device=quantized.device, dtype=torch.uint8)
     wt = None if weights is None else torch.as_tensor(list(weights), dtype=torch.float64).to(quantized.device)
+    if threshold is not None:
+        threshold = float(threshold)
+        if cq != 1:
+            raise ValueError("robosat_amd: a threshold cuts the one foreground probability of a binary model; these probabilities "
+                             "are of {} classes".format(cq + 1))
+        if not 0 < threshold <= 1:  # (false for nan too)
+            raise ValueError("robosat_amd: the threshold is a probability, 0 < T <= 1, got {}".format(threshold))
+        _call("rs_softvote_masks_threshold", _dev(quantized, "quantized", torch.uint8), _dev(wt, "weights", torch.float64),
+              _dev(_anchors(quantized.device), "anchors", torch.float64), _dev(out, "out", torch.uint8), k, p, ctypes.byref(ctypes.c_double(threshold)), _stream())
+        return out
     _call("rs_softvote_masks", _dev(quantized, "quantized", torch.uint8), _dev(wt, "weights", torch.float64),
           _dev(_anchors(quantized.device), "anchors", torch.float64), _dev(out, "out", torch.uint8), k, p, cq + 1, _stream())
     return out
@@ -2033,6 +2044,30 @@ def mask_confusion(predicted_u8, actual_u8, classes, stitched=False, ignore=None
     _call("rs_eval_confusion", p, a, _dev(counts, "counts", torch.int64), _dev(bad, "bad", torch.int64), pixels,
           pixels if stitched else hw, classes, _stream())
     return counts, bad
+
+
+def prob_histogram(prob_u8, actual_u8, classes, cls, stitched=False, ignore=None):
+    """The probability bytes of class ``cls`` (what ``rs predict`` stores: byte q stands for q / 255) and the labels, both uint8
+    [B, H, W] -> (hist int64 [G, 2, 256], bad int64 [G], ignored int64 [G]): per tile (G = B), or with ``stitched`` for the one
+    raster the B tiles form (G = 1), ``hist[g][pos][q]`` = the pixels with byte q and (label == cls) == pos among the pixels whose
+    label is a class of 0 .. ``classes`` - 1; ``bad``: the pixels whose label is no class and not ``ignore``; ``ignored``: those
+    whose label is ``ignore`` (all zero without one).  Neither kind is in a cell.  2 <= ``classes`` <= 8, 1 <= ``cls`` < ``classes``
+    (``rs_eval_prob_hist``)."""
+
+    classes = int(classes)
+    if not 2 <= classes <= EVAL_MAX_CLASSES:
+        raise ValueError("robosat_amd: 2 to {} classes are counted, got {}".format(EVAL_MAX_CLASSES, classes))
+    if isinstance(cls, bool) or int(cls) != cls or not 1 <= int(cls) < classes:
+        raise ValueError("robosat_amd: the class of the probabilities is a non-background one, 1..{}, got {!r}".format(classes - 1, cls))
+    ignore = _ignore_label(ignore, classes)
+    q, a, pixels, hw = _eval_pair(prob_u8, actual_u8, ("prob", "actual"), torch.uint8)
+    groups = 1 if stitched else prob_u8.shape[0]
+    # (one buffer, `skipped` behind `hist`: the library then zeroes both with one fill)
+    both = torch.empty(groups * 514, device=prob_u8.device, dtype=torch.int64)
+    hist, skipped = both[:groups * 512].view(groups, 2, 256), both[groups * 512:].view(groups, 2)
+    _call("rs_eval_prob_hist", q, a, _dev(hist, "hist", torch.int64), _dev(skipped, "skipped", torch.int64), pixels,
+          pixels if stitched else hw, classes, int(cls), -1 if ignore is None else ignore, _stream())
+    return hist, skipped[:, 0], skipped[:, 1]
 
 
 def boundary_counts(d2_a, d2_b, d, stitched=False):

@@ -16,6 +16,13 @@ With the dataset's ``[common] ignore`` a pixel whose LABEL has that value is in 
 class still ends the run.  With ``--type`` a label tile that holds an ignored pixel ends the run, naming the tile: what a
 boundary or an object cut by an unknown region should count as is not defined yet.
 
+With ``--probs DIR`` (the probability tiles ``rs predict`` wrote for these masks, one model) a fourth view is added: the joint
+histogram of (label is the class, probability byte) per tile (``ops.prob_histogram``), summed over the tiles, from which the host
+forms the 256 operating points "byte >= k", average precision, AUC, the Brier score, a ten-bin calibration table with its ECE, and
+the thresholds with the best F1 and IoU (``--curve`` lists every point; ``rs masks --threshold`` applies one).  The class is
+``--type`` where given, class 1 otherwise.  Because ``--type`` refuses label tiles with ignored pixels, a multi-class dataset with
+ignored pixels has no probability view yet.
+
 The definitions are in ``include/robosat_hip.h`` and DESIGN.md."""
 
 import argparse
@@ -23,16 +30,19 @@ import json
 import os
 import sys
 
+import numpy as np
 import torch
 from PIL import Image
 from tqdm import tqdm
 
 from robosat_amd import ops
 from robosat_amd.config import ignore_label, load_config
-from robosat_amd.evaluate import ObjectScores, boundary_report, build_report, tile_rows, write_tile_rows
+from robosat_amd.evaluate import (ObjectScores, boundary_report, brier_score, build_report, curve_rows, probability_report, tile_rows,
+                                  write_curve_rows, write_tile_rows)
 from robosat_amd.features import group_clusters, pack_clusters, stitch_tables
 from robosat_amd.tiles import tiles_from_slippy_map
 from robosat_amd.tools.features import _load, _tile_sizes
+from robosat_amd.tools.masks import load_quantized
 
 
 def add_parser(subparser):
@@ -63,6 +73,16 @@ def add_parser(subparser):
                         help="path to a CSV with one row per evaluated tile: z, x, y, pixels, the IoU of every class, miou and the share "
                         "of non-background pixels on each side, sorted worst first by the IoU of --type (by miou without it); with the "
                         "dataset's [common] ignore also the tile's ignored label pixels, and pixels are the others")
+    parser.add_argument("--probs", type=str, default=None, metavar="DIR",
+                        help="slippy map directory with the probabilities rs predict wrote for these masks (one model): adds "
+                        "'probability' to the report: the 256 thresholds 'byte >= k' of the class's probability against the labels, "
+                        "average precision, AUC, Brier score, calibration and the thresholds with the best F1 and IoU. The class is "
+                        "--type where given, else class 1; a dataset with more than two classes needs --type. As --type refuses label "
+                        "tiles with ignored pixels, a multi-class dataset with ignored pixels has no probability view yet. With "
+                        "--tiles the rows gain the tile's own Brier score")
+    parser.add_argument("--curve", type=str, default=None, metavar="CSV",
+                        help="with --probs: path to a CSV with the 256 operating points: threshold_byte, threshold, tp, fp, fn, tn, "
+                        "precision, recall, f1, iou")
     parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
     parser.set_defaults(func=main)
 
@@ -95,6 +115,15 @@ def validate(args, classes):
     for name in ("masks", "labels"):
         if not os.path.isdir(getattr(args, name)):
             sys.exit("Error: {} is not a directory".format(getattr(args, name)))
+    if args.probs is None:
+        if args.curve is not None:
+            sys.exit("Error: --curve lists the operating points of the probabilities: not without --probs")
+    else:
+        if not os.path.isdir(args.probs):
+            sys.exit("Error: {} is not a directory".format(args.probs))
+        if len(classes) > 2 and args.type is None:
+            sys.exit("Error: --probs scores the probabilities of one class; the dataset has {} classes: give --type ({})".format(
+                len(classes), ", ".join(classes[1:])))
     if args.stitch and args.boundary:  # (the tile sizes are in the PNG headers: no device needed to say this)
         for h, w in sorted({shape for _, _, shape in _tile_sizes(args.masks)}):
             if args.boundary + 1 > min(h, w):
@@ -107,11 +136,52 @@ def _name(tile):
     return "{}/{}/{}".format(tile.z, tile.x, tile.y)
 
 
+class Probabilities:
+    """``--probs``: the probability tiles of one model, the plane of one class (``channel`` = class index - 1), and the sums of
+    the histograms."""
+
+    def __init__(self, directory, channel, per_tile=False):
+        self.directory, self.channel = directory, channel
+        self.paths = {tile: path for tile, path in tiles_from_slippy_map(directory)}
+        self.pos, self.neg = [0] * 256, [0] * 256  # Python integers: no bound on the pixels of a run
+        self.ignored = 0
+        self.brier = [] if per_tile else None  # (the tiles' own Brier scores: for --tiles alone)
+
+    def load(self, tiles, shape, device):
+        """uint8 [T, H, W]: the bytes of the class, the tiles in order (as ``tools/features.py``'s ``Score.load`` reads them)."""
+
+        planes = []
+        for tile in tiles:
+            path = self.paths.get(tile)
+            if path is None:
+                sys.exit("Error: --probs {} has no probabilities for the mask tile {}".format(self.directory, _name(tile)))
+            q = load_quantized(path)
+            if q.shape[:2] != tuple(shape):
+                sys.exit("Error: {} is {}x{}; the mask tile {} is {}x{}".format(path, q.shape[0], q.shape[1], _name(tile), shape[0], shape[1]))
+            if self.channel >= q.shape[2]:
+                sys.exit("Error: {} (tile {}) holds the probabilities of {} classes; the class to score is class {} of the dataset".format(
+                    path, _name(tile), q.shape[2] + 1, self.channel + 1))
+            planes.append(np.ascontiguousarray(q[:, :, self.channel], dtype=np.uint8))
+        return torch.from_numpy(np.stack(planes)).to(device)
+
+    def add(self, hist, ignored):
+        """``ops.prob_histogram``'s [T, 2, 256] and its [T] ignored pixels: summed over the tiles on the device, and with
+        ``per_tile`` every tile's own Brier score kept."""
+
+        neg, pos = hist.sum(dim=0).tolist()
+        for q in range(256):
+            self.pos[q] += pos[q]
+            self.neg[q] += neg[q]
+        self.ignored += int(ignored.sum())
+        if self.brier is not None:
+            self.brier.extend(brier_score(tile_pos, tile_neg) for tile_neg, tile_pos in hist.tolist())
+
+
 class Evaluation:
     """The sums of a run, and the device stages of one batch (tiles on their own) or call (tiles as one sparse raster)."""
 
-    def __init__(self, classes, index, boundary, objects, ignore=None):
-        self.classes, self.index, self.boundary, self.objects, self.ignore = classes, index, boundary, objects, ignore
+    def __init__(self, classes, index, boundary, objects, ignore=None, probs=None):
+        self.classes, self.index, self.boundary, self.objects, self.ignore, self.probs = classes, index, boundary, objects, ignore, probs
         n = len(classes)
         self.matrix = [[0] * n for _ in range(n)]  # Python integers: no bound on the pixels of a run
         self.band = [0, 0, 0]
@@ -147,6 +217,14 @@ class Evaluation:
             for a, row in enumerate(matrix):
                 for p, v in enumerate(row):
                     self.matrix[a][p] += v
+        if self.probs is not None:  # (a pixel view: per tile with or without --stitch)
+            hist, wrong, unknown = ops.prob_histogram(self.probs.load(tiles, shape, device), actual, len(self.classes),
+                                                      self.probs.channel + 1, ignore=self.ignore)
+            # the histogram's own counts of bad and ignored labels.  A bad byte, in the mask or the label, ended the run above, so no
+            # label is bad here and the ignored labels are the ones the confusion call counted (it counts them over a mask byte that
+            # is a class only): the probability view's pixels + ignored are the report's.
+            assert not wrong.any().item() and (self.ignore is None or unknown.tolist() == ignored), "the two counting calls disagree"
+            self.probs.add(hist, unknown)
         if self.index is None:
             return
         stitched = nbr is not None
@@ -170,6 +248,8 @@ class Evaluation:
 
 
 def main(args):
+    # (callers that build the arguments themselves may predate the two flags)
+    args.probs, args.curve = getattr(args, "probs", None), getattr(args, "curve", None)
     dataset = load_config(args.dataset)
     classes = dataset["common"]["classes"]
     try:
@@ -182,7 +262,8 @@ def main(args):
     device = torch.device("cuda", 0)
     index = None if args.type is None else classes.index(args.type)
     objects = None if index is None else ObjectScores(match, min_area, args.stitch)
-    run = Evaluation(classes, index, args.boundary, objects, ignore)
+    probs = None if args.probs is None else Probabilities(args.probs, (1 if index is None else index) - 1, per_tile=args.tiles is not None)
+    run = Evaluation(classes, index, args.boundary, objects, ignore, probs)
 
     label_paths = {tile: path for tile, path in tiles_from_slippy_map(args.labels)}
     without_label = 0
@@ -224,15 +305,20 @@ def main(args):
     report = build_report(classes, run.matrix, len(run.tiles), without_label, kind=args.type,
                           objects=None if objects is None else objects.report(),
                           boundary=boundary_report(args.boundary, run.band) if args.boundary else None,
-                          **({} if ignore is None else {"ignore": ignore, "ignored": sum(run.ignored)}))
+                          **({} if ignore is None else {"ignore": ignore, "ignored": sum(run.ignored)}),
+                          **({} if probs is None else {"probability": probability_report(
+                              classes[probs.channel + 1], probs.pos, probs.neg, None if ignore is None else probs.ignored)}))
     with open(args.out, "w") as fp:
         json.dump(report, fp, indent=2, allow_nan=False)
         fp.write("\n")
+    if args.curve is not None:
+        write_curve_rows(args.curve, curve_rows(probs.pos, probs.neg))
     if args.tiles is not None:
+        extra = {} if probs is None else {"brier": probs.brier}
         if ignore is None:
-            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type), classes)
+            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, **extra), classes, brier=probs is not None)
         else:
-            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, ignored=run.ignored), classes,
-                            ignored=True)
+            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, ignored=run.ignored, **extra), classes,
+                            ignored=True, brier=probs is not None)
     if without_label:
         print("Evaluate: {} mask tiles without a label were skipped".format(without_label), file=sys.stderr)

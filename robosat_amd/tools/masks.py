@@ -6,7 +6,11 @@ and in the reference's summation order: the masks are byte-identical to numpy's.
 Probability encoding (what ``rs predict`` writes): binary models -> the reference's single-channel mode-P PNG holding the
 quantised foreground probability.  Models with 3 / 4 / 5 classes (which the reference's predict asserts away,
 predict.py:98) -> mode LA / RGB / RGBA PNGs holding the quantised probability of every non-background class; the
-background is 1 - their sum.  ``--dataset`` (optional, extension) takes the palette from the dataset's ``colors``."""
+background is 1 - their sum.  ``--dataset`` (optional, extension) takes the palette from the dataset's ``colors``.
+
+``--threshold T`` (extension, binary models only): the mask is ``voted foreground probability >= T`` in place of the argmax
+(``rs_softvote_masks_threshold``); with one model and ``T`` a threshold that ``rs evaluate --probs`` reports, the mask is that
+report's operating point.  Without the flag nothing changes."""
 
 import argparse
 import os
@@ -37,6 +41,9 @@ def add_parser(subparser):
     parser.add_argument("probs", type=str, nargs="+", help="slippy map directories with class probabilities")
     parser.add_argument("--weights", type=float, nargs="+", help="weights for weighted average soft-voting")
     parser.add_argument("--dataset", type=str, required=False, help="dataset configuration file to take the mask colors from")
+    parser.add_argument("--threshold", type=float, default=None, metavar="T",
+                        help="binary models only: foreground where the voted probability is at least T, 0 < T <= 1, in place of the "
+                        "argmax (for instance best_iou.threshold of rs evaluate --probs)")
     parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
     parser.set_defaults(func=main)
 
@@ -51,9 +58,30 @@ def load_quantized(path):
     return q[:, :, None] if q.ndim == 2 else q
 
 
+def _channels(path):
+    """The channels ``load_quantized`` gives for the PNG at ``path``, from its header."""
+
+    with Image.open(path) as image:
+        return MODE_CHANNELS.get(image.mode, 1)
+
+
+def _refuse_threshold(path, channels):
+    if channels != 1:
+        sys.exit("Error: --threshold cuts the foreground probability of a binary model; {} holds the probabilities of {} classes".format(
+            path, channels + 1))
+
+
 def main(args):
     if args.weights and len(args.probs) != len(args.weights):
         sys.exit("Error: number of slippy map directories and weights must be the same")
+    args.threshold = getattr(args, "threshold", None)  # (callers that build the arguments themselves may predate the flag)
+    if args.threshold is not None:
+        if not 0 < args.threshold <= 1:  # (false for nan too)
+            sys.exit("Error: --threshold is a probability, 0 < T <= 1, got {}".format(args.threshold))
+        for directory in args.probs:  # (the channels are in the PNG header: no device needed to say this)
+            for _, path in tiles_from_slippy_map(directory):
+                _refuse_threshold(path, _channels(path))
+                break
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
@@ -79,7 +107,11 @@ def main(args):
         k, (h, w, cq) = len(stacks[0]), shape
         q = np.stack([np.stack([tileset[m] for tileset in stacks]) for m in range(k)])  # [K, B, H, W, Cq]
         dq = torch.from_numpy(q).to(device).view(k, -1, cq)
-        masks = ops.softvote_masks(dq, args.weights).view(len(group), h, w).cpu().numpy()
+        if args.threshold is None:
+            masks = ops.softvote_masks(dq, args.weights).view(len(group), h, w).cpu().numpy()
+        else:
+            _refuse_threshold(group[0][0][1], cq)
+            masks = ops.softvote_masks(dq, args.weights, threshold=args.threshold).view(len(group), h, w).cpu().numpy()
 
         names = colors or (["denim", "orange"] if cq == 1 else DEFAULT_COLORS[:cq + 1])
         if len(names) < cq + 1:

@@ -49,6 +49,11 @@
            profiles/evaluate/bench_evaluate.json (`--evaluate-leg --stage-loop N`: the calls at the three bounds N times, for
            rocprofv3; `--evaluate-leg --stage-loop N --phases TRACE.csv`: no device, that run's kernel trace -> median us per launch)
 
+  --evaluate-probs-leg   `rs evaluate --probs`: `ops.prob_histogram` beside `ops.mask_confusion` on the same two rasters and
+           `ops.label_histogram_u8` over both, per call, on the blob batch as labels with three probability rasters (blob-like:
+           bytes 1 and 254 with a soft edge; all one byte; uniformly random bytes) and on one tile cut into 8 x 8 tiles, written to
+           profiles/evaluate_probs/bench_evaluate_probs.json (`--stage-loop N` and `--phases TRACE.csv` as for --evaluate-leg)
+
 Compare `device.blobs` with the predict leg of `python bench.py` measured in the same session.  `--stage-loop N` only runs
 the device stage N times (for `rocprofv3 --kernel-trace --stats -- python scripts/bench_features.py --stage-loop 20`)."""
 
@@ -833,6 +838,108 @@ def evaluate_leg(args):
     print(json.dumps(result, sort_keys=True))
 
 
+PROBS_PHASES = ["blobs", "one_byte", "random", "small_tiles"]  # (the stage loop's order)
+
+
+def probs_rasters(batch, size):
+    """The labels (the blob batch, classes 0 / 1) and the probability rasters of `--evaluate-probs-leg`, as numpy: blob-like
+    (the blobs a few pixels away, saturated to bytes 1 and 254 with a soft edge: a 5 x 5 mean of the mask), all one byte, and
+    uniformly random bytes; `small_tiles`: the first blob-like tile and its labels as (size / 8)^2 tiles of 8 x 8, so that a block
+    of 4 096 pixels holds 64 groups."""
+
+    blobs = blob_masks(batch, size, 0)
+    moved = np.roll(blobs, (3, 5), axis=(1, 2)).astype(np.float64)
+    mean = sum(np.roll(moved, (dy, dx), axis=(1, 2)) for dy in range(-2, 3) for dx in range(-2, 3)) / 25.0
+    soft = (1 + np.rint(253 * mean)).astype(np.uint8)
+    rng = np.random.RandomState(9)
+    return {
+        "blobs": (soft, blobs),
+        "one_byte": (np.ones_like(blobs), blobs),
+        "random": (rng.randint(0, 256, size=blobs.shape).astype(np.uint8), blobs),
+        "small_tiles": (soft[0].reshape(-1, 8, 8), blobs[0].reshape(-1, 8, 8)),
+    }
+
+
+def probs_phases(path, loop):
+    """The kernel trace of `--evaluate-probs-leg --stage-loop N` (rocprofv3's *_kernel_trace.csv) -> median us per launch of the
+    probability histogram, of the confusion kernel on the same two rasters and of the label histogram (its two launches, one per
+    raster, summed) in each of the loop's phases, and the ratio of the first to the second."""
+
+    import csv
+    import statistics
+
+    names = ("eval_prob_hist_kernel", "eval_confusion_kernel", "label_histogram_kernel")
+    with open(path) as fp:
+        rows = sorted(csv.DictReader(fp), key=lambda r: int(r["Start_Timestamp"]))
+    result = {"loop": loop, "us_per_launch_median": {}, "prob_hist_over_confusion": {},
+              "note": "eval_confusion_kernel reads the probability bytes as class indices here: a byte above 1 is no class, so on the blob-like "
+                      "and the random raster most pixels meet in its one bad counter per tile, its slow bound. A ratio below 1 on those "
+                      "rasters says that, not that the histogram beats the confusion kernel on class rasters (5.9-7.0 us there)"}
+    for name in names:
+        times = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if name in r["Kernel_Name"]]
+        per = 2 if name == "label_histogram_kernel" else 1
+        if len(times) != per * loop * len(PROBS_PHASES):
+            raise SystemExit("{} launches of {} in {}, {} x {} x {} expected".format(len(times), name, path, len(PROBS_PHASES), loop, per))
+        times = [sum(times[i:i + per]) for i in range(0, len(times), per)]
+        for i, phase in enumerate(PROBS_PHASES):
+            key = name if per == 1 else name + "_both_rasters"
+            result["us_per_launch_median"].setdefault(phase, {})[key] = round(statistics.median(times[i * loop:(i + 1) * loop]), 2)
+    for phase, row in result["us_per_launch_median"].items():
+        result["prob_hist_over_confusion"][phase] = round(row["eval_prob_hist_kernel"] / row["eval_confusion_kernel"], 2)
+    print(json.dumps(result, indent=1, sort_keys=True))
+
+
+def evaluate_probs_leg(args):
+    """`rs evaluate --probs`: `ops.prob_histogram` beside `ops.mask_confusion` on the same two rasters (the yardstick: it reads the
+    same bytes) and beside the label histogram over both (the design to beat), on the three probability rasters and on small tiles."""
+
+    if args.phases:
+        return probs_phases(args.phases, args.stage_loop)
+
+    import torch
+
+    from robosat_amd import ops
+
+    r = args.repeat
+    rasters = {name: tuple(torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0") for a in pair)
+               for name, pair in probs_rasters(args.batch, args.size).items()}
+    hist = torch.zeros(256, dtype=torch.int64, device="cuda:0")
+
+    if args.stage_loop:
+        for name in PROBS_PHASES:  # (in this order in the trace)
+            q, a = rasters[name]
+            for _ in range(args.stage_loop):
+                ops.prob_histogram(q, a, 2, 1)
+                ops.mask_confusion(q, a, 2)
+                ops.label_histogram_u8(q.view(-1), hist)
+                ops.label_histogram_u8(a.view(-1), hist)
+        torch.cuda.synchronize()
+        return
+
+    result = {"batch": args.batch, "size": args.size, "block_pixels": ops.eval_config(), "us_per_call": {}, "nonempty_bins": {}}
+    for name in PROBS_PHASES:  # (calls enqueued back to back: launch + the fill of the outputs, no copy to the host)
+        q, a = rasters[name]
+        counts = ops.prob_histogram(q, a, 2, 1)[0]
+        result["nonempty_bins"][name] = {"tiles": int(counts.shape[0]), "per_tile_mean": float((counts > 0).sum().item() / counts.shape[0])}
+        result["us_per_call"][name] = {
+            "prob_histogram": timed(lambda: ops.prob_histogram(q, a, 2, 1), 10 * r) * 1e6,
+            "mask_confusion": timed(lambda: ops.mask_confusion(q, a, 2), 10 * r) * 1e6,
+            "label_histogram_u8_both_rasters": timed(lambda: (ops.label_histogram_u8(q.view(-1), hist), ops.label_histogram_u8(a.view(-1), hist)),
+                                                     10 * r) * 1e6,
+        }
+    q, a = rasters["blobs"]
+    result["ms_per_batch_with_copy"] = {
+        "prob_histogram": timed(lambda: ops.prob_histogram(q, a, 2, 1)[0].cpu(), r) * 1e3,
+        "mask_confusion": timed(lambda: ops.mask_confusion(q, a, 2)[0].cpu(), r) * 1e3,
+    }
+    out = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "evaluate_probs", "bench_evaluate_probs.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fp:
+        json.dump(result, fp, indent=1, sort_keys=True)
+        fp.write("\n")
+    print(json.dumps(result, sort_keys=True))
+
+
 def device_stage(images, eps):
     import torch
 
@@ -882,7 +989,7 @@ def main():
     ap.add_argument("--centerline-leg", action="store_true", help="only thinning and links, on a road network and on its n x n block")
     ap.add_argument("--dedupe-leg", action="store_true", help="only rs features --dedupe: the stages with and without the reference")
     ap.add_argument("--score-leg", action="store_true", help="only rs features --score: the stages with and without the per-component sums")
-    ap.add_argument("--phases", type=str, default=None, help="--score-leg / --evaluate-leg --stage-loop N: the kernel trace of that run, split by phase (no device)")
+    ap.add_argument("--phases", type=str, default=None, help="--score-leg / --evaluate-leg / --evaluate-probs-leg --stage-loop N: the kernel trace of that run, split by phase (no device)")
     ap.add_argument("--width-leg", action="store_true", help="only rs features --width: the distance transform beside the thinning")
     ap.add_argument("--without-only", action="store_true", help="--width-leg: only the stages without the transform")
     ap.add_argument("--max-width", type=int, default=64, help="--width-leg: as --max_width of rs features (radius N // 2 + 2)")
@@ -892,6 +999,8 @@ def main():
     ap.add_argument("--fused", type=int, default=0, help="--split-leg --stage-loop: the knob grow_fused (0 = the rule)")
     ap.add_argument("--evaluate-leg", action="store_true", help="only rs evaluate: the counting pass, the boundary band and the object stages")
     ap.add_argument("--boundary", type=int, default=3, help="--evaluate-leg: as --boundary of rs evaluate")
+    ap.add_argument("--evaluate-probs-leg", action="store_true",
+                    help="only rs evaluate --probs: the probability histogram beside the confusion kernel and the label histogram")
     ap.add_argument("--block", type=int, default=8, help="tiles per side of the stitched legs' block")
     ap.add_argument("--out", type=str, default=DEFAULT_OUT)
     args = ap.parse_args()
@@ -909,6 +1018,8 @@ def main():
         return split_leg(args)
     if args.evaluate_leg:
         return evaluate_leg(args)
+    if args.evaluate_probs_leg:
+        return evaluate_probs_leg(args)
 
     import torch
 
