@@ -950,6 +950,40 @@ int rs_eval_confusion_ig(const uint8_t* predicted, const uint8_t* actual, int64_
 int rs_eval_prob_hist(const uint8_t* prob, const uint8_t* actual, int64_t* hist, int64_t* skipped, long pixels, long group, int C,
                       int cls, int ignore, rs_stream_t stream);
 
+/* rs_eval_centerline (`rs evaluate --centerline RHO`): the buffer method of Wiedemann and Heipke (1998) for road centre lines, on
+ * rasters.  skel_p, skel_g: uint8 [B][H][W] skeletons (non-zero = set; rs_features_thin's 0/1 bytes) of the predicted and the actual
+ * mask of one class.  nbr NULL: each of the B tiles is a raster and a group of its own, G = B.  nbr int32 [B][8] (the table of
+ * rs_features_halo): the tiles are one sparse raster and one group, G = 1.
+ *   links    those of rs_features_skeleton_links without its labels and table; every link counts.  From a set pixel (x, y): E to
+ *            (x+1, y) where set; S to (x, y+1) where set; SE to (x+1, y+1) where set and neither (x+1, y) nor (x, y+1) is; SW to
+ *            (x-1, y+1) where set and neither (x-1, y) nor (x, y+1) is.  A pixel outside the raster or in an absent tile reads 0;
+ *            across a seam or a corner the neighbour is the facing pixel of the neighbouring tile.  A link belongs to its first pixel,
+ *            and so to that pixel's tile.  E and S links are straight (length 1), SE and SW links diagonal (length sqrt 2); a
+ *            skeleton pixel without links has no length.
+ *   reach    for a skeleton S and a tolerance rho, 1 <= rho <= 127: near_S(q) = rs_features_edt(complement of S, R = rho + 1)[q]
+ *            <= rho*rho: q lies within rho pixels, centre to centre, of a pixel of S on the same raster (0 on S itself; R = rho + 1
+ *            keeps the cap above rho*rho, as for the boundary band).  The transform's rules hold as they stand: nothing is known
+ *            outside the raster or in an absent tile, so a line beyond the edge matches nothing; with nbr a seam is interior.
+ *            d2_to_g is that transform for skel_g, d2_to_p the one for skel_p, both int32 [B][H][W], with the same nbr.
+ *   matched  a link of skel_p is matched iff near_{skel_g} holds at both of its end pixels, a link of skel_g iff near_{skel_p}
+ *            does; the second end is read through nbr like the skeleton.
+ *   counts[g] = (p_straight, p_diag, p_straight_matched, p_diag_matched, g_straight, g_diag, g_straight_matched, g_diag_matched)
+ *            over the links of group g   (int64 [G][8], set by the call, not added to, 8-byte aligned)
+ * from which the host makes, with len(s, d) = s + d * sqrt 2 in float64 over the sums of all groups, P and G the two lengths and
+ * Pm and Gm their matched parts: correctness = Pm / P, completeness = Gm / G, quality = Pm / (P + G - Gm), f1 = their harmonic
+ * mean.  The paper measures vector lengths after matching; here both sides are rasters, length is counted in links and matching is
+ * judged at link ends.
+ *
+ * One launch behind the fill of counts.  A thread owns a run of up to 16 consecutive pixels of one ROW (a row is cdiv(W, 16) runs; a
+ * workgroup of 256 threads takes 256 consecutive runs of the call, so it may straddle tiles or hold many small ones) and reads the
+ * bytes beside and below them, beyond the tile through nbr; the transforms are read only by threads whose run starts a link (its four
+ * rows whole where W is a multiple of 4, else link end by link end).  Per group: bit
+ * counts within a thread, a sum over the wave's lanes, the four waves merged in LDS, one 64-bit atomic add per block, group and
+ * non-zero counter: at most 8.  No workgroup waits for another; every loop is bounded; integers only.  Any H and W work.
+ * RS_EINVAL for rho outside 1..127, B*H*W outside 1 .. 2^31 - 1, a null pointer other than nbr. */
+int rs_eval_centerline(const uint8_t* skel_p, const uint8_t* skel_g, const int32_t* d2_to_g, const int32_t* d2_to_p,
+                       const int32_t* nbr, int64_t* counts, int B, int H, int W, int rho, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

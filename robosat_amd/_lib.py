@@ -198,6 +198,7 @@ SIGNATURES = {
     "rs_eval_boundary": (c_int, [P, P, P, c_long, c_long, c_int, P]),
     "rs_eval_confusion_ig": (c_int, [P, P, P, P, P, c_long, c_long, c_int, P, c_int]),
     "rs_eval_prob_hist": (c_int, [P, P, P, P, c_long, c_long, c_int, c_int, c_int, P]),
+    "rs_eval_centerline": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

@@ -6,7 +6,10 @@
 //   rs_eval_boundary   two capped distance transforms (rs_features_edt) -> per group the sizes of the two boundary bands and of their
 //                      intersection
 //   rs_eval_prob_hist  the probability bytes of one class and the label raster -> per group the 2 x 256 histogram of (label is the
-//                      class, byte) and the numbers of pixels with a bad and with an ignored label (at the end of the file)
+//                      class, byte) and the numbers of pixels with a bad and with an ignored label
+//   rs_eval_centerline two skeletons and the capped distance transforms of their complements -> per group the straight and diagonal
+//                      links of either skeleton and those whose two ends lie within rho of the other (at the end of the file: its
+//                      threads own runs of a ROW, since a link has a neighbour below, not runs of the call)
 //
 // The kernels share one shape.  A block of 256 threads covers kEvalBlock = 4096 consecutive pixels of the whole call, a thread 16
 // consecutive ones, held in registers: a 16-byte load per raster (four for the int32 rasters) where the thread's first address is
@@ -416,5 +419,233 @@ extern "C" int rs_eval_prob_hist(const uint8_t* prob, const uint8_t* actual, int
   eval_prob_hist_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(
       prob, actual, reinterpret_cast<unsigned long long*>(hist), reinterpret_cast<unsigned long long*>(skipped), pixels, group,
       (unsigned int)C, (unsigned int)cls, ignore < 0 ? 256u : (unsigned int)ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+// ---- centre lines: links and matched links per group (rs_eval_centerline) ----------------------------------------------------
+// `rs evaluate --centerline`: the buffer method on two skeletons.  A link runs from a set pixel to its E, S, SE or SW neighbour (the
+// rule of rs_features_skeleton_links), so a thread needs the row below its pixels: runs are laid over ROWS here, not over the call.
+// A row of W pixels is cut into cdiv(W, 16) runs; run r of the call is run r % RW of row r / RW of all B*H rows, a thread owns one
+// run and a block 256 consecutive ones, which lie in consecutive tiles: a block may straddle tiles or hold many small ones.
+//
+// A thread keeps a row of a skeleton as 18 bits: bit 0 the pixel west of its run, bits 1..n its n <= 16 pixels, bit n + 1 the pixel east
+// of them; the same for the row below.  Beyond the tile those pixels are the facing ones of the neighbouring tile through nbr, 0 where
+// the tile is absent or no table was given.  The four kinds of link are then four words of bit logic.  The transforms are read ONLY
+// by threads whose run starts a link (a skeleton is a percent or two of a raster): where W is a multiple of 4 the four rows of a whole
+// run at once, 16-byte loads that do not wait for each other; otherwise the bits of the link ends are walked, one int32 load each, at
+// most 18 per row.  Every index comes from cl_pixel, which gives -1 for anything outside the call's tiles; a distance counts only
+// where a skeleton byte was read as set, so through the same index, and a load that has no pixel reads the call's first ones.
+//
+// Counts are merged as in eval_boundary_kernel: bit counts within a thread, a sum over the wave's lanes, the four waves in LDS, one
+// 64-bit atomic add per block, group and non-zero counter.  The eight counters travel as four words of two 16-bit halves: a thread
+// has at most 32 links of a kind, a wave 2048, a block 8192.  No workgroup waits for another; every loop is bounded (the bit walks
+// by 18, the group loop by the block's 256 runs).
+namespace {
+
+constexpr int kClRun = 16;  // pixels of a thread's run (one row)
+constexpr int kClCounters = 8;
+
+// Slot of the tile at (dx, dy) from `tile` in the neighbour table (order NW N NE W E SW S SE), -1 where absent or out of range.
+__device__ __forceinline__ int cl_slot(const int* __restrict__ nbr, int tile, int dx, int dy, int B) {
+  const int k = (dy + 1) * 3 + (dx + 1);
+  const int n = nbr[(long)tile * 8 + (k > 4 ? k - 1 : k)];
+  return n >= 0 && n < B ? n : -1;
+}
+
+// Index in the call of pixel (x, y) of `tile`, x in -1 .. W and y in 0 .. H: the facing pixel of the neighbouring tile where it lies
+// beyond the tile, -1 where there is none.  (B*H*W < 2^31: every index fits an int.)
+template <bool STITCH>
+__device__ __forceinline__ int cl_pixel(const int* __restrict__ nbr, int tile, int x, int y, int B, int H, int W) {
+  const int dx = x < 0 ? -1 : x >= W ? 1 : 0, dy = y >= H ? 1 : 0;
+  int slot = tile;
+  if (dx | dy) {
+    if (!STITCH) return -1;
+    slot = cl_slot(nbr, tile, dx, dy, B);
+    if (slot < 0) return -1;
+  }
+  return (slot * H + (y - dy * H)) * W + (x - dx * W);
+}
+
+// The three places a thread reads a row at: its own n pixels from `own`, one pixel at `west`, one at `east`; -1 where there is none.
+struct ClRow {
+  int own, west, east;
+};
+
+template <bool STITCH>
+__device__ __forceinline__ ClRow cl_row(const int* __restrict__ nbr, int tile, int x0, int n, int y, int B, int H, int W) {
+  ClRow r;
+  r.own = cl_pixel<STITCH>(nbr, tile, x0, y, B, H, W);
+  r.west = cl_pixel<STITCH>(nbr, tile, x0 - 1, y, B, H, W);
+  r.east = cl_pixel<STITCH>(nbr, tile, x0 + n, y, B, H, W);
+  return r;
+}
+
+// The 18 bits of a skeleton's row (non-zero = set).
+__device__ __forceinline__ unsigned int cl_row_bits(const uint8_t* __restrict__ s, const ClRow& r, int n) {
+  unsigned int bits = 0;
+  if (r.own >= 0) {
+    if (n == kClRun && (reinterpret_cast<uintptr_t>(s + r.own) & 15) == 0) {
+      const u32x4 q = *reinterpret_cast<const u32x4*>(s + r.own);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        // bit 7 of every non-zero byte (no carry leaves a byte: 0x7f + 0x7f), then the four bits side by side: bit 8i moves to
+        // 8i + 7j under the factor's term 2^(7j), no two terms meet, and bits 21 .. 24 are bytes 0 .. 3
+        const unsigned int t = ((q[e] | ((q[e] & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u) >> 7;
+        bits |= ((t * 0x00204081u >> 21) & 15u) << (4 * e + 1);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < kClRun; ++j)
+        if (j < n) bits |= (unsigned int)(s[r.own + j] != 0) << (j + 1);
+    }
+  }
+  // (no branch round the two single loads: where there is no pixel the call's first byte is read and masked away, so that the
+  // loads of all four rows can be in flight together)
+  bits |= (unsigned int)(s[r.west >= 0 ? r.west : 0] != 0) & (unsigned int)(r.west >= 0);
+  bits |= ((unsigned int)(s[r.east >= 0 ? r.east : 0] != 0) & (unsigned int)(r.east >= 0)) << (n + 1);
+  return bits;
+}
+
+// Bit k set where bit k of `need` is and d2 <= rr at that pixel.  `need` holds only pixels that cl_row_bits read as set.
+__device__ __forceinline__ unsigned int cl_near_bits(const int* __restrict__ d2, const ClRow& r, int n, unsigned int need, int rr) {
+  unsigned int bits = 0;
+  for (int it = 0; it < kClRun + 2 && need; ++it) {
+    const int k = __ffs((int)need) - 1;
+    need &= need - 1u;
+    const int at = k == 0 ? r.west : k == n + 1 ? r.east : r.own + (k - 1);
+    if (at >= 0) bits |= (unsigned int)(d2[at] <= rr) << k;  // (at >= 0 by construction)
+  }
+  return bits;
+}
+
+// The same for a whole run of 16 at once, where every row of the transforms begins at a 16-byte boundary (`fast` in the kernel):
+// four 16-byte loads and the two single ones, none depending on another, so that all four rows of a thread are one round trip to
+// memory where the walk above is one per link end.  Where there is no pixel the call's first ones are read (B*H*W >= 16 here);
+// the caller looks at the bits of link ends only, which are pixels that are there.
+__device__ __forceinline__ unsigned int cl_near_row(const int* __restrict__ d2, const ClRow& r, int rr) {
+  const u32x4* own = reinterpret_cast<const u32x4*>(d2 + (r.own >= 0 ? r.own : 0));
+  u32x4 q[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) q[e] = own[e];
+  const int west = d2[r.west >= 0 ? r.west : 0], east = d2[r.east >= 0 ? r.east : 0];
+  unsigned int bits = (unsigned int)(west <= rr) | (unsigned int)(east <= rr) << (kClRun + 1);
+#pragma unroll
+  for (int j = 0; j < kClRun; ++j) bits |= (unsigned int)((int)q[j >> 2][j & 3] <= rr) << (j + 1);
+  return bits;
+}
+
+// The links that start in a thread's run, one word per kind, from the bits c of its row and b of the row below.
+struct ClLinks {
+  unsigned int e, s, se, sw;
+};
+
+__device__ __forceinline__ ClLinks cl_links(unsigned int c, unsigned int b, int n) {
+  const unsigned int own = ((1u << n) - 1u) << 1;
+  ClLinks l;
+  l.e = c & (c >> 1) & own;
+  l.s = c & b & own;
+  l.se = c & (b >> 1) & ~(c >> 1) & ~b & own;
+  l.sw = c & (b << 1) & ~(c << 1) & ~b & own;
+  return l;
+}
+
+// straight | diagonal << 16
+__device__ __forceinline__ unsigned int cl_count(const ClLinks& l) {
+  return (unsigned int)(__popc(l.e) + __popc(l.s)) | (unsigned int)(__popc(l.se) + __popc(l.sw)) << 16;
+}
+
+// The link ends in the thread's row and in the row below: where the other side's transform is looked at.
+__device__ __forceinline__ unsigned int cl_ends_row(const ClLinks& l) { return l.e | l.s | l.se | l.sw | (l.e << 1); }
+__device__ __forceinline__ unsigned int cl_ends_below(const ClLinks& l) { return l.s | (l.se << 1) | (l.sw >> 1); }
+
+// The links with both ends near: nc, nb = the near bits of the row and of the row below, right at least at the link ends.
+__device__ __forceinline__ ClLinks cl_matched(const ClLinks& l, unsigned int nc, unsigned int nb) {
+  ClLinks m;
+  m.e = l.e & nc & (nc >> 1);
+  m.s = l.s & nc & nb;
+  m.se = l.se & nc & (nb >> 1);
+  m.sw = l.sw & nc & (nb << 1);
+  return m;
+}
+
+template <bool STITCH>
+__global__ __launch_bounds__(kEvalThreads) void eval_centerline_kernel(const uint8_t* __restrict__ skel_p, const uint8_t* __restrict__ skel_g,
+                                                                       const int* __restrict__ d2_to_g, const int* __restrict__ d2_to_p,
+                                                                       const int* __restrict__ nbr, unsigned long long* __restrict__ counts,
+                                                                       int B, int H, int W, int rr) {
+  __shared__ unsigned int part[4][kClCounters / 2];
+  const int RW = (W + kClRun - 1) / kClRun;
+  // (runs <= B*H*W < 2^31, and the grid's last run index is below runs + 256: 32-bit arithmetic, whose divisions are cheap)
+  const unsigned int per_tile = (unsigned int)H * RW, runs = per_tile * B;
+  const unsigned int r0 = blockIdx.x * kEvalThreads, r = r0 + threadIdx.x;
+  // every row of both transforms begins at a 16-byte boundary (and then W >= 16 wherever a run is whole)
+  const bool fast = (W & 3) == 0 && ((reinterpret_cast<uintptr_t>(d2_to_g) | reinterpret_cast<uintptr_t>(d2_to_p)) & 15) == 0;
+  unsigned int w[kClCounters / 2] = {0, 0, 0, 0};
+  int tile = -1;
+  if (r < runs) {
+    tile = (int)(r / per_tile);
+    const unsigned int in_tile = r - tile * per_tile;
+    const int y = (int)(in_tile / RW), x0 = (int)(in_tile - y * RW) * kClRun;
+    const int n = W - x0 < kClRun ? W - x0 : kClRun;
+    const ClRow cur = cl_row<STITCH>(nbr, tile, x0, n, y, B, H, W), below = cl_row<STITCH>(nbr, tile, x0, n, y + 1, B, H, W);
+    const unsigned int pc = cl_row_bits(skel_p, cur, n), pb = cl_row_bits(skel_p, below, n);
+    const unsigned int gc = cl_row_bits(skel_g, cur, n), gb = cl_row_bits(skel_g, below, n);
+    const ClLinks lp = cl_links(pc, pb, n), lg = cl_links(gc, gb, n);
+    w[0] = cl_count(lp);
+    w[2] = cl_count(lg);
+    if (w[0] | w[2]) {
+      unsigned int pnc, pnb, gnc, gnb;  // near the OTHER skeleton: the prediction's link ends in d2_to_g, the label's in d2_to_p
+      if (fast && n == kClRun) {
+        pnc = cl_near_row(d2_to_g, cur, rr), pnb = cl_near_row(d2_to_g, below, rr);
+        gnc = cl_near_row(d2_to_p, cur, rr), gnb = cl_near_row(d2_to_p, below, rr);
+      } else {
+        pnc = cl_near_bits(d2_to_g, cur, n, cl_ends_row(lp), rr), pnb = cl_near_bits(d2_to_g, below, n, cl_ends_below(lp), rr);
+        gnc = cl_near_bits(d2_to_p, cur, n, cl_ends_row(lg), rr), gnb = cl_near_bits(d2_to_p, below, n, cl_ends_below(lg), rr);
+      }
+      w[1] = cl_count(cl_matched(lp, pnc, pnb));
+      w[3] = cl_count(cl_matched(lg, gnc, gnb));
+    }
+  }
+  const unsigned int r1 = r0 + kEvalThreads < runs ? r0 + kEvalThreads : runs;  // (r0 < runs: the grid is cdiv(runs, kEvalThreads))
+  const int g0 = STITCH ? 0 : (int)(r0 / per_tile), g1 = STITCH ? 0 : (int)((r1 - 1) / per_tile);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int g = g0; g <= g1; ++g) {
+    const bool mine = tile >= 0 && (STITCH || tile == g);
+#pragma unroll
+    for (int k = 0; k < kClCounters / 2; ++k) {
+      unsigned int v = mine ? w[k] : 0u;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);  // (each half at most 64 * 32: no carry)
+      if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kClCounters) {
+      const int t = threadIdx.x, sh = (t & 1) * 16;
+      const unsigned int tot = ((part[0][t >> 1] >> sh) & 0xffffu) + ((part[1][t >> 1] >> sh) & 0xffffu) + ((part[2][t >> 1] >> sh) & 0xffffu) +
+                               ((part[3][t >> 1] >> sh) & 0xffffu);
+      if (tot) atomicAdd(&counts[(long)g * kClCounters + t], (unsigned long long)tot);
+    }
+    __syncthreads();  // (the next group overwrites the partial sums)
+  }
+}
+
+}  // namespace
+
+extern "C" int rs_eval_centerline(const uint8_t* skel_p, const uint8_t* skel_g, const int32_t* d2_to_g, const int32_t* d2_to_p,
+                                  const int32_t* nbr, int64_t* counts, int B, int H, int W, int rho, rs_stream_t stream) {
+  if (!skel_p || !skel_g || !d2_to_g || !d2_to_p || !counts || ((uintptr_t)counts & 7) || B < 1 || H < 1 || W < 1 || rho < 1 || rho > 127)
+    return RS_EINVAL;
+  const long hw = (long)H * W;  // (H, W < 2^31: no overflow)
+  if (hw >= (1l << 31) || (long)B * hw >= (1l << 31)) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(counts, 0, (nbr ? 1 : (long)B) * kClCounters * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  const long runs = (long)B * H * ((W + kClRun - 1) / kClRun);
+  unsigned long long* c = reinterpret_cast<unsigned long long*>(counts);
+  if (nbr)
+    eval_centerline_kernel<true><<<rs_cdiv(runs, kEvalThreads), kEvalThreads, 0, s>>>(skel_p, skel_g, d2_to_g, d2_to_p, nbr, c, B, H, W, rho * rho);
+  else
+    eval_centerline_kernel<false><<<rs_cdiv(runs, kEvalThreads), kEvalThreads, 0, s>>>(skel_p, skel_g, d2_to_g, d2_to_p, nullptr, c, B, H, W,
+                                                                                      rho * rho);
   return RS_LAUNCH_RESULT();
 }

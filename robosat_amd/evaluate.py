@@ -127,13 +127,55 @@ def boundary_report(d, counts):
     return {"d": int(d), "predicted": predicted, "actual": actual, "shared": shared, "iou": _ratio(shared, predicted + actual - shared)}
 
 
+CENTERLINE_COUNTS = ("straight", "diagonal", "matched_straight", "matched_diagonal")
+SQRT2 = math.sqrt(2.0)
+
+
+def _link_length(straight, diagonal):
+    """The length in pixels of ``straight`` E / S links and ``diagonal`` SE / SW links, float64."""
+
+    return straight + diagonal * SQRT2
+
+
+def centerline_scores(counts):
+    """The eight summed link counts of ``ops.centerline_counts`` -> (completeness, correctness, quality): with P and G the lengths
+    of the predicted and the actual skeleton and Pm, Gm their matched parts, Gm / G, Pm / P and Pm / (P + G - Gm); None where the
+    denominator is zero."""
+
+    ps, pd, pms, pmd, gs, gd, gms, gmd = (int(v) for v in counts)
+    p, pm, g, gm = _link_length(ps, pd), _link_length(pms, pmd), _link_length(gs, gd), _link_length(gms, gmd)
+    return _ratio(gm, g), _ratio(pm, p), _ratio(pm, p + g - gm)
+
+
+def centerline_report(rho, counts):
+    """``rho`` and the eight link counts summed over all groups (``ops.centerline_counts``'s order) -> the report's ``centerline``:
+    the buffer method of Wiedemann and Heipke on skeletons.  Lengths are straight + diagonal * sqrt(2) in float64, formed once from
+    the integers; f1 is the harmonic mean of completeness and correctness; an undefined ratio is None."""
+
+    counts = [int(v) for v in counts]
+    if len(counts) != 8 or min(counts) < 0:
+        raise ValueError("robosat_amd: eight link counts, none below zero")
+    sides = {}
+    for name, four in (("predicted", counts[:4]), ("actual", counts[4:])):
+        side = dict(zip(CENTERLINE_COUNTS, four))
+        sides[name] = {"straight": side["straight"], "diagonal": side["diagonal"], "length": _link_length(four[0], four[1]),
+                       "matched_straight": side["matched_straight"], "matched_diagonal": side["matched_diagonal"],
+                       "matched_length": _link_length(four[2], four[3])}
+    completeness, correctness, quality = centerline_scores(counts)
+    f1 = None
+    if completeness is not None and correctness is not None:
+        f1 = _ratio(2 * completeness * correctness, completeness + correctness)
+    return {"rho": int(rho), "predicted": sides["predicted"], "actual": sides["actual"], "completeness": completeness,
+            "correctness": correctness, "quality": quality, "f1": f1}
+
+
 def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None, ignore=None, ignored=0,
-                 probability=None):
+                 probability=None, centerline=None):
     """The report of one run.  ``matrix``: C x C Python integers summed over every evaluated tile; ``kind``: ``--type`` or None;
     ``objects`` / ``boundary``: ``ObjectScores.report()`` / ``boundary_report()`` or None.  With the dataset's ``ignore`` label the
     report also carries it and ``ignored``, the pixels whose label has that value: they are in no cell, so ``pixels`` (the matrix's
     sum) counts the valid ones and ``pixels + ignored`` is every pixel of the evaluated tiles.  ``probability`` (with ``--probs``):
-    ``probability_report()``, the last key."""
+    ``probability_report()``, the last key.  ``centerline`` (with ``--centerline``): ``centerline_report()``, behind ``boundary``."""
 
     matrix = [[int(v) for v in row] for row in matrix]
     report = {
@@ -152,18 +194,21 @@ def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects
         report["objects"] = objects
     if boundary is not None:
         report["boundary"] = boundary
+    if centerline is not None:
+        report["centerline"] = centerline
     if probability is not None:
         report["probability"] = probability
     return report
 
 
-def tile_rows(tiles, matrices, classes, kind=None, ignored=None, brier=None):
+def tile_rows(tiles, matrices, classes, kind=None, ignored=None, brier=None, centerline=None):
     """One row per evaluated tile: ``tiles`` and their C x C matrices -> dicts with z, x, y, pixels, iou_<class> per class, miou,
     predicted_share, actual_share (the share of non-background pixels on each side), sorted worst first: by the IoU of ``kind``
     (``--type``), or by miou without it, undefined values last, then by (z, x, y).  ``ignored`` (with the dataset's ignore label):
     the tiles' counts of ignored label pixels, an ``ignored`` entry of each row; ``pixels`` and the shares are over the valid ones.
     ``brier`` (with ``--probs``): the tiles' own Brier scores (``brier_score``), a ``brier`` entry of each row; it has no say in the
-    order."""
+    order.  ``centerline`` (with ``--centerline``, per tile): the tiles' own eight link counts; the rows gain
+    ``centerline_completeness``, ``centerline_correctness`` and ``centerline_quality``, which have no say in the order either."""
 
     rows = []
     for i, (tile, matrix) in enumerate(zip(tiles, matrices)):
@@ -180,24 +225,30 @@ def tile_rows(tiles, matrices, classes, kind=None, ignored=None, brier=None):
         row["actual_share"] = _ratio(total - int(matrix[0, :].sum()), total)
         if brier is not None:
             row["brier"] = brier[i]
+        if centerline is not None:
+            for name, value in zip(CENTERLINE_COLUMNS, centerline_scores(centerline[i])):
+                row[name] = value
         rows.append(row)
     column = "miou" if kind is None else "iou_" + kind
     rows.sort(key=lambda r: (r[column] is None, r[column] if r[column] is not None else 0.0, r["z"], r["x"], r["y"]))
     return rows
 
 
-def tile_columns(classes, ignored=False, brier=False):
+CENTERLINE_COLUMNS = ["centerline_completeness", "centerline_correctness", "centerline_quality"]
+
+
+def tile_columns(classes, ignored=False, brier=False, centerline=False):
     return (["z", "x", "y", "pixels"] + (["ignored"] if ignored else []) + ["iou_" + name for name in classes]
-            + ["miou", "predicted_share", "actual_share"] + (["brier"] if brier else []))
+            + ["miou", "predicted_share", "actual_share"] + (["brier"] if brier else []) + (CENTERLINE_COLUMNS if centerline else []))
 
 
-def write_tile_rows(path, rows, classes, ignored=False, brier=False):
+def write_tile_rows(path, rows, classes, ignored=False, brier=False, centerline=False):
     """``tile_rows`` as CSV; an undefined value is an empty field, a float is written with ``repr`` (it reads back as it was).
-    ``ignored`` / ``brier``: the rows carry that column (``tile_rows`` was given the values)."""
+    ``ignored`` / ``brier`` / ``centerline``: the rows carry those columns (``tile_rows`` was given the values)."""
 
     with open(path, "w", newline="") as fp:
         writer = csv.writer(fp)
-        columns = tile_columns(classes, ignored, brier)
+        columns = tile_columns(classes, ignored, brier, centerline)
         writer.writerow(columns)
         for row in rows:
             writer.writerow(["" if row[c] is None else repr(row[c]) for c in columns])

@@ -2083,3 +2083,31 @@ def boundary_counts(d2_a, d2_b, d, stitched=False):
     counts = torch.empty((1 if stitched else d2_a.shape[0], 3), device=d2_a.device, dtype=torch.int64)
     _call("rs_eval_boundary", a, b, _dev(counts, "counts", torch.int64), pixels, pixels if stitched else hw, d, _stream())
     return counts
+
+
+# ---- rs evaluate --centerline: the buffer method on two skeletons (rs_eval_centerline; definitions in include/robosat_hip.h) -------
+EVAL_MAX_RHO = EDT_MAX_RADIUS - 1  # the tolerance rho: the transforms behind it have the radius rho + 1
+
+
+def centerline_counts(skel_p, skel_g, rho, nbr=None):
+    """Two uint8 [B, H, W] skeletons (``thin_masks`` of the predicted and the actual mask; non-zero = set) -> int64 [G, 8]: per tile
+    (G = B), or with ``nbr`` int32 [B, 8] for the one sparse raster the tiles form (G = 1), the links of either skeleton by
+    ``skeleton_links``' rule and those whose two end pixels both lie within ``rho`` pixels of the other skeleton:
+    (p_straight, p_diag, p_straight_matched, p_diag_matched, g_straight, g_diag, g_straight_matched, g_diag_matched).  "Within
+    ``rho``" is ``distance_transform(complement of the skeleton, rho + 1, nbr) <= rho^2``, so nothing beyond the raster's edge or in
+    an absent tile is near.  1 <= ``rho`` <= 127; with ``nbr`` ``rho + 1`` fits min(H, W) (the transform says so)."""
+
+    rho = int(rho)
+    if not 1 <= rho <= EVAL_MAX_RHO:
+        raise ValueError("robosat_amd: the centerline tolerance is in 1..{}, got {}".format(EVAL_MAX_RHO, rho))
+    p, g, _, _ = _eval_pair(skel_p, skel_g, ("skel_p", "skel_g"), torch.uint8)
+    b, h, w = skel_p.shape
+    if nbr is not None and (nbr.shape != (b, 8) or nbr.device != skel_p.device):
+        raise ValueError("robosat_amd: nbr is [T, 8] on the skeletons' device, got {} on {}".format(tuple(nbr.shape), nbr.device))
+    # (the complement is glue: a skeleton is 0/1 bytes, and a byte compare keeps "non-zero = set" for any other)
+    d2_to_p = distance_transform((skel_p == 0).to(torch.uint8), rho + 1, nbr)
+    d2_to_g = distance_transform((skel_g == 0).to(torch.uint8), rho + 1, nbr)
+    counts = torch.empty((b if nbr is None else 1, 8), device=skel_p.device, dtype=torch.int64)
+    _call("rs_eval_centerline", p, g, _dev(d2_to_g, "d2_to_g", torch.int32), _dev(d2_to_p, "d2_to_p", torch.int32),
+          _dev(nbr, "nbr", torch.int32), _dev(counts, "counts", torch.int64), b, h, w, rho, _stream())
+    return counts

@@ -11,6 +11,12 @@ views, all counted on the MI355X (``csrc/evaluate.hip`` and the ``rs features`` 
     by IoU at ``--match``; predicted, actual, matched, precision, recall, F1.  Per tile an object cut by a tile border counts once per
     tile; ``--stitch`` evaluates the one sparse raster the tiles of a zoom level form, where it is one object on both sides.
 
+With ``--type --centerline RHO`` a view for roads is added, the buffer method of Wiedemann and Heipke (1998) on rasters: both
+class masks are thinned to skeletons (``ops.thin_masks``), the skeletons' links are counted as straight and diagonal ones, and a
+link is matched where both of its end pixels lie within RHO pixels of the other side's skeleton (``ops.centerline_counts``).
+Correctness is the matched share of the predicted length, completeness that of the actual length, quality matched predicted
+length / (predicted + unmatched actual length).  Pixel and boundary IoU depend on a road's width; these do not.
+
 With the dataset's ``[common] ignore`` a pixel whose LABEL has that value is in no cell of the pixel view: the report and the
 ``--tiles`` rows count it as ``ignored`` and their ``pixels`` are the valid ones.  A mask byte, or another label byte, that is no
 class still ends the run.  With ``--type`` a label tile that holds an ignored pixel ends the run, naming the tile: what a
@@ -37,8 +43,8 @@ from tqdm import tqdm
 
 from robosat_amd import ops
 from robosat_amd.config import ignore_label, load_config
-from robosat_amd.evaluate import (ObjectScores, boundary_report, brier_score, build_report, curve_rows, probability_report, tile_rows,
-                                  write_curve_rows, write_tile_rows)
+from robosat_amd.evaluate import (ObjectScores, boundary_report, brier_score, build_report, centerline_report, curve_rows,
+                                  probability_report, tile_rows, write_curve_rows, write_tile_rows)
 from robosat_amd.features import group_clusters, pack_clusters, stitch_tables
 from robosat_amd.tiles import tiles_from_slippy_map
 from robosat_amd.tools.features import _load, _tile_sizes
@@ -61,6 +67,13 @@ def add_parser(subparser):
                         "pixels of a pixel that is not, shared / (predicted + actual - shared). The edge of the raster is not a "
                         "boundary (nothing is known beyond it; the paper's code pads with zeros), nor with --stitch a seam between two "
                         "tiles. With --stitch D + 1 pixels must fit the tile's smaller side")
+    parser.add_argument("--centerline", type=int, default=0, metavar="RHO",
+                        help="with --type: completeness, correctness and quality of the class's centre lines (Wiedemann and Heipke's "
+                        "buffer method), 0 = off, else 1..127: both sides are thinned to skeletons, and a piece of one is matched "
+                        "where it lies within RHO pixels of the other. Roads want --stitch: per tile a skeleton stops about half a "
+                        "road's width short of every tile border, on both sides alike, and a line just beyond the tile edge is unknown "
+                        "and matches nothing. With --stitch RHO + 1 pixels must fit the tile's smaller side, and --tiles gets no "
+                        "centerline columns")
     parser.add_argument("--match", type=float, default=None, metavar="T",
                         help="with --type: a predicted and an actual object match where their IoU is at least T, 0 < T <= 1 (0.5 where "
                         "not given); pairs are taken greedily, best IoU first")
@@ -96,7 +109,7 @@ def validate(args, classes):
     if not 2 <= len(classes) <= ops.EVAL_MAX_CLASSES:
         sys.exit("Error: 2 to {} classes are counted, the dataset has {}".format(ops.EVAL_MAX_CLASSES, len(classes)))
     if args.type is None:
-        for given, flag in ((args.boundary != 0, "--boundary"), (args.match is not None, "--match"), (args.min_area is not None, "--min_area"),
+        for given, flag in ((args.boundary != 0, "--boundary"), (args.centerline != 0, "--centerline"), (args.match is not None, "--match"), (args.min_area is not None, "--min_area"),
                             (args.stitch, "--stitch")):
             if given:
                 sys.exit("Error: {} scores the boundaries or objects of one class: not without --type".format(flag))
@@ -104,6 +117,8 @@ def validate(args, classes):
         sys.exit("Error: --type must be a non-background class of the dataset ({}), got '{}'".format(", ".join(classes[1:]), args.type))
     if not 0 <= args.boundary <= ops.EVAL_MAX_DISTANCE:
         sys.exit("Error: --boundary must be in 1..{} (0 = off), got {}".format(ops.EVAL_MAX_DISTANCE, args.boundary))
+    if not 0 <= args.centerline <= ops.EVAL_MAX_RHO:
+        sys.exit("Error: --centerline must be in 1..{} (0 = off), got {}".format(ops.EVAL_MAX_RHO, args.centerline))
     match = MATCH_DEFAULT if args.match is None else args.match
     if not 0 < match <= 1:  # (false for nan too)
         sys.exit("Error: --match is an intersection over union, 0 < T <= 1, got {}".format(match))
@@ -129,6 +144,11 @@ def validate(args, classes):
             if args.boundary + 1 > min(h, w):
                 sys.exit("Error: --boundary {} needs a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
                          .format(args.boundary, args.boundary + 1, h, w, min(h, w) - 1))
+    if args.stitch and args.centerline:
+        for h, w in sorted({shape for _, _, shape in _tile_sizes(args.masks)}):
+            if args.centerline + 1 > min(h, w):
+                sys.exit("Error: --centerline {} needs a border of {} pixels from the neighbouring tiles; tiles of {}x{} take at most {}"
+                         .format(args.centerline, args.centerline + 1, h, w, min(h, w) - 1))
     return match, min_area
 
 
@@ -180,8 +200,11 @@ class Probabilities:
 class Evaluation:
     """The sums of a run, and the device stages of one batch (tiles on their own) or call (tiles as one sparse raster)."""
 
-    def __init__(self, classes, index, boundary, objects, ignore=None, probs=None):
+    def __init__(self, classes, index, boundary, objects, ignore=None, probs=None, centerline=0):
         self.classes, self.index, self.boundary, self.objects, self.ignore, self.probs = classes, index, boundary, objects, ignore, probs
+        self.centerline = centerline
+        self.links = [0] * 8   # the eight link counts of --centerline, summed
+        self.tile_links = []   # and per tile, for --tiles (stays empty for stitched calls: they have no per-tile counts)
         n = len(classes)
         self.matrix = [[0] * n for _ in range(n)]  # Python integers: no bound on the pixels of a run
         self.band = [0, 0, 0]
@@ -236,6 +259,13 @@ class Evaluation:
             for row in ops.boundary_counts(d2_p, d2_g, self.boundary, stitched=stitched).tolist():
                 for k in range(3):
                     self.band[k] += row[k]
+        if self.centerline:
+            counts = ops.centerline_counts(ops.thin_masks(mask_p, nbr), ops.thin_masks(mask_g, nbr), self.centerline, nbr).tolist()
+            for row in counts:
+                for k in range(8):
+                    self.links[k] += row[k]
+            if not stitched:
+                self.tile_links.extend(counts)
         labels_p, labels_g = ops.label_components(mask_p), ops.label_components(mask_g)
         if stitched:
             labels_p, labels_g = ops.stitch_labels(labels_p, nbr, inplace=True), ops.stitch_labels(labels_g, nbr, inplace=True)
@@ -248,8 +278,9 @@ class Evaluation:
 
 
 def main(args):
-    # (callers that build the arguments themselves may predate the two flags)
+    # (callers that build the arguments themselves may predate these flags)
     args.probs, args.curve = getattr(args, "probs", None), getattr(args, "curve", None)
+    args.centerline = getattr(args, "centerline", 0)
     dataset = load_config(args.dataset)
     classes = dataset["common"]["classes"]
     try:
@@ -263,7 +294,7 @@ def main(args):
     index = None if args.type is None else classes.index(args.type)
     objects = None if index is None else ObjectScores(match, min_area, args.stitch)
     probs = None if args.probs is None else Probabilities(args.probs, (1 if index is None else index) - 1, per_tile=args.tiles is not None)
-    run = Evaluation(classes, index, args.boundary, objects, ignore, probs)
+    run = Evaluation(classes, index, args.boundary, objects, ignore, probs, args.centerline)
 
     label_paths = {tile: path for tile, path in tiles_from_slippy_map(args.labels)}
     without_label = 0
@@ -305,6 +336,7 @@ def main(args):
     report = build_report(classes, run.matrix, len(run.tiles), without_label, kind=args.type,
                           objects=None if objects is None else objects.report(),
                           boundary=boundary_report(args.boundary, run.band) if args.boundary else None,
+                          centerline=centerline_report(args.centerline, run.links) if args.centerline else None,
                           **({} if ignore is None else {"ignore": ignore, "ignored": sum(run.ignored)}),
                           **({} if probs is None else {"probability": probability_report(
                               classes[probs.channel + 1], probs.pos, probs.neg, None if ignore is None else probs.ignored)}))
@@ -315,10 +347,14 @@ def main(args):
         write_curve_rows(args.curve, curve_rows(probs.pos, probs.neg))
     if args.tiles is not None:
         extra = {} if probs is None else {"brier": probs.brier}
+        columns = {"brier": probs is not None}
+        if args.centerline and not args.stitch:
+            extra["centerline"] = run.tile_links
+            columns["centerline"] = True
         if ignore is None:
-            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, **extra), classes, brier=probs is not None)
+            write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, **extra), classes, **columns)
         else:
             write_tile_rows(args.tiles, tile_rows(run.tiles, run.matrices, classes, kind=args.type, ignored=run.ignored, **extra), classes,
-                            ignored=True, brier=probs is not None)
+                            ignored=True, **columns)
     if without_label:
         print("Evaluate: {} mask tiles without a label were skipped".format(without_label), file=sys.stderr)
