@@ -245,6 +245,66 @@ int rs_lovasz_fwd_ig(const float* logits, const long long* targets, float* loss,
 int rs_lovasz_softmax_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out, int N,
                              int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream, int ignore);
 
+/* BOUNDARY-WEIGHTED CrossEntropy / Focal (`rs train`: `[opt] boundary_weight`, `boundary_sigma`): the border weight map of the U-Net
+ * paper (Ronneberger et al. 2015, its first term), a per-pixel weight that decays with the distance from the nearest label boundary,
+ * made from the label raster on the device at every step.
+ *
+ * Inputs:
+ * - targets: int64 [N][H][W]
+ * - C classes
+ * - an optional ignore label
+ * - w0 > 0
+ * - sigma > 0, with R = ceil(3*sigma) and 1 <= R <= 128
+ *
+ * Rules:
+ * - A pixel is *valid* if its label is not the ignore label.
+ * - A *boundary pixel* is a valid pixel with a 4-neighbour inside the same image that is valid and has another label.
+ *   - The edge of the image is no boundary.
+ *   - The edge of an ignored region is no boundary.
+ *   - This is the rule rs_features_edt and rs_eval_boundary already follow: nothing is known there.
+ *   - Images never see each other.
+ * - d2(p) = min(R^2, squared centre-to-centre distance from p to the nearest boundary pixel of its image).
+ *   - This is rs_features_edt(complement of the boundary set, R), which gives 0 on a boundary pixel.
+ *   - An image without a boundary has R^2 everywhere.
+ * - The host makes a table in float64 and rounds it once to float32: table[k] = float32(1 + w0*exp(-k / (2*sigma^2))), k = 0 .. R^2-1.
+ * - The weight plane m is float32 [N][H][W]:
+ *   - m(p) = table[d2(p)] where d2(p) < R^2
+ *   - exactly 1.0f where d2(p) == R^2
+ *   - exactly 0.0f at an ignored pixel
+ *   - Because d2 is an integer and the table comes from the host, the plane is defined bit for bit.
+ * - Loss, for CrossEntropy and Focal alike:
+ *   - loss = sum_valid m_p*w[t_p]*l_p / sum_valid m_p*w[t_p]
+ *   - stats[1] is that denominator.
+ *   - A denominator of 0 gives loss 0 and gradient 0.
+ *   - dlogits = grad_out * m_p*w[t_p] * dl/dx / stats[1]
+ *   - The gradient is exactly +0.0f in every class plane of an ignored pixel.
+ *   - Sums are accumulated in double, as in nll_fwd_kernel.
+ *   - There are no float atomics.  The same input gives the same bits in every run.
+ *   - There is no host synchronisation.  Every call can be captured into a graph.
+ *
+ * The paper's second term (d1 + d2 to the two nearest OBJECTS, which opens gaps between touching cells) needs a feature transform
+ * (the identity of the nearest object, not only its distance) and is not built.
+ *
+ * rs_boundary_weight_plane: targets, table [R*R] (device), R, ignore (-1 for none) -> plane m.  Four launches: the uint8 complement
+ * of the boundary set (0 = boundary pixel, 1 = any other valid pixel, 2 = ignored; non-zero = set) from the int64 labels, the two
+ * passes of rs_features_edt on it (called as it is), the lookup d2 -> m.  The mask, g and d2 planes live in `workspace`
+ * (rs_boundary_weight_plane_workspace_bytes(N, H, W) = 6 bytes per pixel; RS_EINVAL for sizes rs_features_edt refuses: N > 65535,
+ * H or W > 4096, N*H*W >= 2^29).  Labels >= C other than `ignore` are undefined, as in the losses.
+ * rs_nll_loss_fwd_pw / rs_nll_loss_bwd_pw: the base signature plus `pixel_weight` [N][H][W] (ANY non-negative finite plane, not only
+ * one made above) plus `ignore` (-1 for none), with the base call's workspace: the sums above with m = pixel_weight.  They are the
+ * `_ig` kernels with one more load and one more multiply per pixel (an ignored pixel's weight is never read); with a plane of 1.0f
+ * they do the base call's arithmetic in its order.
+ * RS_EINVAL: R outside 1..128, C outside 1..8, an ignore label that is neither -1 nor in C..255, a non-positive size. */
+long rs_boundary_weight_plane_workspace_bytes(int N, int H, int W);
+int rs_boundary_weight_plane(const long long* targets, const float* table, float* plane, int N, int C, int H, int W, int R, int ignore,
+                             void* workspace, rs_stream_t stream);
+int rs_nll_loss_fwd_pw(const float* logits, const long long* targets, const float* weight, float* loss, float* stats, int N,
+                       int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream, const float* pixel_weight,
+                       int ignore);
+int rs_nll_loss_bwd_pw(const float* logits, const long long* targets, const float* weight, const float* stats,
+                       const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                       rs_stream_t stream, const float* pixel_weight, int ignore);
+
 /* Metrics.add over a whole batch (metrics.py:27-41): counts[0..3] += (tn, fn, fp, tp) in the reference's naming. */
 int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C, int H,
                         int W, rs_stream_t stream);

@@ -78,6 +78,11 @@ SIGNATURES = {
     "rs_miou_loss_bwd_ig": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int]),
     "rs_lovasz_fwd_ig": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P, c_int]),
     "rs_lovasz_softmax_fwd_ig": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int]),
+    # boundary-weighted CrossEntropy / Focal: the weight plane from the labels, and the base signature + pixel_weight + int ignore
+    "rs_boundary_weight_plane_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "rs_boundary_weight_plane": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "rs_nll_loss_fwd_pw": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, c_int]),
+    "rs_nll_loss_bwd_pw": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, c_int]),
     # bf16 path (activations typed by a dtype code / bf16 entry points)
     "rs_conv2d_fwd_bf16": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "rs_conv2d_tile_bf16": (c_int, [POINTER(ConvDesc)]),

@@ -2,6 +2,7 @@
 
 Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, loss
          [augment] zoom, brightness, contrast, saturation, gamma   (extension, optional: robosat_amd/augment.py)
+         [opt] boundary_weight, boundary_sigma   (extension, optional: the boundary weight of CrossEntropy / Focal, ``boundary_options`` below)
 Dataset: [common] dataset, classes, colors                   [weights] values
          [common] ignore   (extension, optional: the label value of pixels that carry no class, ``ignore_label`` below)
 ``cuda = true`` means "use the MI355X" (the HIP device shows up as torch's ``cuda``); ``cuda = false`` is rejected by
@@ -39,6 +40,41 @@ def ignore_label(dataset):
         raise ValueError("[common] ignore must be an integer in {}..255 (no class index of the {} classes, and a byte), got {}".format(
             num_classes, num_classes, _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)))
     return value
+
+
+BOUNDARY_LOSSES = ("CrossEntropy", "Focal")
+BOUNDARY_DEFAULT_SIGMA = 3.0
+BOUNDARY_MAX_REACH = 128  # (the radius rs_features_edt takes: include/robosat_hip.h)
+
+
+def boundary_options(model):
+    """The model config's optional ``[opt] boundary_weight`` (w0) and ``[opt] boundary_sigma`` (pixels, 3.0 when only the weight is
+    given): the boundary weight ``1 + w0 exp(-d^2 / (2 sigma^2))`` of CrossEntropy and Focal.  Returns ``None`` without the keys, else
+    ``(w0, sigma)``; raises ``ValueError("[opt] boundary_...")`` on a value that is no finite number > 0, on ``ceil(3 sigma) > 128``, on
+    a sigma without a weight and on a loss that has no per-pixel weight."""
+
+    import math
+
+    opt = model["opt"]
+    if "boundary_weight" not in opt:
+        if "boundary_sigma" in opt:
+            raise ValueError("[opt] boundary_sigma needs [opt] boundary_weight (the weight w0 at a boundary pixel)")
+        return None
+    values = {}
+    for key, default in (("boundary_weight", None), ("boundary_sigma", BOUNDARY_DEFAULT_SIGMA)):
+        value = opt.get(key, default)
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not value > 0:
+            raise ValueError("[opt] {} must be a finite number > 0, got {}".format(
+                key, _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)))
+        values[key] = float(value)
+    reach = int(math.ceil(3.0 * values["boundary_sigma"]))
+    if reach > BOUNDARY_MAX_REACH:
+        raise ValueError("[opt] boundary_sigma = {} reaches ceil(3 sigma) = {} pixels; at most {}".format(
+            _fmt(values["boundary_sigma"]), reach, BOUNDARY_MAX_REACH))
+    if opt.get("loss") not in BOUNDARY_LOSSES:
+        raise ValueError("[opt] boundary_weight weighs the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
+            " and ".join(BOUNDARY_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
+    return values["boundary_weight"], values["boundary_sigma"]
 
 
 def load_config(path):

@@ -735,3 +735,184 @@ extern "C" int rs_miou_loss_bwd_ig(const float* logits, const long long* targets
   hipStream_t s = (hipStream_t)stream;
   RS_DISPATCH_C(C, run_miou_bwd_ig<K>(logits, targets, weight, stats, grad_out, dlogits, N, HW, ignore, s));
 }
+
+// ---- boundary-weighted CrossEntropy / Focal (rs_boundary_weight_plane, rs_nll_loss_*_pw in include/robosat_hip.h) ----------------
+// The weight plane m [N][H][W] from the label raster in four launches: the complement of the boundary set as a byte mask, the two
+// passes of rs_features_edt on it (features.hip, called as it is), the lookup d2 -> m.  The loss kernels are the `_ig` kernels above
+// with one more load and one more multiply per pixel; those and the base kernels are left as they are.
+namespace {
+
+constexpr int kPlaneMaxR = 128;
+
+bool ignore_ok_pw(int ignore, int C) { return ignore == -1 || ignore_ok(ignore, C); }
+
+// mask[p] = 0 at a boundary pixel (a valid pixel with a valid 4-neighbour of another label inside its image), 1 at any other valid
+// pixel, 2 at an ignored one: non-zero = set for rs_features_edt, and the lookup needs no second look at the labels.  One thread per
+// pixel; every neighbour read is guarded by its own row / column test, so W == 1 and H == 1 read nothing but the pixel itself.
+__global__ __launch_bounds__(256) void boundary_mask_kernel(const long long* __restrict__ tgt, uint8_t* __restrict__ mask, long P,
+                                                            int H, int W, long long ignore) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const long row = p / W;  // n * H + y
+  const int x = (int)(p - row * W), y = (int)(row % H);
+  const long long t = tgt[p];
+  if (t == ignore) {
+    mask[p] = 2;
+    return;
+  }
+  bool edge = false;
+  if (x > 0) {
+    const long long q = tgt[p - 1];
+    edge |= q != t && q != ignore;
+  }
+  if (x + 1 < W) {
+    const long long q = tgt[p + 1];
+    edge |= q != t && q != ignore;
+  }
+  if (y > 0) {
+    const long long q = tgt[p - W];
+    edge |= q != t && q != ignore;
+  }
+  if (y + 1 < H) {
+    const long long q = tgt[p + W];
+    edge |= q != t && q != ignore;
+  }
+  mask[p] = edge ? 0 : 1;
+}
+
+// m[p] = 0 at an ignored pixel, 1 at the cap, table[d2] below it (d2 < cap = R * R = the table's length)
+__global__ __launch_bounds__(256) void boundary_lookup_kernel(const int* __restrict__ d2, const uint8_t* __restrict__ mask,
+                                                              const float* __restrict__ table, float* __restrict__ m, long P, int cap) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const int d = d2[p];
+  float v = 1.f;
+  if (d >= 0 && d < cap) v = table[d];
+  m[p] = mask[p] == 2 ? 0.f : v;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void nll_fwd_pw_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                         const float* __restrict__ weight, const float* __restrict__ pixw,
+                                                         double* __restrict__ partial, long P, long HW, int mode, float gamma,
+                                                         int ignore) {
+  __shared__ double red[2][4];
+  double sl = 0, sw = 0;
+  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
+    const int t = (int)tgt[p];
+    if (t == ignore) continue;
+    const long n = p / HW, hw = p - n * HW;
+    float v[C];
+    load_logits<C>(x, n, hw, HW, v);
+    const float w = pixw[p] * (weight ? weight[t] : 1.f);
+    const float l = pixel_loss<C>(v, t, mode, gamma, nullptr);
+    sl += (double)(w * l);
+    sw += (double)w;
+  }
+  sl = rs_wave_sum(sl);
+  sw = rs_wave_sum(sw);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    red[0][wave] = sl;
+    red[1][wave] = sw;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partial[blockIdx.x * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+    partial[blockIdx.x * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void nll_bwd_pw_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                         const float* __restrict__ weight, const float* __restrict__ pixw,
+                                                         const float* __restrict__ stats, const float* __restrict__ gout,
+                                                         float* __restrict__ dx, long P, long HW, int mode, float gamma, int ignore) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const long n = p / HW, hw = p - n * HW;
+  const int t = (int)tgt[p];
+  if (t == ignore || !(stats[1] > 0.f)) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
+    return;
+  }
+  float v[C], g[C];
+  load_logits<C>(x, n, hw, HW, v);
+  const float w = pixw[p] * (weight ? weight[t] : 1.f);
+  pixel_loss<C>(v, t, mode, gamma, &g);
+  const float k = (gout ? gout[0] : 1.f) * w / stats[1];
+#pragma unroll
+  for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = k * g[c];
+}
+
+template <int C>
+int run_fwd_pw(const float* x, const long long* t, const float* w, const float* pixw, float* loss, float* stats, double* part, long P,
+               long HW, int mode, float gamma, int ignore, hipStream_t s) {
+  const long nb = (P + 255) / 256;
+  const int grid = nb < kLossBlocks ? (int)nb : kLossBlocks;
+  nll_fwd_pw_kernel<C><<<grid, 256, 0, s>>>(x, t, w, pixw, part, P, HW, mode, gamma, ignore);
+  nll_finalize_ig_kernel<<<1, 256, 0, s>>>(part, grid, loss, stats);
+  return RS_LAUNCH_RESULT();
+}
+
+template <int C>
+int run_bwd_pw(const float* x, const long long* t, const float* w, const float* pixw, const float* stats, const float* gout, float* dx,
+               long P, long HW, int mode, float gamma, int ignore, hipStream_t s) {
+  nll_bwd_pw_kernel<C><<<rs_cdiv(P, 256), 256, 0, s>>>(x, t, w, pixw, stats, gout, dx, P, HW, mode, gamma, ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+// (the sizes rs_features_edt takes: its own check refuses the rest, this one keeps the workspace query in step with it)
+bool plane_shape_ok(int N, int H, int W) {
+  return N > 0 && N <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)N * H * W < (1l << 29);
+}
+
+}  // namespace
+
+extern "C" long rs_boundary_weight_plane_workspace_bytes(int N, int H, int W) {
+  if (!plane_shape_ok(N, H, W)) return RS_EINVAL;
+  return 6 * (long)N * H * W;  // d2 int32, then the mask and g bytes
+}
+
+extern "C" int rs_boundary_weight_plane(const long long* targets, const float* table, float* plane, int N, int C, int H, int W, int R,
+                                        int ignore, void* workspace, rs_stream_t stream) {
+  if (!targets || !table || !plane || !workspace || ((uintptr_t)workspace & 3) || !plane_shape_ok(N, H, W) || C <= 0 || C > kMaxC ||
+      R < 1 || R > kPlaneMaxR || !ignore_ok_pw(ignore, C))
+    return RS_EINVAL;
+  const long P = (long)N * H * W;
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* d2 = static_cast<int32_t*>(workspace);
+  uint8_t* mask = reinterpret_cast<uint8_t*>(d2 + P);
+  uint8_t* g = mask + P;
+  boundary_mask_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(targets, mask, P, H, W, (long long)ignore);
+  int rc = RS_LAUNCH_RESULT();
+  if (rc) return rc;
+  rc = rs_features_edt(mask, nullptr, g, d2, N, H, W, R, stream);
+  if (rc) return rc;
+  boundary_lookup_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(d2, mask, table, plane, P, R * R);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_nll_loss_fwd_pw(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
+                                  int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream,
+                                  const float* pixel_weight, int ignore) {
+  if (!logits || !targets || !loss || !stats || !workspace || !pixel_weight || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
+      mode < 0 || mode > 1 || !ignore_ok_pw(ignore, C))
+    return RS_EINVAL;
+  const long HW = (long)H * W, P = (long)N * HW;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(workspace);
+  RS_DISPATCH_C(C, run_fwd_pw<K>(logits, targets, weight, pixel_weight, loss, stats, part, P, HW, mode, gamma, ignore, s));
+}
+
+extern "C" int rs_nll_loss_bwd_pw(const float* logits, const long long* targets, const float* weight, const float* stats,
+                                  const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                                  rs_stream_t stream, const float* pixel_weight, int ignore) {
+  if (!logits || !targets || !stats || !dlogits || !pixel_weight || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || mode < 0 ||
+      mode > 1 || !ignore_ok_pw(ignore, C))
+    return RS_EINVAL;
+  const long HW = (long)H * W, P = (long)N * HW;
+  hipStream_t s = (hipStream_t)stream;
+  RS_DISPATCH_C(C, run_bwd_pw<K>(logits, targets, weight, pixel_weight, stats, grad_out, dlogits, P, HW, mode, gamma, ignore, s));
+}

@@ -6,7 +6,10 @@ the arithmetic in ``librobosat_hip.so`` (``rs_nll_loss_*``, ``rs_lovasz_fwd``), 
 Every loss takes ``ignore_index=None``, the ``ignore_index`` of ``nn.CrossEntropyLoss`` for all five: a label value (no class, at
 most 255) whose pixels are left out -- the loss is the same definition evaluated on the other pixels only, as if the ignored
 ones had been cut out of every image (``rs_*_ig``, include/robosat_hip.h; DESIGN.md "Ignore label").  ``None`` makes exactly the
-calls made without the argument."""
+calls made without the argument.
+
+``CrossEntropyLoss2d`` and ``FocalLoss2d`` also take ``boundary=(w0, sigma)``: the U-Net paper's border weight map on top of the class
+weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``).  ``mIoULoss2d`` and the two Lovasz forms do not."""
 
 import torch
 import torch.nn as nn
@@ -117,6 +120,28 @@ class _NLLFn(torch.autograd.Function):
         return ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma, ignore=ctx.ignore), None, None, None, None, None, None
 
 
+class _NLLBoundaryFn(torch.autograd.Function):
+    """``_NLLFn`` with the boundary weight plane (``ops.boundary_weight_plane``) made from ``targets`` in forward and kept for
+    backward; the exchange of ``stats[1]`` is the same one."""
+
+    @staticmethod
+    def forward(ctx, inputs, targets, weight, mode, gamma, global_batch, ignore, boundary):
+        x = inputs.detach().float()
+        plane = ops.boundary_weight_plane(targets, boundary[0], boundary[1], ignore=ignore, classes=x.shape[1])
+        loss, stats = ops.nll_loss_fwd(x, targets, weight, mode, gamma, ignore=ignore, pixel_weight=plane)
+        loss = _global_batch_normaliser(loss, stats, global_batch)
+        ctx.save_for_backward(x, targets, stats, plane)
+        ctx.weight, ctx.mode, ctx.gamma, ctx.ignore = weight, mode, gamma, ignore
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, stats, plane = ctx.saved_tensors
+        g = grad_out.detach().float().contiguous()
+        dx = ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma, ignore=ctx.ignore, pixel_weight=plane)
+        return dx, None, None, None, None, None, None, None
+
+
 class _MIoUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, targets, weight, global_batch=False, ignore=None):
@@ -172,27 +197,51 @@ class _WeightedLoss(nn.Module):
         self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32).clone())
 
 
+def _check_boundary(boundary):
+    """``boundary`` = ``(w0, sigma)`` of the boundary weight (``None`` passes): both finite and > 0, ``ceil(3 sigma) <= 128``."""
+
+    if boundary is None:
+        return None
+    try:
+        w0, sigma = boundary
+    except (TypeError, ValueError):
+        raise ValueError("boundary must be None or a pair (w0, sigma), got {!r}".format(boundary))
+    ops.boundary_reach(w0, sigma)
+    return (float(w0), float(sigma))
+
+
 class CrossEntropyLoss2d(_WeightedLoss):
-    """Cross-entropy: weighted NLL of log_softmax over the class axis (reference losses.py:8-25)."""
+    """Cross-entropy: weighted NLL of log_softmax over the class axis (reference losses.py:8-25).  ``boundary=(w0, sigma)``: every
+    pixel's term is also weighted by ``1 + w0 exp(-d^2 / (2 sigma^2))``, d its distance to the nearest label boundary, made from
+    ``targets`` on the device in every call (include/robosat_hip.h; DESIGN.md "Boundary weight"); ``None`` makes today's calls."""
+
+    def __init__(self, weight=None, ignore_index=None, boundary=None):
+        super().__init__(weight, ignore_index)
+        self.boundary = _check_boundary(boundary)
 
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
         ignore = _check_ignore(self.ignore_index, inputs)
+        if self.boundary is not None:
+            return _NLLBoundaryFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch, ignore, self.boundary)
         if ignore is None:
             return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch)
         return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch, ignore)
 
 
 class FocalLoss2d(_WeightedLoss):
-    """Focal loss, gamma = 2 by default (reference losses.py:28-50)."""
+    """Focal loss, gamma = 2 by default (reference losses.py:28-50); ``boundary`` as in ``CrossEntropyLoss2d``."""
 
-    def __init__(self, gamma=2, weight=None, ignore_index=None):
+    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None):
         super().__init__(weight, ignore_index)
         self.gamma = gamma
+        self.boundary = _check_boundary(boundary)
 
     def forward(self, inputs, targets):
         inputs, targets = _check(inputs, targets)
         ignore = _check_ignore(self.ignore_index, inputs)
+        if self.boundary is not None:
+            return _NLLBoundaryFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch, ignore, self.boundary)
         if ignore is None:
             return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch)
         return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch, ignore)

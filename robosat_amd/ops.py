@@ -1268,15 +1268,82 @@ def _ignore_label(ignore, classes):
     return int(ignore)
 
 
-def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None):
+BOUNDARY_MAX_REACH = 128
+_BOUNDARY_TABLES = {}
+
+
+def boundary_reach(w0, sigma):
+    """R = ceil(3 * sigma), the reach in pixels of the boundary weight ``1 + w0 * exp(-d^2 / (2 sigma^2))`` (include/robosat_hip.h);
+    raises ``ValueError`` unless both are finite numbers > 0 and 1 <= R <= 128."""
+
+    import math
+
+    for name, value in (("w0", w0), ("sigma", sigma)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not value > 0:
+            raise ValueError("robosat_amd: the boundary weight's {} is a finite number > 0, got {!r}".format(name, value))
+    reach = int(math.ceil(3.0 * float(sigma)))
+    if not 1 <= reach <= BOUNDARY_MAX_REACH:
+        raise ValueError("robosat_amd: the boundary weight reaches ceil(3 * sigma) = {} pixels, more than {}".format(reach, BOUNDARY_MAX_REACH))
+    return reach
+
+
+def boundary_table(w0, sigma):
+    """float32 numpy [R * R]: ``table[k] = float32(1 + w0 * exp(-k / (2 sigma^2)))``, made in float64 and rounded once."""
+
+    import numpy as np
+
+    reach = boundary_reach(w0, sigma)
+    k = np.arange(reach * reach, dtype=np.float64)
+    return (1.0 + float(w0) * np.exp(-k / (2.0 * float(sigma) * float(sigma)))).astype(np.float32)
+
+
+def _boundary_table_on(w0, sigma, device):
+    """The table on ``device``, cached per (w0, sigma, device): made and uploaded once, before any capture that uses it."""
+
+    key = (float(w0), float(sigma), str(device))
+    table = _BOUNDARY_TABLES.get(key)
+    if table is None:
+        table = torch.from_numpy(boundary_table(w0, sigma)).to(device)
+        _BOUNDARY_TABLES[key] = table
+    return table
+
+
+def boundary_weight_plane(targets, w0, sigma, ignore=None, classes=None):
+    """int64 [N, H, W] labels -> float32 [N, H, W]: the boundary weight plane of ``rs_boundary_weight_plane``
+    (include/robosat_hip.h): ``table[d2]`` within ``ceil(3 sigma)`` pixels of a label boundary, exactly 1 beyond, exactly 0 at a pixel
+    whose label is ``ignore``.  ``classes`` (the logits' class count) lets ``ignore`` be checked against it here; without it the
+    loss call does that."""
+
+    n, h, w = targets.shape
+    reach = boundary_reach(w0, sigma)
+    c = 1 if classes is None else int(classes)
+    ignore = _ignore_label(ignore, c)
+    tgt = _dev(targets, "targets", torch.int64)  # (a CPU tensor raises before anything is loaded or sized)
+    lib = _lib.lib()
+    table = _boundary_table_on(w0, sigma, targets.device)
+    plane = torch.empty((n, h, w), device=targets.device, dtype=torch.float32)
+    _call("rs_boundary_weight_plane", tgt, _dev(table, "table"), _dev(plane, "plane"), n, c, h, w, reach, -1 if ignore is None else ignore,
+          _workspace(lib.rs_boundary_weight_plane_workspace_bytes(n, h, w), targets.device), _stream())
+    return plane
+
+
+def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None, pixel_weight=None):
     """``ignore`` (here and in the four losses below): the label value whose pixels are left out of the loss
-    (``rs_*_ig`` in include/robosat_hip.h); ``None`` calls the entry point without it."""
+    (``rs_*_ig`` in include/robosat_hip.h); ``None`` calls the entry point without it.  ``pixel_weight`` float32 [N, H, W]
+    (``rs_nll_loss_*_pw``): a non-negative weight per pixel on top of the class weight; ``None`` makes the calls made without it."""
 
     n, c, h, w = logits.shape
     lib = _lib.lib()
     ignore = _ignore_label(ignore, c)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     stats = torch.empty(2, device=logits.device, dtype=torch.float32)
+    if pixel_weight is not None:
+        assert tuple(pixel_weight.shape) == (n, h, w), "pixel_weight is [N, H, W]"
+        _call("rs_nll_loss_fwd_pw", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma),
+              _workspace(lib.rs_nll_loss_workspace_bytes(), logits.device), _stream(), _dev(pixel_weight, "pixel_weight"),
+              -1 if ignore is None else ignore)
+        return loss, stats
     if ignore is not None:
         _call("rs_nll_loss_fwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
               _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma),
@@ -1288,10 +1355,16 @@ def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None):
     return loss, stats
 
 
-def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0, ignore=None):
+def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0, ignore=None, pixel_weight=None):
     n, c, h, w = logits.shape
     ignore = _ignore_label(ignore, c)
     dlogits = torch.empty_like(logits)
+    if pixel_weight is not None:
+        assert tuple(pixel_weight.shape) == (n, h, w), "pixel_weight is [N, H, W]"
+        _call("rs_nll_loss_bwd_pw", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mode, ctypes.c_float(gamma),
+              _stream(), _dev(pixel_weight, "pixel_weight"), -1 if ignore is None else ignore)
+        return dlogits
     if ignore is not None:
         _call("rs_nll_loss_bwd_ig", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
               _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mode, ctypes.c_float(gamma),

@@ -24,12 +24,16 @@ Differences by design:
     ``device_augment``, ``grad_dtype`` (bf16 gradient exchange), ``graph`` (the step as one hipGraph replay).
   * dataset ``[common] ignore`` (extension key, optional: robosat_amd/config.py): the label value of pixels that carry no class.
     They are left out of the loss (the criterion's ``ignore_index``) and, as every label outside the classes, of the metrics.
+  * ``[opt] boundary_weight`` / ``boundary_sigma`` (extension keys, optional: robosat_amd/config.py): CrossEntropy and Focal weigh
+    every pixel by ``1 + w0 exp(-d^2 / (2 sigma^2))``, d its distance to the nearest label boundary, from a plane made on the device
+    out of the batch's label raster as it is after the augmentation (robosat_amd/losses.py); training and validation alike.
   * ``[augment]`` (extension table, optional: robosat_amd/augment.py): a random zoom-in crop and brightness / contrast /
     saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.
 """
 
 import argparse
 import collections
+import math
 import os
 import sys
 import time
@@ -44,7 +48,7 @@ from tqdm import tqdm
 from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
-from robosat_amd.config import check_num_classes, ignore_label, load_config
+from robosat_amd.config import boundary_options, check_num_classes, ignore_label, load_config
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
 from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, mIoULoss2d
@@ -143,6 +147,7 @@ def main(args):
     dataset = load_config(args.dataset)
     try:
         ignore = ignore_label(dataset)  # (dataset `[common] ignore`, optional: label pixels that are left out of the loss)
+        boundary = boundary_options(model)  # (model `[opt] boundary_weight / boundary_sigma`, optional: None without the keys)
     except ValueError as err:
         sys.exit("Error: {}".format(err))  # (before any work starts)
 
@@ -235,12 +240,14 @@ def main(args):
     loss_name = model["opt"]["loss"]
     # (without `[common] ignore` the criteria are built and called exactly as before)
     ignored = {} if ignore is None else {"ignore_index": ignore}
+    # (and without `[opt] boundary_weight` likewise; with it the loss is CrossEntropy or Focal: boundary_options)
+    weighted = {} if boundary is None else {"boundary": boundary}
     if loss_name == "CrossEntropy":
-        criterion = CrossEntropyLoss2d(weight=weight, **ignored).to(device)
+        criterion = CrossEntropyLoss2d(weight=weight, **ignored, **weighted).to(device)
     elif loss_name == "mIoU":
         criterion = mIoULoss2d(weight=weight, **ignored).to(device)
     elif loss_name == "Focal":
-        criterion = FocalLoss2d(weight=weight, **ignored).to(device)
+        criterion = FocalLoss2d(weight=weight, **ignored, **weighted).to(device)
     elif loss_name == "Lovasz":
         criterion = LovaszLoss2d(**ignored).to(device)
     elif loss_name == "LovaszSoftmax":
@@ -292,6 +299,8 @@ def main(args):
         say("Weights :\t {}".format(dataset["weights"]["values"]))
     if ignore is not None:
         say("Ignore label:\t {}".format(ignore))
+    if boundary is not None:
+        say("Boundary weight:\t w0 = {}, sigma = {} px (reach {} px)".format(boundary[0], boundary[1], int(math.ceil(3.0 * boundary[1]))))
     if jitter is not None:
         say("Augmentation:\t {}".format(describe_jitter(jitter)))
     say("---")
