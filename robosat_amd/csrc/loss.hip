@@ -8,12 +8,31 @@
 //   Metrics.add (robosat/metrics.py:27-41): argmax over classes, then the reference's pred/actual quotient trick.
 //
 // HBM-bound: one thread per pixel, plane-wise coalesced reads; reductions in fp64, two deterministic stages.
+//
+// Every loss kernel is ONE body with the per-pixel variant as a compile-time parameter (Px):
+//   Plain          every pixel counts (rs_nll_loss_*, rs_miou_loss_*)
+//   Ignore         the loss of the pixels whose label is not `ignore`, as if the ignored ones had been cut out of every image: an
+//                  ignored pixel has no weight, no loss and a gradient of +0.0f in every class plane, its label byte never indexes
+//                  `weight`, and its logits reach no result (rs_*_ig in include/robosat_hip.h)
+//   IgnoreWeight   Ignore with one more load and one more multiply per pixel: the weight plane `pixw` [N][H][W] on top of the class
+//                  weight (rs_nll_loss_*_pw; the plane itself: rs_boundary_weight_plane, further down)
+// The variant's statements stand under `if constexpr`, each variant in the statement order it has always had (Plain reads the label
+// behind the logits, the other two in front of them: an ignored pixel's logits are never read), so with no pixel ignored all
+// three do the same arithmetic in the same order.  What a variant needs beyond the Plain arguments travels as one trailing kernel
+// argument (see IgnoreAndWeight below), so a Plain or Ignore instantiation compiles to the instructions of the separate kernel it
+// replaced; the IgnoreWeight ones take `pixw` in another place than theirs did and differ in how the arguments are loaded
+// (profiles/loss_variants/).  A body shared through an inlined function does not keep the instructions: it is simplified on its
+// own before it is inlined.
+#include <initializer_list>
+
 #include "common.h"
 
 namespace {
 
 constexpr int kMaxC = 8;
 constexpr int kLossBlocks = 1024;
+
+enum class Px { Plain, Ignore, IgnoreWeight };
 
 template <int C>
 __device__ __forceinline__ void load_logits(const float* __restrict__ x, long n, long hw, long HW, float (&v)[C]) {
@@ -58,18 +77,37 @@ __device__ __forceinline__ float pixel_loss(const float (&v)[C], int t, int mode
   return -pw * logp;
 }
 
-template <int C>
+// What a variant's kernel needs beyond the Plain arguments is ONE trailing argument: the pack `extra` holds nothing (Plain, which
+// so keeps the argument list it has always had), `int ignore` (Ignore) or an IgnoreAndWeight, and `(extra, ...)` is that argument.
+struct IgnoreAndWeight {
+  int ignore;
+  const float* pixw;
+};
+
+// partial[block] = (sum w*l, sum w) of the block
+template <int C, Px V, typename... Extra>
 __global__ __launch_bounds__(256) void nll_fwd_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
                                                       const float* __restrict__ weight, double* __restrict__ partial,
-                                                      long P, long HW, int mode, float gamma) {
+                                                      long P, long HW, int mode, float gamma, Extra... extra) {
   __shared__ double red[2][4];
+  [[maybe_unused]] int ignore = 0;
+  [[maybe_unused]] const float* pixw = nullptr;
+  if constexpr (V == Px::Ignore) ignore = (extra, ...);
+  if constexpr (V == Px::IgnoreWeight) ignore = (extra, ...).ignore, pixw = (extra, ...).pixw;
   double sl = 0, sw = 0;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
+    int t;
+    if constexpr (V != Px::Plain) {
+      t = (int)tgt[p];
+      if (t == ignore) continue;
+    }
     const long n = p / HW, hw = p - n * HW;
     float v[C];
     load_logits<C>(x, n, hw, HW, v);
-    const int t = (int)tgt[p];
-    const float w = weight ? weight[t] : 1.f;
+    if constexpr (V == Px::Plain) t = (int)tgt[p];
+    float w;
+    if constexpr (V == Px::IgnoreWeight) w = pixw[p] * (weight ? weight[t] : 1.f);
+    else w = weight ? weight[t] : 1.f;
     const float l = pixel_loss<C>(v, t, mode, gamma, nullptr);
     sl += (double)(w * l);
     sw += (double)w;
@@ -88,7 +126,9 @@ __global__ __launch_bounds__(256) void nll_fwd_kernel(const float* __restrict__ 
   }
 }
 
-// loss = sum(w*l) / sum(w); stats[0] = loss, stats[1] = sum(w)
+// loss = sum(w*l) / sum(w); stats[0] = loss, stats[1] = sum(w).  Guarded (the Ignore variants): no valid weight at all
+// (sum(w) == 0) gives loss 0, and stats[1] = 0 tells the backward; unguarded (Plain) it stays the NaN of 0 / 0.
+template <bool Guarded>
 __global__ void nll_finalize_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss,
                                     float* __restrict__ stats) {
   __shared__ double red[2][256];
@@ -108,7 +148,9 @@ __global__ void nll_finalize_kernel(const double* __restrict__ partial, int nblo
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const float l = (float)(red[0][0] / red[1][0]);
+    float l;
+    if constexpr (Guarded) l = red[1][0] > 0.0 ? (float)(red[0][0] / red[1][0]) : 0.f;
+    else l = (float)(red[0][0] / red[1][0]);
     loss[0] = l;
     stats[0] = l;
     stats[1] = (float)red[1][0];
@@ -116,18 +158,33 @@ __global__ void nll_finalize_kernel(const double* __restrict__ partial, int nblo
 }
 
 // dx[c][p] = gout * w[t_p] * dl_p/dx_c / sum(w)
-template <int C>
+template <int C, Px V, typename... Extra>
 __global__ __launch_bounds__(256) void nll_bwd_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
                                                       const float* __restrict__ weight, const float* __restrict__ stats,
                                                       const float* __restrict__ gout, float* __restrict__ dx, long P, long HW,
-                                                      int mode, float gamma) {
+                                                      int mode, float gamma, Extra... extra) {
+  [[maybe_unused]] int ignore = 0;
+  [[maybe_unused]] const float* pixw = nullptr;
+  if constexpr (V == Px::Ignore) ignore = (extra, ...);
+  if constexpr (V == Px::IgnoreWeight) ignore = (extra, ...).ignore, pixw = (extra, ...).pixw;
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= P) return;
   const long n = p / HW, hw = p - n * HW;
+  int t;
+  if constexpr (V != Px::Plain) {
+    t = (int)tgt[p];
+    if (t == ignore || !(stats[1] > 0.f)) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
+      return;
+    }
+  }
   float v[C], g[C];
   load_logits<C>(x, n, hw, HW, v);
-  const int t = (int)tgt[p];
-  const float w = weight ? weight[t] : 1.f;
+  if constexpr (V == Px::Plain) t = (int)tgt[p];
+  float w;
+  if constexpr (V == Px::IgnoreWeight) w = pixw[p] * (weight ? weight[t] : 1.f);
+  else w = weight ? weight[t] : 1.f;
   pixel_loss<C>(v, t, mode, gamma, &g);
   const float k = (gout ? gout[0] : 1.f) * w / stats[1];
 #pragma unroll
@@ -176,28 +233,35 @@ __global__ __launch_bounds__(256) void confusion_kernel(const float* __restrict_
   if (threadIdx.x < 4) atomicAdd(&counts[threadIdx.x], (unsigned long long)red[threadIdx.x]);
 }
 
-template <int C>
-int run_fwd(const float* x, const long long* t, const float* w, float* loss, float* stats, double* part, long P, long HW,
-            int mode, float gamma, hipStream_t s) {
+inline int loss_grid(long P) {
   const long nb = (P + 255) / 256;
-  const int grid = nb < kLossBlocks ? (int)nb : kLossBlocks;
-  nll_fwd_kernel<C><<<grid, 256, 0, s>>>(x, t, w, part, P, HW, mode, gamma);
-  nll_finalize_kernel<<<1, 256, 0, s>>>(part, grid, loss, stats);
+  return nb < kLossBlocks ? (int)nb : kLossBlocks;
+}
+
+// (extra: the variant's trailing kernel arguments)
+template <int C, Px V, typename... Extra>
+int run_fwd(const float* x, const long long* t, const float* w, float* loss, float* stats, void* workspace, int N, int H, int W,
+            int mode, float gamma, rs_stream_t stream, Extra... extra) {
+  const long HW = (long)H * W, P = (long)N * HW;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(workspace);
+  const int grid = loss_grid(P);
+  nll_fwd_kernel<C, V><<<grid, 256, 0, s>>>(x, t, w, part, P, HW, mode, gamma, extra...);
+  nll_finalize_kernel<V != Px::Plain><<<1, 256, 0, s>>>(part, grid, loss, stats);
   return RS_LAUNCH_RESULT();
 }
 
-template <int C>
-int run_bwd(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, long P,
-            long HW, int mode, float gamma, hipStream_t s) {
-  nll_bwd_kernel<C><<<rs_cdiv(P, 256), 256, 0, s>>>(x, t, w, stats, gout, dx, P, HW, mode, gamma);
+template <int C, Px V, typename... Extra>
+int run_bwd(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, int N, int H, int W,
+            int mode, float gamma, rs_stream_t stream, Extra... extra) {
+  const long HW = (long)H * W, P = (long)N * HW;
+  nll_bwd_kernel<C, V><<<rs_cdiv(P, 256), 256, 0, (hipStream_t)stream>>>(x, t, w, stats, gout, dx, P, HW, mode, gamma, extra...);
   return RS_LAUNCH_RESULT();
 }
 
 template <int C>
 int run_conf(const float* x, const long long* t, unsigned long long* counts, long P, long HW, hipStream_t s) {
-  const long nb = (P + 255) / 256;
-  const int grid = nb < kLossBlocks ? (int)nb : kLossBlocks;
-  confusion_kernel<C><<<grid, 256, 0, s>>>(x, t, counts, P, HW);
+  confusion_kernel<C><<<loss_grid(P), 256, 0, s>>>(x, t, counts, P, HW);
   return RS_LAUNCH_RESULT();
 }
 
@@ -206,10 +270,11 @@ int run_conf(const float* x, const long long* t, unsigned long long* counts, lon
 // soft IoU per (class c, image n): inter = sum_p s_c m_c, union = sum_p (s_c + m_c - s_c m_c); miou = 1 - mean(inter/union);
 // the reference returns Python max(miou, weighted NLL): whichever is larger, gradient through that branch only.
 // Per-(n,c) sums: A = sum_{p: t=c} s_c, B = sum_p s_c, cnt = #{p: t=c}  =>  inter = A, union = B + cnt - A.
-template <int C>
+// Ignore: A, B, cnt and the two NLL sums all leave an ignored pixel out.
+template <int C, bool Ignore, typename... Extra>
 __global__ __launch_bounds__(256) void miou_partial_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
                                                            const float* __restrict__ weight, double* __restrict__ partial,
-                                                           long HW, int nblk) {
+                                                           long HW, int nblk, Extra... extra) {
   // partial[(n*nblk + b)][3*C + 2]
   __shared__ double red[4][3 * C + 2];
   const long n = blockIdx.y;
@@ -217,9 +282,14 @@ __global__ __launch_bounds__(256) void miou_partial_kernel(const float* __restri
 #pragma unroll
   for (int i = 0; i < 3 * C + 2; ++i) acc[i] = 0;
   for (long hw = (long)blockIdx.x * 256 + threadIdx.x; hw < HW; hw += (long)nblk * 256) {
+    int t;
+    if constexpr (Ignore) {
+      t = (int)tgt[n * HW + hw];
+      if (t == (extra, ...)) continue;
+    }
     float v[C];
     load_logits<C>(x, n, hw, HW, v);
-    const int t = (int)tgt[n * HW + hw];
+    if constexpr (!Ignore) t = (int)tgt[n * HW + hw];
     float mx = v[0];
 #pragma unroll
     for (int c = 1; c < C; ++c) mx = fmaxf(mx, v[c]);
@@ -255,6 +325,11 @@ __global__ __launch_bounds__(256) void miou_partial_kernel(const float* __restri
   }
 }
 
+// The two finalize kernels stay two: they are different algorithms, not one body with a compare more.  The `_ig` form has to know
+// whether an image has any valid pixel before it writes the image's coefficients, so it keeps A, B and cnt of all C classes in
+// per-class arrays, and costs 16-53 % more for it (profiles/ignore_label/README.md); one template would either slow the plain
+// path or be an `if constexpr` around two whole bodies.
+//
 // stats: [0] loss, [1] sum w, [2] branch (0 = miou, 1 = nll), [3 + n*C + c] = g for m=1, [3 + N*C + n*C + c] = g for m=0,
 // [3 + 2*N*C] = the miou branch's value, [4 + 2*N*C] = the nll branch's numerator sum_i w_i l_i (data-parallel ranks
 // exchange these two and [1] to take the reference's ONE branch decision over the global batch: robosat_amd/losses.py)
@@ -293,289 +368,6 @@ __global__ void miou_finalize_kernel(const double* __restrict__ partial, int N, 
   stats[2] = use_nll ? 1.f : 0.f;
   stats[3 + 2 * N * C] = miou;
   stats[4 + 2 * N * C] = (float)sl;
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void miou_bwd_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                       const float* __restrict__ weight, const float* __restrict__ stats,
-                                                       const float* __restrict__ gout, float* __restrict__ dx, int N, long HW) {
-  const long hw = (long)blockIdx.x * 256 + threadIdx.x;
-  const long n = blockIdx.y;
-  if (hw >= HW) return;
-  float v[C], g[C];
-  load_logits<C>(x, n, hw, HW, v);
-  const int t = (int)tgt[n * HW + hw];
-  const float go = gout ? gout[0] : 1.f;
-  if (stats[2] > 0.5f) {
-    const float w = weight ? weight[t] : 1.f;
-    pixel_loss<C>(v, t, 0, 0.f, &g);
-    const float k = go * w / stats[1];
-#pragma unroll
-    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = k * g[c];
-    return;
-  }
-  float mx = v[0];
-#pragma unroll
-  for (int c = 1; c < C; ++c) mx = fmaxf(mx, v[c]);
-  float sum = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    v[c] = expf(v[c] - mx);
-    sum += v[c];
-  }
-  float dot = 0.f;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    v[c] = v[c] / sum;
-    g[c] = (c == t) ? stats[3 + n * C + c] : stats[3 + N * C + n * C + c];
-    dot += g[c] * v[c];
-  }
-#pragma unroll
-  for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = go * v[c] * (g[c] - dot);
-}
-
-constexpr int kMiouBlocks = 64;  // per image
-
-template <int C>
-int run_miou_fwd(const float* x, const long long* t, const float* w, float* loss, float* stats, double* part, int N, long HW,
-                 hipStream_t s) {
-  const long nb = (HW + 255) / 256;
-  const int nblk = nb < kMiouBlocks ? (int)nb : kMiouBlocks;
-  miou_partial_kernel<C><<<dim3(nblk, N), 256, 0, s>>>(x, t, w, part, HW, nblk);
-  miou_finalize_kernel<<<1, 64, 0, s>>>(part, N, C, nblk, loss, stats);
-  return RS_LAUNCH_RESULT();
-}
-
-template <int C>
-int run_miou_bwd(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, int N,
-                 long HW, hipStream_t s) {
-  miou_bwd_kernel<C><<<dim3(rs_cdiv(HW, 256), N), 256, 0, s>>>(x, t, w, stats, gout, dx, N, HW);
-  return RS_LAUNCH_RESULT();
-}
-
-#define RS_DISPATCH_C(C, CALL)              \
-  switch (C) {                              \
-    case 1: { constexpr int K = 1; return CALL; } \
-    case 2: { constexpr int K = 2; return CALL; } \
-    case 3: { constexpr int K = 3; return CALL; } \
-    case 4: { constexpr int K = 4; return CALL; } \
-    case 5: { constexpr int K = 5; return CALL; } \
-    case 6: { constexpr int K = 6; return CALL; } \
-    case 7: { constexpr int K = 7; return CALL; } \
-    default: { constexpr int K = 8; return CALL; } \
-  }
-
-}  // namespace
-
-extern "C" long rs_nll_loss_workspace_bytes(void) { return (long)kLossBlocks * 2 * (long)sizeof(double); }
-
-extern "C" int rs_nll_loss_fwd(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
-                               int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream) {
-  if (!logits || !targets || !loss || !stats || !workspace || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
-      mode < 0 || mode > 1)
-    return RS_EINVAL;
-  const long HW = (long)H * W, P = (long)N * HW;
-  hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(workspace);
-  RS_DISPATCH_C(C, run_fwd<K>(logits, targets, weight, loss, stats, part, P, HW, mode, gamma, s));
-}
-
-extern "C" int rs_nll_loss_bwd(const float* logits, const long long* targets, const float* weight, const float* stats,
-                               const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
-                               rs_stream_t stream) {
-  if (!logits || !targets || !stats || !dlogits || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || mode < 0 || mode > 1)
-    return RS_EINVAL;
-  const long HW = (long)H * W, P = (long)N * HW;
-  hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH_C(C, run_bwd<K>(logits, targets, weight, stats, grad_out, dlogits, P, HW, mode, gamma, s));
-}
-
-extern "C" int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C,
-                                   int H, int W, rs_stream_t stream) {
-  if (!scores || !targets || !counts || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0) return RS_EINVAL;
-  const long HW = (long)H * W, P = (long)N * HW;
-  hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH_C(C, run_conf<K>(scores, targets, counts, P, HW, s));
-}
-
-extern "C" long rs_miou_loss_workspace_bytes(int N, int C) {
-  if (N <= 0 || C <= 0 || C > kMaxC) return RS_EINVAL;
-  return (long)N * kMiouBlocks * (3 * C + 2) * (long)sizeof(double);
-}
-
-extern "C" int rs_miou_loss_fwd(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
-                                int N, int C, int H, int W, void* workspace, rs_stream_t stream) {
-  if (!logits || !targets || !loss || !stats || !workspace || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0)
-    return RS_EINVAL;
-  const long HW = (long)H * W;
-  hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(workspace);
-  RS_DISPATCH_C(C, run_miou_fwd<K>(logits, targets, weight, loss, stats, part, N, HW, s));
-}
-
-extern "C" int rs_miou_loss_bwd(const float* logits, const long long* targets, const float* weight, const float* stats,
-                                const float* grad_out, float* dlogits, int N, int C, int H, int W, rs_stream_t stream) {
-  if (!logits || !targets || !stats || !dlogits || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0) return RS_EINVAL;
-  const long HW = (long)H * W;
-  hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH_C(C, run_miou_bwd<K>(logits, targets, weight, stats, grad_out, dlogits, N, HW, s));
-}
-
-// ---- the same losses over the pixels whose label is not `ignore` (rs_*_ig in include/robosat_hip.h) -----------------------------
-// The loss of the valid pixels alone, as if the ignored ones had been cut out of every image: an ignored pixel has no weight, no
-// loss and a gradient of +0.0f in every class plane, its label byte never indexes `weight`, and its logits reach no result.  The
-// kernels above are left as they are (the same instructions as before, profiles/ignore_label/asm_identity.txt); these are their
-// copies with the one compare per pixel, so that with no pixel ignored they do the same arithmetic in the same order.
-namespace {
-
-bool ignore_ok(int ignore, int C) { return ignore >= C && ignore <= 255; }
-
-template <int C>
-__global__ __launch_bounds__(256) void nll_fwd_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                         const float* __restrict__ weight, double* __restrict__ partial,
-                                                         long P, long HW, int mode, float gamma, int ignore) {
-  __shared__ double red[2][4];
-  double sl = 0, sw = 0;
-  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
-    const int t = (int)tgt[p];
-    if (t == ignore) continue;
-    const long n = p / HW, hw = p - n * HW;
-    float v[C];
-    load_logits<C>(x, n, hw, HW, v);
-    const float w = weight ? weight[t] : 1.f;
-    const float l = pixel_loss<C>(v, t, mode, gamma, nullptr);
-    sl += (double)(w * l);
-    sw += (double)w;
-  }
-  sl = rs_wave_sum(sl);
-  sw = rs_wave_sum(sw);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wave] = sl;
-    red[1][wave] = sw;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    partial[blockIdx.x * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
-
-// nll_finalize_kernel; no valid weight at all (sum(w) == 0) gives loss 0, and stats[1] = 0 tells the backward
-__global__ void nll_finalize_ig_kernel(const double* __restrict__ partial, int nblocks, float* __restrict__ loss,
-                                       float* __restrict__ stats) {
-  __shared__ double red[2][256];
-  double sl = 0, sw = 0;
-  for (int b = threadIdx.x; b < nblocks; b += 256) {
-    sl += partial[b * 2];
-    sw += partial[b * 2 + 1];
-  }
-  red[0][threadIdx.x] = sl;
-  red[1][threadIdx.x] = sw;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      red[0][threadIdx.x] += red[0][threadIdx.x + o];
-      red[1][threadIdx.x] += red[1][threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const float l = red[1][0] > 0.0 ? (float)(red[0][0] / red[1][0]) : 0.f;
-    loss[0] = l;
-    stats[0] = l;
-    stats[1] = (float)red[1][0];
-  }
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void nll_bwd_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                         const float* __restrict__ weight, const float* __restrict__ stats,
-                                                         const float* __restrict__ gout, float* __restrict__ dx, long P, long HW,
-                                                         int mode, float gamma, int ignore) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= P) return;
-  const long n = p / HW, hw = p - n * HW;
-  const int t = (int)tgt[p];
-  if (t == ignore || !(stats[1] > 0.f)) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
-    return;
-  }
-  float v[C], g[C];
-  load_logits<C>(x, n, hw, HW, v);
-  const float w = weight ? weight[t] : 1.f;
-  pixel_loss<C>(v, t, mode, gamma, &g);
-  const float k = (gout ? gout[0] : 1.f) * w / stats[1];
-#pragma unroll
-  for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = k * g[c];
-}
-
-template <int C>
-int run_fwd_ig(const float* x, const long long* t, const float* w, float* loss, float* stats, double* part, long P, long HW,
-               int mode, float gamma, int ignore, hipStream_t s) {
-  const long nb = (P + 255) / 256;
-  const int grid = nb < kLossBlocks ? (int)nb : kLossBlocks;
-  nll_fwd_ig_kernel<C><<<grid, 256, 0, s>>>(x, t, w, part, P, HW, mode, gamma, ignore);
-  nll_finalize_ig_kernel<<<1, 256, 0, s>>>(part, grid, loss, stats);
-  return RS_LAUNCH_RESULT();
-}
-
-template <int C>
-int run_bwd_ig(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, long P,
-               long HW, int mode, float gamma, int ignore, hipStream_t s) {
-  nll_bwd_ig_kernel<C><<<rs_cdiv(P, 256), 256, 0, s>>>(x, t, w, stats, gout, dx, P, HW, mode, gamma, ignore);
-  return RS_LAUNCH_RESULT();
-}
-
-// miou_partial_kernel over the valid pixels: A, B, cnt and the two NLL sums all leave an ignored pixel out
-template <int C>
-__global__ __launch_bounds__(256) void miou_partial_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                              const float* __restrict__ weight, double* __restrict__ partial,
-                                                              long HW, int nblk, int ignore) {
-  __shared__ double red[4][3 * C + 2];
-  const long n = blockIdx.y;
-  double acc[3 * C + 2];
-#pragma unroll
-  for (int i = 0; i < 3 * C + 2; ++i) acc[i] = 0;
-  for (long hw = (long)blockIdx.x * 256 + threadIdx.x; hw < HW; hw += (long)nblk * 256) {
-    const int t = (int)tgt[n * HW + hw];
-    if (t == ignore) continue;
-    float v[C];
-    load_logits<C>(x, n, hw, HW, v);
-    float mx = v[0];
-#pragma unroll
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, v[c]);
-    float e[C], sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      e[c] = expf(v[c] - mx);
-      sum += e[c];
-    }
-    float xt = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float sc = e[c] / sum;
-      acc[c] += (c == t) ? (double)sc : 0.0;
-      acc[C + c] += (double)sc;
-      acc[2 * C + c] += (c == t) ? 1.0 : 0.0;
-      xt = (c == t) ? v[c] : xt;
-    }
-    const float w = weight ? weight[t] : 1.f;
-    acc[3 * C] += (double)(w * ((logf(sum) + mx) - xt));
-    acc[3 * C + 1] += (double)w;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 3 * C + 2; ++i) {
-    const double s = rs_wave_sum(acc[i]);
-    if (lane == 0) red[wave][i] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3 * C + 2) {
-    const int i = threadIdx.x;
-    partial[(n * nblk + blockIdx.x) * (3 * C + 2) + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-  }
 }
 
 // miou_finalize_kernel with the stats layout kept.  An image with no valid pixel (sum_c cnt == 0) has ratio 1 and coefficients 0
@@ -628,22 +420,26 @@ __global__ void miou_finalize_ig_kernel(const double* __restrict__ partial, int 
   stats[4 + 2 * N * C] = (float)sl;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void miou_bwd_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                          const float* __restrict__ weight, const float* __restrict__ stats,
-                                                          const float* __restrict__ gout, float* __restrict__ dx, int N, long HW,
-                                                          int ignore) {
+template <int C, bool Ignore, typename... Extra>
+__global__ __launch_bounds__(256) void miou_bwd_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                       const float* __restrict__ weight, const float* __restrict__ stats,
+                                                       const float* __restrict__ gout, float* __restrict__ dx, int N, long HW,
+                                                       Extra... extra) {
   const long hw = (long)blockIdx.x * 256 + threadIdx.x;
   const long n = blockIdx.y;
   if (hw >= HW) return;
-  const int t = (int)tgt[n * HW + hw];
-  if (t == ignore) {
+  int t;
+  if constexpr (Ignore) {
+    t = (int)tgt[n * HW + hw];
+    if (t == (extra, ...)) {
 #pragma unroll
-    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
-    return;
+      for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
+      return;
+    }
   }
   float v[C], g[C];
   load_logits<C>(x, n, hw, HW, v);
+  if constexpr (!Ignore) t = (int)tgt[n * HW + hw];
   const float go = gout ? gout[0] : 1.f;
   if (stats[2] > 0.5f) {
     const float w = weight ? weight[t] : 1.f;
@@ -673,78 +469,148 @@ __global__ __launch_bounds__(256) void miou_bwd_ig_kernel(const float* __restric
   for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = go * v[c] * (g[c] - dot);
 }
 
-template <int C>
-int run_miou_fwd_ig(const float* x, const long long* t, const float* w, float* loss, float* stats, double* part, int N, long HW,
-                    int ignore, hipStream_t s) {
-  const long nb = (HW + 255) / 256;
+constexpr int kMiouBlocks = 64;  // per image
+
+template <int C, bool Ignore, typename... Extra>
+int run_miou_fwd(const float* x, const long long* t, const float* w, float* loss, float* stats, void* workspace, int N, int H, int W,
+                 rs_stream_t stream, Extra... extra) {
+  const long HW = (long)H * W, nb = (HW + 255) / 256;
+  hipStream_t s = (hipStream_t)stream;
+  double* part = reinterpret_cast<double*>(workspace);
   const int nblk = nb < kMiouBlocks ? (int)nb : kMiouBlocks;
-  miou_partial_ig_kernel<C><<<dim3(nblk, N), 256, 0, s>>>(x, t, w, part, HW, nblk, ignore);
-  miou_finalize_ig_kernel<<<1, 64, 0, s>>>(part, N, C, nblk, loss, stats);
+  miou_partial_kernel<C, Ignore><<<dim3(nblk, N), 256, 0, s>>>(x, t, w, part, HW, nblk, extra...);
+  if constexpr (Ignore) miou_finalize_ig_kernel<<<1, 64, 0, s>>>(part, N, C, nblk, loss, stats);
+  else miou_finalize_kernel<<<1, 64, 0, s>>>(part, N, C, nblk, loss, stats);
   return RS_LAUNCH_RESULT();
 }
 
-template <int C>
-int run_miou_bwd_ig(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, int N,
-                    long HW, int ignore, hipStream_t s) {
-  miou_bwd_ig_kernel<C><<<dim3(rs_cdiv(HW, 256), N), 256, 0, s>>>(x, t, w, stats, gout, dx, N, HW, ignore);
+template <int C, bool Ignore, typename... Extra>
+int run_miou_bwd(const float* x, const long long* t, const float* w, const float* stats, const float* gout, float* dx, int N, int H,
+                 int W, rs_stream_t stream, Extra... extra) {
+  const long HW = (long)H * W;
+  miou_bwd_kernel<C, Ignore><<<dim3(rs_cdiv(HW, 256), N), 256, 0, (hipStream_t)stream>>>(x, t, w, stats, gout, dx, N, HW, extra...);
   return RS_LAUNCH_RESULT();
+}
+
+#define RS_DISPATCH_C(C, ...)                            \
+  switch (C) {                                           \
+    case 1: { constexpr int K = 1; return __VA_ARGS__; } \
+    case 2: { constexpr int K = 2; return __VA_ARGS__; } \
+    case 3: { constexpr int K = 3; return __VA_ARGS__; } \
+    case 4: { constexpr int K = 4; return __VA_ARGS__; } \
+    case 5: { constexpr int K = 5; return __VA_ARGS__; } \
+    case 6: { constexpr int K = 6; return __VA_ARGS__; } \
+    case 7: { constexpr int K = 7; return __VA_ARGS__; } \
+    default: { constexpr int K = 8; return __VA_ARGS__; } \
+  }
+
+// a variant's ignore label: none to check (Plain); no class and a label byte (Ignore); that, or -1 for "no pixel is ignored"
+// (IgnoreWeight, and the weight plane itself)
+bool ignore_ok(Px v, int ignore, int C) {
+  if (v == Px::Plain) return true;
+  return (v == Px::IgnoreWeight && ignore == -1) || (ignore >= C && ignore <= 255);
+}
+
+// What every entry point of the NLL and mIoU families refuses: a null among the pointers it requires (`weight` and `grad_out` may be
+// null everywhere and are not among them), a shape or class count out of range, a mode that is neither CrossEntropy nor Focal (the
+// mIoU entry points have none and pass 0), an ignore label its variant does not take.
+bool loss_args_ok(std::initializer_list<const void*> required, int N, int C, int H, int W, int mode, Px v, int ignore) {
+  for (const void* p : required)
+    if (!p) return false;
+  return N > 0 && C > 0 && C <= kMaxC && H > 0 && W > 0 && mode >= 0 && mode <= 1 && ignore_ok(v, ignore, C);
 }
 
 }  // namespace
 
+extern "C" long rs_nll_loss_workspace_bytes(void) { return (long)kLossBlocks * 2 * (long)sizeof(double); }
+
+extern "C" int rs_nll_loss_fwd(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
+                               int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream) {
+  if (!loss_args_ok({logits, targets, loss, stats, workspace}, N, C, H, W, mode, Px::Plain, 0)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_fwd<K, Px::Plain>(logits, targets, weight, loss, stats, workspace, N, H, W, mode, gamma, stream));
+}
+
 extern "C" int rs_nll_loss_fwd_ig(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
                                   int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream,
                                   int ignore) {
-  if (!logits || !targets || !loss || !stats || !workspace || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
-      mode < 0 || mode > 1 || !ignore_ok(ignore, C))
-    return RS_EINVAL;
-  const long HW = (long)H * W, P = (long)N * HW;
-  hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(workspace);
-  RS_DISPATCH_C(C, run_fwd_ig<K>(logits, targets, weight, loss, stats, part, P, HW, mode, gamma, ignore, s));
+  if (!loss_args_ok({logits, targets, loss, stats, workspace}, N, C, H, W, mode, Px::Ignore, ignore)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_fwd<K, Px::Ignore>(logits, targets, weight, loss, stats, workspace, N, H, W, mode, gamma, stream, ignore));
+}
+
+extern "C" int rs_nll_loss_fwd_pw(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
+                                  int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream,
+                                  const float* pixel_weight, int ignore) {
+  if (!loss_args_ok({logits, targets, loss, stats, workspace, pixel_weight}, N, C, H, W, mode, Px::IgnoreWeight, ignore)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_fwd<K, Px::IgnoreWeight>(logits, targets, weight, loss, stats, workspace, N, H, W, mode, gamma, stream,
+                                                IgnoreAndWeight{ignore, pixel_weight}));
+}
+
+extern "C" int rs_nll_loss_bwd(const float* logits, const long long* targets, const float* weight, const float* stats,
+                               const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                               rs_stream_t stream) {
+  if (!loss_args_ok({logits, targets, stats, dlogits}, N, C, H, W, mode, Px::Plain, 0)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_bwd<K, Px::Plain>(logits, targets, weight, stats, grad_out, dlogits, N, H, W, mode, gamma, stream));
 }
 
 extern "C" int rs_nll_loss_bwd_ig(const float* logits, const long long* targets, const float* weight, const float* stats,
                                   const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
                                   rs_stream_t stream, int ignore) {
-  if (!logits || !targets || !stats || !dlogits || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || mode < 0 || mode > 1 ||
-      !ignore_ok(ignore, C))
-    return RS_EINVAL;
+  if (!loss_args_ok({logits, targets, stats, dlogits}, N, C, H, W, mode, Px::Ignore, ignore)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_bwd<K, Px::Ignore>(logits, targets, weight, stats, grad_out, dlogits, N, H, W, mode, gamma, stream, ignore));
+}
+
+extern "C" int rs_nll_loss_bwd_pw(const float* logits, const long long* targets, const float* weight, const float* stats,
+                                  const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                                  rs_stream_t stream, const float* pixel_weight, int ignore) {
+  if (!loss_args_ok({logits, targets, stats, dlogits, pixel_weight}, N, C, H, W, mode, Px::IgnoreWeight, ignore)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_bwd<K, Px::IgnoreWeight>(logits, targets, weight, stats, grad_out, dlogits, N, H, W, mode, gamma, stream,
+                                                IgnoreAndWeight{ignore, pixel_weight}));
+}
+
+extern "C" int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C,
+                                   int H, int W, rs_stream_t stream) {
+  if (!scores || !targets || !counts || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0) return RS_EINVAL;
   const long HW = (long)H * W, P = (long)N * HW;
   hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH_C(C, run_bwd_ig<K>(logits, targets, weight, stats, grad_out, dlogits, P, HW, mode, gamma, ignore, s));
+  RS_DISPATCH_C(C, run_conf<K>(scores, targets, counts, P, HW, s));
+}
+
+extern "C" long rs_miou_loss_workspace_bytes(int N, int C) {
+  if (N <= 0 || C <= 0 || C > kMaxC) return RS_EINVAL;
+  return (long)N * kMiouBlocks * (3 * C + 2) * (long)sizeof(double);
+}
+
+extern "C" int rs_miou_loss_fwd(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
+                                int N, int C, int H, int W, void* workspace, rs_stream_t stream) {
+  if (!loss_args_ok({logits, targets, loss, stats, workspace}, N, C, H, W, 0, Px::Plain, 0)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_miou_fwd<K, false>(logits, targets, weight, loss, stats, workspace, N, H, W, stream));
 }
 
 extern "C" int rs_miou_loss_fwd_ig(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
                                    int N, int C, int H, int W, void* workspace, rs_stream_t stream, int ignore) {
-  if (!logits || !targets || !loss || !stats || !workspace || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
-      !ignore_ok(ignore, C))
-    return RS_EINVAL;
-  const long HW = (long)H * W;
-  hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(workspace);
-  RS_DISPATCH_C(C, run_miou_fwd_ig<K>(logits, targets, weight, loss, stats, part, N, HW, ignore, s));
+  if (!loss_args_ok({logits, targets, loss, stats, workspace}, N, C, H, W, 0, Px::Ignore, ignore)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_miou_fwd<K, true>(logits, targets, weight, loss, stats, workspace, N, H, W, stream, ignore));
+}
+
+extern "C" int rs_miou_loss_bwd(const float* logits, const long long* targets, const float* weight, const float* stats,
+                                const float* grad_out, float* dlogits, int N, int C, int H, int W, rs_stream_t stream) {
+  if (!loss_args_ok({logits, targets, stats, dlogits}, N, C, H, W, 0, Px::Plain, 0)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_miou_bwd<K, false>(logits, targets, weight, stats, grad_out, dlogits, N, H, W, stream));
 }
 
 extern "C" int rs_miou_loss_bwd_ig(const float* logits, const long long* targets, const float* weight, const float* stats,
                                    const float* grad_out, float* dlogits, int N, int C, int H, int W, rs_stream_t stream,
                                    int ignore) {
-  if (!logits || !targets || !stats || !dlogits || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || !ignore_ok(ignore, C))
-    return RS_EINVAL;
-  const long HW = (long)H * W;
-  hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH_C(C, run_miou_bwd_ig<K>(logits, targets, weight, stats, grad_out, dlogits, N, HW, ignore, s));
+  if (!loss_args_ok({logits, targets, stats, dlogits}, N, C, H, W, 0, Px::Ignore, ignore)) return RS_EINVAL;
+  RS_DISPATCH_C(C, run_miou_bwd<K, true>(logits, targets, weight, stats, grad_out, dlogits, N, H, W, stream, ignore));
 }
 
-// ---- boundary-weighted CrossEntropy / Focal (rs_boundary_weight_plane, rs_nll_loss_*_pw in include/robosat_hip.h) ----------------
-// The weight plane m [N][H][W] from the label raster in four launches: the complement of the boundary set as a byte mask, the two
-// passes of rs_features_edt on it (features.hip, called as it is), the lookup d2 -> m.  The loss kernels are the `_ig` kernels above
-// with one more load and one more multiply per pixel; those and the base kernels are left as they are.
+// ---- the boundary weight plane (rs_boundary_weight_plane in include/robosat_hip.h) -------------------------------------------------
+// The weight plane m [N][H][W] of the IgnoreWeight variant from the label raster in four launches: the complement of the boundary set
+// as a byte mask, the two passes of rs_features_edt on it (features.hip, called as it is), the lookup d2 -> m.
 namespace {
 
 constexpr int kPlaneMaxR = 128;
-
-bool ignore_ok_pw(int ignore, int C) { return ignore == -1 || ignore_ok(ignore, C); }
 
 // mask[p] = 0 at a boundary pixel (a valid pixel with a valid 4-neighbour of another label inside its image), 1 at any other valid
 // pixel, 2 at an ignored one: non-zero = set for rs_features_edt, and the lookup needs no second look at the labels.  One thread per
@@ -791,78 +657,6 @@ __global__ __launch_bounds__(256) void boundary_lookup_kernel(const int* __restr
   m[p] = mask[p] == 2 ? 0.f : v;
 }
 
-template <int C>
-__global__ __launch_bounds__(256) void nll_fwd_pw_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                         const float* __restrict__ weight, const float* __restrict__ pixw,
-                                                         double* __restrict__ partial, long P, long HW, int mode, float gamma,
-                                                         int ignore) {
-  __shared__ double red[2][4];
-  double sl = 0, sw = 0;
-  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
-    const int t = (int)tgt[p];
-    if (t == ignore) continue;
-    const long n = p / HW, hw = p - n * HW;
-    float v[C];
-    load_logits<C>(x, n, hw, HW, v);
-    const float w = pixw[p] * (weight ? weight[t] : 1.f);
-    const float l = pixel_loss<C>(v, t, mode, gamma, nullptr);
-    sl += (double)(w * l);
-    sw += (double)w;
-  }
-  sl = rs_wave_sum(sl);
-  sw = rs_wave_sum(sw);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    red[0][wave] = sl;
-    red[1][wave] = sw;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    partial[blockIdx.x * 2] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    partial[blockIdx.x * 2 + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
-
-template <int C>
-__global__ __launch_bounds__(256) void nll_bwd_pw_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                         const float* __restrict__ weight, const float* __restrict__ pixw,
-                                                         const float* __restrict__ stats, const float* __restrict__ gout,
-                                                         float* __restrict__ dx, long P, long HW, int mode, float gamma, int ignore) {
-  const long p = (long)blockIdx.x * 256 + threadIdx.x;
-  if (p >= P) return;
-  const long n = p / HW, hw = p - n * HW;
-  const int t = (int)tgt[p];
-  if (t == ignore || !(stats[1] > 0.f)) {
-#pragma unroll
-    for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
-    return;
-  }
-  float v[C], g[C];
-  load_logits<C>(x, n, hw, HW, v);
-  const float w = pixw[p] * (weight ? weight[t] : 1.f);
-  pixel_loss<C>(v, t, mode, gamma, &g);
-  const float k = (gout ? gout[0] : 1.f) * w / stats[1];
-#pragma unroll
-  for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = k * g[c];
-}
-
-template <int C>
-int run_fwd_pw(const float* x, const long long* t, const float* w, const float* pixw, float* loss, float* stats, double* part, long P,
-               long HW, int mode, float gamma, int ignore, hipStream_t s) {
-  const long nb = (P + 255) / 256;
-  const int grid = nb < kLossBlocks ? (int)nb : kLossBlocks;
-  nll_fwd_pw_kernel<C><<<grid, 256, 0, s>>>(x, t, w, pixw, part, P, HW, mode, gamma, ignore);
-  nll_finalize_ig_kernel<<<1, 256, 0, s>>>(part, grid, loss, stats);
-  return RS_LAUNCH_RESULT();
-}
-
-template <int C>
-int run_bwd_pw(const float* x, const long long* t, const float* w, const float* pixw, const float* stats, const float* gout, float* dx,
-               long P, long HW, int mode, float gamma, int ignore, hipStream_t s) {
-  nll_bwd_pw_kernel<C><<<rs_cdiv(P, 256), 256, 0, s>>>(x, t, w, pixw, stats, gout, dx, P, HW, mode, gamma, ignore);
-  return RS_LAUNCH_RESULT();
-}
-
 // (the sizes rs_features_edt takes: its own check refuses the rest, this one keeps the workspace query in step with it)
 bool plane_shape_ok(int N, int H, int W) {
   return N > 0 && N <= 65535 && H > 0 && W > 0 && H <= 4096 && W <= 4096 && (long)N * H * W < (1l << 29);
@@ -878,7 +672,7 @@ extern "C" long rs_boundary_weight_plane_workspace_bytes(int N, int H, int W) {
 extern "C" int rs_boundary_weight_plane(const long long* targets, const float* table, float* plane, int N, int C, int H, int W, int R,
                                         int ignore, void* workspace, rs_stream_t stream) {
   if (!targets || !table || !plane || !workspace || ((uintptr_t)workspace & 3) || !plane_shape_ok(N, H, W) || C <= 0 || C > kMaxC ||
-      R < 1 || R > kPlaneMaxR || !ignore_ok_pw(ignore, C))
+      R < 1 || R > kPlaneMaxR || !ignore_ok(Px::IgnoreWeight, ignore, C))
     return RS_EINVAL;
   const long P = (long)N * H * W;
   hipStream_t s = (hipStream_t)stream;
@@ -892,27 +686,4 @@ extern "C" int rs_boundary_weight_plane(const long long* targets, const float* t
   if (rc) return rc;
   boundary_lookup_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(d2, mask, table, plane, P, R * R);
   return RS_LAUNCH_RESULT();
-}
-
-extern "C" int rs_nll_loss_fwd_pw(const float* logits, const long long* targets, const float* weight, float* loss, float* stats,
-                                  int N, int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream,
-                                  const float* pixel_weight, int ignore) {
-  if (!logits || !targets || !loss || !stats || !workspace || !pixel_weight || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 ||
-      mode < 0 || mode > 1 || !ignore_ok_pw(ignore, C))
-    return RS_EINVAL;
-  const long HW = (long)H * W, P = (long)N * HW;
-  hipStream_t s = (hipStream_t)stream;
-  double* part = reinterpret_cast<double*>(workspace);
-  RS_DISPATCH_C(C, run_fwd_pw<K>(logits, targets, weight, pixel_weight, loss, stats, part, P, HW, mode, gamma, ignore, s));
-}
-
-extern "C" int rs_nll_loss_bwd_pw(const float* logits, const long long* targets, const float* weight, const float* stats,
-                                  const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
-                                  rs_stream_t stream, const float* pixel_weight, int ignore) {
-  if (!logits || !targets || !stats || !dlogits || !pixel_weight || N <= 0 || C <= 0 || C > kMaxC || H <= 0 || W <= 0 || mode < 0 ||
-      mode > 1 || !ignore_ok_pw(ignore, C))
-    return RS_EINVAL;
-  const long HW = (long)H * W, P = (long)N * HW;
-  hipStream_t s = (hipStream_t)stream;
-  RS_DISPATCH_C(C, run_bwd_pw<K>(logits, targets, weight, pixel_weight, stats, grad_out, dlogits, P, HW, mode, gamma, ignore, s));
 }

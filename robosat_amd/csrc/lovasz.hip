@@ -21,6 +21,22 @@
 //
 // The same sort and scans also carry the multi-class Lovasz-Softmax loss (rs_lovasz_softmax_fwd, further down): the sort then
 // runs over N*C (or C) segments of one class's errors instead of N segments of C*H*W hinge errors.
+//
+// Both losses also exist over the pixels whose label is not `ignore` (rs_lovasz_fwd_ig, rs_lovasz_softmax_fwd_ig): the loss of the
+// valid pixels alone, as if the ignored ones had been cut out of every image and the rest packed in (n, h, w) order.  The kernels
+// that look at a label or an error are templates over `bool Ignore`, the variant's statements under `if constexpr`; the sort, the
+// scans and the workspace serve both as they are.  An ignored pixel's C entries get a key that sorts strictly behind every valid
+// key -- an error of -inf in the hinge form (valid errors are finite), of -1 in the softmax form (valid errors lie in [0, 1]) -- and
+// label bit 0.  The sort is stable, so they form the TAIL of their segment and the valid entries keep the order, the ranks and the
+// label prefix counts they would have without them: every valid rank keeps its delta.  Each segment's gts is its number of set
+// label bits, which only valid pixels have (in the hinge form: one per valid pixel, so gts = K of the image where the plain form
+// has H*W).  The apply kernels add 0 to the loss for a tail entry and write +0.0f as its gradient.  With no pixel ignored an Ignore
+// instantiation does the arithmetic of the plain one in the same order: the same bits.  A variant's kernel takes the arguments it
+// uses, the plain ones in the places they have always had, so the instantiations are the instructions of the separate kernels they
+// replaced, bar the few that profiles/loss_variants/README.md lists and times (an operand order in the apply kernels, which now
+// share lovasz_load4, and the argument loads of the two Ignore kernels whose arguments moved).
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -48,23 +64,38 @@ __device__ __forceinline__ float key_to_float(uint32_t key) {
   return __uint_as_float(u);
 }
 
+// What an Ignore instantiation needs beyond the plain arguments is ONE trailing argument: the pack `extra` holds nothing (plain, which
+// so keeps the argument list it has always had) or `int ignore` -- an IgnoredLabels where the plain kernel reads no labels -- and
+// `(extra, ...)` is that argument.  (Written out where it is used: an accessor function inside a select's condition changed the
+// instructions of lovasz_keys_kernel.)
+struct IgnoredLabels {
+  const long long* tgt;
+  int ignore;
+};
+
+template <bool Ignore, typename... Extra>
 __global__ void lovasz_keys_kernel(const float* __restrict__ x, const long long* __restrict__ tgt, uint32_t* __restrict__ keys,
-                                   uint32_t* __restrict__ vals, long P, long HW) {
+                                   uint32_t* __restrict__ vals, long P, long HW, Extra... extra) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long n = blockIdx.y;
   if (i >= P) return;
   const long c = i / HW, hw = i - c * HW;
-  const uint32_t m = (tgt[n * HW + hw] == c) ? 1u : 0u;
+  const long long t = tgt[n * HW + hw];
+  const uint32_t m = (t == c) ? 1u : 0u;
   const float v = x[n * P + i];
-  const float err = 1.f - (m ? v : -v);  // 1 - (2m-1)*x
+  float err;  // 1 - (2m-1)*x
+  if constexpr (Ignore) err = (t == (extra, ...)) ? -INFINITY : 1.f - (m ? v : -v);
+  else err = 1.f - (m ? v : -v);
   keys[n * P + i] = desc_key(err);
   vals[n * P + i] = (uint32_t)i | (m << 31);
 }
 
 // The same for HW % 4 == 0 (every tile size the tools produce): four consecutive pixels of one class plane per thread -- one
 // 16-byte load of the logits, two of the int64 labels, two 16-byte stores (round 5: the scalar kernel ran at ~2.5 TB/s).
+template <bool Ignore, typename... Extra>
 __global__ __launch_bounds__(256) void lovasz_keys4_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long P, long HW) {
+                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long P, long HW,
+                                                           Extra... extra) {
   const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const long n = blockIdx.y;
   if (i >= P) return;
@@ -76,7 +107,9 @@ __global__ __launch_bounds__(256) void lovasz_keys4_kernel(const float* __restri
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
     const uint32_t m = (t[e] == c) ? 1u : 0u;
-    const float err = 1.f - (m ? v[e] : -v[e]);
+    float err;
+    if constexpr (Ignore) err = (t[e] == (extra, ...)) ? -INFINITY : 1.f - (m ? v[e] : -v[e]);
+    else err = 1.f - (m ? v[e] : -v[e]);
     k[e] = desc_key(err);
     w[e] = (uint32_t)(i + e) | (m << 31);
   }
@@ -349,30 +382,9 @@ __global__ __launch_bounds__(256) void lovasz_scan_blocks_kernel(uint32_t* __res
     }
 }
 
-// Jaccard deltas, loss partials and the gradient scatter
-__global__ __launch_bounds__(256) void lovasz_apply_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                           const uint32_t* __restrict__ boff, double* __restrict__ partial,
-                                                           float* __restrict__ grad, long P, long HW, int nblk, float inv_n,
-                                                           int xcd_affine) {
-  __shared__ uint32_t sm[4];
-  __shared__ double red[4];
-  // The gradient scatter writes 4-byte values all over ONE image's 4 * P bytes (2 MB at 524 288 keys).  Blocks are dealt
-  // round-robin over the 8 XCDs, each with an L2 of its own: with the natural (block, image) order every XCD holds a slice of
-  // every cache line of the image.  When the image count divides by 8 and an image's gradient is at most half an L2 (2 MB: the
-  // two-class 512^2 tiles of configs[2]), all blocks of an image run on ONE XCD instead (block L of the launch sits on XCD L % 8):
-  // its L2 collects the image's lines whole before they leave -- lovasz_apply 217 -> 130 us at bs 32; at 4 MB per image (four
-  // classes) the lines evict each other and the natural order is 3 % faster, so the rule stops there (profiles/r05/lovasz.txt).
-  long n = blockIdx.y;
-  int bx = blockIdx.x;
-  if (xcd_affine) {
-    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    const int x = (int)(L & 7);
-    const long k = L >> 3;
-    n = x + 8 * (k / nblk);
-    bx = (int)(k % nblk);
-  }
-  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
-  uint32_t lab[4], key[4], idx[4];
+// the four sorted entries of a thread of the apply kernels (ranks r0 .. r0 + 3 of segment n); returns their label count
+__device__ __forceinline__ uint32_t lovasz_load4(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, long n, long P,
+                                                 long r0, uint32_t (&lab)[4], uint32_t (&key)[4], uint32_t (&idx)[4]) {
   uint32_t s = 0;
   if ((P & 3) == 0 && r0 + 3 < P) {
     const lv_u32x4 v = *reinterpret_cast<const lv_u32x4*>(vals + n * P + r0), k = *reinterpret_cast<const lv_u32x4*>(keys + n * P + r0);
@@ -398,9 +410,45 @@ __global__ __launch_bounds__(256) void lovasz_apply_kernel(const uint32_t* __res
       s += lab[e];
     }
   }
+  return s;
+}
+
+// gts of the hinge form: one label per pixel, so H*W itself in the plain form; with pixels ignored, the images' valid pixel counts
+// (gts_px[n], from lovasz_softmax_scan_blocks_kernel)
+template <bool Ignore>
+using hinge_gts_t = std::conditional_t<Ignore, const uint32_t* __restrict__, long>;
+
+// Jaccard deltas, loss partials and the gradient scatter
+template <bool Ignore>
+__global__ __launch_bounds__(256) void lovasz_apply_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
+                                                           const uint32_t* __restrict__ boff, double* __restrict__ partial,
+                                                           float* __restrict__ grad, long P, hinge_gts_t<Ignore> gts_arg, int nblk,
+                                                           float inv_n, int xcd_affine) {
+  __shared__ uint32_t sm[4];
+  __shared__ double red[4];
+  // The gradient scatter writes 4-byte values all over ONE image's 4 * P bytes (2 MB at 524 288 keys).  Blocks are dealt
+  // round-robin over the 8 XCDs, each with an L2 of its own: with the natural (block, image) order every XCD holds a slice of
+  // every cache line of the image.  When the image count divides by 8 and an image's gradient is at most half an L2 (2 MB: the
+  // two-class 512^2 tiles of configs[2]), all blocks of an image run on ONE XCD instead (block L of the launch sits on XCD L % 8):
+  // its L2 collects the image's lines whole before they leave -- lovasz_apply 217 -> 130 us at bs 32; at 4 MB per image (four
+  // classes) the lines evict each other and the natural order is 3 % faster, so the rule stops there (profiles/r05/lovasz.txt).
+  long n = blockIdx.y;
+  int bx = blockIdx.x;
+  if (xcd_affine) {
+    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
+    const int x = (int)(L & 7);
+    const long k = L >> 3;
+    n = x + 8 * (k / nblk);
+    bx = (int)(k % nblk);
+  }
+  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
+  uint32_t lab[4], key[4], idx[4];
+  const uint32_t s = lovasz_load4(keys, vals, n, P, r0, lab, key, idx);
   uint32_t total;
   uint32_t cs = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
-  const float gts = (float)HW;
+  float gts;
+  if constexpr (Ignore) gts = (float)gts_arg[n];
+  else gts = (float)gts_arg;
   double acc = 0;
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -417,8 +465,13 @@ __global__ __launch_bounds__(256) void lovasz_apply_kernel(const uint32_t* __res
         delta = jac - jac_p;
       }
       const float err = key_to_float(key[e]);
+      // (the tail has err = -inf: not above 0, like every valid entry inside its margin -- no loss term, gradient +0.0f)
       const float pos = err > 0.f ? err : 0.f;
-      acc += (double)(pos * delta);
+      if constexpr (Ignore) {
+        if (err > 0.f) acc += (double)(pos * delta);
+      } else {
+        acc += (double)(pos * delta);
+      }
       if (grad) {
         const float g = err > 0.f ? delta : 0.f;
         grad[n * P + idx[e]] = (lab[e] ? -g : g) * inv_n;
@@ -516,11 +569,14 @@ __device__ __forceinline__ long lvs_seg_off(long q, long n, long hw, int c, int 
   return per_image ? ((n * C + c) * HW + hw) : ((long)c * NHW + q);
 }
 
+constexpr float kIgnoredSoftmaxErr = -1.f;  // the error of an ignored pixel's entries: behind every valid one, which lie in [0, 1]
+
 // one thread per VEC consecutive pixels of one image (VEC = 4 needs HW % 4 == 0): C keys + C payloads each (probs: NCHW p)
-template <int VEC>
+template <int VEC, bool Ignore, typename... Extra>
 __global__ __launch_bounds__(256) void lovasz_softmax_keys_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
                                                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                                  float* __restrict__ probs, long NHW, long HW, int C, int per_image) {
+                                                                  float* __restrict__ probs, long NHW, long HW, int C, int per_image,
+                                                                  Extra... extra) {
   // the key must be fp32(1 - p) of the very p this kernel writes out: no fusing of 1 - e * inv_sum into one fma
 #pragma clang fp contract(off)
   const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
@@ -544,7 +600,8 @@ __global__ __launch_bounds__(256) void lovasz_softmax_keys_kernel(const float* _
     for (int e = 0; e < VEC; ++e) {
       pr[e] = lvs_prob(v[e], mx[e], sum[e]);
       const uint32_t m = (t[e] == c) ? 1u : 0u;
-      k[e] = desc_key(m ? 1.f - pr[e] : pr[e]);
+      if constexpr (Ignore) k[e] = desc_key(t[e] == (extra, ...) ? kIgnoredSoftmaxErr : m ? 1.f - pr[e] : pr[e]);
+      else k[e] = desc_key(m ? 1.f - pr[e] : pr[e]);
       w[e] = (pos + (uint32_t)e) | (m << 31);
     }
     const long o = lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image);
@@ -592,7 +649,9 @@ __global__ __launch_bounds__(256) void lovasz_softmax_weights_kernel(const uint3
   for (int c = 0; c < C; ++c) w[(long)n * C + c] = (all_classes || gts[(long)n * C + c] > 0) ? inv : 0.0;
 }
 
-// closed-form deltas, weighted fp64 loss partials and the scatter of the weighted dL/dp (segment-major, like the keys)
+// closed-form deltas, weighted fp64 loss partials and the scatter of the weighted dL/dp (segment-major, like the keys); Ignore: a
+// tail entry (negative error) adds nothing and gets dL/dp = +0.0f, whatever its delta
+template <bool Ignore>
 __global__ __launch_bounds__(256) void lovasz_softmax_apply_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
                                                                    const uint32_t* __restrict__ boff, const uint32_t* __restrict__ gts,
                                                                    const double* __restrict__ w, double* __restrict__ partial,
@@ -609,31 +668,7 @@ __global__ __launch_bounds__(256) void lovasz_softmax_apply_kernel(const uint32_
   }
   const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
   uint32_t lab[4], key[4], idx[4];
-  uint32_t s = 0;
-  if ((P & 3) == 0 && r0 + 3 < P) {
-    const lv_u32x4 v = *reinterpret_cast<const lv_u32x4*>(vals + n * P + r0), k = *reinterpret_cast<const lv_u32x4*>(keys + n * P + r0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lab[e] = v[e] >> 31;
-      idx[e] = v[e] & 0x7fffffffu;
-      key[e] = k[e];
-      s += lab[e];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lab[e] = 0;
-      key[e] = 0;
-      idx[e] = 0;
-      if (r0 + e < P) {
-        const uint32_t v = vals[n * P + r0 + e];
-        lab[e] = v >> 31;
-        idx[e] = v & 0x7fffffffu;
-        key[e] = keys[n * P + r0 + e];
-      }
-      s += lab[e];
-    }
-  }
+  const uint32_t s = lovasz_load4(keys, vals, n, P, r0, lab, key, idx);
   uint32_t total;
   long long k = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
   const long long g = gts[n];
@@ -648,8 +683,15 @@ __global__ __launch_bounds__(256) void lovasz_softmax_apply_kernel(const uint32_
       const long long I = g - k, U = g + r + 1 - k;
       // U_r >= 1 always (U_r - I_r = r + 1); at r = 0, U_{-1} = g may be 0 and delta_0 = J_0 = 1 / U_0
       const double delta = r == 0 ? 1.0 / (double)U : (double)(Ip * U - I * Up) / (double)(U * Up);
-      acc += (double)key_to_float(key[e]) * delta;
-      if (gp) gp[n * P + idx[e]] = (float)(ws * (lab[e] ? -delta : delta));
+      if constexpr (Ignore) {
+        const float err = key_to_float(key[e]);
+        const bool tail = err < 0.f;
+        if (!tail) acc += (double)err * delta;
+        if (gp) gp[n * P + idx[e]] = tail ? 0.f : (float)(ws * (lab[e] ? -delta : delta));
+      } else {
+        acc += (double)key_to_float(key[e]) * delta;
+        if (gp) gp[n * P + idx[e]] = (float)(ws * (lab[e] ? -delta : delta));
+      }
     }
   }
   acc = rs_wave_sum(acc);
@@ -658,15 +700,22 @@ __global__ __launch_bounds__(256) void lovasz_softmax_apply_kernel(const uint32_
   if (threadIdx.x == 0) partial[n * nblk + bx] = ws * ((red[0] + red[1]) + (red[2] + red[3]));
 }
 
-// per VEC pixels: grad[n, c] = p_c (G_c - sum_k p_k G_k) with G the weighted dL/dp (segment-major), in fp64
-template <int VEC>
+// per VEC pixels: grad[n, c] = p_c (G_c - sum_k p_k G_k) with G the weighted dL/dp (segment-major), in fp64; Ignore (which
+// reads the labels for it: IgnoredLabels): +0.0f in every class plane of an ignored pixel
+template <int VEC, bool Ignore, typename... Extra>
 __global__ __launch_bounds__(256) void lovasz_softmax_jacobian_kernel(const float* __restrict__ x, const float* __restrict__ gp,
-                                                                      float* __restrict__ grad, long NHW, long HW, int C, int per_image) {
+                                                                      float* __restrict__ grad, long NHW, long HW, int C, int per_image,
+                                                                      Extra... extra) {
   const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
   if (q >= NHW) return;
   const long n = q / HW, hw = q - n * HW;
   const float* xp = x + n * C * HW + hw;
   float mx[VEC], sum[VEC], v[VEC], gv[VEC], out[VEC];
+  [[maybe_unused]] bool skip[VEC];
+  if constexpr (Ignore) {
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) skip[e] = (extra, ...).tgt[q + e] == (extra, ...).ignore;
+  }
   lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
   double dot[VEC];
 #pragma unroll
@@ -681,7 +730,10 @@ __global__ __launch_bounds__(256) void lovasz_softmax_jacobian_kernel(const floa
     lvs_load<VEC>(xp + c * HW, v);
     lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) out[e] = (float)((double)lvs_prob(v[e], mx[e], sum[e]) * ((double)gv[e] - dot[e]));
+    for (int e = 0; e < VEC; ++e) {
+      if constexpr (Ignore) out[e] = skip[e] ? 0.f : (float)((double)lvs_prob(v[e], mx[e], sum[e]) * ((double)gv[e] - dot[e]));
+      else out[e] = (float)((double)lvs_prob(v[e], mx[e], sum[e]) * ((double)gv[e] - dot[e]));
+    }
     lvs_write<VEC>(grad + (n * C + c) * HW + hw, out);
   }
 }
@@ -740,52 +792,54 @@ void radix_sort_segments(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1,
   }
 }
 
-}  // namespace
+// the workspace as typed pointers
+struct SortBuffers {
+  uint32_t *k0, *v0, *k1, *v1, *counts, *bsum;
+  double* partial;
+};
 
-extern "C" long rs_lovasz_workspace_bytes(int N, int C, int H, int W) {
-  if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (long)C * H * W >= (1L << 31)) return RS_EINVAL;
-  return (long)carve(N, C, H, W).total;
+SortBuffers sort_buffers(void* workspace, const Carve& cv) {
+  char* ws = reinterpret_cast<char*>(workspace);
+  auto u32 = [ws](size_t offset) { return reinterpret_cast<uint32_t*>(ws + offset); };
+  return {u32(cv.keys0), u32(cv.vals0), u32(cv.keys1), u32(cv.vals1), u32(cv.counts), u32(cv.bsum), reinterpret_cast<double*>(ws + cv.partial)};
 }
 
-extern "C" int rs_lovasz_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C,
-                             int H, int W, void* workspace, rs_stream_t stream) {
-  if (!logits || !targets || !loss || !workspace || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (long)C * H * W >= (1L << 31))
-    return RS_EINVAL;
+bool lovasz_shape_ok(int N, int C, int H, int W) { return N > 0 && C > 0 && H > 0 && W > 0 && (long)C * H * W < (1L << 31); }
+
+bool lovasz_ignore_ok(int ignore, int C) { return ignore >= C && ignore <= 255; }
+
+// rs_lovasz_fwd (no `ignore`) and rs_lovasz_fwd_ig (`ignore` = the label)
+template <bool Ignore, typename... Extra>
+int lovasz_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C, int H, int W, void* workspace,
+               rs_stream_t stream, Extra... ignore) {
   const Carve cv = carve(N, C, H, W);
-  char* ws = reinterpret_cast<char*>(workspace);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
-  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
-  double* partial = reinterpret_cast<double*>(ws + cv.partial);
+  const SortBuffers b = sort_buffers(workspace, cv);
   hipStream_t s = (hipStream_t)stream;
   const long P = cv.P, HW = (long)H * W;
   // the sort's scatter passes keep an image's tiles on one XCD too (its digit runs of 64-128 bytes then meet their neighbours'
   // in one L2): -5 % on a bs-32 sort, -3.5 % with four classes, +3 % at 8 images (one image per XCD: no slack) -> from 16 images
   const int sc_affine = (N % 8 == 0 && N >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
 
-  if ((HW & 3) == 0) lovasz_keys4_kernel<<<dim3(rs_cdiv(P / 4, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW);
-  else lovasz_keys_kernel<<<dim3(rs_cdiv(P, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW);
-  radix_sort_segments(k0, v0, k1, v1, counts, N, cv, sc_affine, s);
+  if ((HW & 3) == 0) lovasz_keys4_kernel<Ignore><<<dim3(rs_cdiv(P / 4, 256), N), 256, 0, s>>>(logits, targets, b.k0, b.v0, P, HW, ignore...);
+  else lovasz_keys_kernel<Ignore><<<dim3(rs_cdiv(P, 256), N), 256, 0, s>>>(logits, targets, b.k0, b.v0, P, HW, ignore...);
+  radix_sort_segments(b.k0, b.v0, b.k1, b.v1, b.counts, N, cv, sc_affine, s);
   // after 4 passes the sorted data is back in (k0, v0)
-  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(v0, bsum, P, cv.nblk_scan);
-  lovasz_scan_blocks_kernel<<<N, 256, 0, s>>>(bsum, cv.nblk_scan);
+  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(b.v0, b.bsum, P, cv.nblk_scan);
   const float inv_n = 1.f / (float)N;
   const int xcd_affine = (N % 8 == 0 && P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
-  lovasz_apply_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(k0, v0, bsum, partial, grad_unit, P, HW, cv.nblk_scan, inv_n, xcd_affine);
-  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, (long)N * cv.nblk_scan, inv_n, loss);
+  if constexpr (Ignore) {
+    // the sort is done with its digit counts (at least 256 words per image): their first N words take the images' valid pixel
+    // counts, so the workspace is rs_lovasz_workspace_bytes' as it stands
+    uint32_t* gts_px = b.counts;
+    lovasz_softmax_scan_blocks_kernel<<<N, 256, 0, s>>>(b.bsum, gts_px, cv.nblk_scan);
+    lovasz_apply_kernel<true><<<dim3(cv.nblk_scan, N), 256, 0, s>>>(b.k0, b.v0, b.bsum, b.partial, grad_unit, P, gts_px, cv.nblk_scan, inv_n, xcd_affine);
+  } else {
+    lovasz_scan_blocks_kernel<<<N, 256, 0, s>>>(b.bsum, cv.nblk_scan);
+    lovasz_apply_kernel<false><<<dim3(cv.nblk_scan, N), 256, 0, s>>>(b.k0, b.v0, b.bsum, b.partial, grad_unit, P, HW, cv.nblk_scan, inv_n, xcd_affine);
+  }
+  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(b.partial, (long)N * cv.nblk_scan, inv_n, loss);
   return RS_LAUNCH_RESULT();
 }
-
-extern "C" int rs_scale_by_scalar(const float* src, const float* scalar, float* dst, long n, rs_stream_t stream) {
-  if (!src || !scalar || !dst || n <= 0) return RS_EINVAL;
-  scale_by_scalar_kernel<<<rs_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(src, scalar, dst, n);
-  return RS_LAUNCH_RESULT();
-}
-
-namespace {
 
 // the Lovasz-Softmax workspace: the sort / scan carve of its S segments, then g (uint32) and w (fp64) per segment
 struct SoftmaxCarve {
@@ -816,7 +870,70 @@ SoftmaxCarve carve_softmax(int N, int C, int H, int W, int per_image) {
   return c;
 }
 
+// rs_lovasz_softmax_fwd (no `ignore`) and rs_lovasz_softmax_fwd_ig (`ignore` = the label)
+template <bool Ignore, typename... Extra>
+int lovasz_softmax_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out, int N, int C, int H,
+                       int W, int per_image, int all_classes, void* workspace, rs_stream_t stream, Extra... ignore) {
+  const SoftmaxCarve sc = carve_softmax(N, C, H, W, per_image);
+  const Carve& cv = sc.cv;
+  const SortBuffers b = sort_buffers(workspace, cv);
+  char* ws = reinterpret_cast<char*>(workspace);
+  uint32_t* gts = reinterpret_cast<uint32_t*>(ws + sc.gts);
+  double* w = reinterpret_cast<double*>(ws + sc.w);
+  hipStream_t s = (hipStream_t)stream;
+  const long S = sc.S, HW = (long)H * W, NHW = (long)N * HW;
+  const int pi = per_image ? 1 : 0;
+  const int sc_affine = (S % 8 == 0 && S >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;  // (the rule of lovasz_fwd, per segment)
+
+  if ((HW & 3) == 0)
+    lovasz_softmax_keys_kernel<4, Ignore><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, b.k0, b.v0, probs_out, NHW, HW, C, pi, ignore...);
+  else lovasz_softmax_keys_kernel<1, Ignore><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, b.k0, b.v0, probs_out, NHW, HW, C, pi, ignore...);
+  radix_sort_segments(b.k0, b.v0, b.k1, b.v1, b.counts, S, cv, sc_affine, s, sc.chunked_scan ? reinterpret_cast<uint32_t*>(ws + sc.csum) : nullptr);
+  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(b.v0, b.bsum, cv.P, cv.nblk_scan);
+  lovasz_softmax_scan_blocks_kernel<<<S, 256, 0, s>>>(b.bsum, gts, cv.nblk_scan);  // (g of a segment: its valid pixels of the class)
+  const int groups = per_image ? N : 1;
+  lovasz_softmax_weights_kernel<<<rs_cdiv(groups, 256), 256, 0, s>>>(gts, w, groups, C, all_classes ? 1 : 0);
+  // the sort is done with (k1, v1): k1 holds the weighted dL/dp, segment-major
+  float* gp = grad_unit ? reinterpret_cast<float*>(b.k1) : nullptr;
+  const int xcd_affine = (S % 8 == 0 && cv.P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;  // (lovasz_fwd's rule)
+  lovasz_softmax_apply_kernel<Ignore><<<dim3(cv.nblk_scan, S), 256, 0, s>>>(b.k0, b.v0, b.bsum, gts, w, b.partial, gp, cv.P, cv.nblk_scan, xcd_affine);
+  if (grad_unit) {
+    auto jacobian = [&](auto... extra) {
+      if ((HW & 3) == 0)
+        lovasz_softmax_jacobian_kernel<4, Ignore><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, gp, grad_unit, NHW, HW, C, pi, extra...);
+      else lovasz_softmax_jacobian_kernel<1, Ignore><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, gp, grad_unit, NHW, HW, C, pi, extra...);
+    };
+    if constexpr (Ignore) jacobian(IgnoredLabels{targets, ignore...});  // (it reads the labels to write exact zeros)
+    else jacobian();
+  }
+  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(b.partial, S * cv.nblk_scan, 1.f, loss);
+  return RS_LAUNCH_RESULT();
+}
+
 }  // namespace
+
+extern "C" long rs_lovasz_workspace_bytes(int N, int C, int H, int W) {
+  if (!lovasz_shape_ok(N, C, H, W)) return RS_EINVAL;
+  return (long)carve(N, C, H, W).total;
+}
+
+extern "C" int rs_lovasz_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C,
+                             int H, int W, void* workspace, rs_stream_t stream) {
+  if (!logits || !targets || !loss || !workspace || !lovasz_shape_ok(N, C, H, W)) return RS_EINVAL;
+  return lovasz_fwd<false>(logits, targets, loss, grad_unit, N, C, H, W, workspace, stream);
+}
+
+extern "C" int rs_lovasz_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C,
+                                int H, int W, void* workspace, rs_stream_t stream, int ignore) {
+  if (!logits || !targets || !loss || !workspace || !lovasz_shape_ok(N, C, H, W) || !lovasz_ignore_ok(ignore, C)) return RS_EINVAL;
+  return lovasz_fwd<true>(logits, targets, loss, grad_unit, N, C, H, W, workspace, stream, ignore);
+}
+
+extern "C" int rs_scale_by_scalar(const float* src, const float* scalar, float* dst, long n, rs_stream_t stream) {
+  if (!src || !scalar || !dst || n <= 0) return RS_EINVAL;
+  scale_by_scalar_kernel<<<rs_cdiv(n, 256), 256, 0, (hipStream_t)stream>>>(src, scalar, dst, n);
+  return RS_LAUNCH_RESULT();
+}
 
 extern "C" long rs_lovasz_softmax_workspace_bytes(int N, int C, int H, int W, int per_image) {
   if (!lovasz_softmax_shape_ok(N, C, H, W, per_image)) return RS_EINVAL;
@@ -826,368 +943,13 @@ extern "C" long rs_lovasz_softmax_workspace_bytes(int N, int C, int H, int W, in
 extern "C" int rs_lovasz_softmax_fwd(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out,
                                      int N, int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream) {
   if (!logits || !targets || !loss || !workspace || !lovasz_softmax_shape_ok(N, C, H, W, per_image)) return RS_EINVAL;
-  const SoftmaxCarve sc = carve_softmax(N, C, H, W, per_image);
-  const Carve& cv = sc.cv;
-  char* ws = reinterpret_cast<char*>(workspace);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
-  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
-  double* partial = reinterpret_cast<double*>(ws + cv.partial);
-  uint32_t* gts = reinterpret_cast<uint32_t*>(ws + sc.gts);
-  double* w = reinterpret_cast<double*>(ws + sc.w);
-  hipStream_t s = (hipStream_t)stream;
-  const long S = sc.S, HW = (long)H * W, NHW = (long)N * HW;
-  const int pi = per_image ? 1 : 0;
-  const int sc_affine = (S % 8 == 0 && S >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;  // (the rule of rs_lovasz_fwd, per segment)
-
-  if ((HW & 3) == 0)
-    lovasz_softmax_keys_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi);
-  else lovasz_softmax_keys_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi);
-  radix_sort_segments(k0, v0, k1, v1, counts, S, cv, sc_affine, s, sc.chunked_scan ? reinterpret_cast<uint32_t*>(ws + sc.csum) : nullptr);
-  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(v0, bsum, cv.P, cv.nblk_scan);
-  lovasz_softmax_scan_blocks_kernel<<<S, 256, 0, s>>>(bsum, gts, cv.nblk_scan);
-  const int groups = per_image ? N : 1;
-  lovasz_softmax_weights_kernel<<<rs_cdiv(groups, 256), 256, 0, s>>>(gts, w, groups, C, all_classes ? 1 : 0);
-  // the sort is done with (k1, v1): k1 holds the weighted dL/dp, segment-major
-  float* gp = grad_unit ? reinterpret_cast<float*>(k1) : nullptr;
-  const int xcd_affine = (S % 8 == 0 && cv.P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;  // (rs_lovasz_fwd's rule)
-  lovasz_softmax_apply_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(k0, v0, bsum, gts, w, partial, gp, cv.P, cv.nblk_scan, xcd_affine);
-  if (grad_unit) {
-    if ((HW & 3) == 0)
-      lovasz_softmax_jacobian_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, gp, grad_unit, NHW, HW, C, pi);
-    else lovasz_softmax_jacobian_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, gp, grad_unit, NHW, HW, C, pi);
-  }
-  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, S * cv.nblk_scan, 1.f, loss);
-  return RS_LAUNCH_RESULT();
-}
-
-// ---- both Lovasz losses over the pixels whose label is not `ignore` (rs_lovasz_fwd_ig, rs_lovasz_softmax_fwd_ig) ----------------
-// The loss of the valid pixels alone, as if the ignored ones had been cut out of every image and the rest packed in (n, h, w)
-// order.  The sort, the scans and the workspace are the ones above; the kernels above are left as they are (the same
-// instructions as before: profiles/ignore_label/asm_identity.txt).  An ignored pixel's C entries get a key that sorts strictly
-// behind every valid key -- an error of -inf in the hinge form (valid errors are finite), of -1 in the softmax form (valid errors
-// lie in [0, 1]) -- and label bit 0.  The sort is stable, so they form the TAIL of their segment and the valid entries keep the
-// order, the ranks and the label prefix counts they would have without them: every valid rank keeps its delta.  Each segment's
-// gts is its number of set label bits, which only valid pixels have (in the hinge form: one per valid pixel, so gts = K of the
-// image where the kernel above has H*W).  The apply kernels add 0 to the loss for a tail entry and write +0.0f as its gradient.
-// With no pixel ignored every kernel here does the arithmetic of its twin above in the same order: the same bits.
-namespace {
-
-constexpr float kIgnoredSoftmaxErr = -1.f;
-
-__global__ void lovasz_keys_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt, uint32_t* __restrict__ keys,
-                                      uint32_t* __restrict__ vals, long P, long HW, int ignore) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long n = blockIdx.y;
-  if (i >= P) return;
-  const long c = i / HW, hw = i - c * HW;
-  const long long t = tgt[n * HW + hw];
-  const uint32_t m = (t == c) ? 1u : 0u;
-  const float v = x[n * P + i];
-  const float err = (t == ignore) ? -INFINITY : 1.f - (m ? v : -v);
-  keys[n * P + i] = desc_key(err);
-  vals[n * P + i] = (uint32_t)i | (m << 31);
-}
-
-__global__ __launch_bounds__(256) void lovasz_keys4_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                              uint32_t* __restrict__ keys, uint32_t* __restrict__ vals, long P, long HW,
-                                                              int ignore) {
-  const long i = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  const long n = blockIdx.y;
-  if (i >= P) return;
-  const long c = i / HW, hw = i - c * HW;  // (HW % 4 == 0: the four elements share the class plane)
-  const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * P + i);
-  const lv_i64x2 t0 = *reinterpret_cast<const lv_i64x2*>(tgt + n * HW + hw), t1 = *reinterpret_cast<const lv_i64x2*>(tgt + n * HW + hw + 2);
-  const long long t[4] = {t0[0], t0[1], t1[0], t1[1]};
-  lv_u32x4 k, w;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const uint32_t m = (t[e] == c) ? 1u : 0u;
-    const float err = (t[e] == ignore) ? -INFINITY : 1.f - (m ? v[e] : -v[e]);
-    k[e] = desc_key(err);
-    w[e] = (uint32_t)(i + e) | (m << 31);
-  }
-  *reinterpret_cast<lv_u32x4*>(keys + n * P + i) = k;
-  *reinterpret_cast<lv_u32x4*>(vals + n * P + i) = w;
-}
-
-// the four sorted entries of a thread of the apply kernels (ranks r0 .. r0 + 3 of segment n); returns their label count
-__device__ __forceinline__ uint32_t lovasz_load4(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals, long n, long P,
-                                                 long r0, uint32_t (&lab)[4], uint32_t (&key)[4], uint32_t (&idx)[4]) {
-  uint32_t s = 0;
-  if ((P & 3) == 0 && r0 + 3 < P) {
-    const lv_u32x4 v = *reinterpret_cast<const lv_u32x4*>(vals + n * P + r0), k = *reinterpret_cast<const lv_u32x4*>(keys + n * P + r0);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lab[e] = v[e] >> 31;
-      idx[e] = v[e] & 0x7fffffffu;
-      key[e] = k[e];
-      s += lab[e];
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      lab[e] = 0;
-      key[e] = 0;
-      idx[e] = 0;
-      if (r0 + e < P) {
-        const uint32_t v = vals[n * P + r0 + e];
-        lab[e] = v >> 31;
-        idx[e] = v & 0x7fffffffu;
-        key[e] = keys[n * P + r0 + e];
-      }
-      s += lab[e];
-    }
-  }
-  return s;
-}
-
-// lovasz_apply_kernel with gts = the image's number of valid pixels (gts_px[n], from lovasz_softmax_scan_blocks_kernel)
-__global__ __launch_bounds__(256) void lovasz_apply_ig_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                              const uint32_t* __restrict__ boff, const uint32_t* __restrict__ gts_px,
-                                                              double* __restrict__ partial, float* __restrict__ grad, long P,
-                                                              int nblk, float inv_n, int xcd_affine) {
-  __shared__ uint32_t sm[4];
-  __shared__ double red[4];
-  long n = blockIdx.y;
-  int bx = blockIdx.x;
-  if (xcd_affine) {
-    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    const int x = (int)(L & 7);
-    const long k = L >> 3;
-    n = x + 8 * (k / nblk);
-    bx = (int)(k % nblk);
-  }
-  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
-  uint32_t lab[4], key[4], idx[4];
-  const uint32_t s = lovasz_load4(keys, vals, n, P, r0, lab, key, idx);
-  uint32_t total;
-  uint32_t cs = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
-  const float gts = (float)gts_px[n];
-  double acc = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const long r = r0 + e;
-    if (r < P) {
-      const float cs_prev = (float)cs;
-      cs += lab[e];
-      const float cs_inc = (float)cs;
-      const float jac = 1.f - (gts - cs_inc) / (gts + ((float)(r + 1) - cs_inc));
-      float delta = jac;
-      if (r > 0) {
-        const float jac_p = 1.f - (gts - cs_prev) / (gts + ((float)r - cs_prev));
-        delta = jac - jac_p;
-      }
-      const float err = key_to_float(key[e]);
-      // (the tail has err = -inf: not above 0, like every valid entry inside its margin -- no loss term, gradient +0.0f)
-      const float pos = err > 0.f ? err : 0.f;
-      if (err > 0.f) acc += (double)(pos * delta);
-      if (grad) {
-        const float g = err > 0.f ? delta : 0.f;
-        grad[n * P + idx[e]] = (lab[e] ? -g : g) * inv_n;
-      }
-    }
-  }
-  acc = rs_wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[n * nblk + bx] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-template <int VEC>
-__global__ __launch_bounds__(256) void lovasz_softmax_keys_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                                     uint32_t* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                                     float* __restrict__ probs, long NHW, long HW, int C, int per_image,
-                                                                     int ignore) {
-#pragma clang fp contract(off)
-  const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
-  if (q >= NHW) return;
-  const long n = q / HW, hw = q - n * HW;
-  const float* xp = x + n * C * HW + hw;
-  float mx[VEC], sum[VEC], v[VEC], pr[VEC];
-  lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
-  long long t[VEC];
-  if constexpr (VEC == 4) {
-    const lv_i64x2 t0 = *reinterpret_cast<const lv_i64x2*>(tgt + q), t1 = *reinterpret_cast<const lv_i64x2*>(tgt + q + 2);
-    t[0] = t0[0]; t[1] = t0[1]; t[2] = t1[0]; t[3] = t1[1];
-  } else {
-    t[0] = tgt[q];
-  }
-  const uint32_t pos = (uint32_t)(per_image ? hw : q);
-  for (int c = 0; c < C; ++c) {
-    lvs_load<VEC>(xp + c * HW, v);
-    uint32_t k[VEC], w[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      pr[e] = lvs_prob(v[e], mx[e], sum[e]);
-      const uint32_t m = (t[e] == c) ? 1u : 0u;
-      k[e] = desc_key(t[e] == ignore ? kIgnoredSoftmaxErr : m ? 1.f - pr[e] : pr[e]);
-      w[e] = (pos + (uint32_t)e) | (m << 31);
-    }
-    const long o = lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image);
-    if constexpr (VEC == 4) {
-      *reinterpret_cast<lv_u32x4*>(keys + o) = lv_u32x4{k[0], k[1], k[2], k[3]};
-      *reinterpret_cast<lv_u32x4*>(vals + o) = lv_u32x4{w[0], w[1], w[2], w[3]};
-    } else {
-      keys[o] = k[0];
-      vals[o] = w[0];
-    }
-    if (probs) lvs_write<VEC>(probs + (n * C + c) * HW + hw, pr);
-  }
-}
-
-// lovasz_softmax_apply_kernel; a tail entry (negative error) adds nothing and gets dL/dp = +0.0f, whatever its delta
-__global__ __launch_bounds__(256) void lovasz_softmax_apply_ig_kernel(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals,
-                                                                      const uint32_t* __restrict__ boff, const uint32_t* __restrict__ gts,
-                                                                      const double* __restrict__ w, double* __restrict__ partial,
-                                                                      float* __restrict__ gp, long P, int nblk, int xcd_affine) {
-  __shared__ uint32_t sm[4];
-  __shared__ double red[4];
-  long n = blockIdx.y;  // the segment
-  int bx = blockIdx.x;
-  if (xcd_affine) {
-    const long L = (long)blockIdx.y * gridDim.x + blockIdx.x;
-    const long k = L >> 3;
-    n = (L & 7) + 8 * (k / nblk);
-    bx = (int)(k % nblk);
-  }
-  const long r0 = (long)bx * kScanChunk + threadIdx.x * 4;
-  uint32_t lab[4], key[4], idx[4];
-  const uint32_t s = lovasz_load4(keys, vals, n, P, r0, lab, key, idx);
-  uint32_t total;
-  long long k = block_exclusive_scan_256(s, sm, &total) + boff[n * nblk + bx];  // labels strictly before r0
-  const long long g = gts[n];
-  const double ws = w[n];
-  double acc = 0;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const long long r = r0 + e;
-    if (r < P) {
-      const long long Ip = g - k, Up = g + r - k;  // I_{r-1}, U_{r-1}
-      k += lab[e];
-      const long long I = g - k, U = g + r + 1 - k;
-      const double delta = r == 0 ? 1.0 / (double)U : (double)(Ip * U - I * Up) / (double)(U * Up);
-      const float err = key_to_float(key[e]);
-      const bool tail = err < 0.f;
-      if (!tail) acc += (double)err * delta;
-      if (gp) gp[n * P + idx[e]] = tail ? 0.f : (float)(ws * (lab[e] ? -delta : delta));
-    }
-  }
-  acc = rs_wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[n * nblk + bx] = ws * ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
-// lovasz_softmax_jacobian_kernel; +0.0f in every class plane of an ignored pixel
-template <int VEC>
-__global__ __launch_bounds__(256) void lovasz_softmax_jacobian_ig_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
-                                                                         const float* __restrict__ gp, float* __restrict__ grad, long NHW,
-                                                                         long HW, int C, int per_image, int ignore) {
-  const long q = ((long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
-  if (q >= NHW) return;
-  const long n = q / HW, hw = q - n * HW;
-  const float* xp = x + n * C * HW + hw;
-  float mx[VEC], sum[VEC], v[VEC], gv[VEC], out[VEC];
-  bool skip[VEC];
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) skip[e] = tgt[q + e] == ignore;
-  lvs_softmax_stats<VEC>(xp, HW, C, mx, sum);
-  double dot[VEC];
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) dot[e] = 0.0;
-  for (int c = 0; c < C; ++c) {
-    lvs_load<VEC>(xp + c * HW, v);
-    lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) dot[e] += (double)lvs_prob(v[e], mx[e], sum[e]) * (double)gv[e];
-  }
-  for (int c = 0; c < C; ++c) {
-    lvs_load<VEC>(xp + c * HW, v);
-    lvs_load<VEC>(gp + lvs_seg_off(q, n, hw, c, C, NHW, HW, per_image), gv);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e)
-      out[e] = skip[e] ? 0.f : (float)((double)lvs_prob(v[e], mx[e], sum[e]) * ((double)gv[e] - dot[e]));
-    lvs_write<VEC>(grad + (n * C + c) * HW + hw, out);
-  }
-}
-
-}  // namespace
-
-extern "C" int rs_lovasz_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, int N, int C,
-                                int H, int W, void* workspace, rs_stream_t stream, int ignore) {
-  if (!logits || !targets || !loss || !workspace || N <= 0 || C <= 0 || H <= 0 || W <= 0 || (long)C * H * W >= (1L << 31) ||
-      ignore < C || ignore > 255)
-    return RS_EINVAL;
-  const Carve cv = carve(N, C, H, W);
-  char* ws = reinterpret_cast<char*>(workspace);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
-  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
-  double* partial = reinterpret_cast<double*>(ws + cv.partial);
-  hipStream_t s = (hipStream_t)stream;
-  const long P = cv.P, HW = (long)H * W;
-  const int sc_affine = (N % 8 == 0 && N >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
-
-  if ((HW & 3) == 0) lovasz_keys4_ig_kernel<<<dim3(rs_cdiv(P / 4, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW, ignore);
-  else lovasz_keys_ig_kernel<<<dim3(rs_cdiv(P, 256), N), 256, 0, s>>>(logits, targets, k0, v0, P, HW, ignore);
-  radix_sort_segments(k0, v0, k1, v1, counts, N, cv, sc_affine, s);
-  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(v0, bsum, P, cv.nblk_scan);
-  // the sort is done with its digit counts (at least 256 words per image): their first N words take the images' valid pixel
-  // counts, so the workspace is rs_lovasz_workspace_bytes' as it stands
-  uint32_t* gts_px = counts;
-  lovasz_softmax_scan_blocks_kernel<<<N, 256, 0, s>>>(bsum, gts_px, cv.nblk_scan);
-  const float inv_n = 1.f / (float)N;
-  const int xcd_affine = (N % 8 == 0 && P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
-  lovasz_apply_ig_kernel<<<dim3(cv.nblk_scan, N), 256, 0, s>>>(k0, v0, bsum, gts_px, partial, grad_unit, P, cv.nblk_scan, inv_n, xcd_affine);
-  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, (long)N * cv.nblk_scan, inv_n, loss);
-  return RS_LAUNCH_RESULT();
+  return lovasz_softmax_fwd<false>(logits, targets, loss, grad_unit, probs_out, N, C, H, W, per_image, all_classes, workspace, stream);
 }
 
 extern "C" int rs_lovasz_softmax_fwd_ig(const float* logits, const long long* targets, float* loss, float* grad_unit, float* probs_out,
                                         int N, int C, int H, int W, int per_image, int all_classes, void* workspace, rs_stream_t stream,
                                         int ignore) {
-  if (!logits || !targets || !loss || !workspace || !lovasz_softmax_shape_ok(N, C, H, W, per_image) || ignore < C || ignore > 255)
+  if (!logits || !targets || !loss || !workspace || !lovasz_softmax_shape_ok(N, C, H, W, per_image) || !lovasz_ignore_ok(ignore, C))
     return RS_EINVAL;
-  const SoftmaxCarve sc = carve_softmax(N, C, H, W, per_image);
-  const Carve& cv = sc.cv;
-  char* ws = reinterpret_cast<char*>(workspace);
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(ws + cv.keys0);
-  uint32_t* v0 = reinterpret_cast<uint32_t*>(ws + cv.vals0);
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(ws + cv.keys1);
-  uint32_t* v1 = reinterpret_cast<uint32_t*>(ws + cv.vals1);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(ws + cv.counts);
-  uint32_t* bsum = reinterpret_cast<uint32_t*>(ws + cv.bsum);
-  double* partial = reinterpret_cast<double*>(ws + cv.partial);
-  uint32_t* gts = reinterpret_cast<uint32_t*>(ws + sc.gts);
-  double* w = reinterpret_cast<double*>(ws + sc.w);
-  hipStream_t s = (hipStream_t)stream;
-  const long S = sc.S, HW = (long)H * W, NHW = (long)N * HW;
-  const int pi = per_image ? 1 : 0;
-  const int sc_affine = (S % 8 == 0 && S >= 16 && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
-
-  if ((HW & 3) == 0)
-    lovasz_softmax_keys_ig_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi, ignore);
-  else lovasz_softmax_keys_ig_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, k0, v0, probs_out, NHW, HW, C, pi, ignore);
-  radix_sort_segments(k0, v0, k1, v1, counts, S, cv, sc_affine, s, sc.chunked_scan ? reinterpret_cast<uint32_t*>(ws + sc.csum) : nullptr);
-  lovasz_blocksum_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(v0, bsum, cv.P, cv.nblk_scan);
-  lovasz_softmax_scan_blocks_kernel<<<S, 256, 0, s>>>(bsum, gts, cv.nblk_scan);  // (g of a segment: its valid pixels of the class)
-  const int groups = per_image ? N : 1;
-  lovasz_softmax_weights_kernel<<<rs_cdiv(groups, 256), 256, 0, s>>>(gts, w, groups, C, all_classes ? 1 : 0);
-  float* gp = grad_unit ? reinterpret_cast<float*>(k1) : nullptr;
-  const int xcd_affine = (S % 8 == 0 && cv.P * 4 <= (2L << 20) && rs_knobs().lovasz_xcd != 0) ? 1 : 0;
-  lovasz_softmax_apply_ig_kernel<<<dim3(cv.nblk_scan, S), 256, 0, s>>>(k0, v0, bsum, gts, w, partial, gp, cv.P, cv.nblk_scan, xcd_affine);
-  if (grad_unit) {
-    if ((HW & 3) == 0)
-      lovasz_softmax_jacobian_ig_kernel<4><<<rs_cdiv(NHW / 4, 256), 256, 0, s>>>(logits, targets, gp, grad_unit, NHW, HW, C, pi, ignore);
-    else lovasz_softmax_jacobian_ig_kernel<1><<<rs_cdiv(NHW, 256), 256, 0, s>>>(logits, targets, gp, grad_unit, NHW, HW, C, pi, ignore);
-  }
-  lovasz_finalize_kernel<<<1, 1024, 0, s>>>(partial, S * cv.nblk_scan, 1.f, loss);
-  return RS_LAUNCH_RESULT();
+  return lovasz_softmax_fwd<true>(logits, targets, loss, grad_unit, probs_out, N, C, H, W, per_image, all_classes, workspace, stream, ignore);
 }
