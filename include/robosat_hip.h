@@ -305,6 +305,60 @@ int rs_nll_loss_bwd_pw(const float* logits, const long long* targets, const floa
                        const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
                        rs_stream_t stream, const float* pixel_weight, int ignore);
 
+/* HARD-PIXEL MINING for CrossEntropy / Focal (`rs train`: `[opt] hard_fraction`, `hard_below`): online hard example mining, also
+ * called bootstrapped cross-entropy or top-k pixel loss.  Per image, only the hardest share of the pixels keeps its weight; the others
+ * get weight 0 in the `_pw` loss above.  DESIGN.md section 7e.
+ *
+ * For every image n of the batch, independently:
+ * - Key.  A pixel whose label is not the ignore label is *valid*.  Its key is its unweighted cross-entropy l = lse - x_t, computed in
+ *   fp32 by the function the loss kernels use (pixel_loss, mode 0), whatever the loss's own mode.
+ *   - Focal is monotone in the true class's probability, so the ranking by cross-entropy is the ranking by Focal.
+ *   - The ranking does not depend on the class weights.
+ *   - As a uint32 the key is bits(l) if l > 0, else 0: -0.0f, a tiny negative rounding result and NaN become 0.
+ *   - The bit patterns of non-negative floats order like the floats.
+ * - Count.  V_n is the number of valid pixels.
+ *   - k_n = 0 if V_n = 0.
+ *   - Otherwise k_n = min(V_n, max(1, (int64) ceil(fraction * (double) V_n))).
+ *   - `fraction` is a double and the product one IEEE double multiply: the same integer on the host and on the device.
+ * - Threshold.  tau_n is the k_n-th largest key among the valid pixels of image n (0 where V_n = 0).
+ *   - tau_n = min(tau_n, cap); cap = bits(float32(-ln m)) for a probability bound m in (0, 1), made by the host in float64 and rounded
+ *     once.  0xFFFFFFFF means "no cap".
+ *   - So a pixel whose true class has a probability below m is always kept, and `fraction` reads "at least this share".
+ * - Plane: float32 [N][H][W].
+ *   - A valid pixel with key >= tau_n is *kept* and gets base[p], or exactly 1.0f without a base plane.
+ *   - Every other pixel gets exactly +0.0f.
+ *   - Ties at tau_n are all kept: kept_n >= k_n, and the set depends on no traversal order.
+ *   - V_n = 0 keeps nothing.
+ * - Loss: rs_nll_loss_fwd_pw / bwd_pw with that plane, sum_kept base*w[t]*l / sum_kept base*w[t].  The selection is piecewise
+ *   constant: no gradient flows through it, and a dropped pixel's gradient is +0.0f in every class plane.
+ * - Per image, not per batch: an image's selection depends neither on its companions in the batch nor on how the batch is split over
+ *   ranks.
+ *
+ * info: int64 [N][4] = (V_n, k_n, tau_n, kept_n).
+ * rs_hard_pixel_select: the selection and the plane on a key plane the caller supplies (any uint32 values): the histograms zeroed on
+ * the stream, then an exact radix select over the 32 key bits in three rounds of 11 / 11 / 10 bits from the top -- a histogram of the
+ * round's digit over the valid keys that carry the prefix found so far (per block in LDS, the lanes of a wave that hold one digit
+ * added as one, one integer atomic per non-empty bin into the image's histogram), then one block per image that walks the bins from
+ * the top, finds the digit that holds the k_n-th largest and writes the longer prefix and the remaining rank (the first round's also
+ * makes V_n and k_n) -- then the plane and kept_n.  Eight launches for every shape, the first of which zeroes the histograms; integer
+ * sums only, so the same input gives the same bits in every run; no allocation, no host synchronisation: the call can be captured
+ * into a graph.
+ * rs_hard_pixel_plane: the key kernel (one thread per pixel, an ignored pixel's logits are not read; into `keys_out` where that is
+ * given, else into the workspace) followed by exactly those stages.
+ * `targets` of rs_hard_pixel_select may be null iff ignore < 0; `base` and `keys_out` may be null.  `workspace`:
+ * rs_hard_pixel_workspace_bytes(N, H, W) bytes, 16-byte aligned.
+ * The scalar arguments of this ABI are int, long and float (tests/test_host_logic.py binds them by class), so the double `fraction`
+ * travels as `fraction_bits`, the 64 bits of the IEEE double in a long -- exactly, no float in between -- and the uint32 `cap` as a
+ * long in 0..0xFFFFFFFF.
+ * RS_EINVAL: a null pointer that may not be null, a misaligned workspace, C outside 1..8, a fraction that is not finite or not in
+ * (0, 1], a cap outside 0..0xFFFFFFFF, an ignore label that is neither -1 nor in C..255 (select: 0..255), a non-positive size, H*W >= 2^31. */
+long rs_hard_pixel_workspace_bytes(int N, int H, int W);
+int rs_hard_pixel_plane(const float* logits, const long long* targets, const float* base, float* plane, unsigned* keys_out,
+                        long long* info, int N, int C, int H, int W, long fraction_bits, long cap, int ignore, void* workspace,
+                        rs_stream_t stream);
+int rs_hard_pixel_select(const unsigned* keys, const long long* targets, const float* base, float* plane, long long* info, int N,
+                         int H, int W, long fraction_bits, long cap, int ignore, void* workspace, rs_stream_t stream);
+
 /* Metrics.add over a whole batch (metrics.py:27-41): counts[0..3] += (tn, fn, fp, tp) in the reference's naming. */
 int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C, int H,
                         int W, rs_stream_t stream);

@@ -83,6 +83,11 @@ SIGNATURES = {
     "rs_boundary_weight_plane": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rs_nll_loss_fwd_pw": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, c_int]),
     "rs_nll_loss_bwd_pw": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, c_int]),
+    # hard-pixel mining of CrossEntropy / Focal: the weight plane from the logits, and its selection stages on a given key plane
+    "rs_hard_pixel_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    # (`fraction_bits`: the double's 64 bits in a long; `cap`: a uint32 in a long)
+    "rs_hard_pixel_plane": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, c_int, P, P]),
+    "rs_hard_pixel_select": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_long, c_long, c_int, P, P]),
     # bf16 path (activations typed by a dtype code / bf16 entry points)
     "rs_conv2d_fwd_bf16": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "rs_conv2d_tile_bf16": (c_int, [POINTER(ConvDesc)]),

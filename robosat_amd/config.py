@@ -3,6 +3,7 @@
 Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, loss
          [augment] zoom, brightness, contrast, saturation, gamma   (extension, optional: robosat_amd/augment.py)
          [opt] boundary_weight, boundary_sigma   (extension, optional: the boundary weight of CrossEntropy / Focal, ``boundary_options`` below)
+         [opt] hard_fraction, hard_below   (extension, optional: hard-pixel mining of CrossEntropy / Focal, ``hard_options`` below)
 Dataset: [common] dataset, classes, colors                   [weights] values
          [common] ignore   (extension, optional: the label value of pixels that carry no class, ``ignore_label`` below)
 ``cuda = true`` means "use the MI355X" (the HIP device shows up as torch's ``cuda``); ``cuda = false`` is rejected by
@@ -75,6 +76,39 @@ def boundary_options(model):
         raise ValueError("[opt] boundary_weight weighs the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
             " and ".join(BOUNDARY_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
     return values["boundary_weight"], values["boundary_sigma"]
+
+
+HARD_LOSSES = ("CrossEntropy", "Focal")
+
+
+def hard_options(model):
+    """The model config's optional ``[opt] hard_fraction`` (a finite number in (0, 1]) and ``[opt] hard_below`` (a number in (0, 1), needs
+    the fraction): hard-pixel mining of CrossEntropy and Focal -- while training, per image only the ``ceil(fraction * valid pixels)``
+    pixels of the largest cross-entropy, and every pixel whose true class has a probability below ``hard_below``, count in the loss.
+    Returns ``None`` without the keys, else ``(fraction, below | None)``; raises ``ValueError("[opt] hard_...")`` on a bad value, on a
+    bound without a fraction and on a loss that has no per-pixel weight."""
+
+    import math
+
+    opt = model["opt"]
+
+    def number(key, ok, what):
+        value = opt[key]
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not ok(value):
+            raise ValueError("[opt] {} must be {}, got {}".format(
+                key, what, _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)))
+        return float(value)
+
+    if "hard_fraction" not in opt:
+        if "hard_below" in opt:
+            raise ValueError("[opt] hard_below needs [opt] hard_fraction (the share of an image's pixels that is always kept)")
+        return None
+    fraction = number("hard_fraction", lambda v: 0 < v <= 1, "a finite number in (0, 1]")
+    below = number("hard_below", lambda v: 0 < v < 1, "a number in (0, 1)") if "hard_below" in opt else None
+    if opt.get("loss") not in HARD_LOSSES:
+        raise ValueError("[opt] hard_fraction mines the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
+            " and ".join(HARD_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
+    return fraction, below
 
 
 def load_config(path):

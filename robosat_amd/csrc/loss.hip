@@ -179,11 +179,22 @@ __global__ __launch_bounds__(256) void nll_bwd_kernel(const float* __restrict__ 
       return;
     }
   }
+  [[maybe_unused]] float pw = 0.f;
+  if constexpr (V == Px::IgnoreWeight) {
+    // a pixel of weight 0 -- one the hard-pixel plane drops -- is written like an ignored one: +0.0f in every class plane, where
+    // 0 * g[c] would be -0.0f under a negative g[c]; its logits are not read
+    pw = pixw[p];
+    if (pw == 0.f) {
+#pragma unroll
+      for (int c = 0; c < C; ++c) dx[(n * C + c) * HW + hw] = 0.f;
+      return;
+    }
+  }
   float v[C], g[C];
   load_logits<C>(x, n, hw, HW, v);
   if constexpr (V == Px::Plain) t = (int)tgt[p];
   float w;
-  if constexpr (V == Px::IgnoreWeight) w = pixw[p] * (weight ? weight[t] : 1.f);
+  if constexpr (V == Px::IgnoreWeight) w = pw * (weight ? weight[t] : 1.f);
   else w = weight ? weight[t] : 1.f;
   pixel_loss<C>(v, t, mode, gamma, &g);
   const float k = (gout ? gout[0] : 1.f) * w / stats[1];
@@ -686,4 +697,316 @@ extern "C" int rs_boundary_weight_plane(const long long* targets, const float* t
   if (rc) return rc;
   boundary_lookup_kernel<<<rs_cdiv(P, 256), 256, 0, s>>>(d2, mask, table, plane, P, R * R);
   return RS_LAUNCH_RESULT();
+}
+
+// ---- hard-pixel mining (rs_hard_pixel_plane / rs_hard_pixel_select in include/robosat_hip.h) -------------------------------------
+// Per image the k-th largest of up to 2^31 - 1 uint32 keys, exactly, and the plane that keeps the pixels at or above it: the key
+// plane (plane entry point only), then three rounds of [histogram of one digit of the valid keys that carry the prefix found so
+// far; one small block per image that walks the bins from the top], 11 / 11 / 10 bits from the top, then the plane.  Every count is an
+// integer sum, so the result depends on no order; the histograms are zeroed on the stream in every call, and nothing comes back to
+// the host.
+namespace {
+
+constexpr int kHardThreads = 256;
+constexpr int kHardMaxBins = 2048;
+constexpr int kHardHistWords = 3 * kHardMaxBins;  // per image: one histogram per round
+constexpr int kHardStateWords = 4;                // per image: prefix, remaining rank, and two words to spare
+constexpr int kHardVoteRounds = 4;
+
+// round R counts the digit (key >> shift) & (bins - 1) of the keys with key >> (shift + bits) == the prefix of the rounds before it
+template <int R>
+struct HardRound {
+  static constexpr int bits = R == 2 ? 10 : 11;
+  static constexpr int shift = R == 0 ? 21 : R == 1 ? 10 : 0;
+  static constexpr int bins = 1 << bits;
+};
+
+// An image's pixels go to `bpi` blocks, `chunk` (a multiple of the block) consecutive ones each; block b of the launch works on image
+// b / bpi.  Enough blocks to fill the device where the batch is small, at least 2048 pixels per block so that zeroing and flushing
+// a histogram stay small beside counting.
+struct HardGeom {
+  int bpi;
+  unsigned int chunk;
+};
+
+HardGeom hard_geom(int N, long HW) {
+  long bpi = (HW + 2047) / 2048;
+  const long want = (1024 + N - 1) / N;
+  if (bpi > want) bpi = want;
+  long chunk = (HW + bpi - 1) / bpi;
+  chunk = (chunk + kHardThreads - 1) / kHardThreads * kHardThreads;
+  bpi = (HW + chunk - 1) / chunk;  // (no empty block)
+  return HardGeom{(int)bpi, (unsigned int)chunk};
+}
+
+// key = the bits of the unweighted cross-entropy where it is > 0, else 0 (-0.0f, a negative rounding result, NaN); 0 at an ignored
+// pixel, whose logits are not read (its key counts nowhere: validity is decided from the label again).  One thread per pixel.
+template <int C>
+__global__ __launch_bounds__(kHardThreads) void hard_key_kernel(const float* __restrict__ x, const long long* __restrict__ tgt,
+                                                                unsigned int* __restrict__ keys, long P, long HW, int ignore) {
+  const long p = (long)blockIdx.x * kHardThreads + threadIdx.x;
+  if (p >= P) return;
+  const int t = (int)tgt[p];
+  if (t == ignore) {
+    keys[p] = 0u;
+    return;
+  }
+  const long n = p / HW, hw = p - n * HW;
+  float v[C];
+  load_logits<C>(x, n, hw, HW, v);
+  const float l = pixel_loss<C>(v, t, /*mode*/ 0, 0.f, nullptr);
+  keys[p] = l > 0.f ? __float_as_uint(l) : 0u;
+}
+
+// The histograms of all three rounds start from zero in every call.  A kernel of the sequence, not a memset: a graph that holds the
+// call then consists of kernel nodes alone, each ordered behind the one before it.
+__global__ __launch_bounds__(kHardThreads) void hard_zero_kernel(unsigned int* __restrict__ words, long count) {
+  const long i = (long)blockIdx.x * kHardThreads + threadIdx.x;
+  if (i < count) words[i] = 0u;
+}
+
+// One count into the block's LDS histogram per lane that is `on`, with the lanes of a wave that hold the same digit added as one: up
+// to kHardVoteRounds times the first lane still on names its digit, the lanes that hold it are counted by a ballot and leave, and that
+// lane adds the count.  A trained network puts most pixels into one or two bins, which would otherwise be 64 LDS atomics on one
+// address per wave and step; what is left after the votes are the rare digits, one atomic each.  Every lane of the wave calls this.
+__device__ __forceinline__ void hard_vote_add(unsigned int* __restrict__ hist, bool on, unsigned int digit) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(on);
+  for (int r = 0; r < kHardVoteRounds && todo; ++r) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const unsigned int d0 = (unsigned int)__shfl((int)digit, leader, 64);
+    const unsigned long long same = __ballot(on && digit == d0);
+    if (lane == leader) atomicAdd(&hist[d0], (unsigned int)__popcll(same));
+    on = on && digit != d0;
+    todo &= ~same;
+  }
+  if (on) atomicAdd(&hist[digit], 1u);
+}
+
+// ghist[image][round R][digit] += the block's counts: an LDS histogram, flushed with one integer atomic per non-empty bin.
+template <int R>
+__global__ __launch_bounds__(kHardThreads) void hard_hist_kernel(const unsigned int* __restrict__ keys, const long long* __restrict__ tgt,
+                                                                 unsigned int* __restrict__ ghist, const unsigned int* __restrict__ state,
+                                                                 unsigned int HW, int bpi, unsigned int chunk, int ignore) {
+  using Rd = HardRound<R>;
+  __shared__ unsigned int hist[Rd::bins];
+  const int n = blockIdx.x / bpi, b = blockIdx.x - n * bpi;
+  for (int i = threadIdx.x; i < Rd::bins; i += kHardThreads) hist[i] = 0;
+  __syncthreads();
+  [[maybe_unused]] unsigned int prefix = 0;
+  if constexpr (R > 0) prefix = state[(long)n * kHardStateWords];
+  const unsigned int lo = (unsigned int)b * chunk;
+  const unsigned int hi = HW - lo < chunk ? HW : lo + chunk;  // (lo < HW: no block is empty)
+  const long base = (long)n * HW;
+  for (unsigned int at = lo; at < hi; at += kHardThreads) {  // (the whole wave makes every trip: hard_vote_add)
+    const unsigned int hw = at + threadIdx.x;
+    bool on = hw < hi;
+    unsigned int key = 0;
+    if (on) key = keys[base + hw];
+    if constexpr (R > 0) on = on && (key >> (Rd::shift + Rd::bits)) == prefix;
+    if (on && ignore >= 0) on = (int)tgt[base + hw] != ignore;
+    hard_vote_add(hist, on, (key >> Rd::shift) & (Rd::bins - 1));
+  }
+  __syncthreads();
+  unsigned int* out = ghist + (long)n * kHardHistWords + R * kHardMaxBins;
+  for (int i = threadIdx.x; i < Rd::bins; i += kHardThreads) {
+    const unsigned int c = hist[i];
+    if (c) atomicAdd(&out[i], c);
+  }
+}
+
+// One block per image: the digit of round R that holds the rank-th largest key, from the top bin down.  Thread t sums the
+// bins/256 bins below bins - t * (bins/256), an exclusive scan over the threads gives the number of keys above its bins, and the one
+// thread whose bins straddle the rank walks them.  Round 0 first makes V (the histogram's total: every valid key has a first digit)
+// and k = min(V, max(1, ceil(fraction * V))), the rank to look for; the last round writes tau, capped, into info.
+template <int R>
+__global__ __launch_bounds__(kHardThreads) void hard_pick_kernel(const unsigned int* __restrict__ ghist, unsigned int* __restrict__ state,
+                                                                 long long* __restrict__ info, double fraction, unsigned int cap) {
+  using Rd = HardRound<R>;
+  constexpr int per = Rd::bins / kHardThreads;
+  __shared__ unsigned int scan[kHardThreads];
+  const int n = blockIdx.x, t = threadIdx.x;
+  const unsigned int* h = ghist + (long)n * kHardHistWords + R * kHardMaxBins;
+  unsigned int* st = state + (long)n * kHardStateWords;
+  unsigned int c[per], mine = 0;
+#pragma unroll
+  for (int j = 0; j < per; ++j) {
+    c[j] = h[Rd::bins - 1 - (t * per + j)];
+    mine += c[j];
+  }
+  scan[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < kHardThreads; o <<= 1) {  // inclusive scan
+    const unsigned int add = t >= o ? scan[t - o] : 0u;
+    __syncthreads();
+    scan[t] += add;
+    __syncthreads();
+  }
+  const unsigned int above = scan[t] - mine;
+  unsigned int rank, prefix = 0;
+  if constexpr (R == 0) {
+    const unsigned int V = scan[kHardThreads - 1];
+    long long k = 0;
+    if (V) {
+      k = (long long)ceil(fraction * (double)V);
+      k = k < 1 ? 1 : k;
+      k = k > (long long)V ? (long long)V : k;
+    }
+    rank = (unsigned int)k;
+    if (t == 0) {
+      info[(long)n * 4] = (long long)V;
+      info[(long)n * 4 + 1] = k;
+      if (!V) st[0] = 0u, st[1] = 0u;
+    }
+  } else {
+    rank = st[1];
+    prefix = st[0];
+  }
+  __syncthreads();  // (every thread has read the state before one of them rewrites it)
+  if (rank && above < rank && rank <= above + mine) {
+    unsigned int acc = above;
+#pragma unroll
+    for (int j = 0; j < per; ++j) {
+      if (acc < rank && rank <= acc + c[j]) {
+        st[0] = (prefix << Rd::bits) | (unsigned int)(Rd::bins - 1 - (t * per + j));
+        st[1] = rank - acc;
+      }
+      acc += c[j];
+    }
+  }
+  if constexpr (R == 2) {
+    __syncthreads();
+    if (t == 0) {
+      const unsigned int tau = st[0];  // (0 for an image without a valid pixel)
+      info[(long)n * 4 + 2] = (long long)(tau < cap ? tau : cap);
+      info[(long)n * 4 + 3] = 0;
+    }
+  }
+}
+
+// plane = base (1.0f without one) at a valid pixel with key >= tau, +0.0f anywhere else; info[n][3] += the number kept, one integer
+// atomic per block.
+__global__ __launch_bounds__(kHardThreads) void hard_plane_kernel(const unsigned int* __restrict__ keys, const long long* __restrict__ tgt,
+                                                                  const float* __restrict__ basew, float* __restrict__ plane,
+                                                                  long long* __restrict__ info, unsigned int HW, int bpi,
+                                                                  unsigned int chunk, int ignore) {
+  __shared__ unsigned int part[kHardThreads / 64];
+  const int n = blockIdx.x / bpi, b = blockIdx.x - n * bpi;
+  const unsigned int tau = (unsigned int)info[(long)n * 4 + 2];
+  const bool any = info[(long)n * 4] > 0;
+  const unsigned int lo = (unsigned int)b * chunk;
+  const unsigned int hi = HW - lo < chunk ? HW : lo + chunk;
+  const long base = (long)n * HW;
+  unsigned int kept = 0;
+  for (unsigned int hw = lo + threadIdx.x; hw < hi; hw += kHardThreads) {
+    const long p = base + hw;
+    bool keep = any && keys[p] >= tau;
+    if (keep && ignore >= 0) keep = (int)tgt[p] != ignore;
+    float v = 0.f;
+    if (keep) v = basew ? basew[p] : 1.f;
+    plane[p] = v;
+    kept += keep ? 1u : 0u;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) kept += __shfl_xor(kept, o, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = kept;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned int tot = (part[0] + part[1]) + (part[2] + part[3]);
+    if (tot) atomicAdd(reinterpret_cast<unsigned long long*>(info) + (long)n * 4 + 3, (unsigned long long)tot);
+  }
+}
+
+// (an image's pixels are indexed by an unsigned int and counted in one; a launch's blocks by an int)
+bool hard_shape_ok(int N, int H, int W) {
+  if (N <= 0 || H <= 0 || W <= 0) return false;
+  const long HW = (long)H * W;
+  return HW < (1l << 31) && (long)N * ((HW + kHardThreads - 1) / kHardThreads) < (1l << 31);
+}
+
+// The fraction travels as the 64 bits of the double (the scalars of this ABI are int, long and float), the cap as a long that holds
+// a uint32.
+double hard_fraction_of(long bits) {
+  static_assert(sizeof(long) == sizeof(double), "the fraction's bits travel in a long");
+  double f;
+  __builtin_memcpy(&f, &bits, sizeof f);
+  return f;
+}
+
+bool hard_args_ok(int N, int H, int W, double fraction, long cap, int ignore, int C, const void* workspace) {
+  return hard_shape_ok(N, H, W) && workspace && !((uintptr_t)workspace & 15) && fraction > 0.0 && fraction <= 1.0 &&  // (NaN fails both)
+         cap >= 0 && cap <= 0xFFFFFFFFl && (ignore == -1 || (ignore >= C && ignore <= 255));
+}
+
+struct HardWorkspace {
+  unsigned int* hist;
+  unsigned int* state;
+  unsigned int* keys;
+};
+
+HardWorkspace hard_carve(void* workspace, int N) {
+  HardWorkspace ws;
+  ws.hist = static_cast<unsigned int*>(workspace);
+  ws.state = ws.hist + (long)N * kHardHistWords;
+  ws.keys = ws.state + (long)N * kHardStateWords;
+  return ws;
+}
+
+// the selection and the plane on the key plane `keys`: the histograms zeroed, three times (histogram, pick), the plane
+int hard_select(const unsigned int* keys, const long long* t, const float* basew, float* plane, long long* info, int N, long HW,
+                double fraction, unsigned int cap, int ignore, const HardWorkspace& ws, hipStream_t s) {
+  const HardGeom g = hard_geom(N, HW);
+  const int grid = N * g.bpi;
+  hard_zero_kernel<<<rs_cdiv((long)N * kHardHistWords, kHardThreads), kHardThreads, 0, s>>>(ws.hist, (long)N * kHardHistWords);
+  hard_hist_kernel<0><<<grid, kHardThreads, 0, s>>>(keys, t, ws.hist, ws.state, (unsigned int)HW, g.bpi, g.chunk, ignore);
+  hard_pick_kernel<0><<<N, kHardThreads, 0, s>>>(ws.hist, ws.state, info, fraction, cap);
+  hard_hist_kernel<1><<<grid, kHardThreads, 0, s>>>(keys, t, ws.hist, ws.state, (unsigned int)HW, g.bpi, g.chunk, ignore);
+  hard_pick_kernel<1><<<N, kHardThreads, 0, s>>>(ws.hist, ws.state, info, fraction, cap);
+  hard_hist_kernel<2><<<grid, kHardThreads, 0, s>>>(keys, t, ws.hist, ws.state, (unsigned int)HW, g.bpi, g.chunk, ignore);
+  hard_pick_kernel<2><<<N, kHardThreads, 0, s>>>(ws.hist, ws.state, info, fraction, cap);
+  hard_plane_kernel<<<grid, kHardThreads, 0, s>>>(keys, t, basew, plane, info, (unsigned int)HW, g.bpi, g.chunk, ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+template <int C>
+int run_hard_keys(const float* x, const long long* t, unsigned int* keys, long P, long HW, int ignore, hipStream_t s) {
+  hard_key_kernel<C><<<rs_cdiv(P, kHardThreads), kHardThreads, 0, s>>>(x, t, keys, P, HW, ignore);
+  return RS_LAUNCH_RESULT();
+}
+
+int hard_keys(const float* x, const long long* t, unsigned int* keys, int C, long P, long HW, int ignore, hipStream_t s) {
+  RS_DISPATCH_C(C, run_hard_keys<K>(x, t, keys, P, HW, ignore, s));
+}
+
+}  // namespace
+
+extern "C" long rs_hard_pixel_workspace_bytes(int N, int H, int W) {
+  if (!hard_shape_ok(N, H, W)) return RS_EINVAL;
+  return ((long)N * (kHardHistWords + kHardStateWords) + (long)N * H * W) * (long)sizeof(unsigned int);
+}
+
+extern "C" int rs_hard_pixel_select(const unsigned* keys, const long long* targets, const float* base, float* plane, long long* info,
+                                    int N, int H, int W, long fraction_bits, long cap, int ignore, void* workspace,
+                                    rs_stream_t stream) {
+  const double fraction = hard_fraction_of(fraction_bits);
+  // (no class count here: the ignore label is -1 or a label byte; the labels are needed exactly where one is ignored)
+  if (!keys || !plane || !info || !hard_args_ok(N, H, W, fraction, cap, ignore, 0, workspace) || (ignore >= 0 && !targets))
+    return RS_EINVAL;
+  return hard_select(keys, targets, base, plane, info, N, (long)H * W, fraction, (unsigned int)cap, ignore, hard_carve(workspace, N),
+                     (hipStream_t)stream);
+}
+
+extern "C" int rs_hard_pixel_plane(const float* logits, const long long* targets, const float* base, float* plane, unsigned* keys_out,
+                                   long long* info, int N, int C, int H, int W, long fraction_bits, long cap, int ignore,
+                                   void* workspace, rs_stream_t stream) {
+  const double fraction = hard_fraction_of(fraction_bits);
+  if (!logits || !targets || !plane || !info || C <= 0 || C > kMaxC || !hard_args_ok(N, H, W, fraction, cap, ignore, C, workspace))
+    return RS_EINVAL;
+  const long HW = (long)H * W;
+  hipStream_t s = (hipStream_t)stream;
+  const HardWorkspace ws = hard_carve(workspace, N);
+  unsigned int* keys = keys_out ? keys_out : ws.keys;
+  const int rc = hard_keys(logits, targets, keys, C, (long)N * HW, HW, ignore, s);
+  if (rc) return rc;
+  return hard_select(keys, targets, base, plane, info, N, HW, fraction, (unsigned int)cap, ignore, ws, s);
 }

@@ -9,7 +9,9 @@ ones had been cut out of every image (``rs_*_ig``, include/robosat_hip.h; DESIGN
 calls made without the argument.
 
 ``CrossEntropyLoss2d`` and ``FocalLoss2d`` also take ``boundary=(w0, sigma)``: the U-Net paper's border weight map on top of the class
-weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``).  ``mIoULoss2d`` and the two Lovasz forms do not."""
+weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``), and ``hard=fraction`` or ``hard=(fraction, below)``: hard-pixel mining, per
+image only the hardest share of the pixels keeps its weight (``rs_hard_pixel_plane``), in training mode only.  ``mIoULoss2d`` and the two
+Lovasz forms take neither."""
 
 import torch
 import torch.nn as nn
@@ -142,6 +144,32 @@ class _NLLBoundaryFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
+class _NLLHardFn(torch.autograd.Function):
+    """``_NLLFn`` with the hard-pixel plane (``ops.hard_pixel_plane``) made from the logits in forward and kept for backward; with
+    ``boundary`` the boundary weight plane is its base, so a kept pixel carries its boundary weight.  The selection is piecewise
+    constant, so the gradient is the ``_pw`` gradient with the plane as it stands; the exchange of ``stats[1]`` is the same one."""
+
+    @staticmethod
+    def forward(ctx, inputs, targets, weight, mode, gamma, global_batch, ignore, boundary, hard):
+        x = inputs.detach().float()
+        base = None
+        if boundary is not None:
+            base = ops.boundary_weight_plane(targets, boundary[0], boundary[1], ignore=ignore, classes=x.shape[1])
+        plane, _ = ops.hard_pixel_plane(x, targets, hard[0], below=hard[1], ignore=ignore, base=base)
+        loss, stats = ops.nll_loss_fwd(x, targets, weight, mode, gamma, ignore=ignore, pixel_weight=plane)
+        loss = _global_batch_normaliser(loss, stats, global_batch)
+        ctx.save_for_backward(x, targets, stats, plane)
+        ctx.weight, ctx.mode, ctx.gamma, ctx.ignore = weight, mode, gamma, ignore
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, stats, plane = ctx.saved_tensors
+        g = grad_out.detach().float().contiguous()
+        dx = ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma, ignore=ctx.ignore, pixel_weight=plane)
+        return dx, None, None, None, None, None, None, None, None
+
+
 class _MIoUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, targets, weight, global_batch=False, ignore=None):
@@ -210,41 +238,69 @@ def _check_boundary(boundary):
     return (float(w0), float(sigma))
 
 
+def _check_hard(hard):
+    """``hard`` = ``fraction`` or ``(fraction, below)`` of the hard-pixel mining (``None`` passes) as ``(fraction, below | None)``: a
+    finite fraction in (0, 1], a probability bound in (0, 1)."""
+
+    if hard is None:
+        return None
+    if isinstance(hard, (int, float)) and not isinstance(hard, bool):
+        hard = (hard, None)
+    try:
+        fraction, below = hard
+    except (TypeError, ValueError):
+        raise ValueError("hard must be None, a fraction or a pair (fraction, below), got {!r}".format(hard))
+    fraction = ops.hard_fraction(fraction)
+    if below is not None:
+        ops.hard_cap(below)
+        below = float(below)
+    return (fraction, below)
+
+
+def _nll(self, inputs, targets, mode, gamma):
+    """The call ``CrossEntropyLoss2d`` and ``FocalLoss2d`` make: without ``boundary`` and ``hard`` the calls they have always made; mining
+    is a training device, so in eval mode the criterion makes the calls it makes without ``hard``."""
+
+    inputs, targets = _check(inputs, targets)
+    ignore = _check_ignore(self.ignore_index, inputs)
+    if self.hard is not None and self.training:
+        return _NLLHardFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore, self.boundary, self.hard)
+    if self.boundary is not None:
+        return _NLLBoundaryFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore, self.boundary)
+    if ignore is None:
+        return _NLLFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch)
+    return _NLLFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore)
+
+
 class CrossEntropyLoss2d(_WeightedLoss):
     """Cross-entropy: weighted NLL of log_softmax over the class axis (reference losses.py:8-25).  ``boundary=(w0, sigma)``: every
     pixel's term is also weighted by ``1 + w0 exp(-d^2 / (2 sigma^2))``, d its distance to the nearest label boundary, made from
-    ``targets`` on the device in every call (include/robosat_hip.h; DESIGN.md "Boundary weight"); ``None`` makes today's calls."""
+    ``targets`` on the device in every call (include/robosat_hip.h; DESIGN.md "Boundary weight"); ``None`` makes today's calls.
+    ``hard=fraction`` or ``(fraction, below)``: in training mode, per image only the valid pixels whose cross-entropy is among the
+    ``ceil(fraction * V)`` largest, or whose true class has a probability below ``below``, keep their weight (include/robosat_hip.h;
+    DESIGN.md "Hard-pixel mining"); with ``boundary`` a kept pixel keeps its boundary weight.  ``None`` makes today's calls."""
 
-    def __init__(self, weight=None, ignore_index=None, boundary=None):
+    def __init__(self, weight=None, ignore_index=None, boundary=None, hard=None):
         super().__init__(weight, ignore_index)
         self.boundary = _check_boundary(boundary)
+        self.hard = _check_hard(hard)
 
     def forward(self, inputs, targets):
-        inputs, targets = _check(inputs, targets)
-        ignore = _check_ignore(self.ignore_index, inputs)
-        if self.boundary is not None:
-            return _NLLBoundaryFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch, ignore, self.boundary)
-        if ignore is None:
-            return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch)
-        return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_CROSS_ENTROPY, 0.0, self.global_batch, ignore)
+        return _nll(self, inputs, targets, ops.NLL_CROSS_ENTROPY, 0.0)
 
 
 class FocalLoss2d(_WeightedLoss):
-    """Focal loss, gamma = 2 by default (reference losses.py:28-50); ``boundary`` as in ``CrossEntropyLoss2d``."""
+    """Focal loss, gamma = 2 by default (reference losses.py:28-50); ``boundary`` and ``hard`` as in ``CrossEntropyLoss2d`` (the pixels are ranked by
+    their cross-entropy: Focal is monotone in the true class's probability, so that is its ranking too)."""
 
-    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None):
+    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None, hard=None):
         super().__init__(weight, ignore_index)
         self.gamma = gamma
         self.boundary = _check_boundary(boundary)
+        self.hard = _check_hard(hard)
 
     def forward(self, inputs, targets):
-        inputs, targets = _check(inputs, targets)
-        ignore = _check_ignore(self.ignore_index, inputs)
-        if self.boundary is not None:
-            return _NLLBoundaryFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch, ignore, self.boundary)
-        if ignore is None:
-            return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch)
-        return _NLLFn.apply(inputs, targets, self.weight, ops.NLL_FOCAL, float(self.gamma), self.global_batch, ignore)
+        return _nll(self, inputs, targets, ops.NLL_FOCAL, float(self.gamma))
 
 
 class mIoULoss2d(_WeightedLoss):

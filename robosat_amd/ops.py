@@ -1327,6 +1327,91 @@ def boundary_weight_plane(targets, w0, sigma, ignore=None, classes=None):
     return plane
 
 
+HARD_NO_CAP = 0xFFFFFFFF
+
+
+def hard_fraction(fraction):
+    """``fraction`` of the hard-pixel selection as a float: a finite number in (0, 1], else ``ValueError``."""
+
+    import math
+
+    if isinstance(fraction, bool) or not isinstance(fraction, (int, float)) or not math.isfinite(fraction) or not 0 < fraction <= 1:
+        raise ValueError("robosat_amd: the hard-pixel fraction is a finite number in (0, 1], got {!r}".format(fraction))
+    return float(fraction)
+
+
+def hard_cap(below):
+    """The cap on the hard-pixel threshold for the probability bound ``below`` in (0, 1): the bits of ``float32(-ln below)``, made in
+    float64 and rounded once (include/robosat_hip.h).  A pixel whose true class has a probability below ``below`` has a key above
+    the cap and is always kept."""
+
+    import math
+    import struct
+
+    if isinstance(below, bool) or not isinstance(below, (int, float)) or not 0 < below < 1:  # (NaN fails both comparisons)
+        raise ValueError("robosat_amd: the hard-pixel probability bound is a number in (0, 1), got {!r}".format(below))
+    return struct.unpack("<I", struct.pack("<f", -math.log(float(below))))[0]
+
+
+def hard_fraction_bits(fraction):
+    """The checked ``fraction`` as the C ABI takes it: the 64 bits of the double in an integer (``fraction_bits``)."""
+
+    import struct
+
+    return struct.unpack("<q", struct.pack("<d", hard_fraction(fraction)))[0]
+
+
+def _hard_args(shape, fraction, below, ignore, classes, base, device):
+    """What the two hard-pixel wrappers share: the checked scalars as the C ABI takes them and the outputs."""
+
+    n, h, w = shape
+    fraction = hard_fraction_bits(fraction)
+    cap = HARD_NO_CAP if below is None else hard_cap(below)
+    ignore = _ignore_label(ignore, classes)
+    if base is not None:
+        assert tuple(base.shape) == (n, h, w), "base is [N, H, W]"
+    plane = torch.empty((n, h, w), device=device, dtype=torch.float32)
+    info = torch.empty((n, 4), device=device, dtype=torch.int64)
+    return fraction, cap, -1 if ignore is None else ignore, plane, info
+
+
+def hard_pixel_plane(logits, targets, fraction, below=None, ignore=None, base=None, want_keys=False):
+    """float32 [N, C, H, W] logits, int64 [N, H, W] labels -> ``(plane, info)`` of ``rs_hard_pixel_plane`` (include/robosat_hip.h):
+    per image the valid pixels whose cross-entropy is among the ``ceil(fraction * V)`` largest (ties kept), or above ``-ln below``,
+    get ``base`` (float32 [N, H, W]; 1.0 without one) in the float32 [N, H, W] ``plane``, every other pixel +0.0; ``info`` int64
+    [N, 4] = (valid pixels, k, threshold key, kept pixels).  ``want_keys`` adds the key plane: int32 [N, H, W] that holds the
+    uint32 bits."""
+
+    n, c, h, w = logits.shape
+    x, tgt = _dev(logits, "logits"), _dev(targets, "targets", torch.int64)  # (a CPU tensor raises before anything is loaded or sized)
+    assert tuple(targets.shape) == (n, h, w), "targets is [N, H, W]"
+    fraction, cap, ignore, plane, info = _hard_args((n, h, w), fraction, below, ignore, c, base, logits.device)
+    keys = torch.empty((n, h, w), device=logits.device, dtype=torch.int32) if want_keys else None
+    lib = _lib.lib()
+    _call("rs_hard_pixel_plane", x, tgt, _dev(base, "base"), _dev(plane, "plane"), _dev(keys, "keys", torch.int32),
+          _dev(info, "info", torch.int64), n, c, h, w, fraction, cap, ignore,
+          _workspace(lib.rs_hard_pixel_workspace_bytes(n, h, w), logits.device), _stream())
+    return (plane, info, keys) if want_keys else (plane, info)
+
+
+def hard_pixel_select(keys, fraction, below=None, targets=None, ignore=None, base=None):
+    """``rs_hard_pixel_select``: the selection of ``hard_pixel_plane`` on a key plane of the caller's, int32 [N, H, W] that holds
+    any uint32 bits -> ``(plane, info)``.  ``targets`` is needed with ``ignore`` (any label byte here: there is no class count)."""
+
+    n, h, w = keys.shape
+    k = _dev(keys, "keys", torch.int32)
+    if (ignore is None) != (targets is None):
+        raise ValueError("robosat_amd: hard_pixel_select takes targets and ignore together")
+    if targets is not None:
+        assert tuple(targets.shape) == (n, h, w), "targets is [N, H, W]"
+    fraction, cap, ignore, plane, info = _hard_args((n, h, w), fraction, below, ignore, 0, base, keys.device)
+    lib = _lib.lib()
+    _call("rs_hard_pixel_select", k, _dev(targets, "targets", torch.int64), _dev(base, "base"), _dev(plane, "plane"),
+          _dev(info, "info", torch.int64), n, h, w, fraction, cap, ignore,
+          _workspace(lib.rs_hard_pixel_workspace_bytes(n, h, w), keys.device), _stream())
+    return plane, info
+
+
 def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None, pixel_weight=None):
     """``ignore`` (here and in the four losses below): the label value whose pixels are left out of the loss
     (``rs_*_ig`` in include/robosat_hip.h); ``None`` calls the entry point without it.  ``pixel_weight`` float32 [N, H, W]

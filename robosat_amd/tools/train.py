@@ -27,6 +27,10 @@ Differences by design:
   * ``[opt] boundary_weight`` / ``boundary_sigma`` (extension keys, optional: robosat_amd/config.py): CrossEntropy and Focal weigh
     every pixel by ``1 + w0 exp(-d^2 / (2 sigma^2))``, d its distance to the nearest label boundary, from a plane made on the device
     out of the batch's label raster as it is after the augmentation (robosat_amd/losses.py); training and validation alike.
+  * ``[opt] hard_fraction`` / ``hard_below`` (extension keys, optional: robosat_amd/config.py): hard-pixel mining of CrossEntropy and
+    Focal -- while training, per image only the hardest share of the valid pixels (and every pixel whose true class has a probability
+    below ``hard_below``) counts in the loss (robosat_amd/losses.py).  The criterion then follows the network into train / eval mode,
+    and the logged validation loss is the unmined loss.
   * ``[augment]`` (extension table, optional: robosat_amd/augment.py): a random zoom-in crop and brightness / contrast /
     saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.
 """
@@ -48,7 +52,7 @@ from tqdm import tqdm
 from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
-from robosat_amd.config import boundary_options, check_num_classes, ignore_label, load_config
+from robosat_amd.config import boundary_options, check_num_classes, hard_options, ignore_label, load_config
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
 from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, mIoULoss2d
@@ -148,6 +152,7 @@ def main(args):
     try:
         ignore = ignore_label(dataset)  # (dataset `[common] ignore`, optional: label pixels that are left out of the loss)
         boundary = boundary_options(model)  # (model `[opt] boundary_weight / boundary_sigma`, optional: None without the keys)
+        hard = hard_options(model)  # (model `[opt] hard_fraction / hard_below`, optional: None without the keys)
     except ValueError as err:
         sys.exit("Error: {}".format(err))  # (before any work starts)
 
@@ -242,6 +247,9 @@ def main(args):
     ignored = {} if ignore is None else {"ignore_index": ignore}
     # (and without `[opt] boundary_weight` likewise; with it the loss is CrossEntropy or Focal: boundary_options)
     weighted = {} if boundary is None else {"boundary": boundary}
+    # (and without `[opt] hard_fraction`; with it the loss is CrossEntropy or Focal: hard_options)
+    if hard is not None:
+        weighted["hard"] = hard
     if loss_name == "CrossEntropy":
         criterion = CrossEntropyLoss2d(weight=weight, **ignored, **weighted).to(device)
     elif loss_name == "mIoU":
@@ -301,6 +309,9 @@ def main(args):
         say("Ignore label:\t {}".format(ignore))
     if boundary is not None:
         say("Boundary weight:\t w0 = {}, sigma = {} px (reach {} px)".format(boundary[0], boundary[1], int(math.ceil(3.0 * boundary[1]))))
+    if hard is not None:
+        say("Hard pixels:\t the hardest {} of every image's valid pixels{} (training only; validation loss unmined)".format(
+            hard[0], "" if hard[1] is None else ", and every pixel with p(true class) < {}".format(hard[1])))
     if jitter is not None:
         say("Augmentation:\t {}".format(describe_jitter(jitter)))
     say("---")
@@ -434,6 +445,10 @@ def _epoch(loader, num_classes, device, net, criterion, master, optimizer=None, 
     metrics = Metrics(range(num_classes))
 
     net.train() if training else net.eval()
+    if getattr(criterion, "hard", None) is not None:
+        # hard-pixel mining is a training device: the criterion follows the network's mode, and the validation loss is the unmined
+        # loss, comparable between runs with different fractions (without the keys the criterion is never touched)
+        criterion.train(training)
     started = time.perf_counter()
 
     # A step is ~600 kernel launches issued by this thread; a full cyclic-GC pass in the middle of an epoch stalls it for
