@@ -769,6 +769,31 @@ int rs_augment_tiles_jitter(const uint8_t* images, const uint8_t* masks, const i
                             const float* std, float* out_images, int64_t* out_masks, int N, int S, int C, int rgb,
                             rs_stream_t stream);
 
+/* Free rotation on top of the zoom (`[augment] rotate`): rs_augment_tiles_jitter with the window of item n turned about its
+ * centre by the angle whose cosine and sine are rot[n] = (c, s) in units of 2^-16 (HOST array [N][2], like geom), the content
+ * counter-clockwise as displayed for a positive angle (the sense of np.rot90).  op[n] is undone first, giving (x, y) in the
+ * frame, so the rotation acts on the window and the flip and quarter turns come last.  All in 64-bit integers:
+ *   A  = floor((2*c*w + S) / (2*S))        B = floor((2*s*w + S) / (2*S))      (once per item, on the host)
+ *   dx = 2x + 1 - S                        dy = 2y + 1 - S
+ *   Ux = A*dx - B*dy + (2*x0 + w)*65536    Uy = B*dx + A*dy + (2*y0 + w)*65536
+ * (Ux, Uy) is where the pixel's centre falls in the source tile, in units of 2^-17 pixels.  With >> the arithmetic shift:
+ *   mask:   the label at (fold(Ux >> 17), fold(Uy >> 17));
+ *   image:  per axis i0 = (U - 65536) >> 17, i1 = i0 + 1, weight of the second tap f = float((U - 65536) & 131071) / 131072
+ *           (exact), taps fold(i0) and fold(i1), interpolated as above: top = a + fx*(b - a), v = top + fy*(bot - top);
+ *   fold(i) = -1 - i for i < 0, 2S - 1 - i for i >= S, i otherwise: the tile mirrored about its edges, the edge pixel repeated.
+ * The taps are NOT clamped to the window: a turned window reads its true neighbours in the tile, and past the tile the mirror,
+ * image and mask alike.  One fold is enough: the window lies in the tile, so no sample is further than 0.21 S outside.  The
+ * colour stages and the normalisation are rs_augment_tiles_jitter's, on the interpolated value; the contrast stage's band means
+ * stay those of the whole source tile.  A and B are rounded to 2^-16, so a sample sits at most S * 2^-17 pixels from the ideal
+ * rotation; the quantised map is the definition.  (c, s) = (65536, 0) with w = S reads every byte itself (f = 0), and the quarter
+ * turns (0, +-65536), (-65536, 0) are np.rot90 exactly.
+ * RS_EINVAL: as rs_augment_tiles_jitter, and |c| or |s| above 65536, or |c*c + s*s - 2^32| above 2^17 (the two roundings move the
+ * sum by 92 700 at the most): a pair that is no rotation is refused before it can address memory. */
+int rs_augment_tiles_rotate(const uint8_t* images, const uint8_t* masks, const int32_t* index, const int32_t* op,
+                            const int32_t* geom, const int32_t* rot, const float* color, const int64_t* band_sums,
+                            const float* mean, const float* std, float* out_images, int64_t* out_masks, int N, int S, int C,
+                            int rgb, rs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * `rs features` (robosat/tools/features.py, robosat/features/core.py): the raster stages on the device
  * (csrc/features.hip).  Batched over B tiles of equal H x W, 1 <= H, W <= 4096, B <= 65535,

@@ -175,6 +175,8 @@ SIGNATURES = {
     "rs_tile_band_sums": (c_int, [P, P, c_int, c_int, c_int, P]),
     "rs_augment_tiles_jitter": (c_int, [P, P, P, P, POINTER(c_int32), POINTER(c_float), P, POINTER(c_float), POINTER(c_float), P, P,
                                         c_int, c_int, c_int, c_int, P]),
+    "rs_augment_tiles_rotate": (c_int, [P, P, P, P, POINTER(c_int32), POINTER(c_int32), POINTER(c_float), P, POINTER(c_float),
+                                        POINTER(c_float), P, P, c_int, c_int, c_int, c_int, P]),
     # rs features: raster stages (csrc/features.hip)
     "rs_features_clean_form": (c_int, [c_int, c_int]),
     "rs_features_clean_workspace_bytes": (c_long, [c_int, c_int, c_int]),

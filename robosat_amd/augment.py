@@ -7,21 +7,26 @@ reference's eight views (an extension; the reference has neither).
       contrast   = [0.8, 1.2]
       saturation = [0.8, 1.2]   # needs the first image source in mode RGB or RGBA (robosat_amd.bands)
       gamma      = [0.8, 1.25]
+      rotate     = 180          # largest turn of the window about its centre in degrees, 0 <= rotate <= 180 (0 = off)
 
 An absent key is the identity; an absent table is the loaders as they are without this module.  The table applies to the
 training split only.  Everything here is host logic: the parsing, and the seven draws per item that follow the four of
-``datasets.draw_flip_rotations``.  The pixels are made on the device (``ops.augment_tiles_jitter``, csrc/augment.hip); what the
-window and the factors mean is stated in include/robosat_hip.h.
+``datasets.draw_flip_rotations`` -- eight with ``rotate``, whose draw is made only when the key is set, so that a table without
+it yields the batches it always did.  The pixels are made on the device (``ops.augment_tiles_jitter``, or
+``ops.augment_tiles_rotate`` for every item of a table with ``rotate``; csrc/augment.hip); what the window, the angle and the
+factors mean is stated in include/robosat_hip.h.
 """
 
 import collections
 import math
 import random
 
-KEYS = ("zoom", "brightness", "contrast", "saturation", "gamma")
+KEYS = ("zoom", "brightness", "contrast", "saturation", "gamma", "rotate")
 MAX_ZOOM = MAX_FACTOR = 4.0
+MAX_ROTATE = 180.0
+ROT_ONE = 65536  # the angle travels as (cos, sin) in units of 2**-16
 
-Jitter = collections.namedtuple("Jitter", ["zoom", "brightness", "contrast", "saturation", "gamma", "rgb"])
+Jitter = collections.namedtuple("Jitter", ["zoom", "brightness", "contrast", "saturation", "gamma", "rgb", "rotate"], defaults=(0.0,))
 
 
 def _number(v):
@@ -44,7 +49,7 @@ def jitter_from_config(model, bands):
     if not _number(zoom) or not 1.0 <= zoom <= MAX_ZOOM:
         raise ValueError("[augment] zoom must be a number in 1..{:g} (the largest zoom-in factor; 1 = off), got {!r}".format(MAX_ZOOM, zoom))
     ranges = {}
-    for key in KEYS[1:]:
+    for key in KEYS[1:5]:
         r = table.get(key, [1.0, 1.0])
         if not (isinstance(r, (list, tuple)) and len(r) == 2 and all(_number(v) for v in r) and 0.0 < r[0] <= r[1] <= MAX_FACTOR):
             raise ValueError("[augment] {} must be [lo, hi] with 0 < lo <= hi <= {:g}, got {!r}".format(key, MAX_FACTOR, r))
@@ -53,14 +58,19 @@ def jitter_from_config(model, bands):
     if ranges["saturation"] != (1.0, 1.0) and not rgb:
         raise ValueError("[augment] saturation needs the first image source in mode RGB or RGBA; [common] image_modes gives {!r}"
                          .format(bands.modes[0]))
-    return Jitter(float(zoom), ranges["brightness"], ranges["contrast"], ranges["saturation"], ranges["gamma"], rgb)
+    rotate = table.get("rotate", 0.0)
+    if not _number(rotate) or not 0.0 <= rotate <= MAX_ROTATE:
+        raise ValueError("[augment] rotate must be a number of degrees in 0..{:g} (the largest turn either way; 0 = off), got {!r}"
+                         .format(MAX_ROTATE, rotate))
+    return Jitter(float(zoom), ranges["brightness"], ranges["contrast"], ranges["saturation"], ranges["gamma"], rgb, float(rotate))
 
 
 def describe(jitter):
     """The table as one line of the training log."""
 
-    return "zoom <= {:g}, brightness {}, contrast {}, saturation {}, gamma {}".format(
+    line = "zoom <= {:g}, brightness {}, contrast {}, saturation {}, gamma {}".format(
         jitter.zoom, *("[{:g}, {:g}]".format(*r) for r in (jitter.brightness, jitter.contrast, jitter.saturation, jitter.gamma)))
+    return line + ", rotate <= {:g} deg".format(jitter.rotate) if jitter.rotate > 0 else line
 
 
 def window(size, zoom, r_w, r_x, r_y):
@@ -80,3 +90,18 @@ def draw_jitter(jitter, size):
     geom = window(size, jitter.zoom, r[0], r[1], r[2])
     color = tuple(lo + v * (hi - lo) for v, (lo, hi) in zip(r[3:], (jitter.brightness, jitter.contrast, jitter.saturation, jitter.gamma)))
     return geom, color
+
+
+def rotation(rotate, r_a):
+    """``(c, s)``: the angle theta = (2 r_a - 1) * rotate degrees that one uniform draw picks, as the two integers the kernel
+    takes, floor(65536 cos theta + 1/2) and floor(65536 sin theta + 1/2)."""
+
+    theta = math.radians((2.0 * r_a - 1.0) * rotate)
+    return int(math.floor(ROT_ONE * math.cos(theta) + 0.5)), int(math.floor(ROT_ONE * math.sin(theta) + 0.5))
+
+
+def draw_rotation(jitter):
+    """The eighth draw of one item, r_a, behind the seven of ``draw_jitter``.  The caller makes it only when ``jitter.rotate > 0``:
+    a table without the key consumes the draws it always did."""
+
+    return rotation(jitter.rotate, random.random())

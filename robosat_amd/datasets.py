@@ -151,7 +151,8 @@ class UnaugmentedTiles(torch.utils.data.Dataset):
     A tile crosses the DataLoader's queues and PCIe as 1 MiB of bytes instead of 5 MiB of floats + int64 labels.
 
     With ``jitter`` (``robosat_amd.augment.Jitter``, the model config's ``[augment]`` table; needs ``draw``) seven more numbers
-    are drawn behind the four and the items are ``(image, mask, op code, window int32 [3], factors float32 [4], tiles)``."""
+    are drawn behind the four and the items are ``(image, mask, op code, window int32 [3], factors float32 [4], tiles)``; with
+    ``jitter.rotate > 0`` an eighth follows and the angle, int32 [2] = (cos, sin) in units of 2**-16, stands before ``tiles``."""
 
     def __init__(self, image_dirs, label_dir, size, draw, modes=None, jitter=None):
         super().__init__()
@@ -187,11 +188,13 @@ class UnaugmentedTiles(torch.utils.data.Dataset):
         mask = torch.from_numpy(np.array(mask, dtype=np.uint8))
         code = draw_flip_rotations() if self.draw else 0
         if self.jitter is not None:
-            from .augment import draw_jitter
+            from .augment import draw_jitter, draw_rotation
 
             geom, color = draw_jitter(self.jitter, self.size)
-            return (image, mask, code, torch.tensor(geom, dtype=torch.int32), torch.tensor(color, dtype=torch.float32),
-                    [tile for _, tile in tiles_and_images])
+            head = (image, mask, code, torch.tensor(geom, dtype=torch.int32), torch.tensor(color, dtype=torch.float32))
+            if self.jitter.rotate > 0:
+                head += (torch.tensor(draw_rotation(self.jitter), dtype=torch.int32),)
+            return head + ([tile for _, tile in tiles_and_images],)
         return image, mask, code, [tile for _, tile in tiles_and_images]
 
 
@@ -238,7 +241,8 @@ class HostDecodeLoader:
     distribution, same seeded draws per worker as the host chain, bit-equal tensors (tests/test_gpu_tools.py).
 
     With ``jitter`` (the ``[augment]`` table) the workers draw the window and the colour factors too, and the one kernel is
-    ``rs_augment_tiles_jitter``, with the band sums of each uploaded batch."""
+    ``rs_augment_tiles_jitter``, with the band sums of each uploaded batch; with ``jitter.rotate > 0`` they draw the angle as
+    well and the kernel is ``rs_augment_tiles_rotate`` for every item."""
 
     def __init__(self, image_dirs, label_dir, size, batch_sampler, workers, device, mean, std, modes=None, jitter=None):
         self.dataset = UnaugmentedTiles(image_dirs, label_dir, size, draw=True, modes=modes, jitter=jitter)
@@ -263,6 +267,10 @@ class HostDecodeLoader:
             op = codes.to(torch.int32).to(self.device, non_blocking=True)
             if self.jitter is None:
                 out, om = ops.augment_tiles(images, masks, index, op, mean, std)
+            elif self.jitter.rotate > 0:
+                geom, color, rot = item[3], item[4], item[5]
+                out, om = ops.augment_tiles_rotate(images, masks, index, op, geom, rot, color, ops.tile_band_sums(images), mean, std,
+                                                   self.jitter.rgb)
             else:
                 geom, color = item[3], item[4]
                 out, om = ops.augment_tiles_jitter(images, masks, index, op, geom, color, ops.tile_band_sums(images), mean, std,
@@ -280,7 +288,8 @@ class DeviceAugmentLoader:
 
     With ``jitter`` (the ``[augment]`` table; the cache must hold its band sums) every item draws its four numbers and then the
     seven of ``robosat_amd.augment.draw_jitter``, as a DataLoader worker of ``HostDecodeLoader`` does, and the one kernel is
-    ``rs_augment_tiles_jitter``."""
+    ``rs_augment_tiles_jitter``; with ``jitter.rotate > 0`` an eighth number is the angle and the kernel is
+    ``rs_augment_tiles_rotate`` for every item."""
 
     def __init__(self, cache, batch_sampler, mean, std, jitter=None):
         self.cache, self.batch_sampler, self.mean, self.std = cache, batch_sampler, list(mean), list(std)
@@ -302,18 +311,23 @@ class DeviceAugmentLoader:
             if self.jitter is None:
                 codes = [self.draw_op() for _ in batch]
             else:
-                from .augment import draw_jitter
+                from .augment import draw_jitter, draw_rotation
 
-                codes, geom, color = [], [], []
-                for _ in batch:  # per item: the four draws, then the seven
+                codes, geom, color, rot = [], [], [], []
+                for _ in batch:  # per item: the four draws, then the seven, then the angle's where the table has one
                     codes.append(self.draw_op())
                     g, f = draw_jitter(self.jitter, c.size)
                     geom.append(g)
                     color.append(f)
+                    if self.jitter.rotate > 0:
+                        rot.append(draw_rotation(self.jitter))
             index = torch.tensor(batch, dtype=torch.int32).to(c.device, non_blocking=True)
             op = torch.tensor(codes, dtype=torch.int32).to(c.device, non_blocking=True)
             if self.jitter is None:
                 images, masks = ops.augment_tiles(c.images, c.masks, index, op, mean, std)
+            elif self.jitter.rotate > 0:
+                images, masks = ops.augment_tiles_rotate(c.images, c.masks, index, op, geom, rot, color, c.band_sums, mean, std,
+                                                         self.jitter.rgb)
             else:
                 images, masks = ops.augment_tiles_jitter(c.images, c.masks, index, op, geom, color, c.band_sums, mean, std,
                                                          self.jitter.rgb)

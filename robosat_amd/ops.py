@@ -1640,6 +1640,34 @@ def augment_tiles_jitter(images, masks, index, op, geom, color, band_sums, mean,
     return out, om
 
 
+def augment_tiles_rotate(images, masks, index, op, geom, rot, color, band_sums, mean, std, rgb):
+    """``augment_tiles_jitter`` with the window turned about its centre (include/robosat_hip.h): ``rot`` int32 [N,2] = (c, s),
+    the cosine and sine of each item's angle in units of 2**-16 (``robosat_amd.augment.rotation``), is a HOST value like ``geom``
+    and ``color``.  Where the turned window leaves the tile it reads the tile mirrored about its edges, image and mask alike."""
+
+    t, s, s2, c = images.shape
+    assert s == s2, "square tiles (a 90-degree rotation must keep the shape)"
+    n = index.numel()
+    geom = torch.as_tensor(geom, dtype=torch.int32).contiguous()
+    rot = torch.as_tensor(rot, dtype=torch.int32).contiguous()
+    color = torch.as_tensor(color, dtype=torch.float32).contiguous()
+    if geom.is_cuda or rot.is_cuda or color.is_cuda:
+        raise RuntimeError("robosat_amd: `geom`, `rot` and `color` are host values (the launch checks them and carries them as arguments)")
+    if tuple(geom.shape) != (n, 3) or tuple(rot.shape) != (n, 2) or tuple(color.shape) != (n, 4):
+        raise ValueError("robosat_amd: `geom` must be [N,3], `rot` [N,2] and `color` [N,4] for the N = {} items of `index`".format(n))
+    if band_sums is not None and tuple(band_sums.shape) != (t, c):
+        raise ValueError("robosat_amd: `band_sums` must be [T,C] = [{},{}], the sums of these `images`".format(t, c))
+    out = torch.empty((n, c, s, s), device=images.device, dtype=torch.float32)
+    om = torch.empty((n, s, s), device=images.device, dtype=torch.int64) if masks is not None else None
+    fm, fs = (ctypes.c_float * c)(*mean), (ctypes.c_float * c)(*std)
+    _call("rs_augment_tiles_rotate", _dev(images, "images", torch.uint8), _dev(masks, "masks", torch.uint8),
+          _dev(index, "index", torch.int32), _dev(op, "op", torch.int32), ctypes.cast(geom.data_ptr(), ctypes.POINTER(ctypes.c_int32)),
+          ctypes.cast(rot.data_ptr(), ctypes.POINTER(ctypes.c_int32)), ctypes.cast(color.data_ptr(), ctypes.POINTER(ctypes.c_float)),
+          _dev(band_sums, "band_sums", torch.int64), fm, fs, _dev(out, "out"), _dev(om, "out_masks", torch.int64), n, s, c,
+          int(bool(rgb)), _stream())
+    return out, om
+
+
 # ---- rs features: raster stages (csrc/features.hip; definitions in include/robosat_hip.h) --------------------------------
 CLEAN_AUTO, CLEAN_LDS, CLEAN_HBM = 0, 1, 2
 

@@ -32,7 +32,10 @@ Differences by design:
     below ``hard_below``) counts in the loss (robosat_amd/losses.py).  The criterion then follows the network into train / eval mode,
     and the logged validation loss is the unmined loss.
   * ``[augment]`` (extension table, optional: robosat_amd/augment.py): a random zoom-in crop and brightness / contrast /
-    saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.
+    saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.  Its key
+    ``rotate = A`` (degrees, 0 < A <= 180) also turns every window about its centre by an angle drawn from [-A, A]; where the turned
+    window leaves the tile it reads the tile mirrored about its edges, image and label alike.  The log's ``Augmentation:`` line
+    (``robosat_amd.augment.describe``) names the key only when it is set.
 """
 
 import argparse
@@ -519,7 +522,7 @@ class ShardedBatchSampler:
 def get_split_loaders(model, dataset, workers, device, rank=0, world=1):
     """The loaders of ``get_dataset_loaders`` with the transform chain split between the DataLoader workers (decode, mode
     conversion, resize, crop, the random draws) and the device (flip, rotations, ToTensor, Normalize).  The model config's
-    ``[augment]`` table (``robosat_amd.augment``) adds its zoom and colour jitter to the training loader alone."""
+    ``[augment]`` table (``robosat_amd.augment``) adds its zoom, rotation and colour jitter to the training loader alone."""
     from robosat_amd.datasets import HostDecodeLoader
 
     size = model["common"]["image_size"]
@@ -541,7 +544,8 @@ def get_split_loaders(model, dataset, workers, device, rank=0, world=1):
 
 def get_device_loaders(model, dataset, device, rank=0, world=1, workers=0):
     """The loaders of ``get_dataset_loaders`` with the tiles decoded once into HBM and augmented on the device; with the
-    model config's ``[augment]`` table the training cache also holds its band sums and the training loader jitters."""
+    model config's ``[augment]`` table the training cache also holds its band sums and the training loader jitters (and, with its
+    ``rotate`` key, turns every window by an angle of its own)."""
     from robosat_amd.datasets import DecodedTileCache, DeviceAugmentLoader
 
     size = model["common"]["image_size"]
