@@ -359,6 +359,54 @@ int rs_hard_pixel_plane(const float* logits, const long long* targets, const flo
 int rs_hard_pixel_select(const unsigned* keys, const long long* targets, const float* base, float* plane, long long* info, int N,
                          int H, int W, long fraction_bits, long cap, int ignore, void* workspace, rs_stream_t stream);
 
+/* THE TVERSKY LOSS FAMILY with a fused cross-entropy term (`rs train`: `[opt] loss = "Tversky"`): Dice, the Tversky index (Salehi et
+ * al. 2017), the focal Tversky loss (Abraham & Khan 2019) and "that term plus cross-entropy".  DESIGN.md section 7g.
+ *
+ * Inputs: logits [N][C][H][W] fp32 with 2 <= C <= 8, targets int64 [N][H][W], an optional `weight` [C] (it weighs the cross-entropy
+ * term only) and `ignore`, -1 for none or a label value with C <= ignore <= 255.  A pixel is *valid* if its label is not `ignore`; an
+ * ignored pixel enters no sum, its gradient is exactly +0.0f in every class plane and its logits are never read.  With p = softmax
+ * over C:
+ * - Segment.  s = (image n, class c) when per_image, class c over the whole batch otherwise.
+ * - Sums over the valid pixels of a segment: TP = sum_{t=c} p_c, SP = sum p_c, cnt = #{t=c}; FP = SP - TP, FN = cnt - TP.
+ * - Tversky index: TI_s = (TP + eps) / (TP + alpha*FP + beta*FN + eps), and TI_s = 1 where the denominator is 0.
+ * - Segment loss: l_s = max(1 - TI_s, 0)^gamma.  Where 1 - TI_s <= 0, d l_s / d TI_s is -1 for gamma == 1 and 0 otherwise; a segment
+ *   whose denominator is 0 has no gradient.
+ * - Segments that count.  Without all_classes those with cnt > 0; with it every segment of an image that has a valid pixel (batch
+ *   form: every class, if the batch has a valid pixel).
+ * - Tversky term.  Per image T = (1/N) sum_n mean_{c in P_n} l_{n,c}: an image with empty P_n contributes 0 and the divisor stays N.
+ *   Batch form T = mean_{c in P} l_c, 0 for empty P.
+ * - Pixel term.  CE = sum_valid w[t] (-log p_t) / sum_valid w[t]; a zero denominator gives 0 and no gradient, as in rs_nll_loss_fwd_ig.
+ * - loss = T + lambda*CE.  With lambda == 0 the pixel term adds nothing to loss or gradient.
+ * alpha = beta = 0.5 is Dice; alpha = beta = 1 the soft Jaccard, which with eps = 0, gamma = 1, all_classes and per_image is the
+ * soft-IoU term of rs_miou_loss_fwd.  beta > alpha favours recall.  alpha, beta >= 0 and not both 0, gamma > 0, eps >= 0, lambda >= 0,
+ * all finite: float32 values, used as the doubles they convert to.
+ *
+ * The forward is two calls, so that data-parallel ranks can exchange the sums between them:
+ * rs_tversky_sums: one pass over logits and targets (one thread per pixel, at most 64 blocks per image; fp64 partial sums per block),
+ * then one block that adds them in a fixed order.  sums (fp64) per image: [N][C][3] = (TP, SP, cnt), then the CE numerator and
+ * denominator (3*N*C + 2 doubles); batch form: [C][3], the images added in ascending order, then the same two (3*C + 2 doubles).
+ * `workspace`: rs_tversky_workspace_bytes(N, C) bytes, 8-byte aligned; every word the call reads was written by the same call.
+ * rs_tversky_finalize: one launch, from `sums` to loss[0] and stats [4 + 2*S] floats, S = N*C per image and C otherwise:
+ * [0] the loss, [1] T, [2] the CE numerator, [3] the CE denominator / world (what the backward divides by), [4 + s] d loss / d p_c
+ * for a pixel with t == c of segment s, [4 + S + s] for a valid pixel with t != c.  `world` >= 1 is the number of data-parallel ranks
+ * whose sums were added into `sums` before the call (1: none).  Per image only the CE denominator is exchanged, and
+ * loss = T + lambda * numerator / (denominator / world): the mean of the ranks' losses is the global batch's.  In the batch form the
+ * whole block is exchanged, every rank's loss is the global one and its coefficients are multiplied by world, so that the mean of the
+ * ranks' gradients is the gradient of the one evaluation over the concatenated batch.
+ * rs_tversky_bwd: one pass, dlogits_c = grad_out[0] * ( p_c (g_c - sum_j p_j g_j) + lambda * w[t] (p_c - 1[c == t]) / stats[3] ), g_c
+ * the coefficient of the pixel's segment of class c; grad_out NULL = 1; per_image, lambda and ignore as given to the forward.
+ * Every reduction is fp64 in a fixed order, without float atomics: the same input gives the same bits in every run, with `ignore`
+ * = -1 and with an ignore label that no pixel carries alike.  No host synchronisation: every call can be captured into a graph.
+ * RS_EINVAL: a null pointer other than weight and grad_out, C outside 2..8, a non-positive size, N > 65535, N*C*H*W >= 2^31, an ignore
+ * label that is neither -1 nor in C..255, a misaligned workspace, world < 1, a parameter out of range or not finite. */
+long rs_tversky_workspace_bytes(int N, int C);
+int rs_tversky_sums(const float* logits, const long long* targets, const float* weight, double* sums, int N, int C, int H, int W,
+                    int per_image, int ignore, void* workspace, rs_stream_t stream);
+int rs_tversky_finalize(const double* sums, float* loss, float* stats, int N, int C, float alpha, float beta, float gamma, float eps,
+                        float lambda, int all_classes, int per_image, int world, rs_stream_t stream);
+int rs_tversky_bwd(const float* logits, const long long* targets, const float* weight, const float* stats, const float* grad_out,
+                   float* dlogits, int N, int C, int H, int W, int per_image, float lambda, int ignore, rs_stream_t stream);
+
 /* Metrics.add over a whole batch (metrics.py:27-41): counts[0..3] += (tn, fn, fp, tp) in the reference's naming. */
 int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C, int H,
                         int W, rs_stream_t stream);

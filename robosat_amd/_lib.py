@@ -88,6 +88,11 @@ SIGNATURES = {
     # (`fraction_bits`: the double's 64 bits in a long; `cap`: a uint32 in a long)
     "rs_hard_pixel_plane": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_long, c_long, c_int, P, P]),
     "rs_hard_pixel_select": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_long, c_long, c_int, P, P]),
+    # the Tversky family with a fused cross-entropy term: the sums, the scalar stage (the data-parallel exchange sits between), backward
+    "rs_tversky_workspace_bytes": (c_long, [c_int, c_int]),
+    "rs_tversky_sums": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    "rs_tversky_finalize": (c_int, [P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int, P]),
+    "rs_tversky_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
     # bf16 path (activations typed by a dtype code / bf16 entry points)
     "rs_conv2d_fwd_bf16": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "rs_conv2d_tile_bf16": (c_int, [POINTER(ConvDesc)]),

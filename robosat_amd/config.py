@@ -4,6 +4,8 @@ Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, l
          [augment] zoom, brightness, contrast, saturation, gamma   (extension, optional: robosat_amd/augment.py)
          [opt] boundary_weight, boundary_sigma   (extension, optional: the boundary weight of CrossEntropy / Focal, ``boundary_options`` below)
          [opt] hard_fraction, hard_below   (extension, optional: hard-pixel mining of CrossEntropy / Focal, ``hard_options`` below)
+         [opt] tversky_alpha, tversky_beta, tversky_gamma, tversky_smooth, tversky_per_image, tversky_classes, tversky_ce
+               (extension, optional: the parameters of ``loss = "Tversky"``, ``tversky_options`` below)
 Dataset: [common] dataset, classes, colors                   [weights] values
          [common] ignore   (extension, optional: the label value of pixels that carry no class, ``ignore_label`` below)
 ``cuda = true`` means "use the MI355X" (the HIP device shows up as torch's ``cuda``); ``cuda = false`` is rejected by
@@ -109,6 +111,52 @@ def hard_options(model):
         raise ValueError("[opt] hard_fraction mines the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
             " and ".join(HARD_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
     return fraction, below
+
+
+TVERSKY_LOSS = "Tversky"
+TVERSKY_KEYS = ("tversky_alpha", "tversky_beta", "tversky_gamma", "tversky_smooth", "tversky_per_image", "tversky_classes", "tversky_ce")
+
+
+def tversky_options(model):
+    """The model config's optional ``[opt] tversky_alpha`` / ``tversky_beta`` (the weights of false positives / false negatives, 0.5
+    each = Dice; >= 0 and not both 0), ``tversky_gamma`` (> 0, 1.0; below 1 = focal Tversky), ``tversky_smooth`` (>= 0, 1.0),
+    ``tversky_per_image`` (true), ``tversky_classes`` ("present" | "all", "present") and ``tversky_ce`` (>= 0, 0.0: the factor of the
+    fused cross-entropy term) of ``[opt] loss = "Tversky"``.  Returns ``None`` for another loss, else the keyword arguments of
+    ``TverskyLoss2d``; raises ``ValueError("[opt] tversky_...")`` on a bad value, and on any of the keys beside another loss."""
+
+    import math
+
+    opt = model["opt"]
+    given = [key for key in TVERSKY_KEYS if key in opt]
+    if opt.get("loss") != TVERSKY_LOSS:
+        if given:
+            raise ValueError("[opt] {} belongs to [opt] loss = {}; [opt] loss = {} does not read it".format(
+                given[0], _fmt(TVERSKY_LOSS), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
+        return None
+
+    def shown(value):
+        return _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)
+
+    def number(key, default, ok, what):
+        value = opt.get(key, default)
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not ok(value):
+            raise ValueError("[opt] {} must be {}, got {}".format(key, what, shown(value)))
+        return float(value)
+
+    alpha = number("tversky_alpha", 0.5, lambda v: v >= 0, "a finite number >= 0")
+    beta = number("tversky_beta", 0.5, lambda v: v >= 0, "a finite number >= 0")
+    if alpha == 0 and beta == 0:
+        raise ValueError("[opt] tversky_alpha and tversky_beta must not both be 0 (the index would ignore every error)")
+    gamma = number("tversky_gamma", 1.0, lambda v: v > 0, "a finite number > 0")
+    smooth = number("tversky_smooth", 1.0, lambda v: v >= 0, "a finite number >= 0")
+    ce = number("tversky_ce", 0.0, lambda v: v >= 0, "a finite number >= 0")
+    per_image = opt.get("tversky_per_image", True)
+    if not isinstance(per_image, bool):
+        raise ValueError("[opt] tversky_per_image must be true or false, got {}".format(shown(per_image)))
+    classes = opt.get("tversky_classes", "present")
+    if classes not in ("present", "all"):
+        raise ValueError("[opt] tversky_classes must be \"present\" or \"all\", got {}".format(shown(classes)))
+    return {"alpha": alpha, "beta": beta, "gamma": gamma, "smooth": smooth, "per_image": per_image, "classes": classes, "ce": ce}
 
 
 def load_config(path):

@@ -1,17 +1,18 @@
 """Losses of the reference (``robosat/losses.py``) on the MI355X: same class names, constructor arguments and
 ``forward(inputs[N,C,H,W] float32, targets[N,H,W] int64) -> 0-dim tensor`` contract (tools/train.py:97-106,185), with
-the arithmetic in ``librobosat_hip.so`` (``rs_nll_loss_*``, ``rs_lovasz_fwd``), and one loss the reference does not have:
-``LovaszSoftmax2d`` (``rs_lovasz_softmax_fwd``).  No CPU path.
+the arithmetic in ``librobosat_hip.so`` (``rs_nll_loss_*``, ``rs_lovasz_fwd``), and two losses the reference does not have:
+``LovaszSoftmax2d`` (``rs_lovasz_softmax_fwd``) and ``TverskyLoss2d`` (``rs_tversky_*``): Dice, the Tversky index and the focal
+Tversky loss, per image or over the batch, with an optional cross-entropy term fused into the same passes.  No CPU path.
 
-Every loss takes ``ignore_index=None``, the ``ignore_index`` of ``nn.CrossEntropyLoss`` for all five: a label value (no class, at
+Every loss takes ``ignore_index=None``, the ``ignore_index`` of ``nn.CrossEntropyLoss`` for all six: a label value (no class, at
 most 255) whose pixels are left out -- the loss is the same definition evaluated on the other pixels only, as if the ignored
 ones had been cut out of every image (``rs_*_ig``, include/robosat_hip.h; DESIGN.md "Ignore label").  ``None`` makes exactly the
 calls made without the argument.
 
 ``CrossEntropyLoss2d`` and ``FocalLoss2d`` also take ``boundary=(w0, sigma)``: the U-Net paper's border weight map on top of the class
 weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``), and ``hard=fraction`` or ``hard=(fraction, below)``: hard-pixel mining, per
-image only the hardest share of the pixels keeps its weight (``rs_hard_pixel_plane``), in training mode only.  ``mIoULoss2d`` and the two
-Lovasz forms take neither."""
+image only the hardest share of the pixels keeps its weight (``rs_hard_pixel_plane``), in training mode only.  ``mIoULoss2d``,
+``TverskyLoss2d`` and the two Lovasz forms take neither."""
 
 import torch
 import torch.nn as nn
@@ -186,6 +187,45 @@ class _MIoUFn(torch.autograd.Function):
         return ops.miou_loss_bwd(x, targets, ctx.weight, stats, grad_out.detach().float().contiguous(), ignore=ctx.ignore), None, None, None, None
 
 
+def _global_batch_tversky(sums, per_image, global_batch):
+    """Data-parallel ranks: the sums of ``TverskyLoss2d`` made the GLOBAL batch's between its two forward stages; returns the world
+    size ``rs_tversky_finalize`` is told.
+
+    Per image the Tversky term is a mean over images, so the mean of the ranks' terms is the global one already and only the
+    cross-entropy denominator (the last of the sums) is exchanged, as in ``_global_batch_normaliser``.  The batch form is a function
+    of the per-class sums over every image of every rank: the whole block is exchanged (SUM, float64, 3 C + 2 numbers, on the device,
+    no host sync), every rank then reports the global loss, and its gradient coefficients are multiplied by the world size so that
+    the reducer's average of the ranks' gradients is the gradient of the one evaluation over the concatenated batch -- exact, unlike
+    the flattened Lovasz-Softmax, which would need one sort over the global batch.  Opt-in like ``_global_batch_normaliser``."""
+
+    import torch.distributed as dist
+
+    world = _dp_world(global_batch)
+    if world > 1:
+        dist.all_reduce(sums[-1:] if per_image else sums)
+    return world
+
+
+class _TverskyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, inputs, targets, weight, params, per_image, classes, global_batch=False, ignore=None):
+        x = inputs.detach().float()
+        alpha, beta, gamma, smooth, ce = params
+        sums = ops.tversky_sums(x, targets, weight, per_image, ignore=ignore)
+        world = _global_batch_tversky(sums, per_image, global_batch)
+        loss, stats = ops.tversky_finalize(sums, x.shape[0], x.shape[1], alpha, beta, gamma, smooth, ce, classes, per_image, world)
+        ctx.save_for_backward(x, targets, stats)
+        ctx.weight, ctx.ce, ctx.per_image, ctx.ignore = weight, ce, per_image, ignore
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, stats = ctx.saved_tensors
+        g = grad_out.detach().float().contiguous()
+        dx = ops.tversky_bwd(x, targets, ctx.weight, stats, g, ctx.ce, ctx.per_image, ignore=ctx.ignore)
+        return dx, None, None, None, None, None, None, None
+
+
 class _LovaszFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, targets, ignore=None):
@@ -314,6 +354,37 @@ class mIoULoss2d(_WeightedLoss):
         if ignore is None:
             return _MIoUFn.apply(inputs, targets, self.weight, self.global_batch)
         return _MIoUFn.apply(inputs, targets, self.weight, self.global_batch, ignore)
+
+
+class TverskyLoss2d(_WeightedLoss):
+    """The Tversky loss family, a region-overlap loss the reference does not have, with an optional fused cross-entropy term
+    (``rs_tversky_sums`` / ``rs_tversky_finalize`` / ``rs_tversky_bwd``; include/robosat_hip.h).
+
+    With p = softmax over the classes and, per segment -- (image, class) with ``per_image``, class over the whole batch without --
+    TP = sum of p_c over the pixels of the class, FP = sum of p_c over the others, FN = (pixels of the class) - TP:
+    ``TI = (TP + smooth) / (TP + alpha FP + beta FN + smooth)``, the segment's loss ``(1 - TI) ** gamma``, averaged over the classes
+    present (``classes="present"``) or over all of them (``"all"``), per image then over the batch or once over the whole batch; plus
+    ``ce`` times the cross-entropy weighted by ``weight`` (which weighs that term only).  ``alpha = beta = 0.5`` is Dice (the default),
+    ``alpha = beta = 1`` the soft Jaccard, ``beta > alpha`` favours recall (Salehi et al. 2017), ``gamma < 1`` is the focal Tversky loss
+    of Abraham & Khan 2019.  With ``global_batch`` the batch-level terms are the data-parallel job's global batch's
+    (``_global_batch_tversky``).  It takes neither ``boundary`` nor ``hard``."""
+
+    def __init__(self, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, per_image=True, classes="present", ce=0.0, weight=None,
+                 ignore_index=None):
+        super().__init__(weight, ignore_index)
+        self.alpha, self.beta, self.gamma, self.smooth, self.ce = ops.tversky_params(alpha, beta, gamma, smooth, ce)
+        if classes not in ("present", "all"):
+            raise ValueError("classes must be \"present\" or \"all\" (got {!r})".format(classes))
+        if not isinstance(per_image, bool):
+            raise ValueError("per_image must be True or False (got {!r})".format(per_image))
+        self.per_image = per_image
+        self.classes = classes
+
+    def forward(self, inputs, targets):
+        inputs, targets = _check(inputs, targets)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        params = (self.alpha, self.beta, self.gamma, self.smooth, self.ce)
+        return _TverskyFn.apply(inputs, targets, self.weight, params, self.per_image, self.classes, self.global_batch, ignore)
 
 
 class LovaszLoss2d(nn.Module):

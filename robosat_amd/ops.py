@@ -1489,6 +1489,73 @@ def miou_loss_bwd(logits, targets, weight, stats, grad_out, ignore=None):
     return dlogits
 
 
+def tversky_params(alpha, beta, gamma, smooth, ce):
+    """``(alpha, beta, gamma, smooth, ce)`` of the Tversky family as floats; raises ``ValueError`` unless all are finite numbers with
+    alpha, beta >= 0 and not both 0, gamma > 0, smooth >= 0, ce >= 0 (what ``rs_tversky_finalize`` takes)."""
+
+    import math
+
+    values = []
+    for name, value in (("alpha", alpha), ("beta", beta), ("gamma", gamma), ("smooth", smooth), ("ce", ce)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value):
+            raise ValueError("tversky: {} must be a finite number, got {!r}".format(name, value))
+        values.append(float(value))
+    alpha, beta, gamma, smooth, ce = values
+    if alpha < 0 or beta < 0 or (alpha == 0 and beta == 0):
+        raise ValueError("tversky: alpha and beta must be >= 0 and not both 0, got {!r} and {!r}".format(alpha, beta))
+    if not gamma > 0:
+        raise ValueError("tversky: gamma must be > 0, got {!r}".format(gamma))
+    if smooth < 0:
+        raise ValueError("tversky: smooth must be >= 0, got {!r}".format(smooth))
+    if ce < 0:
+        raise ValueError("tversky: ce must be >= 0, got {!r}".format(ce))
+    return alpha, beta, gamma, smooth, ce
+
+
+def tversky_sums(logits, targets, weight=None, per_image=True, ignore=None):
+    """``rs_tversky_sums``: the float64 sums of the Tversky family in one pass -- per image ``[N*C*3 + 2]`` = (TP, SP, cnt) of every
+    (image, class), then the cross-entropy numerator and denominator; batch form ``[C*3 + 2]``.  ``weight`` weighs the cross-entropy
+    sums only."""
+
+    n, c, h, w = logits.shape
+    lib = _lib.lib()
+    ignore = _ignore_label(ignore, c)
+    sums = torch.empty(3 * (n if per_image else 1) * c + 2, device=logits.device, dtype=torch.float64)
+    _call("rs_tversky_sums", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+          _dev(sums, "sums", torch.float64), n, c, h, w, 1 if per_image else 0, -1 if ignore is None else ignore,
+          _workspace(lib.rs_tversky_workspace_bytes(n, c), logits.device), _stream())
+    return sums
+
+
+def tversky_finalize(sums, n, c, alpha=0.5, beta=0.5, gamma=1.0, smooth=1.0, ce=0.0, classes="present", per_image=True, world=1):
+    """``rs_tversky_finalize``: (loss, stats) from the sums of ``tversky_sums`` for logits of ``n`` images and ``c`` classes; ``world`` = the
+    number of data-parallel ranks whose sums were added into ``sums`` (include/robosat_hip.h)."""
+
+    if classes not in ("present", "all"):
+        raise ValueError("classes must be \"present\" or \"all\" (got {!r})".format(classes))
+    segments = (n if per_image else 1) * c
+    assert sums.numel() == 3 * segments + 2, "sums does not belong to this shape and form"
+    loss = torch.empty((), device=sums.device, dtype=torch.float32)
+    stats = torch.empty(4 + 2 * segments, device=sums.device, dtype=torch.float32)
+    _call("rs_tversky_finalize", _dev(sums, "sums", torch.float64), _dev(loss, "loss"), _dev(stats, "stats"), n, c,
+          ctypes.c_float(alpha), ctypes.c_float(beta), ctypes.c_float(gamma), ctypes.c_float(smooth), ctypes.c_float(ce),
+          1 if classes == "all" else 0, 1 if per_image else 0, int(world), _stream())
+    return loss, stats
+
+
+def tversky_bwd(logits, targets, weight, stats, grad_out, ce=0.0, per_image=True, ignore=None):
+    """``rs_tversky_bwd``: d loss / d logits from the ``stats`` of ``tversky_finalize``; ``grad_out`` may be ``None`` (= 1)."""
+
+    n, c, h, w = logits.shape
+    ignore = _ignore_label(ignore, c)
+    assert stats.numel() == 4 + 2 * (n if per_image else 1) * c, "stats does not belong to this shape and form"
+    dlogits = torch.empty_like(logits)
+    _call("rs_tversky_bwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"), _dev(stats, "stats"),
+          _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, 1 if per_image else 0, ctypes.c_float(ce),
+          -1 if ignore is None else ignore, _stream())
+    return dlogits
+
+
 def lovasz_fwd(logits, targets, want_grad=True, ignore=None):
     """Returns (loss, d loss / d logits for grad_out = 1 or None)."""
 

@@ -31,6 +31,13 @@ Differences by design:
     Focal -- while training, per image only the hardest share of the valid pixels (and every pixel whose true class has a probability
     below ``hard_below``) counts in the loss (robosat_amd/losses.py).  The criterion then follows the network into train / eval mode,
     and the logged validation loss is the unmined loss.
+  * ``[opt] loss = "Tversky"`` (robosat_amd/losses.py: ``TverskyLoss2d``): the Tversky loss family -- Dice by default, the Tversky index
+    with ``[opt] tversky_alpha`` / ``tversky_beta`` (``beta > alpha`` favours recall), the focal Tversky loss with ``tversky_gamma``,
+    smoothing ``tversky_smooth``, per image or over the whole batch (``tversky_per_image``), over the classes present or all
+    (``tversky_classes``) -- plus ``tversky_ce`` times the cross-entropy, fused into the same passes over the logits
+    (robosat_amd/config.py: ``tversky_options``).  ``[weights] values`` weigh the cross-entropy term where present and are not
+    required.  Under data parallelism the per-image form exchanges the cross-entropy normaliser only; the batch form exchanges
+    its per-class sums (3 C + 2 doubles, one all-reduce) and is exact over the global batch.  The log gains a ``Tversky:`` line.
   * ``[augment]`` (extension table, optional: robosat_amd/augment.py): a random zoom-in crop and brightness / contrast /
     saturation / gamma jitter of the training tiles, made on the device in the kernel that flips, rotates and normalises.  Its key
     ``rotate = A`` (degrees, 0 < A <= 180) also turns every window about its centre by an angle drawn from [-A, A]; where the turned
@@ -55,10 +62,10 @@ from tqdm import tqdm
 from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
-from robosat_amd.config import boundary_options, check_num_classes, hard_options, ignore_label, load_config
+from robosat_amd.config import boundary_options, check_num_classes, hard_options, ignore_label, load_config, tversky_options
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
-from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, mIoULoss2d
+from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, TverskyLoss2d, mIoULoss2d
 from robosat_amd.metrics import Metrics
 from robosat_amd.transforms import (
     CenterCrop, ConvertImageMode, ImageToTensor, JointCompose, JointRandomHorizontalFlip, JointRandomRotation,
@@ -156,6 +163,7 @@ def main(args):
         ignore = ignore_label(dataset)  # (dataset `[common] ignore`, optional: label pixels that are left out of the loss)
         boundary = boundary_options(model)  # (model `[opt] boundary_weight / boundary_sigma`, optional: None without the keys)
         hard = hard_options(model)  # (model `[opt] hard_fraction / hard_below`, optional: None without the keys)
+        tversky = tversky_options(model)  # (model `[opt] tversky_*`: None unless `[opt] loss = "Tversky"`)
     except ValueError as err:
         sys.exit("Error: {}".format(err))  # (before any work starts)
 
@@ -264,6 +272,8 @@ def main(args):
     elif loss_name == "LovaszSoftmax":
         per_image, classes = lovasz_softmax_options(model, world)
         criterion = LovaszSoftmax2d(per_image=per_image, classes=classes, **ignored).to(device)
+    elif loss_name == "Tversky":
+        criterion = TverskyLoss2d(weight=weight, **tversky, **ignored).to(device)
     else:
         sys.exit("Error: Unknown [opt][loss] value !")
     if world > 1 and hasattr(criterion, "global_batch"):
@@ -315,6 +325,10 @@ def main(args):
     if hard is not None:
         say("Hard pixels:\t the hardest {} of every image's valid pixels{} (training only; validation loss unmined)".format(
             hard[0], "" if hard[1] is None else ", and every pixel with p(true class) < {}".format(hard[1])))
+    if tversky is not None:
+        say("Tversky:\t alpha = {}, beta = {}, gamma = {}, smooth = {}, {}, classes {}, + {} x cross-entropy".format(
+            tversky["alpha"], tversky["beta"], tversky["gamma"], tversky["smooth"],
+            "per image" if tversky["per_image"] else "over the batch", tversky["classes"], tversky["ce"]))
     if jitter is not None:
         say("Augmentation:\t {}".format(describe_jitter(jitter)))
     say("---")
