@@ -1171,6 +1171,50 @@ int rs_eval_prob_hist(const uint8_t* prob, const uint8_t* actual, int64_t* hist,
 int rs_eval_centerline(const uint8_t* skel_p, const uint8_t* skel_g, const int32_t* d2_to_g, const int32_t* d2_to_p,
                        const int32_t* nbr, int64_t* counts, int B, int H, int W, int rho, rs_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * The optimiser step of `rs train` (csrc/optim.hip; an extension: the `[opt] weight_decay / schedule / clip_norm / ema` keys,
+ * robosat_amd/optim.py).  torch.optim.AdamW's update -- Adam's with wd = 0 -- with the learning-rate schedule, gradient clipping by
+ * the global norm and an exponential moving average (EMA) of the weights in the one pass that reads and writes every parameter.
+ *
+ * items   a HOST array of n items, read before the call returns: one per parameter tensor with a gradient.  p, g, m, v and the
+ *         optional shadow s (NULL: none) are fp32 device arrays of numel elements in the same memory order, 4-byte aligned (16-byte
+ *         aligned items take 16-byte accesses); decay != 0 applies the weight decay to the item.  The items travel by value in
+ *         launch-argument blocks of at most RS_OPTIM_ITEMS; one workgroup walks RS_OPTIM_CHUNK elements of one item
+ *         (rs_optim_limits exports both).  No device-side table, no allocation, no synchronisation: every call can be captured.
+ * ctl     32 bytes of device memory, 8-byte aligned: int64 step (the number of steps taken) at 0, double sumsq at 8, float coef
+ *         at 16.
+ * table   fp32 [T][4], 16-byte aligned: row t = (a_t, b_t, c_t, d_t) = (lr_t / (1 - beta1^(t+1)), 1 / sqrt(1 - beta2^(t+1)),
+ *         1 - lr_t wd, the EMA decay of step t), made by the host in float64 and rounded once.  Step t uses row min(t, T - 1).
+ *
+ * rs_optim_grad_norm: sumsq = the sum of g^2 over all items in float64 and coef = min(1, clip / (sqrt(sumsq) + 1e-6)) as a float
+ * (torch.nn.utils.clip_grad_norm_ with error_if_nonfinite=False; a NaN norm gives a NaN coef), written to ctl.  Per item range,
+ * never across the padding between items.  One fp64 partial per chunk in `workspace` (rs_optim_workspace_bytes(total chunks),
+ * 8-byte aligned; chunks of an item = ceil(numel / RS_OPTIM_CHUNK)), summed by one block in a fixed order: no float atomics, the
+ * same input gives the same bits.  Only g and numel of an item are read.
+ *
+ * rs_optim_step: with the row of ctl.step and g^ = coef g (use_coef != 0: ctl.coef as rs_optim_grad_norm left it) or g, per element
+ *   m' = beta1 m + (1 - beta1) g^,  v' = beta2 v + (1 - beta2) g^ g^,  u = a_t m' / (sqrt(v') b_t + eps),
+ *   p' = (decay ? c_t p : p) - u,   s' = d_t s + (1 - d_t) p' where s is given.
+ * g is read only.  A one-thread launch behind the element pass then adds 1 to ctl.step.
+ *
+ * RS_EINVAL: a null (other than s) or misaligned pointer, n <= 0, numel <= 0, T <= 0, a beta outside [0, 1), a non-finite or negative
+ * eps or clip. */
+typedef struct rs_optim_item {
+  float* p;
+  const float* g;
+  float* m; /* exp_avg */
+  float* v; /* exp_avg_sq */
+  float* s; /* EMA shadow, or NULL */
+  long numel;
+  int decay;
+  int reserved;
+} rs_optim_item;
+int rs_optim_limits(int* chunk, int* items);
+long rs_optim_workspace_bytes(long total_chunks);
+int rs_optim_grad_norm(const rs_optim_item* items, int n, float clip, void* ctl, void* workspace, rs_stream_t stream);
+int rs_optim_step(const rs_optim_item* items, int n, const float* table, int T, void* ctl, float beta1, float beta2, float eps,
+                  int use_coef, rs_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,61 @@ def tversky_options(model):
     return {"alpha": alpha, "beta": beta, "gamma": gamma, "smooth": smooth, "per_image": per_image, "classes": classes, "ce": ce}
 
 
+OPTIMIZER_KEYS = ("weight_decay", "schedule", "schedule_power", "warmup_steps", "lr_min", "clip_norm", "ema")
+OPTIMIZER_SCHEDULES = ("constant", "poly", "cosine")
+
+
+def optimizer_options(model):
+    """The model config's optional ``[opt] weight_decay`` (>= 0), ``schedule`` ("constant" | "poly" | "cosine") with ``schedule_power``
+    (> 0, 0.9; poly's exponent), ``warmup_steps`` (an integer >= 0, 0) and ``lr_min`` (>= 0 and <= lr, 0), ``clip_norm`` (> 0) and
+    ``ema`` (in (0, 1)): any one of them selects the native optimiser (``robosat_amd.optim.AdamW``).  Returns ``None`` without the
+    keys -- the reference's ``Adam(lr)`` --, else ``{"weight_decay", "schedule" | None, "schedule_power", "warmup_steps", "lr_min",
+    "clip_norm" | None, "ema" | None}``; raises ``ValueError("[opt] ...")`` on a bad value, and on ``schedule_power``, ``warmup_steps``
+    or ``lr_min`` without ``schedule``."""
+
+    import math
+
+    opt = model["opt"]
+    if not any(key in opt for key in OPTIMIZER_KEYS):
+        return None
+
+    def shown(value):
+        return _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)
+
+    def number(key, default, ok, what):
+        value = opt.get(key, default)
+        if value is None:
+            return None
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not ok(value):
+            raise ValueError("[opt] {} must be {}, got {}".format(key, what, shown(value)))
+        return float(value)
+
+    schedule = opt.get("schedule")
+    if schedule is None:
+        for key in ("schedule_power", "warmup_steps", "lr_min"):
+            if key in opt:
+                raise ValueError("[opt] {} needs [opt] schedule (one of {})".format(
+                    key, ", ".join('"{}"'.format(s) for s in OPTIMIZER_SCHEDULES)))
+    elif schedule not in OPTIMIZER_SCHEDULES:
+        raise ValueError("[opt] schedule must be one of {}, got {}".format(
+            ", ".join('"{}"'.format(s) for s in OPTIMIZER_SCHEDULES), shown(schedule)))
+    lr = opt.get("lr")
+    if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not math.isfinite(lr) or not lr > 0:
+        raise ValueError("[opt] lr must be a finite number > 0 for the native optimiser, got {}".format(shown(lr)))
+    warmup = opt.get("warmup_steps", 0)
+    if isinstance(warmup, bool) or not isinstance(warmup, int) or warmup < 0:
+        raise ValueError("[opt] warmup_steps must be an integer >= 0, got {}".format(shown(warmup)))
+    return {
+        "weight_decay": number("weight_decay", 0.0, lambda v: v >= 0, "a finite number >= 0"),
+        "schedule": schedule,
+        "schedule_power": number("schedule_power", 0.9, lambda v: v > 0, "a finite number > 0"),
+        "warmup_steps": warmup,
+        "lr_min": number("lr_min", 0.0, lambda v: 0 <= v <= lr, "a finite number in [0, lr]"),
+        "clip_norm": number("clip_norm", None, lambda v: v > 0, "a finite number > 0"),
+        "ema": number("ema", None, lambda v: 0 < v < 1, "a number in (0, 1)"),
+    }
+
+
 def load_config(path):
     """Parses the TOML file at ``path`` into a dictionary."""
 

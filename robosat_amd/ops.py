@@ -2364,3 +2364,84 @@ def centerline_counts(skel_p, skel_g, rho, nbr=None):
     _call("rs_eval_centerline", p, g, _dev(d2_to_g, "d2_to_g", torch.int32), _dev(d2_to_p, "d2_to_p", torch.int32),
           _dev(nbr, "nbr", torch.int32), _dev(counts, "counts", torch.int64), b, h, w, rho, _stream())
     return counts
+
+
+# ---- the optimiser step of rs train (csrc/optim.hip; definitions in include/robosat_hip.h, the optimizer in robosat_amd/optim.py) ----
+class _OptimItem(ctypes.Structure):  # rs_optim_item (include/robosat_hip.h)
+    _fields_ = [("p", ctypes.c_void_p), ("g", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("s", ctypes.c_void_p),
+                ("numel", ctypes.c_long), ("decay", ctypes.c_int), ("reserved", ctypes.c_int)]
+
+
+OPTIM_CTL_BYTES = 32  # int64 step @ 0, double sumsq @ 8, float coef @ 16
+
+
+def optim_limits():
+    """``(RS_OPTIM_CHUNK, RS_OPTIM_ITEMS)``: the elements one block walks per item chunk, the items one launch carries."""
+
+    chunk, items = ctypes.c_int(0), ctypes.c_int(0)
+    _call("rs_optim_limits", ctypes.byref(chunk), ctypes.byref(items))
+    return chunk.value, items.value
+
+
+def _storage_order(t):
+    """The (size, stride) pairs of ``t`` from the outermost to the innermost dimension in memory, after checking that ``t`` covers
+    its storage range densely: what makes an element-wise pass over raw pointers legal (a KRSC weight and its gradient, a vector)."""
+
+    dims = sorted(((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1), reverse=True)
+    want = 1
+    for st, sz in reversed(dims):
+        if st != want:
+            raise ValueError("robosat_amd: an optimizer tensor must be dense in memory, got shape {} strides {}".format(
+                tuple(t.shape), t.stride()))
+        want *= sz
+    return tuple(dims)
+
+
+def optim_items(entries):
+    """The host array of ``rs_optim_item`` for ``entries`` = ``(p, g, m, v, s | None, decay)`` tensors per parameter: fp32, on one
+    device, dense and in one memory order per entry (a channels-last weight with its KRSC gradient is; nothing is copied).
+    Returns ``(items, total_chunks)``; the array holds raw addresses, so the tensors must outlive its use."""
+
+    chunk, _ = optim_limits()
+    items = (_OptimItem * len(entries))()
+    chunks = 0
+    for i, (p, g, m, v, s, decay) in enumerate(entries):
+        order = _storage_order(p)
+        for name, t in (("p", p), ("g", g), ("m", m), ("v", v), ("s", s)):
+            if t is None and name == "s":
+                continue
+            if not t.is_cuda or t.device != p.device:
+                raise RuntimeError("robosat_amd: optimizer `{}` is on {} -- the step only runs on the MI355X".format(name, t.device))
+            if t.dtype != torch.float32:
+                raise TypeError("robosat_amd: optimizer `{}` must be torch.float32, got {}".format(name, t.dtype))
+            if t.numel() != p.numel() or _storage_order(t) != order:
+                raise ValueError("robosat_amd: optimizer `{}` {} / {} is not laid out like its parameter {} / {}".format(
+                    name, tuple(t.shape), t.stride(), tuple(p.shape), p.stride()))
+        items[i] = _OptimItem(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), None if s is None else s.data_ptr(),
+                              p.numel(), int(bool(decay)), 0)
+        chunks += (p.numel() + chunk - 1) // chunk
+    return items, chunks
+
+
+def optim_workspace_bytes(total_chunks):
+    nbytes = _lib.lib().rs_optim_workspace_bytes(int(total_chunks))
+    if nbytes <= 0:
+        raise ValueError("rs_optim_workspace_bytes: invalid arguments")
+    return nbytes
+
+
+def optim_grad_norm(items, clip, ctl, workspace):
+    """``ctl.sumsq`` = the float64 sum of squares of every item's gradient, ``ctl.coef`` = min(1, clip / (norm + 1e-6)); ``workspace``:
+    uint8, at least ``optim_workspace_bytes(total chunks of the items)``."""
+
+    _call("rs_optim_grad_norm", items, len(items), ctypes.c_float(clip), _dev(ctl, "ctl", torch.uint8),
+          _dev(workspace, "workspace", torch.uint8), _stream())
+
+
+def optim_step(items, table, ctl, beta1, beta2, eps, use_coef):
+    """One AdamW step of every item with row ``ctl.step`` of ``table`` (fp32 [T, 4]); then ``ctl.step`` += 1."""
+
+    if table.dim() != 2 or table.shape[1] != 4:
+        raise ValueError("robosat_amd: the schedule table is [T, 4], got {}".format(tuple(table.shape)))
+    _call("rs_optim_step", items, len(items), _dev(table, "table"), table.shape[0], _dev(ctl, "ctl", torch.uint8),
+          ctypes.c_float(beta1), ctypes.c_float(beta2), ctypes.c_float(eps), int(bool(use_coef)), _stream())

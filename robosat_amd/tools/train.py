@@ -43,6 +43,14 @@ Differences by design:
     ``rotate = A`` (degrees, 0 < A <= 180) also turns every window about its centre by an angle drawn from [-A, A]; where the turned
     window leaves the tile it reads the tile mirrored about its edges, image and label alike.  The log's ``Augmentation:`` line
     (``robosat_amd.augment.describe``) names the key only when it is set.
+  * ``[opt] weight_decay`` / ``schedule`` (+ ``schedule_power`` / ``warmup_steps`` / ``lr_min``) / ``clip_norm`` / ``ema`` (extension keys,
+    optional: robosat_amd/config.py ``optimizer_options``): any one of them replaces torch's fused Adam by the native AdamW step
+    (robosat_amd/optim.py) -- decoupled weight decay on the convolution weights, a constant / poly / cosine learning rate with a linear
+    warm-up over ``epochs x batches`` steps, gradient clipping by the global norm, an exponential moving average of the weights -- in
+    one pass over the parameters.  With ``ema`` the validation runs on the averaged weights (BatchNorm statistics stay the live ones)
+    and every epoch also writes ``checkpoint-N-of-M-ema.pth`` (``{epoch, state_dict}``: what ``rs predict`` / ``rs serve`` load);
+    ``checkpoint-N-of-M.pth`` keeps the raw weights, with the shadow inside ``optimizer`` for ``--resume``.  The log gains an
+    ``Optimizer:`` line and, per epoch, the learning rate of its first and last step.  Without the keys: the reference's ``Adam(lr)``.
 """
 
 import argparse
@@ -62,7 +70,9 @@ from tqdm import tqdm
 from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
-from robosat_amd.config import boundary_options, check_num_classes, hard_options, ignore_label, load_config, tversky_options
+from robosat_amd.config import (
+    boundary_options, check_num_classes, hard_options, ignore_label, load_config, optimizer_options, tversky_options,
+)
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
 from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, TverskyLoss2d, mIoULoss2d
@@ -164,6 +174,7 @@ def main(args):
         boundary = boundary_options(model)  # (model `[opt] boundary_weight / boundary_sigma`, optional: None without the keys)
         hard = hard_options(model)  # (model `[opt] hard_fraction / hard_below`, optional: None without the keys)
         tversky = tversky_options(model)  # (model `[opt] tversky_*`: None unless `[opt] loss = "Tversky"`)
+        native = optimizer_options(model)  # (model `[opt] weight_decay / schedule / clip_norm / ema`, optional: None without the keys)
     except ValueError as err:
         sys.exit("Error: {}".format(err))  # (before any work starts)
 
@@ -240,15 +251,21 @@ def main(args):
     # branch behind the main branch instead of beside it), so it is the option for hosts too slow to issue ~600 launches in
     # 23 ms, not the default.
     use_graph = bool(model.get("model", {}).get("graph", False)) and world == 1
-    optimizer = Adam(net.parameters(), lr=model["opt"]["lr"], fused=device.type == "cuda", capturable=use_graph)
+    # (with any of the `[opt] weight_decay / schedule / clip_norm / ema` keys: the native step, made below once the loaders tell the
+    # number of steps its schedule spans)
+    optimizer = None
+    if native is None:
+        optimizer = Adam(net.parameters(), lr=model["opt"]["lr"], fused=device.type == "cuda", capturable=use_graph)
 
     resume = 0
+    chkpt = None
     if args.checkpoint:
         chkpt = torch.load(args.checkpoint, map_location=device)
         net.load_state_dict(chkpt["state_dict"])
         if args.resume:
-            optimizer.load_state_dict(chkpt["optimizer"])
-            _reassert_optimizer_flags(optimizer, use_graph, device)
+            if optimizer is not None:
+                optimizer.load_state_dict(chkpt["optimizer"])
+                _reassert_optimizer_flags(optimizer, use_graph, device)
             resume = chkpt["epoch"]
     # replicas must start identical (each rank drew its own random decoder): rank 0's parameters and buffers everywhere
     parallel.broadcast_module(net)
@@ -298,6 +315,14 @@ def main(args):
     if resume >= num_epochs:
         sys.exit("Error: Epoch {} set in {} already reached by the checkpoint provided".format(num_epochs, args.model))
 
+    if native is not None:
+        optimizer = native_optimizer(net, model, native, num_epochs * len(train_loader))
+        if args.checkpoint and args.resume:
+            # (the moments, the shadow and the device's step counter -- the schedule goes on where it stopped -- from this optimiser's
+            # checkpoint or a plain Adam's)
+            optimizer.load_state_dict(chkpt["optimizer"])
+    chkpt = None
+
     from robosat_amd.graph import TrainStepGraph
 
     stepper = TrainStepGraph(net, criterion, optimizer, enabled=use_graph)
@@ -331,6 +356,8 @@ def main(args):
             "per image" if tversky["per_image"] else "over the batch", tversky["classes"], tversky["ce"]))
     if jitter is not None:
         say("Augmentation:\t {}".format(describe_jitter(jitter)))
+    if native is not None:
+        say("Optimizer:\t {}".format(optimizer.describe()))
     say("---")
 
     fmt = "{} loss: {:.4f}, mIoU: {:.3f}, {} IoU: {:.3f}, MCC: {:.3f}"
@@ -340,13 +367,26 @@ def main(args):
         say("Epoch: {}/{}".format(epoch + 1, num_epochs))
         train_loader.batch_sampler.set_epoch(epoch)
 
+        first_step = optimizer.steps_taken() if native is not None else 0
         train_hist = train(train_loader, num_classes, device, net, optimizer, criterion, master, stepper=stepper)
         say(fmt.format("Train   ", train_hist["loss"], train_hist["miou"], fg, train_hist["fg_iou"], train_hist["mcc"]))
+        if native is not None:
+            last_step = max(first_step, optimizer.steps_taken() - 1)
+            say("Learning rate:\t {:.6e} -> {:.6e} (steps {} .. {})".format(
+                optimizer.lr_at(first_step), optimizer.lr_at(last_step), first_step + 1, last_step + 1))
         for k, v in train_hist.items():
             history["train " + k].append(v)
 
         parallel.broadcast_bn_buffers(net)  # validate (and save) the model rank 0 holds
-        val_hist = validate(val_loader, num_classes, device, net, criterion, master)
+        ema_state = None
+        if native is not None and optimizer.ema is not None:
+            # validate -- and write as `-ema.pth` -- the averaged weights; the BatchNorm running statistics are the live ones
+            with optimizer.swap_ema(net):
+                val_hist = validate(val_loader, num_classes, device, net, criterion, master)
+                if master:
+                    ema_state = {k: v.detach().clone() for k, v in net.state_dict().items()}
+        else:
+            val_hist = validate(val_loader, num_classes, device, net, criterion, master)
         say(fmt.format("Validate", val_hist["loss"], val_hist["miou"], fg, val_hist["fg_iou"], val_hist["mcc"]))
         for k, v in val_hist.items():
             history["val " + k].append(v)
@@ -360,8 +400,26 @@ def main(args):
             checkpoint = "checkpoint-{:05d}-of-{:05d}.pth".format(epoch + 1, num_epochs)
             states = {"epoch": epoch + 1, "state_dict": net.state_dict(), "optimizer": _portable_optimizer_state(optimizer)}
             torch.save(states, os.path.join(model["common"]["checkpoint"], checkpoint))
+            if ema_state is not None:
+                # the layout `rs predict`, `rs serve` and the reference load (they read `state_dict` alone)
+                torch.save({"epoch": epoch + 1, "state_dict": ema_state},
+                           os.path.join(model["common"]["checkpoint"], checkpoint[:-len(".pth")] + "-ema.pth"))
         if world > 1:
             dist.barrier()
+
+
+def native_optimizer(net, model, options, total_steps):
+    """``robosat_amd.optim.AdamW`` over ``net``'s parameters from ``optimizer_options``' dictionary; the schedule spans ``total_steps``
+    (epochs x batches per epoch).  The shadow starts from the parameters as they are now: loaded and broadcast."""
+
+    from robosat_amd.optim import AdamW
+
+    schedule = None
+    if options["schedule"] is not None:
+        schedule = {"kind": options["schedule"], "total_steps": max(1, total_steps), "power": options["schedule_power"],
+                    "warmup_steps": options["warmup_steps"], "lr_min": options["lr_min"]}
+    return AdamW(net.parameters(), lr=model["opt"]["lr"], weight_decay=options["weight_decay"], clip_norm=options["clip_norm"],
+                 ema=options["ema"], schedule=schedule)
 
 
 def _portable_optimizer_state(optimizer):
