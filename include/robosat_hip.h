@@ -559,6 +559,12 @@ int rs_conv2d_fwd_splitk(const rs_conv_desc* d, int form, const float* src1, con
  * the fp32 path, whose matrix cores (157 TFLOP/s) are the bottleneck of these layers (conv_wino_f32.hip).  `d` describes the
  * layer like rs_conv2d_fwd_phase_dt (ups = 1, 3x3, pad 1, Ho = 2 Hs); the epilogue is the model's: optional ReLU (d->relu).
  * `u` = [4][9][Cout][C1+C2] from rs_pack_wino_phase_weight(phase pack [4][Cout][2][2][Cin] of rs_pack_phase_weight_dt).
+ * rs_conv2d_fwd_phase_wino takes ANY phase pack's four 2x2 parity filter sets (also rs_pack_s2_dgrad_phase_weight_dt's: the 3x3 /
+ * stride-2 data gradient over dy) and runs one parity per work item (the tile form).  rs_conv2d_fwd_upsampled_wino, same arguments,
+ * is for the DecoderBlock alone: `u` MUST come from one 3x3 filter over the upsample (rs_pack_phase_weight_dt), whose parity filters
+ * are sums of the same three taps along each axis -- then the p8 blocks compute all four parities per SOURCE PIXEL from nine of the
+ * 36 filter slabs (the pixel form; knob "wino_pixel", ROBOSAT_WINO_PIXEL=0: the tile form).  Other filters give wrong results there.
+ * The two entry points differ in fp32 summation order; _ok and _name hold for both.
  * rs_conv2d_phase_wino_ok: 0 if this form cannot run `d` (needs >= 4 tiles per image side, channel counts % 16, Cout % 32,
  * 32-bit offsets): use rs_conv2d_fwd_phase_dt; 1 if it can and should; 2 if it can but should not (fewer than 8 tiles per image
  * side: the generic kernel is faster).  The answer depends on the layer's geometry only, never on N: the two forms differ in
@@ -568,6 +574,8 @@ const char* rs_conv2d_phase_wino_name(const rs_conv_desc* d);
 int rs_pack_wino_phase_weight(const float* w_phase, float* u, int Cout, int Cin, rs_stream_t stream);
 int rs_conv2d_fwd_phase_wino(const rs_conv_desc* d, const float* src1, const float* src2, const float* u, float* out,
                              rs_stream_t stream);
+int rs_conv2d_fwd_upsampled_wino(const rs_conv_desc* d, const float* src1, const float* src2, const float* u, float* out,
+                                 rs_stream_t stream);
 /* The DATA gradient of that DecoderBlock (autograd of unet.py:63-73 under tools/train.py:186) in the same Winograd machinery: the
  * 4x4 / stride-2 convolution over dz is four 2x2 correlations over dz's parity planes that accumulate into one source-resolution
  * tile, each of them the forward's parity item on its plane -- 9/16 of rs_conv2d_fwd_dt's multiply-adds on that launch.

@@ -228,6 +228,7 @@ struct RsKnobs {
   int wgrad_ring = 3;          // RS_WGRAD_RING: chunk buffers of the tap-per-block bf16 weight-gradient kernel.  3 = two chunks in flight, counted waits (-0.1 ms on the step at 96 blocks); 2 = the drained two-buffer pipeline; 4 = the race screen's positive control (the round-5 defect kept on purpose, one tile); 5-7 = the bisect's variants (`make EXP=1`)
   int lovasz_xcd = 1;          // RS_LOVASZ_XCD: the Lovasz gradient scatter keeps an image's blocks on one XCD (0: natural order)
   int wino_wide = 1;           // ROBOSAT_WINO_WIDE: the 128 x 64 block of the fp32 Winograd DecoderBlock kernel
+  int wino_pixel = 1;          // ROBOSAT_WINO_PIXEL: the pixel form of the fp32 Winograd DecoderBlock forward (0: the tile form, for the A/B)
   int grow_fused = 0;          // RS_GROW_FUSED: growth steps per launch of rs_features_grow (features.hip), 1 .. 16; 0 = the measured rule (profiles/features_split)
 };
 __attribute__((visibility("hidden"))) RsKnobs& rs_knobs();

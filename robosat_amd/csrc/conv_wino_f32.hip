@@ -32,6 +32,30 @@
 //            chunk are bank-conflict free (scripts/probes/wino_lds.py re-derives and checks it; SQ_LDS_BANK_CONFLICT = 0).
 //   store  = A^T M A on the accumulators (3 adds per output element), ReLU, 16-byte stores straight from registers: a lane
 //            holds 4 consecutive couts of its tile's pixels; no LDS staging, nothing to wait for.
+//
+// Two arrangements of the same arithmetic.  The TILE form above (the data gradient, the p4 blocks, rs_conv2d_fwd_phase_wino -- any
+// phase pack's filters --, and rs_conv2d_fwd_upsampled_wino behind ROBOSAT_WINO_PIXEL=0) makes every parity its own work item: the four items of an m block run on four CUs, each fetches the same
+// source region shifted by one pixel, each carries a (2 * 8 + 1)^2 = 289-pixel halo per 64 rows.  The PIXEL form (PIX = true: the p8
+// forward blocks of rs_conv2d_fwd_upsampled_wino, whose filters are ONE 3x3 filter's) arranges it on source pixels.  In one dimension, taps w0 w1 w2 over the x2-nearest upsample, x[-1] = x[W] = 0:
+//     out[2i] = w0 (x[i-1] - x[i]) + (w0+w1+w2) x[i],     out[2i+1] = (w0+w1+w2) x[i] + w2 (x[i+1] - x[i])
+// so per source pixel the 3x3 patch AROUND it, through the same input transform [d0 - d1, d1, d2 - d1] along each axis, times nine
+// filters gives all four parity outputs of the pixel: the same 2.25 multiplies per output, the same output transform with (u, v) the
+// output PARITY instead of the pixel inside the tile, stored to (2y + u, 2x + v).  The nine filters are already in the pack:
+// position (r, c) is slab [2 (r == 2) + (c == 2)][3r + c] of U [4][9][Cout][Cin] (G g G^T of parity 0 is [w0, w0+w1+w2, ..] along an
+// axis, of parity 1 [.., w0+w1+w2, w2]).
+//   rows   = source pixels; a sub-block is an 8 x 8 patch of pixels with a 10 x 10 halo at origin (8 bby - 1, 8 bbx - 1), a wave's 16
+//            rows one 4 x 4 block of it; items are (m block, cout block), nsub = N ceil(Hs / 8) ceil(Ws / 8); pixels past Hs / Ws of a
+//            ragged patch are masked per pixel in the epilogue.
+//   LDS    = halo lines in x order at pitch 10 (100 rows, padded to 104 per sub-block), the same swizzle, lane l -> pixel (l & 3,
+//            l >> 2): all nine unit-stride patch reads conflict free (scripts/probes/wino_lds.py --search).  Filter rows as above.
+//   DMA    = rows per 16-channel chunk, halo + filters: 128 x 64 block 592 + 576 -> 208 + 576 (-33 %), 128 x 32 592 + 288 -> 208 + 288
+//            (-44 %), 64 x 64 296 + 576 -> 112 + 576 (-21 %: seven 16-row pieces over 104 rows); halo pieces per wave 5 -> 2, gather-table rows per thread 2 -> 1, LDS per
+//            block 158 -> 104 KB; a launch reads 9 of the 36 filter slabs, and a source pixel's halo is fetched by one CU, not four.
+//   One descriptor spans the four filter sets (4 * 9 * Cout * Cin * 4 bytes < 2^31: wino_plan); a filter piece's 16 rows lie in one
+//   position, so the position's slab is one scalar offset per piece of the wave, formed once per block.
+// MFMA count and order, accumulators, fragment reads and transform VALU per MFMA are the tile form's; outputs differ from it in fp32
+// summation order (both within 2e-5 of float64: tests/test_gpu_wino_pixel.py, tests/test_wino_pixel_cpu.py).  Measured
+// (profiles/wino_pixel): dec1 711 -> 694, dec2 434 -> 423, dec3 1 481 -> 1 437, dec4 690 -> 661 us per launch, dec0 340 -> 338.
 // Weights: rs_pack_wino_phase_weight turns the phase pack [4][Cout][2][2][Cin] into U = G g G^T, [4][9][Cout][Cin].
 // Which layers: decided on the layer's GEOMETRY alone (>= 8 tiles per image side), never on the batch size -- the two forms
 // differ in fp32 summation order, and a tile's probabilities must not depend on the batch it travels in.
@@ -70,11 +94,12 @@ struct WinoArgs {
   int csplit;
 };
 
-template <int PB>
+template <int PB, bool PIX = false>
 struct WinoGeom {
-  static constexpr int HW = 2 * PB + 1;  // halo width of a PB x PB patch of tiles ("sub-block")
-  static constexpr int PITCH = HW;       // LDS rows per halo line
-  static constexpr int HALF = PB + 1;    // even x first, then odd x
+  // halo width of a sub-block: a PB x PB patch of tiles (2 PB + 1), or, pixel form, an 8 x 8 patch of source pixels (10)
+  static constexpr int HW = PIX ? 10 : 2 * PB + 1;
+  static constexpr int PITCH = HW;     // LDS rows per halo line
+  static constexpr int HALF = PB + 1;  // tile form: even x first, then odd x (the pixel form stores a line in x order)
   // rows per sub-block, padded to a multiple of 8: the swizzle reads row bits 0..2, so every sub-block sees the pattern the
   // conflict-free search was run on
   static constexpr int SBROWS = (HW * PITCH + 7) / 8 * 8;
@@ -87,6 +112,10 @@ __device__ __forceinline__ int wino_lane_tile(int l) {
   if constexpr (PB == 8) return ((l & 1) << 1) | (((l >> 1) & 1) << 2) | ((l >> 2) & 1) | (l & 8);
   return ((l & 1) << 1) | (((l >> 1) & 1) << 3) | ((l >> 2) & 1) | (((l >> 3) & 1) << 2);
 }
+// pixel form: lane (0..15) -> pixel (ly, lx) of the wave's 4 x 4 block.  With halo lines in x order at pitch 10 and the same
+// swizzle, this transposed order makes all nine patch reads conflict free (scripts/probes/wino_lds.py searches and checks it).
+__device__ __forceinline__ int wino_lane_pixel_y(int l) { return l & 3; }
+__device__ __forceinline__ int wino_lane_pixel_x(int l) { return (l >> 2) & 3; }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk_sub(f32x2 a, f32x2 b) {  // a - b on two floats: v_pk_add_f32 with the second operand negated
   f32x2 d;
@@ -110,11 +139,15 @@ __device__ __forceinline__ int wino_swz(int row) { return (row ^ (row >> 1)) & 3
 // same transforms -- except that the four parities ACCUMULATE into one output tile instead of interleaving into four.  So a block
 // owns an output item for four consecutive "units" (one per plane: its own halo table, source offsets and filter set, as for a
 // forward item), keeps the accumulators across them and writes A^T M A once: 9/16 of the generic 4x4 kernel's multiply-adds.
-template <int PB, int TG, int CG, int NM = 2, bool DG = false>
+// PIX: the forward's pixel form -- GEMM rows are SOURCE PIXELS, all four parities of a pixel from one 3x3 patch around it (see the
+// header).  Same pipeline, same transforms and MFMA order; a sub-block is an 8 x 8 patch of pixels, an item has no parity.
+template <int PB, int TG, int CG, int NM = 2, bool DG = false, bool PIX = false>
 __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p) {
-  using G = WinoGeom<PB>;
+  using G = WinoGeom<PB, PIX>;
   constexpr int NW = TG * CG;
   static_assert(NW == 8, "8 waves");
+  static_assert(!PIX || (PB == 8 && !DG), "the pixel form: forward, 64-row sub-blocks");
+  constexpr bool PAR = !DG && !PIX;  // the output parity is part of the item index
   constexpr int BMT = 16 * TG, BN = 16 * NM * CG;
   constexpr int SB = BMT / (PB * PB);
   static_assert(SB * PB * PB == BMT, "whole sub-blocks per block");
@@ -137,7 +170,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   const int per_img = p.BBY * p.BBX;
   const int Cin = p.C1 + p.C2;
   const int nk = Cin / KC;
-  const int ntiles = ((p.nsub + SB - 1) / SB) * p.ncb * (DG ? 1 : 4);  // work items: (m block, cout block[, parity]); DG: output items
+  const int ntiles = ((p.nsub + SB - 1) / SB) * p.ncb * (PAR ? 4 : 1);  // work items: (m block, cout block[, parity]); DG: output items
   const int first = rs_xcd_remap(blockIdx.x, gridDim.x);
   // this block walks items first, first + grid, ...; DG: each output item as four consecutive units (the parity planes of dz)
   const int nitems = (ntiles - first + (int)gridDim.x - 1) / (int)gridDim.x * (DG ? 4 : 1);
@@ -159,13 +192,14 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   };
   const int uni_first = __builtin_amdgcn_readfirstlane(first), uni_grid = __builtin_amdgcn_readfirstlane((int)gridDim.x);
   // forward: item = 4 rest + parity, + gridDim.x per item; DG: rest = the output item, + gridDim.x once its four planes are through
-  const int d_step = DG ? uni_grid : uni_grid >> 2, d_parstep = DG ? 1 : uni_grid & 3;
-  int d_par = DG ? 0 : uni_first & 3;
-  int d_mblk = (DG ? uni_first : uni_first >> 2) / p.ncb, d_nblk = (DG ? uni_first : uni_first >> 2) - d_mblk * p.ncb;
+  // pixel form: item = rest, + gridDim.x per item, no parity and no carry
+  const int d_step = PAR ? uni_grid >> 2 : uni_grid, d_parstep = DG ? 1 : uni_grid & 3;
+  int d_par = PAR ? uni_first & 3 : 0;
+  int d_mblk = (PAR ? uni_first >> 2 : uni_first) / p.ncb, d_nblk = (PAR ? uni_first >> 2 : uni_first) - d_mblk * p.ncb;
   const int dq = d_step / p.ncb, dr = d_step - dq * p.ncb;
   auto decode_next = [&](Item& s) __attribute__((always_inline)) {
-    s.py = d_par >> 1;
-    s.px = d_par & 1;
+    s.py = PIX ? 0 : d_par >> 1;
+    s.px = PIX ? 0 : d_par & 1;
     if (!DG || d_par == 0) {  // (DG: the four units of an output item share everything but the plane)
       s.nblk = d_nblk;
       const int sub0 = s.sub0 = d_mblk * SB;
@@ -178,8 +212,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
       for (int sb = 0; sb < SBS; ++sb) {
         s.live[sb] = sub0 + sb < p.nsub;
         s.n[sb] = n;
-        s.y0[sb] = 2 * bby * PB - 1;
-        s.x0[sb] = 2 * bbx * PB - 1;
+        s.y0[sb] = (PIX ? 8 : 2 * PB) * bby - 1;
+        s.x0[sb] = (PIX ? 8 : 2 * PB) * bbx - 1;
         if (++bbx == p.BBX) {
           bbx = 0;
           if (++bby == p.BBY) {
@@ -189,12 +223,15 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
         }
       }
     }
-    d_par += d_parstep;
-    const int carry = d_par >> 2;
-    d_par &= 3;
+    int carry = 0;
+    if constexpr (!PIX) {
+      d_par += d_parstep;
+      carry = d_par >> 2;
+      d_par &= 3;
+    }
     if (!DG || carry) {
       d_mblk += dq;
-      d_nblk += dr + (DG ? 0 : carry);
+      d_nblk += dr + (PAR ? carry : 0);
       if (d_nblk >= p.ncb) {
         d_nblk -= p.ncb;
         ++d_mblk;
@@ -231,7 +268,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
     const int rho = tid + 64 * NW * e;
     const int sb = rho / G::SBROWS, rem = rho - sb * G::SBROWS;
     const int hy = rem / G::PITCH, xs = rem - hy * G::PITCH;
-    const int hx = xs < G::HALF ? 2 * xs : 2 * (xs - G::HALF) + 1;
+    const int hx = PIX ? xs : xs < G::HALF ? 2 * xs : 2 * (xs - G::HALF) + 1;
     trows[rho] = ((rho < AROWS && hy < G::HW) ? hy << 16 : -(1 << 28)) | (hx << 8) | sb;
   }
   auto build_table = [&](const Item& s, int seq) __attribute__((always_inline)) {  // all threads; visible after the next barrier
@@ -245,7 +282,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
         bool live;
         const int row = trows[rho];
         sub_block(s, row & 255, n, y0, x0, live);
-        const int y = y0 + s.py + (row >> 16), x = x0 + s.px + ((row >> 8) & 255);
+        const int y = y0 + (PIX ? 0 : s.py) + (row >> 16), x = x0 + (PIX ? 0 : s.px) + ((row >> 8) & 255);
         const bool in = live && (unsigned)y < (unsigned)p.Hs && (unsigned)x < (unsigned)p.Ws;
         const int v = DG ? ((n - s.nfirst) * 2 * p.Hs + 2 * y + 1 - s.py) * (2 * p.Ws) + 2 * x + 1 - s.px  // plane (1 - py, 1 - px) of dz, pixel (y, x)
                          : ((n - s.nfirst) * p.Hs + y) * p.Ws + x;
@@ -264,19 +301,28 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   //      goes into the DMA's scalar offset with the item's cout block and the chunk; the parity's filter set is the descriptor's base.
   const int ra = lane >> 2, pp = lane & 3;
   static_assert(128 % BN == 0, "a wave's filter pieces: the same cout, whole positions apart");
-  int doff[JA], doffu;
+  //      Pixel form: one descriptor spans all four filter sets, and position xi = 3 r + c takes its rows from set 2 (r == 2) + (c == 2)
+  //      (G g G^T of parity 0 is [w0, w0 + w1 + w2, ..] along an axis, of parity 1 [.., w0 + w1 + w2, w2]).  A piece's 16 rows lie in
+  //      one position (BN is a multiple of 16), so that is one scalar per piece of the wave, formed once per block.
+  int doff[JA], doffu, upos[JB];
   {
-    const int w = 16 * wave + ra, xi = w / BN, co = w - xi * BN;
+    const int w = 16 * wave + ra, xi = PIX ? 0 : w / BN, co = w - (w / BN) * BN;
     doffu = ((xi * p.Cout + co) * Cin) * 4 + ((pp ^ wino_swz(w)) & 3) * 16;
   }
   const int ustep = (128 / BN) * p.Cout * Cin * 4;
+#pragma unroll
+  for (int j = 0; j < JB; ++j) {
+    const int fi = wave + NW * j, xi = fi < IB ? 16 * fi / BN : 8, r = xi / 3, c = xi - 3 * r;
+    upos[j] = PIX ? __builtin_amdgcn_readfirstlane(((2 * (r == 2) + (c == 2)) * 9 + xi) * p.Cout * Cin * 4) : 0;
+  }
   int f_seq = 0, f_kc = 0, f_g = 0;  // item / chunk / global chunk being fetched
   int f_nb = 0, f_nfirst = 0;        // of item f_seq: byte offset of its cout block's filter rows, first image
-  __amdgpu_buffer_rsrc_t rsrcs = rs_dma_rsrc<kDmaClamp>(p.src1, 0), rsrcu = rsrcs;
+  __amdgpu_buffer_rsrc_t rsrcs = rs_dma_rsrc<kDmaClamp>(p.src1, 0);
+  __amdgpu_buffer_rsrc_t rsrcu = PIX ? rs_dma_rsrc<kDmaClamp>(p.u, (long)36 * p.Cout * Cin * 4) : rsrcs;
   auto fetch_item = [&](const Item& s) __attribute__((always_inline)) {  // f_seq changed: what the new item's pieces need
     f_nfirst = s.nfirst;
     f_nb = s.nblk * BN * Cin * 4;
-    rsrcu = rs_dma_rsrc<kDmaClamp>(p.u + (long)(2 * s.py + s.px) * 9 * p.Cout * Cin, (long)9 * p.Cout * Cin * 4);
+    if constexpr (!PIX) rsrcu = rs_dma_rsrc<kDmaClamp>(p.u + (long)(2 * s.py + s.px) * 9 * p.Cout * Cin, (long)9 * p.Cout * Cin * 4);
   };
   auto set_source = [&](bool src_first) __attribute__((always_inline)) {
     const int cb = (src_first ? p.C1 : p.C2) * 4;
@@ -316,7 +362,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
         if (j < JA - 1 || JA * NW == IA || ii < IA) rs_dma16(rsrcs, fL + ii * 1024, doff[j], fsa);
       } else {
         const int fi = wave + NW * (j - JA);
-        if (j < NI - 1 || JB * NW == IB || fi < IB) rs_dma16(rsrcu, fL + (IA + fi) * 1024, doffu, fsu + (j - JA) * ustep);
+        if (j < NI - 1 || JB * NW == IB || fi < IB) rs_dma16(rsrcu, fL + (IA + fi) * 1024, doffu, fsu + (PIX ? upos[j - JA] : (j - JA) * ustep));
       }
     });
     ++f_g;
@@ -331,14 +377,17 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   const int t = 16 * tg + wino_lane_tile<PB>(l15);
   const int tsb = 16 * tg / (PB * PB), tq = t - tsb * (PB * PB);  // (the wave's 16 tiles lie in one sub-block: wave-uniform)
   const int tty = tq / PB, ttx = tq - tty * PB;
+  // pixel form: the wave's 4 x 4 pixel block (wby, wbx) of the sub-block's 2 x 2
+  const int wby = (tg >> 1) & 1, wbx = tg & 1;
   int addrA[3][3];
   {
-    const int rho0 = tsb * G::SBROWS + 2 * tty * G::PITCH + ttx;
+    const int rho0 = PIX ? tsb * G::SBROWS + (4 * wby + wino_lane_pixel_y(l15)) * G::PITCH + 4 * wbx + wino_lane_pixel_x(l15)
+                         : tsb * G::SBROWS + 2 * tty * G::PITCH + ttx;
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const int rho = rho0 + r * G::PITCH + (c == 0 ? 0 : (c == 1 ? G::HALF : 1));
+        const int rho = rho0 + r * G::PITCH + (PIX ? c : c == 0 ? 0 : (c == 1 ? G::HALF : 1));
         addrA[r][c] = rho * 64 + ((pc ^ wino_swz(rho)) & 3) * 16;
       }
   }
@@ -366,11 +415,19 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
   // positions behind the barrier (0: the unpipelined loop -- barrier, patch reads and transform between two chunks' MFMAs).  The
   // 128 x 64 block needs one: 16 MFMAs cover every wave's nine patch reads.  The NM = 2 forms, 8 MFMAs per position, each keep what
   // measured fastest (profiles/wino_items/ab_steps.txt): none for 128 x 32 (dec4) and the data gradient, one for 64 x 64 (dec0); the p4
-  // blocks were not measured and keep their two.  (RS_WINO_TAIL2: a measurement build's value for all NM = 2 forms.)
-#ifdef RS_WINO_TAIL2
-  constexpr int TAIL = NM >= 4 ? 1 : RS_WINO_TAIL2;
+  // blocks were not measured and keep their two.  The pixel forms, with fewer DMA pieces to spread and two fewer offset registers, all
+  // run fastest without (profiles/wino_pixel/ab_tail.txt: 128 x 64 -1.0 .. -1.6 % against one position, 64 x 64 -0.7 %; 128 x 32 +0.5 %
+  // with one).  (RS_WINO_TAIL2 / RS_WINO_TAIL4: a measurement build's value for all NM = 2 / NM = 4 forms.)
+#if defined(RS_WINO_TAIL2) || defined(RS_WINO_TAIL4)  // (measurement builds: a value for all NM = 2 forms / for the NM = 4 forms)
+#ifndef RS_WINO_TAIL2
+#define RS_WINO_TAIL2 (PIX ? 0 : PB == 4 ? 2 : (DG || TG == 8) ? 0 : 1)
+#endif
+#ifndef RS_WINO_TAIL4
+#define RS_WINO_TAIL4 (PIX ? 0 : 1)
+#endif
+  constexpr int TAIL = NM >= 4 ? RS_WINO_TAIL4 : RS_WINO_TAIL2;
 #else
-  constexpr int TAIL = NM >= 4 ? 1 : PB == 4 ? 2 : (DG || TG == 8) ? 0 : 1;
+  constexpr int TAIL = PIX ? 0 : NM >= 4 ? 1 : PB == 4 ? 2 : (DG || TG == 8) ? 0 : 1;
 #endif
   static_assert(TAIL >= 0 && TAIL <= 2, "positions behind the barrier");
   constexpr int NMMA = 36 * NM, NHEAD = (9 - TAIL) * 4 * NM, NT = TAIL * 4 * NM;
@@ -524,6 +581,27 @@ __global__ __launch_bounds__(512, 1) void conv_wino_f32_kernel(const WinoArgs p)
             }
           }
       }
+    } else if constexpr (PIX) {
+      // the lane's pixel (a, b): rows past Hs / Ws of a ragged patch are masked per pixel; its four parities go to (2 a + u, 2 b + v)
+      const int a = e_y0 + 1 + 4 * wby + wino_lane_pixel_y(e_lane & 15), b = e_x0 + 1 + 4 * wbx + wino_lane_pixel_x(e_lane & 15);
+      if (e_live && a < p.Hs && b < p.Ws) {
+        float* obase = p.out + cur.nblk * BN + 16 * NM * cg + 4 * e_pc + ((long)(e_n * Ho + 2 * a) * Wo + 2 * b) * p.Cout;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+          for (int v = 0; v < 2; ++v) {
+            float* o = obase + ((long)u * Wo + v) * p.Cout;
+#pragma unroll
+            for (int m = 0; m < NM; ++m) {
+              f32x4 y = (acc[u * 3 + v][m] + acc[u * 3 + v + 1][m]) + (acc[(u + 1) * 3 + v][m] + acc[(u + 1) * 3 + v + 1][m]);
+              if (p.relu) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) y[e] = fmaxf(y[e], 0.f);
+              }
+              *reinterpret_cast<f32x4*>(o + 16 * m) = y;
+            }
+          }
+      }
     } else if (e_live) {
       float* obase = p.out + cur.nblk * BN + 16 * NM * cg + 4 * e_pc;
 #pragma unroll
@@ -584,14 +662,31 @@ bool wino_wide() {  // (A/B knob while the wide block is being measured: ROBOSAT
   return rs_knobs().wino_wide != 0;
 }
 
+// The forward's pixel form (ROBOSAT_WINO_PIXEL=0: the tile form everywhere, for the A/B), decided per cout width of the p8 blocks at
+// compile time from what measured faster (profiles/wino_pixel).  The two 64-cout blocks go together: `wide` may depend on the batch
+// size, and the two forms differ in fp32 summation order, so a layer's form must not follow its block shape.
+constexpr bool kWinoPixel64 = true, kWinoPixel32 = true;
+bool wino_pixel(int wgn) { return (wgn == 2 ? kWinoPixel64 : kWinoPixel32) && rs_knobs().wino_pixel != 0; }
+
+// The 128-row block instead of the 64-row one where that still leaves two work items per CU.  Counted in REGIONS of 16 x 16 source
+// pixels (an 8 x 8 patch of tiles = four 8 x 8 pixel sub-blocks), two per wide block; `units` work items per region pair and cout
+// block: 4 on the forward side (the tile form's parities = the pixel form's four sub-blocks of a region), 1 for the data gradient
+// (an output item accumulates its four planes).  One rule for the name queries and the launches.
+bool wino_wide_rule(long regions, int ncb, int units) {
+  return wino_wide() && (regions + 1) / 2 * ncb * units >= 2L * rs_cu_count();
+}
+
 struct WinoPlan {
   int pb, wgn;  // 8 | 4; 2 (64 couts per block) | 1 (32)
   int sb;       // sub-blocks per block
+  bool pix;     // pixel form (p8 forward only)
   bool worth;   // enough work items to fill the chip (else the generic phase kernel is the faster choice)
   bool wide;    // 128 tiles x 64 couts per block instead of 64 x 64 (see wino_plan)
 };
 
-bool wino_plan(const rs_conv_desc* d, WinoPlan* pl) {
+// `upsampled`: the launch's parity filters come from ONE 3x3 filter over the nearest-x2 upsample (rs_conv2d_fwd_upsampled_wino), which
+// is what the pixel form's slab mapping needs; the plan's other answers (ok, names, `wide`) do not depend on it.
+bool wino_plan(const rs_conv_desc* d, WinoPlan* pl, bool fwd = true, bool upsampled = false) {
   if (!d || d->N <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->C1 <= 0 || (d->C1 % 16) || d->C2 < 0 || (d->C2 % 16) || d->Cout <= 0 ||
       (d->Cout % 32))
     return false;
@@ -606,6 +701,9 @@ bool wino_plan(const rs_conv_desc* d, WinoPlan* pl) {
   if ((long)(pl->sb + 1) * d->Hs * d->Ws * cmax * 4 >= (1L << 31)) return false;  // 32-bit byte offsets within a block's images
   if ((long)9 * d->Cout * (d->C1 + d->C2) * 4 >= (1L << 31)) return false;
   if ((long)d->N * d->Ho * d->Wo >= (1L << 31)) return false;
+  // (pixel form: one descriptor spans the four filter sets, and the position's set goes into a 32-bit scalar offset; a layer whose
+  // four sets do not fit keeps the tile form)
+  pl->pix = fwd && upsampled && pl->pb == 8 && wino_pixel(pl->wgn) && (long)4 * 9 * d->Cout * (d->C1 + d->C2) * 4 < (1L << 31);
   // one block per CU and no other block to hide behind: a launch with fewer work items than ~half the CUs (the `center`
   // block at small batches) is faster on the generic phase kernel's 4-blocks-per-CU grid
   // Worth it -- a decision on the layer's GEOMETRY alone, never on the batch size: a tile's probabilities must not depend on
@@ -618,12 +716,8 @@ bool wino_plan(const rs_conv_desc* d, WinoPlan* pl) {
   // (dec0 at bs 16: 128 wide items on 256 CUs would halve the chip).  Either shape accumulates every output in the same order
   // -- they differ in which wave computes what --, so the choice may depend on the batch size without making a tile's
   // output depend on it.
-  pl->wide = false;
-  if (pl->pb == 8 && pl->wgn == 2 && wino_wide()) {
-    const long nsub = (long)d->N * rs_cdiv(ty, 8) * rs_cdiv(tx, 8);
-    pl->wide = (nsub + 1) / 2 * (d->Cout / 64) * 4 >= 2L * rs_cu_count();
-    if (pl->wide) pl->sb = 2;
-  }
+  pl->wide = pl->pb == 8 && pl->wgn == 2 && wino_wide_rule((long)d->N * rs_cdiv(d->Hs, 16) * rs_cdiv(d->Ws, 16), d->Cout / 64, 4);
+  if (pl->wide) pl->sb = 2;
   return true;
 }
 
@@ -649,10 +743,11 @@ extern "C" int rs_pack_wino_phase_weight(const float* w_phase, float* u, int Cou
   return RS_LAUNCH_RESULT();
 }
 
-extern "C" int rs_conv2d_fwd_phase_wino(const rs_conv_desc* d, const float* src1, const float* src2, const float* u, float* out,
-                                        rs_stream_t stream) {
+namespace {
+int wino_fwd_launch(const rs_conv_desc* d, const float* src1, const float* src2, const float* u, float* out, rs_stream_t stream,
+                    bool upsampled) {
   WinoPlan pl;
-  if (!wino_plan(d, &pl) || !src1 || !u || !out || (d->C2 > 0 && !src2)) return RS_EINVAL;
+  if (!wino_plan(d, &pl, true, upsampled) || !src1 || !u || !out || (d->C2 > 0 && !src2)) return RS_EINVAL;
   WinoArgs a;
   a.src1 = src1;
   a.src2 = src2;
@@ -666,25 +761,44 @@ extern "C" int rs_conv2d_fwd_phase_wino(const rs_conv_desc* d, const float* src1
   a.Cout = d->Cout;
   a.TY = (d->Hs + 1) / 2;
   a.TX = (d->Ws + 1) / 2;
-  a.BBY = rs_cdiv(a.TY, pl.pb);
-  a.BBX = rs_cdiv(a.TX, pl.pb);
+  // sub-blocks: PB x PB patches of tiles, each parity an item of its own; pixel form: 8 x 8 patches of source pixels
+  a.BBY = pl.pix ? rs_cdiv(d->Hs, 8) : rs_cdiv(a.TY, pl.pb);
+  a.BBX = pl.pix ? rs_cdiv(d->Ws, 8) : rs_cdiv(a.TX, pl.pb);
+  if ((long)d->N * a.BBY * a.BBX >= (1L << 31)) return RS_EINVAL;
   a.nsub = d->N * a.BBY * a.BBX;
   a.ncb = d->Cout / (32 * pl.wgn);
   a.relu = d->relu;
   a.out2 = nullptr;
   a.mask1 = a.mask2 = nullptr;
   a.csplit = 0;
-  const long items = (long)rs_cdiv(a.nsub, pl.sb) * a.ncb * 4;
+  const long items = (long)rs_cdiv(a.nsub, pl.sb) * a.ncb * (pl.pix ? 1 : 4);
   if (items >= (1L << 31)) return RS_EINVAL;
   // persistent: one block per CU (its LDS stages fill the CU), items dealt round-robin
   const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;
-  if (pl.wide) conv_wino_f32_kernel<8, 8, 1, 4><<<grid, 512, 0, s>>>(a);  // 128 tiles x 64 couts
+  if (pl.pix && pl.wide) conv_wino_f32_kernel<8, 8, 1, 4, false, true><<<grid, 512, 0, s>>>(a);  // 128 pixels x 64 couts
+  else if (pl.pix && pl.wgn == 2) conv_wino_f32_kernel<8, 4, 2, 2, false, true><<<grid, 512, 0, s>>>(a);
+  else if (pl.pix) conv_wino_f32_kernel<8, 8, 1, 2, false, true><<<grid, 512, 0, s>>>(a);
+  else if (pl.wide) conv_wino_f32_kernel<8, 8, 1, 4><<<grid, 512, 0, s>>>(a);  // 128 tiles x 64 couts
   else if (pl.pb == 8 && pl.wgn == 2) conv_wino_f32_kernel<8, 4, 2><<<grid, 512, 0, s>>>(a);
   else if (pl.pb == 8) conv_wino_f32_kernel<8, 8, 1><<<grid, 512, 0, s>>>(a);
   else if (pl.wgn == 2) conv_wino_f32_kernel<4, 4, 2><<<grid, 512, 0, s>>>(a);
   else conv_wino_f32_kernel<4, 8, 1><<<grid, 512, 0, s>>>(a);
   return RS_LAUNCH_RESULT();
+}
+}  // namespace
+
+// Any phase pack's four 2x2 parity filter sets (the DecoderBlock's, or the 3x3 / stride-2 data gradient's over dy): the tile form.
+extern "C" int rs_conv2d_fwd_phase_wino(const rs_conv_desc* d, const float* src1, const float* src2, const float* u, float* out,
+                                        rs_stream_t stream) {
+  return wino_fwd_launch(d, src1, src2, u, out, stream, false);
+}
+
+// The DecoderBlock itself: `u` packed from ONE 3x3 filter over the upsample (rs_pack_phase_weight_dt -> rs_pack_wino_phase_weight), so
+// the p8 blocks may take the pixel form.  Other filters give wrong results here: they go through rs_conv2d_fwd_phase_wino.
+extern "C" int rs_conv2d_fwd_upsampled_wino(const rs_conv_desc* d, const float* src1, const float* src2, const float* u, float* out,
+                                            rs_stream_t stream) {
+  return wino_fwd_launch(d, src1, src2, u, out, stream, true);
 }
 
 // ---- the DecoderBlock's data gradient in the same form (round 6) ---------------------------------------------------------------------
@@ -697,10 +811,13 @@ bool wino_dgrad_plan(const rs_conv_desc* d, rs_conv_desc* g, WinoPlan* pl) {
   g->C1 = d->Cout;
   g->C2 = 0;
   g->Cout = d->C1 + d->C2;
-  if (!wino_plan(g, pl) || !pl->worth) return false;
+  if (!wino_plan(g, pl, false) || !pl->worth) return false;
   // (dz images are four times the plan's: 32-bit byte offsets within a block's images)
   if ((long)(pl->sb + 1) * 4 * d->Hs * d->Ws * g->C1 * 4 >= (1L << 31)) return false;
   if (g->Cout % 64) return false;  // (64-cout blocks only: every DecoderBlock input of the U-Net is a multiple of 64 channels)
+  // (the wide block where that leaves two OUTPUT items per CU: there is no parity factor in the item count here)
+  pl->wide = wino_wide_rule((long)d->N * rs_cdiv(d->Hs, 16) * rs_cdiv(d->Ws, 16), g->Cout / 64, 1);
+  pl->sb = pl->wide ? 2 : 1;
   return true;
 }
 }  // namespace
@@ -753,11 +870,8 @@ extern "C" int rs_conv2d_dgrad_phase_wino(const rs_conv_desc* d, const float* dz
   a.nsub = d->N * a.BBY * a.BBX;
   a.ncb = g.Cout / 64;
   a.relu = 0;
-  // (the wide block where that leaves two OUTPUT items per CU: there is no parity factor in the item count here)
-  bool wide = false;
-  if (wino_wide()) wide = (long)((a.nsub + 1) / 2) * a.ncb >= 2L * rs_cu_count();
-  const int sb = wide ? 2 : 1;
-  const long items = (long)rs_cdiv(a.nsub, sb) * a.ncb;
+  const bool wide = pl.wide;
+  const long items = (long)rs_cdiv(a.nsub, pl.sb) * a.ncb;
   if (items >= (1L << 29)) return RS_EINVAL;
   const int grid = (int)(items < rs_cu_count() ? items : rs_cu_count());
   hipStream_t s = (hipStream_t)stream;

@@ -52,6 +52,7 @@ const Entry kEntries[] = {
     {"wgrad_ring", "RS_WGRAD_RING", &RsKnobs::wgrad_ring, 2, 7},
     {"lovasz_xcd", "RS_LOVASZ_XCD", &RsKnobs::lovasz_xcd, 0, 1},
     {"wino_wide", "ROBOSAT_WINO_WIDE", &RsKnobs::wino_wide, 0, 1},
+    {"wino_pixel", "ROBOSAT_WINO_PIXEL", &RsKnobs::wino_pixel, 0, 1},
     {"grow_fused", "RS_GROW_FUSED", &RsKnobs::grow_fused, 0, 16},
 };
 

@@ -443,9 +443,12 @@ def pack_wino_phase_weight(weight_phase):
     return u
 
 
-def conv2d_phase_wino(src1, u, src2=None, relu=False):
+def conv2d_phase_wino(src1, u, src2=None, relu=False, upsampled=False):
     """DecoderBlock in fp32 as a Winograd F(2x2, 2x2) convolution on the phase form (``rs_conv2d_fwd_phase_wino``): same
-    result as ``conv2d_phase`` up to fp32 summation order, 9/16 of its multiply-adds."""
+    result as ``conv2d_phase`` up to fp32 summation order, 9/16 of its multiply-adds.  ``upsampled``: ``u`` comes from
+    ``pack_phase_weight`` -- a 3x3 filter over the nearest-x2 upsample, whose parity filters are sums of the same three taps per
+    axis --, which lets the kernel compute all four parities per source pixel (``rs_conv2d_fwd_upsampled_wino``, the pixel form);
+    False: four free 2x2 parity filter sets (any phase pack, e.g. ``pack_s2_dgrad_phase_weight``'s), one parity per work item."""
 
     n, hs, ws, c1 = src1.shape
     c2 = 0 if src2 is None else src2.shape[3]
@@ -457,7 +460,8 @@ def conv2d_phase_wino(src1, u, src2=None, relu=False):
     d = _phase_desc(n, hs, ws, c1, c2, cout, relu)
     out = torch.empty((n, 2 * hs, 2 * ws, cout), device=src1.device, dtype=torch.float32)
     ev = _start()
-    _call("rs_conv2d_fwd_phase_wino", ctypes.byref(d), _dev(src1, "src1"), _dev(src2, "src2"), _dev(u, "u"), _dev(out, "out"), _stream())
+    _call("rs_conv2d_fwd_upsampled_wino" if upsampled else "rs_conv2d_fwd_phase_wino", ctypes.byref(d),
+          _dev(src1, "src1"), _dev(src2, "src2"), _dev(u, "u"), _dev(out, "out"), _stream())
     if ev:
         _stop(ev)
         name = _lib.lib().rs_conv2d_phase_wino_name(ctypes.byref(d)).decode()

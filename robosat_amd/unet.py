@@ -267,7 +267,7 @@ def decoder_block(conv, skip, prev, dt):
     multiply-adds; the fp32 matrix cores are what bounds these layers), else the phase form itself (bf16; tiny layers)."""
 
     if dt == torch.float32 and ops.wino_ok(skip, prev, conv.cout):
-        return ops.conv2d_phase_wino(skip, conv.phase_wino(), src2=prev, relu=True)
+        return ops.conv2d_phase_wino(skip, conv.phase_wino(), src2=prev, relu=True, upsampled=True)
     return ops.conv2d_phase(skip, conv.phase(dt), src2=prev, relu=True)
 
 

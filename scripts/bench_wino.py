@@ -29,7 +29,7 @@ for name, c1, c2, cout, hs in layers:
     u = ops.pack_wino_phase_weight(wp)
     flops = 2.0 * a.batch * cout * (c1 + c2) * 9 * (2 * hs) ** 2
     if a.wino_only:
-        fn = lambda: ops.conv2d_phase_wino(x1, u, src2=x2, relu=True)
+        fn = lambda: ops.conv2d_phase_wino(x1, u, src2=x2, relu=True, upsampled=True)
         if not ops.wino_ok(x1, x2, cout, force=True):
             continue
         ops.PROFILE = []
@@ -48,7 +48,7 @@ for name, c1, c2, cout, hs in layers:
         continue
     res = {}
     for kind, fn in (("phase", lambda: ops.conv2d_phase(x1, wp, src2=x2, relu=True)),
-                     ("wino", (lambda: ops.conv2d_phase_wino(x1, u, src2=x2, relu=True)) if ops.wino_ok(x1, x2, cout, force=True) else None)):
+                     ("wino", (lambda: ops.conv2d_phase_wino(x1, u, src2=x2, relu=True, upsampled=True)) if ops.wino_ok(x1, x2, cout, force=True) else None)):
         if fn is None:
             res[kind] = None
             continue
@@ -64,7 +64,7 @@ for name, c1, c2, cout, hs in layers:
         tot[kind] += res[kind]
     if res["wino"] is None:
         tot["wino"] += res["phase"]
-    err = float((ops.conv2d_phase(x1, wp, src2=x2, relu=True) - ops.conv2d_phase_wino(x1, u, src2=x2, relu=True)).abs().max()) if res["wino"] else float("nan")
+    err = float((ops.conv2d_phase(x1, wp, src2=x2, relu=True) - ops.conv2d_phase_wino(x1, u, src2=x2, relu=True, upsampled=True)).abs().max()) if res["wino"] else float("nan")
     print("{:7s} {:5d}+{:<4d}->{:<4d} @{:<4d} phase {:7.3f} ms ({:6.1f} TF exec)  wino {} | max|diff| {:.2e}".format(
         name, c1, c2, cout, hs, res["phase"], flops * 4 / 9 / res["phase"] / 1e9,
         "{:7.3f} ms ({:6.1f} TF exec, x{:.2f})".format(res["wino"], flops / 4 / res["wino"] / 1e9, res["phase"] / res["wino"]) if res["wino"] else "   n/a", err))

@@ -5,7 +5,16 @@ MI355X_MICROARCH.md, LDS section); within a group the 16 addresses must fall int
 bank row.  The kernel's layout -- halo rows even-x-first, pitch 2 PB + 1, sub-blocks padded to a multiple of 8 rows, piece
 c of row r stored at c ^ ((r ^ (r >> 1)) & 3), and the lane -> tile bit permutation -- was found by exhaustive search over
 (pitch, row order, swizzle family, permutation); this script re-derives the addresses exactly as the kernel does and counts
-the worst conflict degree per instantiation (expected: 1 everywhere).   python scripts/probes/wino_lds.py"""
+the worst conflict degree per instantiation (expected: 1 everywhere).   python scripts/probes/wino_lds.py
+
+The PIXEL form of the forward (GEMM rows = source pixels, a wave = a 4 x 4 pixel block of an 8 x 8 sub-block with a 10 x 10 halo,
+nine unit-stride patch reads) has its own layout: halo lines in x order at pitch 10 (100 rows, padded to 104 per sub-block), the SAME
+swizzle, lane l -> pixel (y, x) = (l & 3, l >> 2).  `check_pixel` checks it; `--search` re-runs the search it came from (pitch 10..16 x
+the 24 bit permutations of the lane x shift/XOR/multiply swizzle families).  Pitch 12 with piece c at c ^ ((row >> 2) & 3) and lanes
+in row-major order covers the 16 slots of a 256-byte window for 16 CONSECUTIVE lanes, but the hardware's groups are not consecutive
+lanes: it has conflict degree 2 in this model and is not what the search returns."""
+import itertools
+import sys
 
 G0 = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27], [4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31]]
 GROUPS = G0 + [[l + 32 for l in g] for g in G0]
@@ -68,6 +77,63 @@ def check(pb, tg, cg):
     return worst, 2 * (apad + 9 * bn) * 64 + 2 * apad * 4
 
 
+def pixel_worst(pitch, sbrows, perm, f, nsb=2):
+    """Worst conflict degree of the nine patch reads over the 2 x 2 wave positions of `nsb` sub-blocks: lane bit i goes to bit perm[i]
+    of q = 4 ly + lx, halo row rho = sb * sbrows + (4 by + ly + r) * pitch + 4 bx + lx + c, piece pc at pc ^ f(rho)."""
+    worst = 0
+    for sb in range(nsb):
+        for by in range(2):
+            for bx in range(2):
+                for r in range(3):
+                    for c in range(3):
+                        def addr(lane):
+                            l15, pc = lane & 15, lane >> 4
+                            q = sum(((l15 >> i) & 1) << perm[i] for i in range(4))
+                            ly, lx = q >> 2, q & 3
+                            rho = sb * sbrows + (4 * by + ly + r) * pitch + 4 * bx + lx + c
+                            assert rho - sb * sbrows < 10 * pitch
+                            return rho * 64 + ((pc ^ f(rho)) & 3) * 16
+                        worst = max(worst, degree(addr))
+    return worst
+
+
+PIX_PITCH, PIX_SBROWS, PIX_PERM = 10, 104, (2, 3, 0, 1)  # the kernel's: WinoGeom<8, true>, wino_lane_pixel_y / _x
+
+
+def check_pixel(tg, cg, nm):
+    """conv_wino_f32_kernel<8, tg, cg, nm, false, true>: patch reads as above, filter rows as in the tile form."""
+    bn = 16 * nm * cg
+    sb = 16 * tg // 64
+    apad = (sb * PIX_SBROWS + 15) // 16 * 16
+    worst = pixel_worst(PIX_PITCH, PIX_SBROWS, PIX_PERM, swz, sb)
+    for wcg in range(cg):
+        for x in range(9):
+            for m in range(nm):
+                def addrb(lane):
+                    l15, pc = lane & 15, lane >> 4
+                    row = x * bn + 16 * nm * wcg + 16 * m + l15
+                    assert swz(row) == swz(l15)
+                    return apad * 64 + row * 64 + ((pc ^ swz(row)) & 3) * 16
+                worst = max(worst, degree(addrb))
+    return worst, 2 * (apad + 9 * bn) * 64 + 2 * apad * 4
+
+
+def search_pixel():
+    fams = {"(r ^ r >> 1) & 3 [the tile form's]": swz}
+    for a in range(7):
+        fams["(r >> %d) & 3" % a] = (lambda a: lambda r: (r >> a) & 3)(a)
+        for b in range(a + 1, 7):
+            fams["(r >> %d ^ r >> %d) & 3" % (a, b)] = (lambda a, b: lambda r: ((r >> a) ^ (r >> b)) & 3)(a, b)
+        for k in (2, 3):
+            fams["((r >> %d) * %d) & 3" % (a, k)] = (lambda a, k: lambda r: ((r >> a) * k) & 3)(a, k)
+    for pitch in range(10, 17):
+        sbrows = (10 * pitch + 7) // 8 * 8
+        for perm in itertools.permutations(range(4)):
+            for name, f in fams.items():
+                if pixel_worst(pitch, sbrows, perm, f) == 1:
+                    print("pitch {} ({} rows per sub-block), lane bits -> (ly, lx) bits {}, swizzle {}".format(pitch, sbrows, perm, name))
+
+
 def check33(tg, cg):
     """conv_wino33_f32.hip: 8x8 patches of tiles, halo 18 x 18 at pitch 18, 4x4 patch reads, 16 filter positions."""
     pb, hw, half, pitch = 8, 18, 9, 18
@@ -108,6 +174,15 @@ def check33(tg, cg):
 
 
 if __name__ == "__main__":
+    if "--search" in sys.argv:
+        search_pixel()
+        sys.exit(0)
+    w = pixel_worst(12, 120, (0, 1, 2, 3), lambda r: (r >> 2) & 3)
+    print("pixel form, pitch 12, c ^ ((row >> 2) & 3), row-major lanes: worst conflict degree {}".format(w))
+    for cfg in ((8, 1, 4), (4, 2, 2), (8, 1, 2)):
+        w, lds = check_pixel(*cfg)
+        print("pixel form TG {} CG {} NM {}: worst conflict degree {}, LDS bytes {}".format(*cfg, w, lds))
+        assert w == 1
     for cfg in ((4, 2), (8, 1)):
         w, lds = check33(*cfg)
         print("3x3  TG {} CG {}: worst conflict degree {}, LDS bytes {}".format(*cfg, w, lds))

@@ -38,7 +38,7 @@ for name, c1, c2, cout, hs in LAYERS:
     a = torch.randn(16, hs, hs, c1, device=DEV, generator=g)
     b = torch.randn(16, hs, hs, c2, device=DEV, generator=g) if c2 else None
     u = ops.pack_wino_phase_weight(ops.pack_phase_weight(torch.randn(cout, 3, 3, c1 + c2, device=DEV, generator=g) * 0.02))
-    out.append((name,) + timed(lambda: ops.conv2d_phase_wino(a, u, src2=b, relu=True)))
+    out.append((name,) + timed(lambda: ops.conv2d_phase_wino(a, u, src2=b, relu=True, upsampled=True)))
     del a, b, u
 fwd = sum(o[1] for o in out)
 ndg = 0
