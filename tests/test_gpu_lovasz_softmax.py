@@ -5,6 +5,7 @@ keys, same tie order), and against 1 - mean IoU at hard predictions, which needs
 import pytest
 import torch
 
+import lovasz_hinge_ref
 import lovasz_softmax_ref as ref
 from robosat_amd import ops
 from robosat_amd.losses import LovaszSoftmax2d
@@ -57,6 +58,27 @@ def test_exact_permutation_at_real_sizes(shape, per_image):
     want = ref.lovasz_softmax(p, y, per_image=per_image, classes="present", fp32_errors=True)
     want.backward()
     assert abs(got - float(want)) <= 1e-6 * abs(float(want)), (got, float(want))
+    want_dx = ref.softmax_backward(probs.double(), p.grad)
+    scale = float(want_dx.abs().max())
+    assert float((grad.double() - want_dx).abs().max()) <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("shape", [(2, 3, 7, 9), (3, 2, 2, 257), (2, 2, 17, 241), (16, 2, 65, 64)], ids=lambda s: "x".join(map(str, s)))
+@pytest.mark.parametrize("per_image", [True, False])
+@pytest.mark.parametrize("name", ["quant", "two"])
+def test_exact_permutation_at_ties_and_tile_edges(name, shape, per_image):
+    """The same comparison under the same bars where the shared sort can go wrong: logits on a grid (``quant``) or in {-3, 3}
+    (``two``, a handful of keys per segment, so the result hangs on the sort's stability), HW % 4 != 0, a second sort tile of
+    2 keys (flattened, at 2x2x17x241), the XCD-affine orders."""
+
+    x, y = lovasz_hinge_ref.family(name, shape, seed=sum(shape))
+    got, grad, probs = _run(x, y, per_image, "present", want_probs=True)
+    assert torch.allclose(probs, torch.softmax(x.double(), 1).float(), rtol=1e-5, atol=1e-7)
+    p = probs.double().requires_grad_(True)
+    want = ref.lovasz_softmax(p, y, per_image=per_image, classes="present", fp32_errors=True)
+    want.backward()
+    want = want.item()
+    assert abs(got - want) <= 1e-6 * abs(want), (got, want)
     want_dx = ref.softmax_backward(probs.double(), p.grad)
     scale = float(want_dx.abs().max())
     assert float((grad.double() - want_dx).abs().max()) <= 1e-5 * scale
