@@ -282,8 +282,8 @@ int rs_lovasz_softmax_fwd_ig(const float* logits, const long long* targets, floa
  *   - There are no float atomics.  The same input gives the same bits in every run.
  *   - There is no host synchronisation.  Every call can be captured into a graph.
  *
- * The paper's second term (d1 + d2 to the two nearest OBJECTS, which opens gaps between touching cells) needs a feature transform
- * (the identity of the nearest object, not only its distance) and is not built.
+ * The paper's second term (d1 + d2 to the two nearest OBJECTS, which opens gaps between touching cells) is the SEPARATION WEIGHT
+ * further down (rs_separation_weight_plane), which adds onto this plane.
  *
  * rs_boundary_weight_plane: targets, table [R*R] (device), R, ignore (-1 for none) -> plane m.  Four launches: the uint8 complement
  * of the boundary set (0 = boundary pixel, 1 = any other valid pixel, 2 = ignored; non-zero = set) from the int64 labels, the two
@@ -304,6 +304,46 @@ int rs_nll_loss_fwd_pw(const float* logits, const long long* targets, const floa
 int rs_nll_loss_bwd_pw(const float* logits, const long long* targets, const float* weight, const float* stats,
                        const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
                        rs_stream_t stream, const float* pixel_weight, int ignore);
+
+/* SEPARATION WEIGHT for CrossEntropy / Focal (`rs train`: `[opt] separation_weight`, `separation_sigma`): the second term of the U-Net
+ * paper's weight map (Ronneberger et al. 2015, eq. 2), ws*exp(-(d1 + d2)^2 / (2*sigma^2)) with d1 and d2 the distances to the nearest
+ * and the second-nearest OBJECT.  It is large only in a narrow background corridor between two different objects.  DESIGN.md section 7i.
+ *
+ * Per image n of the int64 label raster [N][H][W] with C classes and an optional ignore label:
+ * - A pixel is *valid* if its label is not the ignore label (tested first).  An *object pixel* is a valid pixel whose label is one of
+ *   1 .. C-1; class 0 is the background.  Any other valid pixel counts as background.
+ * - The *objects* are the 4-connected components of the object pixels inside the image (rs_features_label on the object mask).
+ *   - Two touching objects of different classes are one object: there is no gap between them to keep open.
+ *   - An ignored pixel belongs to no object and is no background.  Distances pass over it.
+ *   - Nothing lies beyond the image's edge.  Images never see each other.
+ * - For a valid background pixel p and an object k: delta_k(p) = min over the pixels q of k of |p - q|^2, an integer >= 1.
+ *   - a <= b are the two smallest of the per-object values (a == b where two objects tie for nearest).
+ *   - With fewer than two objects in the image the term is 0.
+ * - s2 = a + b + isqrt(4*a*b), isqrt the exact integer floor square root: s2 = floor((sqrt a + sqrt b)^2), the paper's (d1 + d2)^2
+ *   rounded down to an integer, so the exponent is off by less than 1 / (2*sigma^2).
+ * - Reach D = ceil(3*sigma), 1 <= D <= 32.  term(p) = table[s2] if s2 < D^2, else 0; 0 at every pixel that is no valid background.
+ *   - The host makes the table in float64 and rounds it once: table[k] = float32(ws*exp(-k / (2*sigma^2))), k = 0 .. D^2-1.
+ *   - s2 > b, so only objects with delta < D^2 matter: nothing further than D-1 pixels in x or y is looked at.
+ * - plane[p] = base[p] + term(p), one fp32 addition; without `base`, base is exactly 1.0f at a valid pixel and 0.0f at an ignored one.
+ *   Where the term is 0 the plane is the base to the bit (the base is copied, nothing is added).
+ *
+ * rs_separation_weight_plane: one memset and six launches on `stream`: the class bytes (0 background, 1 object, 2 ignored) and the
+ * object mask; the three launches of rs_features_label (called as it is; labels = root pixel index + 1, so they depend on no
+ * scheduling); a row pass that gives every pixel the two nearest DISTINCT labels of its row within |dx| < D, each with its |dx| (left
+ * before right at equal |dx|; a candidate is (label << 5) | |dx| in one int32, 0 = none); a column pass that merges both candidates
+ * of every row |dy| < D into a running best two by distinct label (value dy^2 + dx^2), walking outward until dy^2 >= the second best,
+ * then makes s2, looks the table up, adds the base and writes the plane -- exactly once per pixel, by one thread.  Two candidates per row
+ * suffice: an object that is third or later in a row stands behind two distinct objects that are at most as far through that row.
+ * No atomics of its own, integer arithmetic up to the lookup: the same input gives the same bits in every run.  No allocation and no
+ * host synchronisation: the call can be captured into a graph.
+ * `workspace`: rs_separation_weight_plane_workspace_bytes(N, H, W) = 16 + 14 bytes per pixel, 16-byte aligned.  Its first int32 is the
+ * labelling's `err` word (rs_features_label), zeroed on the stream in every call and left there for the caller to read if it wants to.
+ * `base` may be null.
+ * RS_EINVAL: a null pointer that may not be null, a misaligned workspace, D outside 1..32, C outside 1..256, an ignore label that is
+ * neither -1 nor in 1..255, the sizes rs_features_label refuses (N > 65535, H or W > 4096, N*H*W >= 2^29, a non-positive size). */
+long rs_separation_weight_plane_workspace_bytes(int N, int H, int W);
+int rs_separation_weight_plane(const long long* targets, const float* table, const float* base, float* plane, int N, int C, int H, int W,
+                               int D, int ignore, void* workspace, rs_stream_t stream);
 
 /* HARD-PIXEL MINING for CrossEntropy / Focal (`rs train`: `[opt] hard_fraction`, `hard_below`): online hard example mining, also
  * called bootstrapped cross-entropy or top-k pixel loss.  Per image, only the hardest share of the pixels keeps its weight; the others

@@ -83,6 +83,9 @@ SIGNATURES = {
     "rs_boundary_weight_plane": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rs_nll_loss_fwd_pw": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, c_int]),
     "rs_nll_loss_bwd_pw": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, c_int]),
+    # the separation weight of CrossEntropy / Focal: the paper's second term added onto a base plane (null: 1 valid / 0 ignored)
+    "rs_separation_weight_plane_workspace_bytes": (c_long, [c_int, c_int, c_int]),
+    "rs_separation_weight_plane": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     # hard-pixel mining of CrossEntropy / Focal: the weight plane from the logits, and its selection stages on a given key plane
     "rs_hard_pixel_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     # (`fraction_bits`: the double's 64 bits in a long; `cap`: a uint32 in a long)

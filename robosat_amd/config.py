@@ -3,6 +3,7 @@
 Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, loss
          [augment] zoom, brightness, contrast, saturation, gamma   (extension, optional: robosat_amd/augment.py)
          [opt] boundary_weight, boundary_sigma   (extension, optional: the boundary weight of CrossEntropy / Focal, ``boundary_options`` below)
+         [opt] separation_weight, separation_sigma   (extension, optional: the separation weight of CrossEntropy / Focal, ``separation_options`` below)
          [opt] hard_fraction, hard_below   (extension, optional: hard-pixel mining of CrossEntropy / Focal, ``hard_options`` below)
          [opt] tversky_alpha, tversky_beta, tversky_gamma, tversky_smooth, tversky_per_image, tversky_classes, tversky_ce
                (extension, optional: the parameters of ``loss = "Tversky"``, ``tversky_options`` below)
@@ -78,6 +79,46 @@ def boundary_options(model):
         raise ValueError("[opt] boundary_weight weighs the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
             " and ".join(BOUNDARY_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
     return values["boundary_weight"], values["boundary_sigma"]
+
+
+SEPARATION_LOSSES = ("CrossEntropy", "Focal")
+SEPARATION_DEFAULT_SIGMA = 5.0  # (the U-Net paper's)
+SEPARATION_MAX_REACH = 32  # (the reach rs_separation_weight_plane takes: include/robosat_hip.h)
+
+
+def separation_options(model, dataset=None):
+    """The model config's optional ``[opt] separation_weight`` (ws) and ``[opt] separation_sigma`` (pixels, 5.0 when only the weight is
+    given): the separation weight ``ws exp(-(d1 + d2)^2 / (2 sigma^2))`` that CrossEntropy and Focal add at a background pixel, d1 and
+    d2 its distances to the two nearest objects.  Returns ``None`` without the keys, else ``(ws, sigma)``; raises
+    ``ValueError("[opt] separation_...")`` on a value that is no finite number > 0, on ``ceil(3 sigma) > 32``, on a sigma without a
+    weight, on a loss that has no per-pixel weight and, where the ``dataset`` config is given, on a dataset with a single class (there
+    is no object class: class 0 is the background)."""
+
+    import math
+
+    opt = model["opt"]
+    if "separation_weight" not in opt:
+        if "separation_sigma" in opt:
+            raise ValueError("[opt] separation_sigma needs [opt] separation_weight (the weight ws in a gap of zero width)")
+        return None
+    values = {}
+    for key, default in (("separation_weight", None), ("separation_sigma", SEPARATION_DEFAULT_SIGMA)):
+        value = opt.get(key, default)
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not value > 0:
+            raise ValueError("[opt] {} must be a finite number > 0, got {}".format(
+                key, _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)))
+        values[key] = float(value)
+    reach = int(math.ceil(3.0 * values["separation_sigma"]))
+    if reach > SEPARATION_MAX_REACH:
+        raise ValueError("[opt] separation_sigma = {} reaches ceil(3 sigma) = {} pixels; at most {}".format(
+            _fmt(values["separation_sigma"]), reach, SEPARATION_MAX_REACH))
+    if opt.get("loss") not in SEPARATION_LOSSES:
+        raise ValueError("[opt] separation_weight weighs the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
+            " and ".join(SEPARATION_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
+    if dataset is not None and len(dataset["common"]["classes"]) < 2:
+        raise ValueError("[opt] separation_weight needs an object class: class 0 is the background and the dataset config lists {} "
+                         "class".format(len(dataset["common"]["classes"])))
+    return values["separation_weight"], values["separation_sigma"]
 
 
 HARD_LOSSES = ("CrossEntropy", "Focal")

@@ -12,7 +12,8 @@ calls made without the argument.
 ``CrossEntropyLoss2d`` and ``FocalLoss2d`` also take ``boundary=(w0, sigma)``: the U-Net paper's border weight map on top of the class
 weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``), and ``hard=fraction`` or ``hard=(fraction, below)``: hard-pixel mining, per
 image only the hardest share of the pixels keeps its weight (``rs_hard_pixel_plane``), in training mode only.  ``mIoULoss2d``,
-``TverskyLoss2d`` and the two Lovasz forms take neither."""
+``TverskyLoss2d`` and the two Lovasz forms take neither.  ``separation=(ws, sigma)`` adds the paper's second term, the weight of the
+narrow background gap between two objects (``rs_separation_weight_plane``), for the same two criteria."""
 
 import torch
 import torch.nn as nn
@@ -171,6 +172,34 @@ class _NLLHardFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None, None
 
 
+class _NLLSeparationFn(torch.autograd.Function):
+    """``_NLLFn`` with the separation weight (``ops.separation_weight_plane``): the boundary weight plane (if any) is made first, the
+    separation term is added onto it, and the hard-pixel mining (if any) takes the sum as its base.  The plane is made from ``targets``
+    per image, so the exchange of ``stats[1]`` is the same one; the criteria without ``separation`` never come here."""
+
+    @staticmethod
+    def forward(ctx, inputs, targets, weight, mode, gamma, global_batch, ignore, boundary, separation, hard):
+        x = inputs.detach().float()
+        base = None
+        if boundary is not None:
+            base = ops.boundary_weight_plane(targets, boundary[0], boundary[1], ignore=ignore, classes=x.shape[1])
+        plane = ops.separation_weight_plane(targets, separation[0], separation[1], ignore=ignore, classes=x.shape[1], base=base)
+        if hard is not None:
+            plane, _ = ops.hard_pixel_plane(x, targets, hard[0], below=hard[1], ignore=ignore, base=plane)
+        loss, stats = ops.nll_loss_fwd(x, targets, weight, mode, gamma, ignore=ignore, pixel_weight=plane)
+        loss = _global_batch_normaliser(loss, stats, global_batch)
+        ctx.save_for_backward(x, targets, stats, plane)
+        ctx.weight, ctx.mode, ctx.gamma, ctx.ignore = weight, mode, gamma, ignore
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, stats, plane = ctx.saved_tensors
+        g = grad_out.detach().float().contiguous()
+        dx = ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma, ignore=ctx.ignore, pixel_weight=plane)
+        return dx, None, None, None, None, None, None, None, None, None
+
+
 class _MIoUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, targets, weight, global_batch=False, ignore=None):
@@ -278,6 +307,19 @@ def _check_boundary(boundary):
     return (float(w0), float(sigma))
 
 
+def _check_separation(separation):
+    """``separation`` = ``(ws, sigma)`` of the separation weight (``None`` passes): both finite and > 0, ``ceil(3 sigma) <= 32``."""
+
+    if separation is None:
+        return None
+    try:
+        ws, sigma = separation
+    except (TypeError, ValueError):
+        raise ValueError("separation must be None or a pair (ws, sigma), got {!r}".format(separation))
+    ops.separation_reach(ws, sigma)
+    return (float(ws), float(sigma))
+
+
 def _check_hard(hard):
     """``hard`` = ``fraction`` or ``(fraction, below)`` of the hard-pixel mining (``None`` passes) as ``(fraction, below | None)``: a
     finite fraction in (0, 1], a probability bound in (0, 1)."""
@@ -298,11 +340,14 @@ def _check_hard(hard):
 
 
 def _nll(self, inputs, targets, mode, gamma):
-    """The call ``CrossEntropyLoss2d`` and ``FocalLoss2d`` make: without ``boundary`` and ``hard`` the calls they have always made; mining
-    is a training device, so in eval mode the criterion makes the calls it makes without ``hard``."""
+    """The call ``CrossEntropyLoss2d`` and ``FocalLoss2d`` make: without ``boundary``, ``separation`` and ``hard`` the calls they have
+    always made; mining is a training device, so in eval mode the criterion makes the calls it makes without ``hard``."""
 
     inputs, targets = _check(inputs, targets)
     ignore = _check_ignore(self.ignore_index, inputs)
+    if self.separation is not None:
+        return _NLLSeparationFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore, self.boundary,
+                                      self.separation, self.hard if self.training else None)
     if self.hard is not None and self.training:
         return _NLLHardFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore, self.boundary, self.hard)
     if self.boundary is not None:
@@ -318,11 +363,16 @@ class CrossEntropyLoss2d(_WeightedLoss):
     ``targets`` on the device in every call (include/robosat_hip.h; DESIGN.md "Boundary weight"); ``None`` makes today's calls.
     ``hard=fraction`` or ``(fraction, below)``: in training mode, per image only the valid pixels whose cross-entropy is among the
     ``ceil(fraction * V)`` largest, or whose true class has a probability below ``below``, keep their weight (include/robosat_hip.h;
-    DESIGN.md "Hard-pixel mining"); with ``boundary`` a kept pixel keeps its boundary weight.  ``None`` makes today's calls."""
+    DESIGN.md "Hard-pixel mining"); with ``boundary`` a kept pixel keeps its boundary weight.  ``None`` makes today's calls.
+    ``separation=(ws, sigma)``: ``ws exp(-(d1 + d2)^2 / (2 sigma^2))`` is added to a background pixel's weight, d1 and d2 its distances
+    to the two nearest objects (the 4-connected components of the pixels of the classes 1 .. C - 1), so that the narrow gap between
+    two neighbouring objects counts (include/robosat_hip.h; DESIGN.md "Separation weight").  It adds onto the boundary plane where
+    that is given too, mining takes the sum as its base, and like ``boundary`` it stays on in eval mode.  ``None`` makes today's calls."""
 
-    def __init__(self, weight=None, ignore_index=None, boundary=None, hard=None):
+    def __init__(self, weight=None, ignore_index=None, boundary=None, hard=None, separation=None):
         super().__init__(weight, ignore_index)
         self.boundary = _check_boundary(boundary)
+        self.separation = _check_separation(separation)
         self.hard = _check_hard(hard)
 
     def forward(self, inputs, targets):
@@ -330,13 +380,14 @@ class CrossEntropyLoss2d(_WeightedLoss):
 
 
 class FocalLoss2d(_WeightedLoss):
-    """Focal loss, gamma = 2 by default (reference losses.py:28-50); ``boundary`` and ``hard`` as in ``CrossEntropyLoss2d`` (the pixels are ranked by
-    their cross-entropy: Focal is monotone in the true class's probability, so that is its ranking too)."""
+    """Focal loss, gamma = 2 by default (reference losses.py:28-50); ``boundary``, ``separation`` and ``hard`` as in ``CrossEntropyLoss2d``
+    (the pixels are ranked by their cross-entropy: Focal is monotone in the true class's probability, so that is its ranking too)."""
 
-    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None, hard=None):
+    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None, hard=None, separation=None):
         super().__init__(weight, ignore_index)
         self.gamma = gamma
         self.boundary = _check_boundary(boundary)
+        self.separation = _check_separation(separation)
         self.hard = _check_hard(hard)
 
     def forward(self, inputs, targets):

@@ -1331,6 +1331,85 @@ def boundary_weight_plane(targets, w0, sigma, ignore=None, classes=None):
     return plane
 
 
+SEPARATION_MAX_REACH = 32
+_SEPARATION_TABLES = {}
+
+
+def separation_reach(ws, sigma):
+    """D = ceil(3 * sigma), the reach in pixels of the separation weight ``ws * exp(-(d1 + d2)^2 / (2 sigma^2))``
+    (include/robosat_hip.h); raises ``ValueError`` unless both are finite numbers > 0 and 1 <= D <= 32."""
+
+    import math
+
+    for name, value in (("ws", ws), ("sigma", sigma)):
+        if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not value > 0:
+            raise ValueError("robosat_amd: the separation weight's {} is a finite number > 0, got {!r}".format(name, value))
+    reach = int(math.ceil(3.0 * float(sigma)))
+    if not 1 <= reach <= SEPARATION_MAX_REACH:
+        raise ValueError("robosat_amd: the separation weight reaches ceil(3 * sigma) = {} pixels, more than {}".format(
+            reach, SEPARATION_MAX_REACH))
+    return reach
+
+
+def separation_table(ws, sigma):
+    """float32 numpy [D * D]: ``table[k] = float32(ws * exp(-k / (2 sigma^2)))``, made in float64 and rounded once."""
+
+    import numpy as np
+
+    reach = separation_reach(ws, sigma)
+    k = np.arange(reach * reach, dtype=np.float64)
+    return (float(ws) * np.exp(-k / (2.0 * float(sigma) * float(sigma)))).astype(np.float32)
+
+
+def _separation_table_on(ws, sigma, device):
+    """The table on ``device``, cached per (ws, sigma, device): made and uploaded once, before any capture that uses it."""
+
+    key = (float(ws), float(sigma), str(device))
+    table = _SEPARATION_TABLES.get(key)
+    if table is None:
+        table = torch.from_numpy(separation_table(ws, sigma)).to(device)
+        _SEPARATION_TABLES[key] = table
+    return table
+
+
+def separation_weight_plane(targets, ws, sigma, ignore=None, classes=None, base=None, check=False):
+    """int64 [N, H, W] labels -> float32 [N, H, W]: ``base`` plus the separation term of ``rs_separation_weight_plane``
+    (include/robosat_hip.h): ``table[s2]`` at a background pixel whose two nearest objects are within reach, s2 = a + b + isqrt(4ab)
+    of their squared distances, nothing elsewhere.  Objects are the 4-connected components of the valid pixels of the classes
+    1 .. ``classes`` - 1 (without ``classes``: of every valid non-zero label).  ``base`` float32 [N, H, W] on the labels' device (the
+    boundary weight plane, say); without it the base is 1 at a valid pixel and 0 at an ignored one.  ``check`` reads the labelling's
+    error word back after the call and raises if it is set: a host synchronisation, so never inside a captured step."""
+
+    n, h, w = targets.shape
+    reach = separation_reach(ws, sigma)
+    if classes is None:
+        ignore, c = _ignore_label(ignore, 1), 256
+    else:
+        c = int(classes)
+        if not 1 <= c <= 256:
+            raise ValueError("robosat_amd: the separation weight takes 1..256 classes, got {!r}".format(classes))
+        ignore = _ignore_label(ignore, c)
+    tgt = _dev(targets, "targets", torch.int64)  # (a CPU tensor raises before anything is loaded or sized)
+    if base is not None:
+        if not isinstance(base, torch.Tensor) or tuple(base.shape) != (n, h, w) or base.dtype != torch.float32 or base.device != targets.device:
+            raise ValueError("robosat_amd: the separation weight's base is float32 [N, H, W] = {} on {}, got {}".format(
+                (n, h, w), targets.device, "{} {} on {}".format(base.dtype, tuple(base.shape), base.device)
+                if isinstance(base, torch.Tensor) else repr(base)))
+    lib = _lib.lib()
+    nbytes = lib.rs_separation_weight_plane_workspace_bytes(n, h, w)
+    table = _separation_table_on(ws, sigma, targets.device)
+    plane = torch.empty((n, h, w), device=targets.device, dtype=torch.float32)
+    workspace = _workspace(nbytes, targets.device)
+    _call("rs_separation_weight_plane", tgt, _dev(table, "table"), _dev(base, "base"), _dev(plane, "plane"), n, c, h, w, reach,
+          -1 if ignore is None else ignore, workspace, _stream())
+    if check:
+        err = _WORKSPACE[(targets.device, torch.cuda.current_stream().cuda_stream)][:4].view(torch.int32)
+        if int(err.item()):
+            raise RuntimeError("rs_separation_weight_plane: a union-find loop of the labelling ran out of its H*W bound (code {})".format(
+                int(err.item())))
+    return plane
+
+
 HARD_NO_CAP = 0xFFFFFFFF
 
 

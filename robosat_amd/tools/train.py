@@ -27,6 +27,10 @@ Differences by design:
   * ``[opt] boundary_weight`` / ``boundary_sigma`` (extension keys, optional: robosat_amd/config.py): CrossEntropy and Focal weigh
     every pixel by ``1 + w0 exp(-d^2 / (2 sigma^2))``, d its distance to the nearest label boundary, from a plane made on the device
     out of the batch's label raster as it is after the augmentation (robosat_amd/losses.py); training and validation alike.
+  * ``[opt] separation_weight`` / ``separation_sigma`` (extension keys, optional: robosat_amd/config.py): CrossEntropy and Focal add
+    ``ws exp(-(d1 + d2)^2 / (2 sigma^2))`` to the weight of a background pixel, d1 and d2 its distances to the two nearest objects
+    (the paper's second term: the narrow gap between two buildings counts), on top of the boundary weight where that is given too;
+    training and validation alike.  The log gains a ``Separation weight:`` line.
   * ``[opt] hard_fraction`` / ``hard_below`` (extension keys, optional: robosat_amd/config.py): hard-pixel mining of CrossEntropy and
     Focal -- while training, per image only the hardest share of the valid pixels (and every pixel whose true class has a probability
     below ``hard_below``) counts in the loss (robosat_amd/losses.py).  The criterion then follows the network into train / eval mode,
@@ -71,7 +75,8 @@ from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
 from robosat_amd.config import (
-    boundary_options, check_num_classes, hard_options, ignore_label, load_config, optimizer_options, tversky_options,
+    boundary_options, check_num_classes, hard_options, ignore_label, load_config, optimizer_options, separation_options,
+    tversky_options,
 )
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
@@ -173,6 +178,7 @@ def main(args):
         ignore = ignore_label(dataset)  # (dataset `[common] ignore`, optional: label pixels that are left out of the loss)
         boundary = boundary_options(model)  # (model `[opt] boundary_weight / boundary_sigma`, optional: None without the keys)
         hard = hard_options(model)  # (model `[opt] hard_fraction / hard_below`, optional: None without the keys)
+        separation = separation_options(model, dataset)  # (model `[opt] separation_weight / separation_sigma`, optional likewise)
         tversky = tversky_options(model)  # (model `[opt] tversky_*`: None unless `[opt] loss = "Tversky"`)
         native = optimizer_options(model)  # (model `[opt] weight_decay / schedule / clip_norm / ema`, optional: None without the keys)
     except ValueError as err:
@@ -278,6 +284,9 @@ def main(args):
     # (and without `[opt] hard_fraction`; with it the loss is CrossEntropy or Focal: hard_options)
     if hard is not None:
         weighted["hard"] = hard
+    # (and without `[opt] separation_weight`; with it the loss is CrossEntropy or Focal: separation_options)
+    if separation is not None:
+        weighted["separation"] = separation
     if loss_name == "CrossEntropy":
         criterion = CrossEntropyLoss2d(weight=weight, **ignored, **weighted).to(device)
     elif loss_name == "mIoU":
@@ -347,6 +356,9 @@ def main(args):
         say("Ignore label:\t {}".format(ignore))
     if boundary is not None:
         say("Boundary weight:\t w0 = {}, sigma = {} px (reach {} px)".format(boundary[0], boundary[1], int(math.ceil(3.0 * boundary[1]))))
+    if separation is not None:
+        say("Separation weight:\t ws = {}, sigma = {} px (reach {} px)".format(
+            separation[0], separation[1], int(math.ceil(3.0 * separation[1]))))
     if hard is not None:
         say("Hard pixels:\t the hardest {} of every image's valid pixels{} (training only; validation loss unmined)".format(
             hard[0], "" if hard[1] is None else ", and every pixel with p(true class) < {}".format(hard[1])))
