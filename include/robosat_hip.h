@@ -447,6 +447,67 @@ int rs_tversky_finalize(const double* sums, float* loss, float* stats, int N, in
 int rs_tversky_bwd(const float* logits, const long long* targets, const float* weight, const float* stats, const float* grad_out,
                    float* dlogits, int N, int C, int H, int W, int per_image, float lambda, int ignore, rs_stream_t stream);
 
+/* THE clDice TOPOLOGY LOSS (`rs train`: `[opt] cldice`, `cldice_iters`, `cldice_smooth`, `cldice_classes`) of Shit et al., "clDice -- a
+ * Novel Topology-Preserving Loss Function for Tubular Structure Segmentation", CVPR 2021: a Dice-like score between each side's soft
+ * skeleton and the other side's mask, added to a region loss.  DESIGN.md section 7j.
+ *
+ * SOFT SKELETON of fp32 planes X [M][H][W] with values in [0, 1], S = skel(X, iters), 0 <= iters <= 64 (the paper's soft_skel):
+ * - E_0 = X, E_{k+1} = erode(E_k), O_k = dilate(E_{k+1}), D_k = relu(E_k - O_k) for k = 0 .. iters.
+ * - S_0 = D_0, S_k = S_{k-1} + relu(D_k - S_{k-1}*D_k), S = S_iters.
+ * - erode(x) = min(v, h), v the minimum over (N, C, S), h the minimum over (W, C, E); dilate = the maximum over the 3x3 square.
+ *   Nothing lies beyond a plane's edge: a cell outside it is never a candidate of a min or a max.  Planes never see each other.
+ * - The paper's code recomputes the erosion inside every opening; this shared form gives the same bits with iters + 1 erosions.
+ * - Forward arithmetic: every subtraction, product and sum is one separately rounded fp32 operation (no FMA contraction), so the
+ *   forward equals the op-by-op fp32 evaluation bit for bit.
+ * - Backward tie rules (what torch's CPU autograd does with the paper's code):
+ *   - v: the gradient goes to the first cell attaining it in the order N, C, S; h: in the order W, C, E.
+ *   - erode: v < h, all through v; h < v, all through h; v == h, half through each, even when both halves land on the same cell.
+ *   - dilate: to the first maximum in row-major order of the 3x3 window.
+ *   - relu'(0) = 0.
+ * rs_soft_skeleton_fwd: iters + 2 launches; launch j reads E_j and writes E_{j+1} and S_{j-1}, so no launch reads a neighbour that a
+ * block of the same launch writes.  `state` holds rs_soft_skeleton_state_floats(M, H, W, iters, save) floats: with `save` the planes
+ * E_1 .. E_{iters+1} then S_0 .. S_{iters-1} (2*iters + 1 planes of M*H*W floats, what the backward reads besides X itself); without
+ * it five planes that the levels use in turn, and the call leaves nothing to keep.  `skel` receives S.
+ * rs_soft_skeleton_bwd: `grad` = dL/dS -> `dplanes` = dL/dX from X and the saved `state`.  One launch for the pixel-local chain through
+ * the S updates, then iters + 2 launches in gather form: every cell of E_k collects from the at most 9 dilation windows and the at
+ * most 5 erosions that selected it, the selections recomputed from E_k by the tie rules.  `workspace`:
+ * rs_soft_skeleton_bwd_workspace_bytes(M, H, W, iters) = (iters + 3) planes, 4-byte aligned.
+ * No atomics: the same input gives the same bits in every run.  No host synchronisation, no allocation: both can be captured.
+ * RS_EINVAL: a null pointer, a non-positive size, iters outside 0..64, M*H*W >= 2^31, a misaligned workspace.
+ *
+ * THE LOSS.  K = the classes of `class_mask` (bit c set = class c; only classes 1 .. C-1), pairs = N*|K| planes in the order
+ * [n][class ascending].  Per pair: P = softmax(logits)[n][c] in fp32, Y = (target == c) as 0/1; both are 0 at a pixel whose label is
+ * `ignore`, and the gradient under such a pixel is exactly 0.  With S_P = skel(P), S_Y = skel(Y) (no gradient through Y):
+ *   Tprec = (sum S_P*Y + smooth) / (sum S_P + smooth), Tsens = (sum S_Y*P + smooth) / (sum S_Y + smooth),
+ *   term = 1 - 2*Tprec*Tsens / (Tprec + Tsens); loss = the mean of the term over ALL pairs (an absent class is not skipped).
+ * A ratio whose denominator is 0 counts as 0 and has no gradient; Tprec + Tsens = 0 gives the term 1 and no gradient (smooth = 0 only).
+ * The divisor depends on the batch size alone: the mean of data-parallel ranks' losses over equal batches is the global value.
+ * rs_cldice_planes: logits [N][C][H][W] fp32 (2 <= C <= 8), targets int64 -> P and Y [pairs][H][W].
+ * rs_cldice_sums: sums[pair][4] = (sum S_P*Y, sum S_P, sum S_Y*P, sum S_Y) in fp64, at most 64 blocks per plane, their partial sums
+ * added in ascending block order; `workspace`: rs_cldice_workspace_bytes(pairs), 8-byte aligned.
+ * rs_cldice_finalize: one block: loss[0] and coef[pair][3] = (alpha, beta, gamma) with dL/dS_P = alpha*Y + beta per pixel and
+ * dL/dP through Tsens = gamma*S_Y.
+ * rs_cldice_skel_grad: grad = alpha*Y + beta, the `grad` of rs_soft_skeleton_bwd.
+ * rs_cldice_bwd: g_c = dP[c] + gamma_c*S_Y[c] for the classes of the mask, 0 for the others and the background;
+ * dlogits_k = grad_out[0] * p_k * (g_k - sum_c g_c*p_c); grad_out NULL = 1; +0.0f in every class plane under an ignored pixel.
+ * Every reduction is fp64 in a fixed order without float atomics; no host synchronisation.
+ * RS_EINVAL: a null pointer other than grad_out, C outside 2..8, an empty mask or one with bit 0 or a bit >= C, a non-positive size,
+ * N or pairs > 65535, N*C*H*W >= 2^31, an ignore label that is neither -1 nor in C..255, a misaligned workspace, smooth < 0 or not finite. */
+long rs_soft_skeleton_state_floats(int M, int H, int W, int iters, int save);
+int rs_soft_skeleton_fwd(const float* planes, float* skel, float* state, int M, int H, int W, int iters, int save, rs_stream_t stream);
+long rs_soft_skeleton_bwd_workspace_bytes(int M, int H, int W, int iters);
+int rs_soft_skeleton_bwd(const float* planes, const float* state, const float* grad, float* dplanes, int M, int H, int W, int iters,
+                         void* workspace, rs_stream_t stream);
+int rs_cldice_planes(const float* logits, const long long* targets, float* P, float* Y, int N, int C, int H, int W, int class_mask,
+                     int ignore, rs_stream_t stream);
+long rs_cldice_workspace_bytes(int pairs);
+int rs_cldice_sums(const float* P, const float* Y, const float* SP, const float* SY, double* sums, int pairs, int H, int W,
+                   void* workspace, rs_stream_t stream);
+int rs_cldice_finalize(const double* sums, float* loss, float* coef, int pairs, float smooth, rs_stream_t stream);
+int rs_cldice_skel_grad(const float* Y, const float* coef, float* grad, int pairs, int H, int W, rs_stream_t stream);
+int rs_cldice_bwd(const float* logits, const long long* targets, const float* dP, const float* SY, const float* coef,
+                  const float* grad_out, float* dlogits, int N, int C, int H, int W, int class_mask, int ignore, rs_stream_t stream);
+
 /* Metrics.add over a whole batch (metrics.py:27-41): counts[0..3] += (tn, fn, fp, tp) in the reference's naming. */
 int rs_confusion_counts(const float* scores, const long long* targets, unsigned long long* counts, int N, int C, int H,
                         int W, rs_stream_t stream);

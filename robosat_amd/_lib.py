@@ -96,6 +96,17 @@ SIGNATURES = {
     "rs_tversky_sums": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "rs_tversky_finalize": (c_int, [P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_int, c_int, P]),
     "rs_tversky_bwd": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
+    # the clDice topology loss: the soft skeleton of fp32 planes with its backward, and the stages of the loss around it
+    "rs_soft_skeleton_state_floats": (c_long, [c_int, c_int, c_int, c_int, c_int]),
+    "rs_soft_skeleton_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "rs_soft_skeleton_bwd_workspace_bytes": (c_long, [c_int, c_int, c_int, c_int]),
+    "rs_soft_skeleton_bwd": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P, P]),
+    "rs_cldice_planes": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "rs_cldice_workspace_bytes": (c_long, [c_int]),
+    "rs_cldice_sums": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P]),
+    "rs_cldice_finalize": (c_int, [P, P, P, c_int, c_float, P]),
+    "rs_cldice_skel_grad": (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    "rs_cldice_bwd": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     # bf16 path (activations typed by a dtype code / bf16 entry points)
     "rs_conv2d_fwd_bf16": (c_int, [POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "rs_conv2d_tile_bf16": (c_int, [POINTER(ConvDesc)]),

@@ -7,7 +7,9 @@ Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, l
          [opt] hard_fraction, hard_below   (extension, optional: hard-pixel mining of CrossEntropy / Focal, ``hard_options`` below)
          [opt] tversky_alpha, tversky_beta, tversky_gamma, tversky_smooth, tversky_per_image, tversky_classes, tversky_ce
                (extension, optional: the parameters of ``loss = "Tversky"``, ``tversky_options`` below)
-Dataset: [common] dataset, classes, colors                   [weights] values
+         [opt] cldice, cldice_iters, cldice_smooth, cldice_classes
+               (extension, optional: the clDice topology term on top of any ``loss``, ``cldice_options`` below)
+Dataset: [common] dataset, classes, colors                  [weights] values
          [common] ignore   (extension, optional: the label value of pixels that carry no class, ``ignore_label`` below)
 ``cuda = true`` means "use the MI355X" (the HIP device shows up as torch's ``cuda``); ``cuda = false`` is rejected by
 the tools because this implementation has no CPU compute path.
@@ -198,6 +200,59 @@ def tversky_options(model):
     if classes not in ("present", "all"):
         raise ValueError("[opt] tversky_classes must be \"present\" or \"all\", got {}".format(shown(classes)))
     return {"alpha": alpha, "beta": beta, "gamma": gamma, "smooth": smooth, "per_image": per_image, "classes": classes, "ce": ce}
+
+
+CLDICE_KEYS = ("cldice_iters", "cldice_smooth", "cldice_classes")
+CLDICE_DEFAULT_ITERS = 10  # (the paper's code takes 3 for thin vessels; a road is wider)
+CLDICE_MAX_ITERS = 64  # (what rs_soft_skeleton_fwd takes: include/robosat_hip.h)
+
+
+def cldice_options(model, dataset):
+    """The model config's optional ``[opt] cldice`` (a, ``0 < a < 1``: the loss becomes ``(1 - a) x [opt] loss + a x clDice``) with
+    ``cldice_iters`` (an integer in 1..64, 10: the iterations of the soft skeleton, at least half the widest road in pixels -- a
+    structure wider than ``2 x iters`` pixels is not thinned to its centre line), ``cldice_smooth`` (>= 0, 1.0) and ``cldice_classes``
+    (a list of non-background class names of the dataset config, all of them by default).  Returns ``None`` without the keys, else the
+    keyword arguments of ``ClDiceLoss2d`` after ``base`` (``classes`` as indices, ``None`` for all); raises
+    ``ValueError("[opt] cldice...")`` on a bad value, on a ``cldice_*`` key without ``cldice`` and on an unknown class name."""
+
+    import math
+
+    opt = model["opt"]
+
+    def shown(value):
+        return _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)
+
+    if "cldice" not in opt:
+        for key in CLDICE_KEYS:
+            if key in opt:
+                raise ValueError("[opt] {} needs [opt] cldice (the weight a of the clDice term, 0 < a < 1)".format(key))
+        return None
+    a = opt["cldice"]
+    if isinstance(a, bool) or not isinstance(a, (int, float)) or not math.isfinite(a) or not 0 < a < 1:
+        raise ValueError("[opt] cldice must be a number with 0 < a < 1, got {}".format(shown(a)))
+    iters = opt.get("cldice_iters", CLDICE_DEFAULT_ITERS)
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 1 <= iters <= CLDICE_MAX_ITERS:
+        raise ValueError("[opt] cldice_iters must be an integer in 1..{}, got {}".format(CLDICE_MAX_ITERS, shown(iters)))
+    smooth = opt.get("cldice_smooth", 1.0)
+    if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not math.isfinite(smooth) or smooth < 0:
+        raise ValueError("[opt] cldice_smooth must be a finite number >= 0, got {}".format(shown(smooth)))
+    names = list(dataset["common"]["classes"])
+    if len(names) < 2:
+        raise ValueError("[opt] cldice needs a non-background class: class 0 is the background and the dataset config lists {} "
+                         "class".format(len(names)))
+    classes = None
+    if "cldice_classes" in opt:
+        picked = opt["cldice_classes"]
+        if not isinstance(picked, list) or not picked or not all(isinstance(name, str) for name in picked):
+            raise ValueError("[opt] cldice_classes must be a non-empty list of class names, got {}".format(shown(picked)))
+        if len(set(picked)) != len(picked):
+            raise ValueError("[opt] cldice_classes names a class twice: {}".format(shown(picked)))
+        for name in picked:
+            if name not in names[1:]:
+                raise ValueError("[opt] cldice_classes: {} is no non-background class of the dataset config ({})".format(
+                    _fmt(name), ", ".join(_fmt(known) for known in names[1:])))
+        classes = tuple(sorted(names.index(name, 1) for name in picked))
+    return {"weight": float(a), "iters": iters, "smooth": float(smooth), "classes": classes}
 
 
 OPTIMIZER_KEYS = ("weight_decay", "schedule", "schedule_power", "warmup_steps", "lr_min", "clip_norm", "ema")

@@ -13,7 +13,9 @@ calls made without the argument.
 weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``), and ``hard=fraction`` or ``hard=(fraction, below)``: hard-pixel mining, per
 image only the hardest share of the pixels keeps its weight (``rs_hard_pixel_plane``), in training mode only.  ``mIoULoss2d``,
 ``TverskyLoss2d`` and the two Lovasz forms take neither.  ``separation=(ws, sigma)`` adds the paper's second term, the weight of the
-narrow background gap between two objects (``rs_separation_weight_plane``), for the same two criteria."""
+narrow background gap between two objects (``rs_separation_weight_plane``), for the same two criteria.
+
+``ClDiceLoss2d(base, weight)`` wraps any of them and adds the clDice topology term (``rs_soft_skeleton_*``, ``rs_cldice_*``)."""
 
 import torch
 import torch.nn as nn
@@ -255,6 +257,29 @@ class _TverskyFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None
 
 
+class _ClDiceFn(torch.autograd.Function):
+    """The clDice term alone: planes, the two soft skeletons, the four sums per (image, class) and the scalar stage; the backward
+    runs the skeleton's gather passes and the softmax Jacobian (``rs_soft_skeleton_*``, ``rs_cldice_*``)."""
+
+    @staticmethod
+    def forward(ctx, inputs, targets, iters, smooth, classes, ignore):
+        x = inputs.detach().float()
+        p, y = ops.cldice_planes(x, targets, classes, ignore)
+        sp, saved = ops.soft_skeleton(p, iters)
+        sy, _ = ops.soft_skeleton(y, iters, save=False)  # (no gradient through the labels: nothing kept)
+        loss, coef = ops.cldice_finalize(ops.cldice_sums(p, y, sp, sy), smooth)
+        ctx.save_for_backward(x, targets, y, sy, coef, saved[0], saved[1])
+        ctx.iters, ctx.classes, ctx.ignore = iters, classes, ignore
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, y, sy, coef, p, state = ctx.saved_tensors
+        dp = ops.soft_skeleton_bwd((p, state, ctx.iters), ops.cldice_skel_grad(y, coef))
+        g = grad_out.detach().float().contiguous()
+        return ops.cldice_bwd(x, targets, dp, sy, coef, g, ctx.classes, ctx.ignore), None, None, None, None, None
+
+
 class _LovaszFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, targets, ignore=None):
@@ -473,3 +498,53 @@ class LovaszSoftmax2d(nn.Module):
         if ignore is None:
             return _LovaszSoftmaxFn.apply(inputs, targets, self.per_image, self.classes)
         return _LovaszSoftmaxFn.apply(inputs, targets, self.per_image, self.classes, ignore)
+
+
+class ClDiceLoss2d(nn.Module):
+    """``(1 - weight) * base(inputs, targets) + weight * clDice(inputs, targets)``: the topology loss of Shit et al. (CVPR 2021) on top
+    of any of the region and pixel losses above (include/robosat_hip.h).
+
+    Per (image, class) of ``classes`` (indices of non-background classes; ``None`` = all of 1 .. C - 1): P = the softmax plane,
+    Y = the 0/1 label plane, S_P and S_Y their soft skeletons after ``iters`` iterations (at least half the widest structure in
+    pixels), ``Tprec = (sum S_P Y + smooth) / (sum S_P + smooth)``, ``Tsens = (sum S_Y P + smooth) / (sum S_Y + smooth)`` and the
+    term ``1 - 2 Tprec Tsens / (Tprec + Tsens)``, averaged over all N * K pairs: an absent class is not skipped.  Pixels of
+    ``ignore_index`` are 0 in both planes and get no gradient.  The divisor depends on the batch size alone, so data-parallel
+    ranks with equal batches need no exchange for this term.  ``train()`` / ``eval()`` reach ``base`` (hard-pixel mining depends on
+    the mode) because it is a submodule."""
+
+    def __init__(self, base, weight, iters=10, smooth=1.0, classes=None, ignore_index=None):
+        super().__init__()
+        import math
+
+        if not isinstance(base, nn.Module):
+            raise ValueError("base must be a criterion module (got {!r})".format(base))
+        if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not 0 < weight < 1:
+            raise ValueError("weight must be a number with 0 < weight < 1 (got {!r})".format(weight))
+        if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= ops.SKELETON_MAX_ITERS:
+            raise ValueError("iters must be an integer in 0..{} (got {!r})".format(ops.SKELETON_MAX_ITERS, iters))
+        if isinstance(smooth, bool) or not isinstance(smooth, (int, float)) or not math.isfinite(smooth) or smooth < 0:
+            raise ValueError("smooth must be a finite number >= 0 (got {!r})".format(smooth))
+        if classes is not None:
+            classes = tuple(classes)
+            if not classes or any(isinstance(k, bool) or not isinstance(k, int) or k < 1 for k in classes) or len(set(classes)) != len(classes):
+                raise ValueError("classes must be distinct indices of non-background classes (got {!r})".format(classes))
+        self.base = base
+        self.cldice_weight, self.iters, self.smooth, self.classes = float(weight), iters, float(smooth), classes
+        self.ignore_index = ignore_index
+
+    @property
+    def hard(self):
+        """``base``'s hard-pixel mining, if it has any: ``rs train`` switches a mining criterion between train and eval mode."""
+
+        return getattr(self.base, "hard", None)
+
+    def term(self, inputs, targets):
+        """The clDice term alone."""
+
+        inputs, targets = _check(inputs, targets)
+        ignore = _check_ignore(self.ignore_index, inputs)
+        return _ClDiceFn.apply(inputs, targets, self.iters, self.smooth, self.classes, ignore)
+
+    def forward(self, inputs, targets):
+        a = self.cldice_weight
+        return (1.0 - a) * self.base(inputs, targets) + a * self.term(inputs, targets)

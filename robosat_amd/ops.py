@@ -1639,6 +1639,129 @@ def tversky_bwd(logits, targets, weight, stats, grad_out, ce=0.0, per_image=True
     return dlogits
 
 
+SKELETON_MAX_ITERS = 64
+
+
+def _skeleton_args(planes, iters):
+    if planes.dim() != 3:
+        raise ValueError("robosat_amd: the soft skeleton takes fp32 planes [M, H, W], got a shape of {}".format(tuple(planes.shape)))
+    if isinstance(iters, bool) or int(iters) != iters or not 0 <= int(iters) <= SKELETON_MAX_ITERS:
+        raise ValueError("robosat_amd: the soft skeleton takes 0..{} iterations, got {!r}".format(SKELETON_MAX_ITERS, iters))
+    return tuple(planes.shape) + (int(iters),)
+
+
+def soft_skeleton(planes, iters, save=True):
+    """``rs_soft_skeleton_fwd``: float32 planes ``[M, H, W]`` with values in [0, 1] -> ``(skeleton [M, H, W], saved)``, the paper's
+    ``soft_skel`` with ``iters`` iterations (include/robosat_hip.h).  ``saved`` is what ``soft_skeleton_bwd`` takes: the planes, the
+    2 * iters + 1 planes of erosions and partial skeletons, and ``iters``.  ``save=False`` keeps nothing and returns ``None`` for it."""
+
+    m, h, w, iters = _skeleton_args(planes, iters)
+    lib = _lib.lib()
+    skel = torch.empty_like(planes)
+    nfloats = lib.rs_soft_skeleton_state_floats(m, h, w, iters, 1 if save else 0)
+    if nfloats < 0:
+        raise ValueError("robosat_amd: the soft skeleton does not take planes of {} (RS_EINVAL)".format((m, h, w)))
+    if save:
+        state = torch.empty(nfloats, device=planes.device, dtype=torch.float32)
+        ptr = _dev(state, "state")
+    else:
+        state, ptr = None, _workspace(4 * nfloats, planes.device)
+    _call("rs_soft_skeleton_fwd", _dev(planes, "planes"), _dev(skel, "skel"), ptr, m, h, w, iters, 1 if save else 0, _stream())
+    return skel, ((planes, state, iters) if save else None)
+
+
+def soft_skeleton_bwd(saved, grad):
+    """``rs_soft_skeleton_bwd``: d loss / d planes from ``grad`` = d loss / d skeleton and the ``saved`` of ``soft_skeleton``."""
+
+    planes, state, iters = saved
+    m, h, w, iters = _skeleton_args(planes, iters)
+    if tuple(grad.shape) != (m, h, w):
+        raise ValueError("robosat_amd: the skeleton's gradient is [M, H, W] = {}, got {}".format((m, h, w), tuple(grad.shape)))
+    lib = _lib.lib()
+    dplanes = torch.empty_like(planes)
+    _call("rs_soft_skeleton_bwd", _dev(planes, "planes"), _dev(state, "state"), _dev(grad, "grad"), _dev(dplanes, "dplanes"), m, h, w,
+          iters, _workspace(lib.rs_soft_skeleton_bwd_workspace_bytes(m, h, w, iters), planes.device), _stream())
+    return dplanes
+
+
+def cldice_class_mask(classes, c):
+    """The bit mask of ``rs_cldice_*`` for logits of ``c`` classes: ``None`` = every class 1 .. c - 1, else the listed indices."""
+
+    if classes is None:
+        picked = list(range(1, c))
+    else:
+        picked = sorted(set(int(k) for k in classes))
+        if not picked or len(picked) != len(list(classes)) or picked[0] < 1 or picked[-1] >= c:
+            raise ValueError("cldice: classes are distinct indices in 1..{} for logits of {} classes (0 is the background), got {!r}".format(
+                c - 1, c, list(classes)))
+    if not picked:
+        raise ValueError("cldice: logits of {} class have no non-background class".format(c))
+    mask = 0
+    for k in picked:
+        mask |= 1 << k
+    return mask, len(picked)
+
+
+def cldice_planes(logits, targets, classes=None, ignore=None):
+    """``rs_cldice_planes``: ``(P, Y)``, each float32 ``[N * K, H, W]`` in the order [image][class ascending]: the softmax plane and the
+    0/1 label plane of every selected class, both 0 at an ignored pixel."""
+
+    n, c, h, w = logits.shape
+    mask, k = cldice_class_mask(classes, c)
+    ignore = _ignore_label(ignore, c)
+    p = torch.empty((n * k, h, w), device=logits.device, dtype=torch.float32)
+    y = torch.empty_like(p)
+    _call("rs_cldice_planes", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(p, "P"), _dev(y, "Y"), n, c, h, w, mask,
+          -1 if ignore is None else ignore, _stream())
+    return p, y
+
+
+def cldice_sums(p, y, sp, sy):
+    """``rs_cldice_sums``: float64 ``[pairs, 4]`` = (sum S_P Y, sum S_P, sum S_Y P, sum S_Y) per plane, in a fixed order."""
+
+    pairs, h, w = p.shape
+    assert p.shape == y.shape == sp.shape == sy.shape
+    lib = _lib.lib()
+    sums = torch.empty((pairs, 4), device=p.device, dtype=torch.float64)
+    _call("rs_cldice_sums", _dev(p, "P"), _dev(y, "Y"), _dev(sp, "SP"), _dev(sy, "SY"), _dev(sums, "sums", torch.float64), pairs, h, w,
+          _workspace(lib.rs_cldice_workspace_bytes(pairs), p.device), _stream())
+    return sums
+
+
+def cldice_finalize(sums, smooth=1.0):
+    """``rs_cldice_finalize``: ``(loss, coef [pairs, 3])`` from the sums; d loss / d S_P = coef[:, 0] Y + coef[:, 1] per pixel and
+    d loss / d P through the sensitivity = coef[:, 2] S_Y."""
+
+    pairs = sums.shape[0]
+    loss = torch.empty((), device=sums.device, dtype=torch.float32)
+    coef = torch.empty((pairs, 3), device=sums.device, dtype=torch.float32)
+    _call("rs_cldice_finalize", _dev(sums, "sums", torch.float64), _dev(loss, "loss"), _dev(coef, "coef"), pairs, ctypes.c_float(smooth),
+          _stream())
+    return loss, coef
+
+
+def cldice_skel_grad(y, coef):
+    """``rs_cldice_skel_grad``: d loss / d S_P = alpha Y + beta, what ``soft_skeleton_bwd`` is given."""
+
+    pairs, h, w = y.shape
+    grad = torch.empty_like(y)
+    _call("rs_cldice_skel_grad", _dev(y, "Y"), _dev(coef, "coef"), _dev(grad, "grad"), pairs, h, w, _stream())
+    return grad
+
+
+def cldice_bwd(logits, targets, dp, sy, coef, grad_out, classes=None, ignore=None):
+    """``rs_cldice_bwd``: d loss / d logits from ``dp`` = the skeleton's backward and the direct term ``coef[:, 2] S_Y``, through the
+    softmax Jacobian restricted to the selected planes; ``grad_out`` may be ``None`` (= 1)."""
+
+    n, c, h, w = logits.shape
+    mask, _ = cldice_class_mask(classes, c)
+    ignore = _ignore_label(ignore, c)
+    dlogits = torch.empty_like(logits)
+    _call("rs_cldice_bwd", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(dp, "dP"), _dev(sy, "SY"), _dev(coef, "coef"),
+          _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mask, -1 if ignore is None else ignore, _stream())
+    return dlogits
+
+
 def lovasz_fwd(logits, targets, want_grad=True, ignore=None):
     """Returns (loss, d loss / d logits for grad_out = 1 or None)."""
 

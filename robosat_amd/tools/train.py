@@ -31,6 +31,10 @@ Differences by design:
     ``ws exp(-(d1 + d2)^2 / (2 sigma^2))`` to the weight of a background pixel, d1 and d2 its distances to the two nearest objects
     (the paper's second term: the narrow gap between two buildings counts), on top of the boundary weight where that is given too;
     training and validation alike.  The log gains a ``Separation weight:`` line.
+  * ``[opt] cldice`` / ``cldice_iters`` / ``cldice_smooth`` / ``cldice_classes`` (extension keys, optional: robosat_amd/config.py): the
+    loss becomes ``(1 - a) x [opt] loss + a x clDice``, the topology term of Shit et al. 2021 between the soft skeletons and the masks
+    of the non-background classes (robosat_amd/losses.py, ``ClDiceLoss2d``); training and validation alike.  The log gains a
+    ``clDice:`` line.
   * ``[opt] hard_fraction`` / ``hard_below`` (extension keys, optional: robosat_amd/config.py): hard-pixel mining of CrossEntropy and
     Focal -- while training, per image only the hardest share of the valid pixels (and every pixel whose true class has a probability
     below ``hard_below``) counts in the loss (robosat_amd/losses.py).  The criterion then follows the network into train / eval mode,
@@ -75,12 +79,14 @@ from robosat_amd import launch, parallel
 from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
 from robosat_amd.config import (
-    boundary_options, check_num_classes, hard_options, ignore_label, load_config, optimizer_options, separation_options,
-    tversky_options,
+    boundary_options, check_num_classes, cldice_options, hard_options, ignore_label, load_config, optimizer_options,
+    separation_options, tversky_options,
 )
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
-from robosat_amd.losses import CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, TverskyLoss2d, mIoULoss2d
+from robosat_amd.losses import (
+    ClDiceLoss2d, CrossEntropyLoss2d, FocalLoss2d, LovaszLoss2d, LovaszSoftmax2d, TverskyLoss2d, mIoULoss2d,
+)
 from robosat_amd.metrics import Metrics
 from robosat_amd.transforms import (
     CenterCrop, ConvertImageMode, ImageToTensor, JointCompose, JointRandomHorizontalFlip, JointRandomRotation,
@@ -180,6 +186,7 @@ def main(args):
         hard = hard_options(model)  # (model `[opt] hard_fraction / hard_below`, optional: None without the keys)
         separation = separation_options(model, dataset)  # (model `[opt] separation_weight / separation_sigma`, optional likewise)
         tversky = tversky_options(model)  # (model `[opt] tversky_*`: None unless `[opt] loss = "Tversky"`)
+        cldice = cldice_options(model, dataset)  # (model `[opt] cldice / cldice_*`, optional: None without the keys)
         native = optimizer_options(model)  # (model `[opt] weight_decay / schedule / clip_norm / ema`, optional: None without the keys)
     except ValueError as err:
         sys.exit("Error: {}".format(err))  # (before any work starts)
@@ -307,6 +314,10 @@ def main(args):
         # reference's one evaluation over the gathered logits (train.py:180-186): a small collective inside forward(), safe
         # here because every rank runs the same number of equally sized batches (ShardedBatchSampler, drop_last)
         criterion.global_batch = True
+    if cldice is not None:
+        # `[opt] cldice`: (1 - a) x the criterion above + a x the clDice topology term (without the key nothing is wrapped).  The term is
+        # a mean over (image, class) pairs whose divisor depends on the batch size alone: equal shards need no exchange for it.
+        criterion = ClDiceLoss2d(criterion, **cldice, **ignored).to(device)
 
     # [model] device_augment = true (extension key): decoded-tile cache in HBM + flip / rot90 / ToTensor / Normalize in one
     # kernel instead of PIL work in DataLoader workers (same augmentation distribution, same seeded draws)
@@ -366,6 +377,11 @@ def main(args):
         say("Tversky:\t alpha = {}, beta = {}, gamma = {}, smooth = {}, {}, classes {}, + {} x cross-entropy".format(
             tversky["alpha"], tversky["beta"], tversky["gamma"], tversky["smooth"],
             "per image" if tversky["per_image"] else "over the batch", tversky["classes"], tversky["ce"]))
+    if cldice is not None:
+        say("clDice:\t a = {}, iters = {}, smooth = {}, classes {}: loss = {} x {} + {} x clDice".format(
+            cldice["weight"], cldice["iters"], cldice["smooth"],
+            "all" if cldice["classes"] is None else ", ".join(dataset["common"]["classes"][k] for k in cldice["classes"]),
+            "{:g}".format(1.0 - cldice["weight"]), loss_name, "{:g}".format(cldice["weight"])))
     if jitter is not None:
         say("Augmentation:\t {}".format(describe_jitter(jitter)))
     if native is not None:
