@@ -345,6 +345,59 @@ long rs_separation_weight_plane_workspace_bytes(int N, int H, int W);
 int rs_separation_weight_plane(const long long* targets, const float* table, const float* base, float* plane, int N, int C, int H, int W,
                                int D, int ignore, void* workspace, rs_stream_t stream);
 
+/* BOUNDARY LABEL RELAXATION for CrossEntropy / Focal (`rs train`: `[opt] relax`): near an outline either neighbouring class is
+ * acceptable (Zhu et al., CVPR 2019, "Improving Semantic Segmentation via Video Propagation and Label Relaxation").  At a pixel whose
+ * neighbourhood holds several classes the loss maximises the probability of their union, -log sum_{c in S} p_c instead of -log p_t.
+ * DESIGN.md section 7k.
+ *
+ * Inputs:
+ * - the int64 label raster [N][H][W] with C <= 8 classes, so a set of classes fits a byte
+ * - an optional ignore label
+ * - the relaxation radius R in pixels, 1 <= R <= 16
+ *
+ * Rules:
+ * - A pixel is *valid* if its label is not the ignore label.
+ * - The label set plane `sets` is uint8 [N][H][W]:
+ *   - For a valid pixel p, bit c of sets(p) is set iff some valid pixel q of the same image has |qx - px| <= R, |qy - py| <= R and
+ *     label c.  The window is a square: it covers every translation of the label layer by up to R pixels per axis.
+ *   - Nothing lies beyond the image's edge.  Images never see each other.  Ignored pixels add no bit.
+ *   - sets(p) = 0 at an ignored pixel.  A valid pixel always holds its own bit.
+ *   - The plane is integers only, so it is defined bit for bit.
+ * - Pixel term, with S = sets(p):
+ *   - lse = logsumexp_c x_c over all classes; lse_S = logsumexp_{c in S} x_c, with its own maximum taken over S
+ *   - log q = lse_S - lse;  r_c = exp(x_c - lse_S) for c in S, 0 otherwise (computed as exp(x_c - max_S) / sum_S)
+ *   - CrossEntropy: l = -log q, dl/dx_c = p_c - r_c
+ *   - Focal: l = -(1 - q)^gamma * log q, dl/dx_c = k*(r_c - p_c), k = gamma*(1 - q)^(gamma-1) * q * log q - (1 - q)^gamma
+ *   - A pixel whose set is its own label alone has lse_S = x_t and r_t = 1 exactly, and does the arithmetic of the `_pw` kernels in
+ *     their order: on such an input loss, stats and gradient are theirs bit for bit.
+ *   - A pixel whose set is all C classes has log q = 0 and a CrossEntropy gradient of exactly 0.
+ * - Loss: loss = sum_valid m_p*w[t_p]*l_p / sum_valid m_p*w[t_p].
+ *   - The class weight is that of the pixel's OWN label, and m is the optional pixel-weight plane.
+ *   - So stats[1] is exactly the `_pw` call's and does not depend on the sets.
+ *   - A denominator of 0 gives loss 0 and gradient 0.
+ *   - The gradient is exactly +0.0f in every class plane of an ignored pixel and of a pixel of weight 0.
+ *   - Sums are accumulated in double in a fixed order.  There are no float atomics: the same input gives the same bits in every run.
+ *   - There is no host synchronisation.  Every call can be captured into a graph.
+ *
+ * rs_label_set_plane: targets, R, ignore (-1 for none) -> sets.  One launch that reads the labels once and writes one byte per pixel: a
+ * block stages a 64 x 64 tile plus an apron of R as class bits in LDS, four pixels per dword, ORs along the rows, then along the
+ * columns, and stores.  A window of 2R+1 is built by doubling, w_2k(i) = w_k(i) | w_k(i+k), and one OR of two overlapping
+ * power-of-two windows: about log2(2R+1) + 1 ORs per pass.  No workspace.  Labels >= C other than `ignore` are undefined, as in
+ * the losses.
+ * rs_nll_loss_fwd_rx / rs_nll_loss_bwd_rx: the `_pw` signatures plus `sets` [N][H][W] (ANY plane of class sets, not only one made
+ * above; a valid pixel's own bit is taken as set), with the base call's workspace and the `_pw` launch geometry.  `pixel_weight`
+ * may be null: every valid pixel then weighs 1.
+ * RS_EINVAL: a null pointer that may not be null, R outside 1..16, C outside 1..8, an ignore label that is neither -1 nor in
+ * C..255, a non-positive size, the sizes the boundary and separation planes refuse (N > 65535, H or W > 4096, N*H*W >= 2^29; the
+ * plane only), a mode that is neither CrossEntropy nor Focal. */
+int rs_label_set_plane(const long long* targets, uint8_t* sets, int N, int C, int H, int W, int R, int ignore, rs_stream_t stream);
+int rs_nll_loss_fwd_rx(const float* logits, const long long* targets, const float* weight, float* loss, float* stats, int N,
+                       int C, int H, int W, int mode, float gamma, void* workspace, rs_stream_t stream, const float* pixel_weight,
+                       int ignore, const uint8_t* sets);
+int rs_nll_loss_bwd_rx(const float* logits, const long long* targets, const float* weight, const float* stats,
+                       const float* grad_out, float* dlogits, int N, int C, int H, int W, int mode, float gamma,
+                       rs_stream_t stream, const float* pixel_weight, int ignore, const uint8_t* sets);
+
 /* HARD-PIXEL MINING for CrossEntropy / Focal (`rs train`: `[opt] hard_fraction`, `hard_below`): online hard example mining, also
  * called bootstrapped cross-entropy or top-k pixel loss.  Per image, only the hardest share of the pixels keeps its weight; the others
  * get weight 0 in the `_pw` loss above.  DESIGN.md section 7e.

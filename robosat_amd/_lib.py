@@ -86,6 +86,10 @@ SIGNATURES = {
     # the separation weight of CrossEntropy / Focal: the paper's second term added onto a base plane (null: 1 valid / 0 ignored)
     "rs_separation_weight_plane_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     "rs_separation_weight_plane": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
+    # boundary label relaxation of CrossEntropy / Focal: the class-set plane from the labels, and the `_pw` signature + sets
+    "rs_label_set_plane": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "rs_nll_loss_fwd_rx": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, c_int, P]),
+    "rs_nll_loss_bwd_rx": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, c_int, P]),
     # hard-pixel mining of CrossEntropy / Focal: the weight plane from the logits, and its selection stages on a given key plane
     "rs_hard_pixel_workspace_bytes": (c_long, [c_int, c_int, c_int]),
     # (`fraction_bits`: the double's 64 bits in a long; `cap`: a uint32 in a long)

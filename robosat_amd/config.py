@@ -5,6 +5,7 @@ Model:   [common] cuda, batch_size, image_size, checkpoint   [opt] epochs, lr, l
          [opt] boundary_weight, boundary_sigma   (extension, optional: the boundary weight of CrossEntropy / Focal, ``boundary_options`` below)
          [opt] separation_weight, separation_sigma   (extension, optional: the separation weight of CrossEntropy / Focal, ``separation_options`` below)
          [opt] hard_fraction, hard_below   (extension, optional: hard-pixel mining of CrossEntropy / Focal, ``hard_options`` below)
+         [opt] relax   (extension, optional: boundary label relaxation of CrossEntropy / Focal, ``relax_options`` below)
          [opt] tversky_alpha, tversky_beta, tversky_gamma, tversky_smooth, tversky_per_image, tversky_classes, tversky_ce
                (extension, optional: the parameters of ``loss = "Tversky"``, ``tversky_options`` below)
          [opt] cldice, cldice_iters, cldice_smooth, cldice_classes
@@ -154,6 +155,33 @@ def hard_options(model):
         raise ValueError("[opt] hard_fraction mines the pixels of {} only; [opt] loss = {} has no per-pixel weight".format(
             " and ".join(HARD_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
     return fraction, below
+
+
+RELAX_LOSSES = ("CrossEntropy", "Focal")
+RELAX_MAX_RADIUS = 16  # (the radius rs_label_set_plane takes: include/robosat_hip.h)
+
+
+def relax_options(model):
+    """The model config's optional ``[opt] relax`` (R, whole pixels): boundary label relaxation of CrossEntropy and Focal -- while
+    training, a pixel within R pixels (in x and in y) of other classes is charged for the probability of all of them together, so
+    labels that are shifted by up to R pixels cost nothing near an outline.  Returns ``None`` without the key, else R; raises
+    ``ValueError("[opt] relax ...")`` unless it is an integer in 1..16, on a loss that has no per-pixel term and beside
+    ``[opt] hard_fraction`` (mining would have to rank the pixels by their relaxed loss, which is not implemented)."""
+
+    opt = model["opt"]
+    if "relax" not in opt:
+        return None
+    value = opt["relax"]
+    if isinstance(value, bool) or not isinstance(value, int) or not 1 <= value <= RELAX_MAX_RADIUS:
+        raise ValueError("[opt] relax must be an integer radius in 1..{} pixels, got {}".format(
+            RELAX_MAX_RADIUS, _fmt(value) if isinstance(value, (bool, int, float, str)) else repr(value)))
+    if opt.get("loss") not in RELAX_LOSSES:
+        raise ValueError("[opt] relax relaxes the pixel terms of {} only; [opt] loss = {} has none".format(
+            " and ".join(RELAX_LOSSES), _fmt(opt.get("loss")) if isinstance(opt.get("loss"), str) else repr(opt.get("loss"))))
+    if "hard_fraction" in opt:
+        raise ValueError("[opt] relax cannot stand beside [opt] hard_fraction: mining ranks the pixels by their strict cross-entropy, "
+                         "which is largest on the band that relaxation forgives; ranking by the relaxed loss is not implemented")
+    return value
 
 
 TVERSKY_LOSS = "Tversky"

@@ -13,7 +13,9 @@ calls made without the argument.
 weights (``rs_boundary_weight_plane``, ``rs_nll_loss_*_pw``), and ``hard=fraction`` or ``hard=(fraction, below)``: hard-pixel mining, per
 image only the hardest share of the pixels keeps its weight (``rs_hard_pixel_plane``), in training mode only.  ``mIoULoss2d``,
 ``TverskyLoss2d`` and the two Lovasz forms take neither.  ``separation=(ws, sigma)`` adds the paper's second term, the weight of the
-narrow background gap between two objects (``rs_separation_weight_plane``), for the same two criteria.
+narrow background gap between two objects (``rs_separation_weight_plane``), for the same two criteria.  ``relax=R`` is boundary
+label relaxation for the same two: in training mode a pixel within R pixels of other classes is charged ``-log`` of the probability
+of all of them together (``rs_label_set_plane``, ``rs_nll_loss_*_rx``).
 
 ``ClDiceLoss2d(base, weight)`` wraps any of them and adds the clDice topology term (``rs_soft_skeleton_*``, ``rs_cldice_*``)."""
 
@@ -202,6 +204,37 @@ class _NLLSeparationFn(torch.autograd.Function):
         return dx, None, None, None, None, None, None, None, None, None
 
 
+class _NLLRelaxFn(torch.autograd.Function):
+    """``_NLLFn`` with boundary label relaxation: the label set plane (``ops.label_set_plane``) made from ``targets`` in forward and
+    kept for backward.  The boundary and separation planes (if any) are made from the strict labels as without relaxation and passed
+    as ``pixel_weight``.  ``stats[1]`` is the sum of the pixels' OWN class weights, which the sets do not enter, so its exchange is
+    the same one; the criteria without ``relax`` never come here."""
+
+    @staticmethod
+    def forward(ctx, inputs, targets, weight, mode, gamma, global_batch, ignore, boundary, separation, relax):
+        x = inputs.detach().float()
+        plane = None
+        if boundary is not None:
+            plane = ops.boundary_weight_plane(targets, boundary[0], boundary[1], ignore=ignore, classes=x.shape[1])
+        if separation is not None:
+            plane = ops.separation_weight_plane(targets, separation[0], separation[1], ignore=ignore, classes=x.shape[1], base=plane)
+        sets = ops.label_set_plane(targets, relax, ignore=ignore, classes=x.shape[1])
+        loss, stats = ops.nll_loss_fwd(x, targets, weight, mode, gamma, ignore=ignore, pixel_weight=plane, label_sets=sets)
+        loss = _global_batch_normaliser(loss, stats, global_batch)
+        ctx.save_for_backward(x, targets, stats, sets, *(() if plane is None else (plane,)))
+        ctx.weight, ctx.mode, ctx.gamma, ctx.ignore = weight, mode, gamma, ignore
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, targets, stats, sets = ctx.saved_tensors[:4]
+        plane = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        g = grad_out.detach().float().contiguous()
+        dx = ops.nll_loss_bwd(x, targets, ctx.weight, stats, g, ctx.mode, ctx.gamma, ignore=ctx.ignore, pixel_weight=plane,
+                              label_sets=sets)
+        return dx, None, None, None, None, None, None, None, None, None
+
+
 class _MIoUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, targets, weight, global_batch=False, ignore=None):
@@ -364,12 +397,30 @@ def _check_hard(hard):
     return (fraction, below)
 
 
+def _check_relax(relax, hard):
+    """``relax`` = the relaxation radius R in pixels (``None`` passes): an int in 1..16, no bool and no float; refused beside
+    ``hard``."""
+
+    if relax is None:
+        return None
+    if isinstance(relax, bool) or not isinstance(relax, int) or not 1 <= relax <= ops.RELAX_MAX_RADIUS:
+        raise ValueError("relax must be None or an integer radius in 1..{} pixels, got {!r}".format(ops.RELAX_MAX_RADIUS, relax))
+    if hard is not None:
+        raise ValueError("relax cannot be combined with hard: hard-pixel mining ranks the pixels by their strict cross-entropy, which "
+                         "is largest exactly on the band that relaxation forgives; ranking by the relaxed loss is not implemented")
+    return relax
+
+
 def _nll(self, inputs, targets, mode, gamma):
-    """The call ``CrossEntropyLoss2d`` and ``FocalLoss2d`` make: without ``boundary``, ``separation`` and ``hard`` the calls they have
-    always made; mining is a training device, so in eval mode the criterion makes the calls it makes without ``hard``."""
+    """The call ``CrossEntropyLoss2d`` and ``FocalLoss2d`` make: without ``boundary``, ``separation``, ``hard`` and ``relax`` the calls
+    they have always made; mining and relaxation are training devices, so in eval mode the criterion makes the calls it makes without
+    ``hard`` and ``relax``."""
 
     inputs, targets = _check(inputs, targets)
     ignore = _check_ignore(self.ignore_index, inputs)
+    if self.relax is not None and self.training:
+        return _NLLRelaxFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore, self.boundary,
+                                 self.separation, self.relax)
     if self.separation is not None:
         return _NLLSeparationFn.apply(inputs, targets, self.weight, mode, gamma, self.global_batch, ignore, self.boundary,
                                       self.separation, self.hard if self.training else None)
@@ -392,13 +443,20 @@ class CrossEntropyLoss2d(_WeightedLoss):
     ``separation=(ws, sigma)``: ``ws exp(-(d1 + d2)^2 / (2 sigma^2))`` is added to a background pixel's weight, d1 and d2 its distances
     to the two nearest objects (the 4-connected components of the pixels of the classes 1 .. C - 1), so that the narrow gap between
     two neighbouring objects counts (include/robosat_hip.h; DESIGN.md "Separation weight").  It adds onto the boundary plane where
-    that is given too, mining takes the sum as its base, and like ``boundary`` it stays on in eval mode.  ``None`` makes today's calls."""
+    that is given too, mining takes the sum as its base, and like ``boundary`` it stays on in eval mode.  ``None`` makes today's calls.
+    ``relax=R`` (an int in 1..16): boundary label relaxation (Zhu et al., CVPR 2019).  In training mode a pixel's term is
+    ``-log sum_{c in S} p_c``, S the classes of the valid pixels within R pixels in x and in y (``rs_label_set_plane``), weighted by
+    the class weight of the pixel's own label; labels that are shifted by up to R pixels then cost nothing near an outline
+    (include/robosat_hip.h; DESIGN.md "Label relaxation").  ``boundary`` and ``separation`` are made from the strict labels and
+    weigh the relaxed terms; in eval mode the criterion makes the strict calls; ``relax`` with ``hard`` is a ``ValueError`` (mining
+    would have to rank by the relaxed loss).  ``None`` makes today's calls."""
 
-    def __init__(self, weight=None, ignore_index=None, boundary=None, hard=None, separation=None):
+    def __init__(self, weight=None, ignore_index=None, boundary=None, hard=None, separation=None, relax=None):
         super().__init__(weight, ignore_index)
         self.boundary = _check_boundary(boundary)
         self.separation = _check_separation(separation)
         self.hard = _check_hard(hard)
+        self.relax = _check_relax(relax, self.hard)
 
     def forward(self, inputs, targets):
         return _nll(self, inputs, targets, ops.NLL_CROSS_ENTROPY, 0.0)
@@ -406,14 +464,16 @@ class CrossEntropyLoss2d(_WeightedLoss):
 
 class FocalLoss2d(_WeightedLoss):
     """Focal loss, gamma = 2 by default (reference losses.py:28-50); ``boundary``, ``separation`` and ``hard`` as in ``CrossEntropyLoss2d``
-    (the pixels are ranked by their cross-entropy: Focal is monotone in the true class's probability, so that is its ranking too)."""
+    (the pixels are ranked by their cross-entropy: Focal is monotone in the true class's probability, so that is its ranking too);
+    ``relax`` as there, with the class set's probability q in place of the true class's: ``-(1 - q)^gamma log q``."""
 
-    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None, hard=None, separation=None):
+    def __init__(self, gamma=2, weight=None, ignore_index=None, boundary=None, hard=None, separation=None, relax=None):
         super().__init__(weight, ignore_index)
         self.gamma = gamma
         self.boundary = _check_boundary(boundary)
         self.separation = _check_separation(separation)
         self.hard = _check_hard(hard)
+        self.relax = _check_relax(relax, self.hard)
 
     def forward(self, inputs, targets):
         return _nll(self, inputs, targets, ops.NLL_FOCAL, float(self.gamma))
@@ -509,8 +569,8 @@ class ClDiceLoss2d(nn.Module):
     pixels), ``Tprec = (sum S_P Y + smooth) / (sum S_P + smooth)``, ``Tsens = (sum S_Y P + smooth) / (sum S_Y + smooth)`` and the
     term ``1 - 2 Tprec Tsens / (Tprec + Tsens)``, averaged over all N * K pairs: an absent class is not skipped.  Pixels of
     ``ignore_index`` are 0 in both planes and get no gradient.  The divisor depends on the batch size alone, so data-parallel
-    ranks with equal batches need no exchange for this term.  ``train()`` / ``eval()`` reach ``base`` (hard-pixel mining depends on
-    the mode) because it is a submodule."""
+    ranks with equal batches need no exchange for this term.  ``train()`` / ``eval()`` reach ``base`` (hard-pixel mining and label
+    relaxation depend on the mode) because it is a submodule."""
 
     def __init__(self, base, weight, iters=10, smooth=1.0, classes=None, ignore_index=None):
         super().__init__()
@@ -537,6 +597,12 @@ class ClDiceLoss2d(nn.Module):
         """``base``'s hard-pixel mining, if it has any: ``rs train`` switches a mining criterion between train and eval mode."""
 
         return getattr(self.base, "hard", None)
+
+    @property
+    def relax(self):
+        """``base``'s label relaxation, if it has any: a training device like ``hard``."""
+
+        return getattr(self.base, "relax", None)
 
     def term(self, inputs, targets):
         """The clDice term alone."""

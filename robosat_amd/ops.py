@@ -1410,6 +1410,34 @@ def separation_weight_plane(targets, ws, sigma, ignore=None, classes=None, base=
     return plane
 
 
+RELAX_MAX_RADIUS = 16
+
+
+def relax_radius(radius):
+    """The relaxation radius R of ``rs_label_set_plane`` as an int; raises ``ValueError`` unless it is an integer (no bool, no float)
+    in 1..16."""
+
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= RELAX_MAX_RADIUS:
+        raise ValueError("robosat_amd: the relaxation radius is an integer in 1..{} pixels, got {!r}".format(RELAX_MAX_RADIUS, radius))
+    return radius
+
+
+def label_set_plane(targets, radius, ignore=None, classes=None):
+    """int64 [N, H, W] labels -> uint8 [N, H, W]: the label set plane of ``rs_label_set_plane`` (include/robosat_hip.h): bit c of a
+    valid pixel's byte says that class c occurs among the valid pixels of its image within ``radius`` pixels in x and in y; 0 at a
+    pixel whose label is ``ignore``.  ``classes`` (the logits' class count) lets ``ignore`` be checked against it here; without it the
+    loss call does that."""
+
+    n, h, w = targets.shape
+    radius = relax_radius(radius)
+    c = 1 if classes is None else int(classes)
+    ignore = _ignore_label(ignore, c)
+    tgt = _dev(targets, "targets", torch.int64)  # (a CPU tensor raises before anything is loaded or sized)
+    sets = torch.empty((n, h, w), device=targets.device, dtype=torch.uint8)
+    _call("rs_label_set_plane", tgt, _dev(sets, "sets", torch.uint8), n, c, h, w, radius, -1 if ignore is None else ignore, _stream())
+    return sets
+
+
 HARD_NO_CAP = 0xFFFFFFFF
 
 
@@ -1495,16 +1523,26 @@ def hard_pixel_select(keys, fraction, below=None, targets=None, ignore=None, bas
     return plane, info
 
 
-def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None, pixel_weight=None):
+def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None, pixel_weight=None, label_sets=None):
     """``ignore`` (here and in the four losses below): the label value whose pixels are left out of the loss
     (``rs_*_ig`` in include/robosat_hip.h); ``None`` calls the entry point without it.  ``pixel_weight`` float32 [N, H, W]
-    (``rs_nll_loss_*_pw``): a non-negative weight per pixel on top of the class weight; ``None`` makes the calls made without it."""
+    (``rs_nll_loss_*_pw``): a non-negative weight per pixel on top of the class weight; ``None`` makes the calls made without it.
+    ``label_sets`` uint8 [N, H, W] (``rs_nll_loss_*_rx``, the plane of ``label_set_plane``): the relaxed loss, the probability of a
+    pixel's whole class set in place of its own class's; ``None`` makes the calls made without it."""
 
     n, c, h, w = logits.shape
     lib = _lib.lib()
     ignore = _ignore_label(ignore, c)
     loss = torch.empty((), device=logits.device, dtype=torch.float32)
     stats = torch.empty(2, device=logits.device, dtype=torch.float32)
+    if label_sets is not None:
+        assert tuple(label_sets.shape) == (n, h, w), "label_sets is [N, H, W]"
+        assert pixel_weight is None or tuple(pixel_weight.shape) == (n, h, w), "pixel_weight is [N, H, W]"
+        _call("rs_nll_loss_fwd_rx", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(loss, "loss"), _dev(stats, "stats"), n, c, h, w, mode, ctypes.c_float(gamma),
+              _workspace(lib.rs_nll_loss_workspace_bytes(), logits.device), _stream(), _dev(pixel_weight, "pixel_weight"),
+              -1 if ignore is None else ignore, _dev(label_sets, "label_sets", torch.uint8))
+        return loss, stats
     if pixel_weight is not None:
         assert tuple(pixel_weight.shape) == (n, h, w), "pixel_weight is [N, H, W]"
         _call("rs_nll_loss_fwd_pw", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
@@ -1523,10 +1561,18 @@ def nll_loss_fwd(logits, targets, weight, mode, gamma=2.0, ignore=None, pixel_we
     return loss, stats
 
 
-def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0, ignore=None, pixel_weight=None):
+def nll_loss_bwd(logits, targets, weight, stats, grad_out, mode, gamma=2.0, ignore=None, pixel_weight=None, label_sets=None):
     n, c, h, w = logits.shape
     ignore = _ignore_label(ignore, c)
     dlogits = torch.empty_like(logits)
+    if label_sets is not None:
+        assert tuple(label_sets.shape) == (n, h, w), "label_sets is [N, H, W]"
+        assert pixel_weight is None or tuple(pixel_weight.shape) == (n, h, w), "pixel_weight is [N, H, W]"
+        _call("rs_nll_loss_bwd_rx", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),
+              _dev(stats, "stats"), _dev(grad_out, "grad_out"), _dev(dlogits, "dlogits"), n, c, h, w, mode, ctypes.c_float(gamma),
+              _stream(), _dev(pixel_weight, "pixel_weight"), -1 if ignore is None else ignore,
+              _dev(label_sets, "label_sets", torch.uint8))
+        return dlogits
     if pixel_weight is not None:
         assert tuple(pixel_weight.shape) == (n, h, w), "pixel_weight is [N, H, W]"
         _call("rs_nll_loss_bwd_pw", _dev(logits, "logits"), _dev(targets, "targets", torch.int64), _dev(weight, "weight"),

@@ -39,6 +39,11 @@ Differences by design:
     Focal -- while training, per image only the hardest share of the valid pixels (and every pixel whose true class has a probability
     below ``hard_below``) counts in the loss (robosat_amd/losses.py).  The criterion then follows the network into train / eval mode,
     and the logged validation loss is the unmined loss.
+  * ``[opt] relax = R`` (extension key, optional: robosat_amd/config.py): boundary label relaxation of CrossEntropy and Focal -- while
+    training, a pixel within R pixels of other classes is charged ``-log`` of the probability of all of them together, so labels
+    that are shifted by up to R pixels cost nothing near an outline (robosat_amd/losses.py).  The criterion follows the network
+    into train / eval mode, and the logged validation loss is the strict loss.  Refused beside ``hard_fraction``.  The log gains a
+    ``Label relaxation:`` line.
   * ``[opt] loss = "Tversky"`` (robosat_amd/losses.py: ``TverskyLoss2d``): the Tversky loss family -- Dice by default, the Tversky index
     with ``[opt] tversky_alpha`` / ``tversky_beta`` (``beta > alpha`` favours recall), the focal Tversky loss with ``tversky_gamma``,
     smoothing ``tversky_smooth``, per image or over the whole batch (``tversky_per_image``), over the classes present or all
@@ -80,7 +85,7 @@ from robosat_amd.augment import describe as describe_jitter, jitter_from_config
 from robosat_amd.bands import bands_from_config, split_per_source
 from robosat_amd.config import (
     boundary_options, check_num_classes, cldice_options, hard_options, ignore_label, load_config, optimizer_options,
-    separation_options, tversky_options,
+    relax_options, separation_options, tversky_options,
 )
 from robosat_amd.datasets import SlippyMapTilesConcatenation
 from robosat_amd.log import Log
@@ -185,6 +190,7 @@ def main(args):
         boundary = boundary_options(model)  # (model `[opt] boundary_weight / boundary_sigma`, optional: None without the keys)
         hard = hard_options(model)  # (model `[opt] hard_fraction / hard_below`, optional: None without the keys)
         separation = separation_options(model, dataset)  # (model `[opt] separation_weight / separation_sigma`, optional likewise)
+        relax = relax_options(model)  # (model `[opt] relax`, optional likewise; refused beside `hard_fraction`)
         tversky = tversky_options(model)  # (model `[opt] tversky_*`: None unless `[opt] loss = "Tversky"`)
         cldice = cldice_options(model, dataset)  # (model `[opt] cldice / cldice_*`, optional: None without the keys)
         native = optimizer_options(model)  # (model `[opt] weight_decay / schedule / clip_norm / ema`, optional: None without the keys)
@@ -294,6 +300,9 @@ def main(args):
     # (and without `[opt] separation_weight`; with it the loss is CrossEntropy or Focal: separation_options)
     if separation is not None:
         weighted["separation"] = separation
+    # (and without `[opt] relax`; with it the loss is CrossEntropy or Focal: relax_options)
+    if relax is not None:
+        weighted["relax"] = relax
     if loss_name == "CrossEntropy":
         criterion = CrossEntropyLoss2d(weight=weight, **ignored, **weighted).to(device)
     elif loss_name == "mIoU":
@@ -373,6 +382,9 @@ def main(args):
     if hard is not None:
         say("Hard pixels:\t the hardest {} of every image's valid pixels{} (training only; validation loss unmined)".format(
             hard[0], "" if hard[1] is None else ", and every pixel with p(true class) < {}".format(hard[1])))
+    if relax is not None:
+        say("Label relaxation:\t R = {} px: near an outline every class within a {} x {} window is accepted (training only; "
+            "validation loss strict)".format(relax, 2 * relax + 1, 2 * relax + 1))
     if tversky is not None:
         say("Tversky:\t alpha = {}, beta = {}, gamma = {}, smooth = {}, {}, classes {}, + {} x cross-entropy".format(
             tversky["alpha"], tversky["beta"], tversky["gamma"], tversky["smooth"],
@@ -548,9 +560,10 @@ def _epoch(loader, num_classes, device, net, criterion, master, optimizer=None, 
     metrics = Metrics(range(num_classes))
 
     net.train() if training else net.eval()
-    if getattr(criterion, "hard", None) is not None:
-        # hard-pixel mining is a training device: the criterion follows the network's mode, and the validation loss is the unmined
-        # loss, comparable between runs with different fractions (without the keys the criterion is never touched)
+    if getattr(criterion, "hard", None) is not None or getattr(criterion, "relax", None) is not None:
+        # hard-pixel mining and label relaxation are training devices: the criterion follows the network's mode, and the validation
+        # loss is the unmined, strict loss, comparable between runs with different fractions and radii (without the keys the
+        # criterion is never touched)
         criterion.train(training)
     started = time.perf_counter()
 
