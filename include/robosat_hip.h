@@ -1333,6 +1333,43 @@ int rs_eval_prob_hist(const uint8_t* prob, const uint8_t* actual, int64_t* hist,
 int rs_eval_centerline(const uint8_t* skel_p, const uint8_t* skel_g, const int32_t* d2_to_g, const int32_t* d2_to_p,
                        const int32_t* nbr, int64_t* counts, int B, int H, int W, int rho, rs_stream_t stream);
 
+/* `rs evaluate --type T --ignored unknown`: the typed views beside ignored label pixels.  a is the label raster, p the mask raster,
+ * t the class index of --type, I the dataset's ignore value (C <= I <= 255).
+ *   U  = {a == I}           the unknown pixels: nothing is known there on either side
+ *   P  = {p == t} \ U       the prediction under an ignored label cannot be judged, so it is no part of P
+ *   G  = {a == t}
+ *   cP = 2 on U, 1 on P, 0 elsewhere; cG likewise with G: the rasters coded UNSET / SET / UNKNOWN.
+ * An ignored pixel is what a pixel outside the raster or in an absent tile already is to rs_features_edt, at pixel granularity.
+ *   outlines      a side's band is its SET pixels with 1 <= d2 <= D*D, d2 the transform of the coded raster with R = D + 1:
+ *                 distances come from UNSET pixels only and pass over unknown ones, and an unknown pixel is in no band.  The edge of
+ *                 an ignored region is no boundary, as the raster's edge is none (and as in rs_boundary_weight_plane).  On the device
+ *                 the transform is rs_features_edt of the coded plane as it stands (non-zero = set): at a SET pixel its value is the
+ *                 definition's; at an unknown pixel it writes a distance where the definition has none, so the count leaves U out
+ *                 (rs_eval_boundary_coded).
+ *   objects       the 4-connected components of P and of G.  An object that an unknown region cuts is cut on both sides alike, the
+ *                 rule that holds at a tile border without --stitch; a predicted object wholly inside U does not exist.  Areas count
+ *                 known pixels; --min_area, the overlap table and the matching are as they are.
+ *   centre lines  P and G are thinned and rs_eval_centerline counts as it stands.  Both skeletons stop about half a road's width
+ *                 short of an unknown region, on both sides alike, and a line beyond it matches nothing.  No pixel of a skeleton
+ *                 lies in U, and the reach is looked at at skeleton pixels only, where the transform of the skeleton's complement
+ *                 has the same value whether U is coded unknown or "not skeleton" (both are passed over).
+ *   probabilities rs_eval_prob_hist leaves ignored labels out already.
+ *
+ * rs_eval_select: predicted, actual: uint8 [pixels] (any address), 0 < pixels < 2^31, 2 <= C <= 8, 1 <= cls <= C - 1,
+ * C <= ignore <= 255 (RS_EINVAL otherwise).  Writes coded_p = cP, coded_g = cG, mask_p = (cP == 1), mask_g = (cG == 1), uint8 [pixels]
+ * each (any address).  A byte that is no class and not the ignore value is set on neither side (rs_eval_confusion_ig counts it as
+ * bad).  One launch of the shape above, without groups: 16 consecutive pixels per thread, 16-byte loads and stores where the run's
+ * first address in that plane is 16-byte aligned and the run ends within `pixels`, single checked accesses otherwise; every output
+ * byte has one writer: no atomic, no LDS.  Each input is read once.
+ *
+ * rs_eval_boundary_coded: rs_eval_boundary over the known pixels.  coded: uint8 [pixels] (any address), cP or cG: U is the same in both.
+ *   counts[g] = (|A_D|, |B_D|, |A_D and B_D|) over the pixels of group g whose coded byte is not 2
+ * Group walk, merge and atomics are rs_eval_boundary's (the kernels are one template); on a plane without a 2 so are the counts. */
+int rs_eval_select(const uint8_t* predicted, const uint8_t* actual, uint8_t* coded_p, uint8_t* coded_g, uint8_t* mask_p, uint8_t* mask_g,
+                   long pixels, int C, int cls, int ignore, rs_stream_t stream);
+int rs_eval_boundary_coded(const int32_t* d2_a, const int32_t* d2_b, const uint8_t* coded, int64_t* counts, long pixels, long group, int D,
+                           rs_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * The optimiser step of `rs train` (csrc/optim.hip; an extension: the `[opt] weight_decay / schedule / clip_norm / ema` keys,
  * robosat_amd/optim.py).  torch.optim.AdamW's update -- Adam's with wd = 0 -- with the learning-rate schedule, gradient clipping by

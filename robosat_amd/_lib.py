@@ -235,6 +235,8 @@ SIGNATURES = {
     "rs_eval_confusion_ig": (c_int, [P, P, P, P, P, c_long, c_long, c_int, P, c_int]),
     "rs_eval_prob_hist": (c_int, [P, P, P, P, c_long, c_long, c_int, c_int, c_int, P]),
     "rs_eval_centerline": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "rs_eval_select": (c_int, [P, P, P, P, P, P, c_long, c_int, c_int, c_int, P]),
+    "rs_eval_boundary_coded": (c_int, [P, P, P, P, c_long, c_long, c_int, P]),
     # the optimiser step of rs train (csrc/optim.hip): the items are a HOST array of rs_optim_item (ops._OptimItem)
     "rs_optim_limits": (c_int, [POINTER(c_int), POINTER(c_int)]),
     "rs_optim_workspace_bytes": (c_long, [c_long]),

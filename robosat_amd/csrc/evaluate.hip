@@ -10,6 +10,9 @@
 //   rs_eval_centerline two skeletons and the capped distance transforms of their complements -> per group the straight and diagonal
 //                      links of either skeleton and those whose two ends lie within rho of the other (at the end of the file: its
 //                      threads own runs of a ROW, since a link has a neighbour below, not runs of the call)
+//   rs_eval_select     (`--ignored unknown`) two class-index rasters, a class and the ignore value -> the two rasters coded unset /
+//                      set / unknown and their set pixels as 0/1 masks: no counting, a pass that writes four byte planes
+//   rs_eval_boundary_coded  rs_eval_boundary over the pixels that a coded plane does not call unknown
 //
 // The kernels share one shape.  A block of 256 threads covers kEvalBlock = 4096 consecutive pixels of the whole call, a thread 16
 // consecutive ones, held in registers: a 16-byte load per raster (four for the int32 rasters) where the thread's first address is
@@ -67,6 +70,35 @@ __device__ __forceinline__ unsigned int eval_load_band(const int* __restrict__ d
       if (base + j < pixels) bits |= (unsigned int)((unsigned int)d2[base + j] - 1u < dd) << j;
   }
   return bits;
+}
+
+// 0x01 in every byte of x that equals k, 0 in the others (exact: 0x7f + 0x7f leaves no carry for the next byte).
+__device__ __forceinline__ unsigned int eval_eq_bytes(unsigned int x, unsigned int k) {
+  const unsigned int t = x ^ (k * 0x01010101u);
+  return (~(t | ((t & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u) >> 7;
+}
+
+// Bit j set where coded[base + j] is not 2 (a pixel beyond `pixels` reads 0: known, and in no band).
+__device__ __forceinline__ unsigned int eval_load_known(const uint8_t* __restrict__ coded, long base, long pixels) {
+  unsigned int w[4], unknown = 0;
+  eval_load_bytes(coded, base, pixels, w);
+#pragma unroll
+  for (int e = 0; e < 4; ++e)  // (the four 0x01 bytes side by side: the product of cl_row_bits below)
+    unknown |= ((eval_eq_bytes(w[e], 2u) * 0x00204081u >> 21) & 15u) << (4 * e);
+  return ~unknown & 0xffffu;
+}
+
+__device__ __forceinline__ void eval_store_bytes(uint8_t* __restrict__ p, long base, long pixels, const unsigned int (&w)[4]) {
+  if (base + kEvalRun <= pixels && (reinterpret_cast<uintptr_t>(p + base) & 15) == 0) {
+    u32x4 q;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] = w[e];
+    *reinterpret_cast<u32x4*>(p + base) = q;
+  } else {
+#pragma unroll
+    for (int j = 0; j < kEvalRun; ++j)
+      if (base + j < pixels) p[base + j] = (uint8_t)(w[j >> 2] >> ((j & 3) * 8));
+  }
 }
 
 // ---- confusion matrix per group --------------------------------------------------------------------------------------
@@ -133,9 +165,12 @@ __global__ __launch_bounds__(kEvalThreads) void eval_confusion_kernel(const uint
 // ---- boundary bands per group ----------------------------------------------------------------------------------------
 // Three counters per group, so no histogram: a thread keeps its 16 pixels as two 16-bit masks, counts the bits of its part of the
 // group, the wave sums over its lanes, the block over its waves, and up to three global atomics go out per block and group.
+// CODED (rs_eval_boundary_coded): a pixel whose byte of `coded` is 2 is unknown and in neither band, whatever the transforms hold
+// there (rs_features_edt takes non-zero for set, so it writes a distance at an unknown pixel); one more byte plane is read.
+template <bool CODED>
 __global__ __launch_bounds__(kEvalThreads) void eval_boundary_kernel(const int* __restrict__ d2_a, const int* __restrict__ d2_b,
                                                                      unsigned long long* __restrict__ counts, long pixels, long group,
-                                                                     unsigned int dd) {
+                                                                     unsigned int dd, const uint8_t* __restrict__ coded) {
   __shared__ unsigned int part[4][3];
   const long block0 = (long)blockIdx.x * kEvalBlock;
   const long base = block0 + (long)threadIdx.x * kEvalRun;
@@ -143,6 +178,11 @@ __global__ __launch_bounds__(kEvalThreads) void eval_boundary_kernel(const int* 
   if (base < pixels) {
     ma = eval_load_band(d2_a, base, pixels, dd);
     mb = eval_load_band(d2_b, base, pixels, dd);
+    if (CODED) {
+      const unsigned int known = eval_load_known(coded, base, pixels);
+      ma &= known;
+      mb &= known;
+    }
   }
   const long block1 = block0 + kEvalBlock < pixels ? block0 + kEvalBlock : pixels;
   const long g0 = block0 / group, g1 = (block1 - 1) / group;
@@ -166,6 +206,33 @@ __global__ __launch_bounds__(kEvalThreads) void eval_boundary_kernel(const int* 
     }
     __syncthreads();  // (the next group overwrites the partial sums)
   }
+}
+
+// ---- the coded rasters of `--ignored unknown` (rs_eval_select) ---------------------------------------------------------------------
+// No counts: a thread reads its 16 bytes of both rasters and writes 16 bytes of each of the four planes, a word of four pixels at a
+// time.  With u = (actual == ignore), set_p = (predicted == cls) and not u, set_g = (actual == cls) (a label that is the class is not
+// the ignore value: ignore >= C > cls): coded = set | u << 1, mask = set.  Every output byte has one writer.
+__global__ __launch_bounds__(kEvalThreads) void eval_select_kernel(const uint8_t* __restrict__ predicted, const uint8_t* __restrict__ actual,
+                                                                   uint8_t* __restrict__ coded_p, uint8_t* __restrict__ coded_g,
+                                                                   uint8_t* __restrict__ mask_p, uint8_t* __restrict__ mask_g, long pixels,
+                                                                   unsigned int cls, unsigned int ignore) {
+  const long base = ((long)blockIdx.x * kEvalThreads + threadIdx.x) * kEvalRun;
+  if (base >= pixels) return;
+  unsigned int pw[4], aw[4], cp[4], cg[4], mp[4], mg[4];
+  eval_load_bytes(predicted, base, pixels, pw);
+  eval_load_bytes(actual, base, pixels, aw);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const unsigned int u = eval_eq_bytes(aw[e], ignore);
+    mp[e] = eval_eq_bytes(pw[e], cls) & ~u;
+    mg[e] = eval_eq_bytes(aw[e], cls);
+    cp[e] = mp[e] | u << 1;
+    cg[e] = mg[e] | u << 1;
+  }
+  eval_store_bytes(coded_p, base, pixels, cp);
+  eval_store_bytes(coded_g, base, pixels, cg);
+  eval_store_bytes(mask_p, base, pixels, mp);
+  eval_store_bytes(mask_g, base, pixels, mg);
 }
 
 bool eval_shape_ok(long pixels, long group) { return pixels > 0 && pixels < (1l << 31) && group > 0 && pixels % group == 0; }
@@ -201,8 +268,29 @@ extern "C" int rs_eval_boundary(const int32_t* d2_a, const int32_t* d2_b, int64_
   hipStream_t s = (hipStream_t)stream;
   const hipError_t e = hipMemsetAsync(counts, 0, pixels / group * 3 * sizeof(int64_t), s);
   if (e != hipSuccess) return (int)e;
-  eval_boundary_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(d2_a, d2_b, reinterpret_cast<unsigned long long*>(counts), pixels,
-                                                                            group, (unsigned int)(D * D));
+  eval_boundary_kernel<false><<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(d2_a, d2_b, reinterpret_cast<unsigned long long*>(counts),
+                                                                                   pixels, group, (unsigned int)(D * D), nullptr);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_eval_boundary_coded(const int32_t* d2_a, const int32_t* d2_b, const uint8_t* coded, int64_t* counts, long pixels,
+                                      long group, int D, rs_stream_t stream) {
+  if (!d2_a || !d2_b || !coded || !counts || ((uintptr_t)counts & 7) || !eval_shape_ok(pixels, group) || D < 1 || D > 127) return RS_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const hipError_t e = hipMemsetAsync(counts, 0, pixels / group * 3 * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  eval_boundary_kernel<true><<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, s>>>(d2_a, d2_b, reinterpret_cast<unsigned long long*>(counts),
+                                                                                  pixels, group, (unsigned int)(D * D), coded);
+  return RS_LAUNCH_RESULT();
+}
+
+extern "C" int rs_eval_select(const uint8_t* predicted, const uint8_t* actual, uint8_t* coded_p, uint8_t* coded_g, uint8_t* mask_p,
+                              uint8_t* mask_g, long pixels, int C, int cls, int ignore, rs_stream_t stream) {
+  if (!predicted || !actual || !coded_p || !coded_g || !mask_p || !mask_g || pixels <= 0 || pixels >= (1l << 31) || C < 2 || C > 8 ||
+      cls < 1 || cls >= C || ignore < C || ignore > 255)
+    return RS_EINVAL;
+  eval_select_kernel<<<rs_cdiv(pixels, kEvalBlock), kEvalThreads, 0, (hipStream_t)stream>>>(predicted, actual, coded_p, coded_g, mask_p, mask_g,
+                                                                                            pixels, (unsigned int)cls, (unsigned int)ignore);
   return RS_LAUNCH_RESULT();
 }
 

@@ -170,12 +170,13 @@ def centerline_report(rho, counts):
 
 
 def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects=None, boundary=None, ignore=None, ignored=0,
-                 probability=None, centerline=None):
+                 probability=None, centerline=None, ignored_as=None):
     """The report of one run.  ``matrix``: C x C Python integers summed over every evaluated tile; ``kind``: ``--type`` or None;
     ``objects`` / ``boundary``: ``ObjectScores.report()`` / ``boundary_report()`` or None.  With the dataset's ``ignore`` label the
     report also carries it and ``ignored``, the pixels whose label has that value: they are in no cell, so ``pixels`` (the matrix's
     sum) counts the valid ones and ``pixels + ignored`` is every pixel of the evaluated tiles.  ``probability`` (with ``--probs``):
-    ``probability_report()``, the last key.  ``centerline`` (with ``--centerline``): ``centerline_report()``, behind ``boundary``."""
+    ``probability_report()``, the last key.  ``centerline`` (with ``--centerline``): ``centerline_report()``, behind ``boundary``.
+    ``ignored_as`` (with ``--ignored unknown``): what the ignored pixels were to the typed views, a key behind ``ignored``."""
 
     matrix = [[int(v) for v in row] for row in matrix]
     report = {
@@ -189,6 +190,8 @@ def build_report(classes, matrix, tiles, tiles_without_label, kind=None, objects
     if ignore is not None:
         report["ignore"] = int(ignore)
         report["ignored"] = int(ignored)
+        if ignored_as is not None:
+            report["ignored_as"] = ignored_as
     if kind is not None:
         report["type"] = kind
         report["objects"] = objects

@@ -2575,19 +2575,49 @@ def prob_histogram(prob_u8, actual_u8, classes, cls, stitched=False, ignore=None
     return hist, skipped[:, 0], skipped[:, 1]
 
 
-def boundary_counts(d2_a, d2_b, d, stitched=False):
+def boundary_counts(d2_a, d2_b, d, stitched=False, coded=None):
     """Two int32 [B, H, W] rasters of ``distance_transform(mask, d + 1)`` (with ``nbr`` for ``stitched``) -> int64 [G, 3]: per tile,
     or with ``stitched`` for the one raster the B tiles form, the pixels in the first mask's band, in the second's and in both.  A
     mask's band is its pixels with 1 <= d2 <= d*d: those within ``d`` pixels of an unset pixel of the raster; the raster's edge is
-    no boundary.  1 <= ``d`` <= 127."""
+    no boundary.  1 <= ``d`` <= 127.
+
+    With ``coded`` (uint8 [B, H, W], a coded plane of ``select_known``, the transforms being those of the two coded planes) a pixel
+    whose byte is 2 is unknown and in neither band (``rs_eval_boundary_coded``)."""
 
     d = int(d)
     if not 1 <= d <= EVAL_MAX_DISTANCE:
         raise ValueError("robosat_amd: the boundary band's distance is in 1..{}, got {}".format(EVAL_MAX_DISTANCE, d))
     a, b, pixels, hw = _eval_pair(d2_a, d2_b, ("d2_a", "d2_b"), torch.int32)
+    if coded is not None and (coded.shape != d2_a.shape or coded.device != d2_a.device):
+        raise ValueError("robosat_amd: coded is [B, H, W] like the transforms and on their device, got {} on {}".format(tuple(coded.shape), coded.device))
     counts = torch.empty((1 if stitched else d2_a.shape[0], 3), device=d2_a.device, dtype=torch.int64)
-    _call("rs_eval_boundary", a, b, _dev(counts, "counts", torch.int64), pixels, pixels if stitched else hw, d, _stream())
+    if coded is None:
+        _call("rs_eval_boundary", a, b, _dev(counts, "counts", torch.int64), pixels, pixels if stitched else hw, d, _stream())
+    else:
+        _call("rs_eval_boundary_coded", a, b, _dev(coded, "coded", torch.uint8), _dev(counts, "counts", torch.int64), pixels,
+              pixels if stitched else hw, d, _stream())
     return counts
+
+
+def select_known(predicted_u8, actual_u8, index, ignore, classes):
+    """``rs evaluate --type --ignored unknown``: two uint8 [B, H, W] class-index rasters, the class ``index`` (1 .. ``classes`` - 1)
+    and the ``ignore`` label (``classes`` .. 255) -> (coded_p, coded_g, mask_p, mask_g), uint8 [B, H, W] each.  With U = (actual ==
+    ignore): coded_p is 2 on U, 1 where predicted == index outside U, 0 elsewhere; coded_g the same with actual == index; mask_p =
+    (coded_p == 1), mask_g = (coded_g == 1) as 0/1 bytes.  One launch (``rs_eval_select``) in place of two ``clean_masks``."""
+
+    classes = int(classes)
+    if not 2 <= classes <= EVAL_MAX_CLASSES:
+        raise ValueError("robosat_amd: 2 to {} classes are counted, got {}".format(EVAL_MAX_CLASSES, classes))
+    if isinstance(index, bool) or int(index) != index or not 1 <= int(index) < classes:
+        raise ValueError("robosat_amd: the class to select is a non-background one, 1..{}, got {!r}".format(classes - 1, index))
+    ignore = _ignore_label(ignore, classes)
+    if ignore is None:
+        raise ValueError("robosat_amd: select_known codes the pixels of an ignore label; without one the masks are clean_masks'")
+    p, a, pixels, _ = _eval_pair(predicted_u8, actual_u8, ("predicted", "actual"), torch.uint8)
+    coded_p, coded_g, mask_p, mask_g = (torch.empty_like(predicted_u8, memory_format=torch.contiguous_format) for _ in range(4))
+    _call("rs_eval_select", p, a, _dev(coded_p, "coded_p", torch.uint8), _dev(coded_g, "coded_g", torch.uint8),
+          _dev(mask_p, "mask_p", torch.uint8), _dev(mask_g, "mask_g", torch.uint8), pixels, classes, int(index), ignore, _stream())
+    return coded_p, coded_g, mask_p, mask_g
 
 
 # ---- rs evaluate --centerline: the buffer method on two skeletons (rs_eval_centerline; definitions in include/robosat_hip.h) -------

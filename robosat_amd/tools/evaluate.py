@@ -19,15 +19,19 @@ length / (predicted + unmatched actual length).  Pixel and boundary IoU depend o
 
 With the dataset's ``[common] ignore`` a pixel whose LABEL has that value is in no cell of the pixel view: the report and the
 ``--tiles`` rows count it as ``ignored`` and their ``pixels`` are the valid ones.  A mask byte, or another label byte, that is no
-class still ends the run.  With ``--type`` a label tile that holds an ignored pixel ends the run, naming the tile: what a
-boundary or an object cut by an unknown region should count as is not defined yet.
+class still ends the run.  With ``--type`` a label tile that holds an ignored pixel ends the run, naming the tile, unless
+``--ignored unknown`` is given.  Then an ignored pixel is to the typed views what a pixel outside the raster already is, unknown:
+the prediction under it is no part of the predicted class, no distance comes from it and it is in no boundary band (the edge of an
+ignored region is no boundary), an object that an ignored region cuts is cut on both sides alike (as at a tile border without
+``--stitch``), a predicted object wholly inside one does not exist, and centre lines stop short of it on both sides.  The masks and
+the coded rasters of both sides come from one pass (``ops.select_known``), and the band count leaves the unknown pixels out.
 
 With ``--probs DIR`` (the probability tiles ``rs predict`` wrote for these masks, one model) a fourth view is added: the joint
 histogram of (label is the class, probability byte) per tile (``ops.prob_histogram``), summed over the tiles, from which the host
 forms the 256 operating points "byte >= k", average precision, AUC, the Brier score, a ten-bin calibration table with its ECE, and
 the thresholds with the best F1 and IoU (``--curve`` lists every point; ``rs masks --threshold`` applies one).  The class is
-``--type`` where given, class 1 otherwise.  Because ``--type`` refuses label tiles with ignored pixels, a multi-class dataset with
-ignored pixels has no probability view yet.
+``--type`` where given, class 1 otherwise.  The histogram leaves ignored labels out by itself, so on a multi-class dataset with
+ignored pixels ``--type --ignored unknown`` is what gives the probability view.
 
 The definitions are in ``include/robosat_hip.h`` and DESIGN.md."""
 
@@ -91,11 +95,16 @@ def add_parser(subparser):
                         "'probability' to the report: the 256 thresholds 'byte >= k' of the class's probability against the labels, "
                         "average precision, AUC, Brier score, calibration and the thresholds with the best F1 and IoU. The class is "
                         "--type where given, else class 1; a dataset with more than two classes needs --type. As --type refuses label "
-                        "tiles with ignored pixels, a multi-class dataset with ignored pixels has no probability view yet. With "
-                        "--tiles the rows gain the tile's own Brier score")
+                        "tiles with ignored pixels by default, a multi-class dataset with ignored pixels has no probability view yet "
+                        "unless --ignored unknown is given. With --tiles the rows gain the tile's own Brier score")
     parser.add_argument("--curve", type=str, default=None, metavar="CSV",
                         help="with --probs: path to a CSV with the 256 operating points: threshold_byte, threshold, tp, fp, fn, tn, "
                         "precision, recall, f1, iou")
+    parser.add_argument("--ignored", type=str, default="refuse", choices=["refuse", "unknown"],
+                        help="with --type on a dataset with [common] ignore: what a label tile with ignored pixels means to the "
+                        "boundary, object, centerline and probability views. refuse: the run ends and names the tile. unknown: an "
+                        "ignored pixel is unknown on both sides, like a pixel outside the raster: it is in no band and no object, no "
+                        "distance comes from it, and objects and centre lines are cut at ignored regions, on both sides alike")
     parser.add_argument("--batch_size", type=int, default=16, help="tiles per device launch")
     parser.set_defaults(func=main)
 
@@ -103,9 +112,17 @@ def add_parser(subparser):
 MATCH_DEFAULT = 0.5
 
 
-def validate(args, classes):
-    """Every check that needs no device; ends the run with a message.  Returns (match threshold, min_area)."""
+def validate(args, classes, ignore=None):
+    """Every check that needs no device; ends the run with a message.  ``ignore``: the dataset's ignore label or None.  Returns
+    (match threshold, min_area)."""
 
+    ignored = getattr(args, "ignored", "refuse")
+    if ignored not in ("refuse", "unknown"):
+        sys.exit("Error: --ignored is refuse or unknown, got '{}'".format(ignored))
+    if ignored == "unknown" and args.type is None:
+        sys.exit("Error: --ignored unknown says what ignored pixels are to the views of one class: not without --type")
+    if ignored == "unknown" and ignore is None:
+        sys.exit("Error: --ignored unknown needs the dataset's [common] ignore: without it no label pixel is ignored")
     if not 2 <= len(classes) <= ops.EVAL_MAX_CLASSES:
         sys.exit("Error: 2 to {} classes are counted, the dataset has {}".format(ops.EVAL_MAX_CLASSES, len(classes)))
     if args.type is None:
@@ -200,9 +217,10 @@ class Probabilities:
 class Evaluation:
     """The sums of a run, and the device stages of one batch (tiles on their own) or call (tiles as one sparse raster)."""
 
-    def __init__(self, classes, index, boundary, objects, ignore=None, probs=None, centerline=0):
+    def __init__(self, classes, index, boundary, objects, ignore=None, probs=None, centerline=0, unknown=False):
         self.classes, self.index, self.boundary, self.objects, self.ignore, self.probs = classes, index, boundary, objects, ignore, probs
         self.centerline = centerline
+        self.unknown = unknown  # --ignored unknown: ignored label pixels are unknown to the typed views instead of ending the run
         self.links = [0] * 8   # the eight link counts of --centerline, summed
         self.tile_links = []   # and per tile, for --tiles (stays empty for stitched calls: they have no per-tile counts)
         n = len(classes)
@@ -226,9 +244,10 @@ class Evaluation:
             counts, bad, ignored = ops.mask_confusion(predicted, actual, len(self.classes), ignore=self.ignore)
             ignored = ignored.tolist()
             for tile, n in zip(tiles, ignored):
-                if n and self.index is not None:
+                if n and self.index is not None and not self.unknown:
                     sys.exit("Error: the label of tile {} has {} pixels of the ignore value {}; --type scores boundaries and objects, "
-                             "which are not defined next to ignored pixels yet: evaluate without --type".format(_name(tile), n, self.ignore))
+                             "which are not defined next to ignored pixels yet: evaluate without --type, or with --ignored unknown to "
+                             "take them as unknown on both sides".format(_name(tile), n, self.ignore))
             self.ignored.extend(ignored)
         for tile, wrong in zip(tiles, bad.tolist()):
             if wrong:
@@ -251,12 +270,19 @@ class Evaluation:
         if self.index is None:
             return
         stitched = nbr is not None
-        # (discs of 0: the class's pixels as they are, on both sides)
-        mask_p, mask_g = ops.clean_masks(predicted, self.index, 0, 0), ops.clean_masks(actual, self.index, 0, 0)
+        if self.unknown:
+            # the same calls whether this batch holds an ignored pixel or not: the coded planes then hold no 2 and every count is
+            # the unflagged one
+            coded_p, coded_g, mask_p, mask_g = ops.select_known(predicted, actual, self.index, self.ignore, len(self.classes))
+        else:
+            # (discs of 0: the class's pixels as they are, on both sides)
+            mask_p, mask_g = ops.clean_masks(predicted, self.index, 0, 0), ops.clean_masks(actual, self.index, 0, 0)
+            coded_p, coded_g = mask_p, mask_g
         if self.boundary:
-            d2_p = ops.distance_transform(mask_p, self.boundary + 1, nbr)
-            d2_g = ops.distance_transform(mask_g, self.boundary + 1, nbr)
-            for row in ops.boundary_counts(d2_p, d2_g, self.boundary, stitched=stitched).tolist():
+            # (of the coded planes: non-zero = set, so distances pass over unknown pixels and come from unset ones only)
+            d2_p = ops.distance_transform(coded_p, self.boundary + 1, nbr)
+            d2_g = ops.distance_transform(coded_g, self.boundary + 1, nbr)
+            for row in ops.boundary_counts(d2_p, d2_g, self.boundary, stitched=stitched, coded=coded_g if self.unknown else None).tolist():
                 for k in range(3):
                     self.band[k] += row[k]
         if self.centerline:
@@ -281,20 +307,21 @@ def main(args):
     # (callers that build the arguments themselves may predate these flags)
     args.probs, args.curve = getattr(args, "probs", None), getattr(args, "curve", None)
     args.centerline = getattr(args, "centerline", 0)
+    args.ignored = getattr(args, "ignored", "refuse")
     dataset = load_config(args.dataset)
     classes = dataset["common"]["classes"]
     try:
         ignore = ignore_label(dataset)
     except ValueError as err:
         sys.exit("Error: {}".format(err))
-    match, min_area = validate(args, classes)
+    match, min_area = validate(args, classes, ignore)
     if not torch.cuda.is_available():
         sys.exit("Error: this build computes on the MI355X only")
     device = torch.device("cuda", 0)
     index = None if args.type is None else classes.index(args.type)
     objects = None if index is None else ObjectScores(match, min_area, args.stitch)
     probs = None if args.probs is None else Probabilities(args.probs, (1 if index is None else index) - 1, per_tile=args.tiles is not None)
-    run = Evaluation(classes, index, args.boundary, objects, ignore, probs, args.centerline)
+    run = Evaluation(classes, index, args.boundary, objects, ignore, probs, args.centerline, unknown=args.ignored == "unknown")
 
     label_paths = {tile: path for tile, path in tiles_from_slippy_map(args.labels)}
     without_label = 0
@@ -338,6 +365,7 @@ def main(args):
                           boundary=boundary_report(args.boundary, run.band) if args.boundary else None,
                           centerline=centerline_report(args.centerline, run.links) if args.centerline else None,
                           **({} if ignore is None else {"ignore": ignore, "ignored": sum(run.ignored)}),
+                          **({"ignored_as": "unknown"} if run.unknown else {}),
                           **({} if probs is None else {"probability": probability_report(
                               classes[probs.channel + 1], probs.pos, probs.neg, None if ignore is None else probs.ignored)}))
     with open(args.out, "w") as fp:
